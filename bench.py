@@ -92,6 +92,23 @@ def parity_gate(ctx, capi, P):
             "seconds": round(time.perf_counter() - t0, 1)}
 
 
+_NATIVE = []
+
+
+def native_oracle():
+    """the oracle built -O3 -march=native on THIS host, once per run, into a private temporary directory (removed at exit): the source tree may be
+    another user's and read-only here, and a native build must never be taken from a tree built on another machine"""
+    if not _NATIVE:
+        import atexit
+        import shutil
+        import tempfile
+        d = tempfile.mkdtemp(prefix="sfg_oracle_native_")
+        atexit.register(shutil.rmtree, d, True)
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "native", "BUILD=" + d], stdout=subprocess.DEVNULL)
+        _NATIVE.append(os.path.join(d, "liboracle_native.so"))
+    return _NATIVE[0]
+
+
 def cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -130,8 +147,7 @@ def cpu_baseline(seconds, L, N, D):
     """the reference's MAC loop (matmult.go:247-289,380-399) restated in C, built -O3 -march=native ON this host, with the
     reference's data layout (shared rotCache[i][baby], u128 accCache[i][giant]); one thread per GRANTED core (affinity mask capped by the
     cgroup quota), every buffer first-touched before the clock starts, >= 3 whole passes over the sample; encode excluded"""
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "native"], stdout=subprocess.DEVNULL)
-    lib = C.CDLL(os.path.join(ROOT, "oracle", "_build", "liboracle_native.so"))
+    lib = C.CDLL(native_oracle())
     lib.orc_bench_mac_ref_layout.restype = C.c_double
     lib.orc_bench_mac_ref_layout.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_double)]
     threads, cores = granted_cores()
@@ -162,8 +178,7 @@ def cpu_end_to_end(ctx, P, threads, cores):
     on the whole block; the reference's big-float encoder is restated at 113 bits (__float128), whose extra cost per diagonal is measured on a 1024 x 1024 block
     (2047 diagonals) and added for all 8192."""
     import numpy as np
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "native"], stdout=subprocess.DEVNULL)
-    os.environ["SFG_ORACLE_SO"] = os.path.join(ROOT, "oracle", "_build", "liboracle_native.so")
+    os.environ["SFG_ORACLE_SO"] = native_oracle()
     ol = oracle_lib()
     ol._lib = None                                          # (the gate ran on the -O2 test build: reload as the native one)
     try:
@@ -374,6 +389,44 @@ def digests_match_pinned(config, digests):
     return (digests["out1_sha256"], digests["out2_sha256"]) == pin
 
 
+# --dump-outputs DIR: what the timed path computed in its last step, for comparing two builds output for output.  Both products are grids of output
+# ciphertexts [i][j] of 2 x L x N ring words (< 2^46, exact in float64); a fixed, seeded sample of whole ciphertexts stays within DUMP_BYTES in all.
+DUMP_BYTES = 64 * 10**6
+DUMP_SEED = 0xD0_5EED
+
+
+def dump_sample(n1, n2, ct_words):
+    """flat [i][j] indices (sorted) of the ciphertexts dumped from Q*X (n1 of them) and Q'*X^T (n2): all of them where they fit, else a seeded sample"""
+    import numpy as np
+    room = DUMP_BYTES // (ct_words * 8)
+    k2 = min(n2, room // 2)
+    k1 = min(n1, room - k2)
+
+    def pick(n, k, salt):
+        if k >= n:
+            return np.arange(n)
+        return np.sort(np.random.default_rng(DUMP_SEED + salt).choice(n, k, replace=False))
+    return pick(n1, k1, 1), pick(n2, k2, 2)
+
+
+def write_dump(path, outputs):
+    """outputs: {name: (ciphertexts [k][2][L][N] of integer words, flat indices, (rows, cols) of the full grid)} -> path/<name>.npy in float64"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    info, total = {}, 0
+    for name, (cts, idx, grid) in outputs.items():
+        cts = np.asarray(cts)
+        if cts.size and int(cts.max()) >= 1 << 53:
+            raise SystemExit(f"--dump-outputs: {name} holds a word float64 cannot represent exactly")
+        arr = cts.astype(np.float64)
+        total += arr.nbytes
+        np.save(os.path.join(path, name + ".npy"), arr)
+        info[name] = {"shape": list(arr.shape), "grid": list(grid), "ciphertexts": [int(x) for x in idx],
+                      "of": f"output ciphertexts at flat [i][j] indices of the {grid[0]} x {grid[1]} grid"}
+    assert total <= DUMP_BYTES, total
+    return {"dir": path, "dtype": "float64", "bytes": total, "seed": DUMP_SEED, "arrays": info}
+
+
 def main_lib_engine(args):
     """N > 1 with the multi-GPU sequence INSIDE the library (sfg_mgpu_*, sfgwas_amd/csrc/mgpu.hip): this script only makes the synthetic inputs, calls the two
     products per step, keeps the clock and hashes the outputs.  One process per GPU (the driver's launch: each rank joins with sfg_mgpu_create_rank and a 128-byte
@@ -382,6 +435,8 @@ def main_lib_engine(args):
     single = args.single_process or (args.gpus == 1 and "RANK" not in os.environ) or bool(solo)
     if solo:
         args.no_check = args.no_digest = True
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: a solo-rank timing run computes no product (SFG_MGPU_SOLO)")
     if not single and "RANK" not in os.environ:           # no launcher around us: start the N ranks as children (never exec after touching the GPU)
         import socket
         with socket.socket() as so:
@@ -577,6 +632,18 @@ def main_lib_engine(args):
             digests = {"out1_sha256": hashlib.sha256(np.concatenate([p[1] for p in parts], axis=1).tobytes()).hexdigest(),
                        "out2_sha256": hashlib.sha256(o2.tobytes()).hexdigest(),
                        "of": "SHA-256 over the per-ciphertext SHA-256s in [i][j] order: Q*X (kp x m_ct) and Q'*X^T (kp x nbr); equal for every world size"}
+    dumped = None
+    if args.dump_outputs:                                   # (see main_torch) every context's own block columns of Q*X, gathered to rank 0; Q'*X^T from rank 0's copy
+        idx1, idx2 = dump_sample(KP * mct_x, KP * nbr_x, 2 * L * N)
+        cts1 = {int(f): out1[i].host_slice((f // mct_x, f % mct_x - blocks[i][0])) for i in range(nloc) for f in idx1 if blocks[i][0] <= f % mct_x < blocks[i][1]}
+        if not single:
+            allc = [None] * world
+            dist.all_gather_object(allc, cts1)
+            cts1 = {k: v for sub in allc for k, v in sub.items()}
+        if rank == 0:
+            dumped = write_dump(args.dump_outputs, {
+                "qx": (np.stack([cts1[int(f)] for f in idx1]), idx1, (KP, mct_x)),
+                "qtxt": (np.stack([out2[0].host_slice((int(f) // nbr_x, int(f) % nbr_x)) for f in idx2]), idx2, (KP, nbr_x))})
     macs_per_step = 2 * n_ind * m_snp * KP * 2 * L * (N // SLOTS)
     value = macs_per_step * args.steps / dt
     if solo:
@@ -616,6 +683,8 @@ def main_lib_engine(args):
         if digests is not None:
             res["digests"] = digests
             res["digests_match_pinned"] = digests_match_pinned(args.config, digests)
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         res["encoder_near_ties"] = {"count": near_ties, "within_2^-50": unprovable.value, "what": "rank 0; see the N = 1 line"}
         if phase_tot.get("mac_small", [0, 0, 0])[1] and "mac_i8_pack_pt" in phase_tot:
             res["roofline"] = roofline_blocks(phase_tot, args, (n_ind, m_snp, nbr_x, mct_x, N, L, D, SLOTS, LEVEL), world, dt, value)
@@ -657,7 +726,14 @@ def main():
                          "engine_fallback: true).  Default: exit non-zero with the failing rank's error - a scaling record must not change what it measures silently")
     ap.add_argument("--devices", default=None, help="--single-process: comma-separated device indices of the N ranks (a repeated device selects the in-process "
                                                     "'direct' transport: a rehearsal of N > 1 on one GPU; timings then mean nothing)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float64): qx = Q*X, qtxt = Q'*X^T, whole output "
+                         "ciphertexts, a fixed seeded sample where the full output exceeds 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     # switches of this script that need more than the product library offers: the timing-only solo rank and the kernel A/B switches live in the experimenters' build
     # (sfgwas_amd/lib_ab, `make -C sfgwas_amd/csrc ab`); the forced exchange at one rank is a test switch of the product library
     if os.environ.get("SFG_MGPU_SOLO") and not os.environ.get("SFG_LIB_PATH"):
@@ -712,6 +788,8 @@ def main_torch(args):
         solo = tuple(int(x) for x in os.environ["SFG_BENCH_SOLO"].split("/"))
         rank, world = solo
         args.no_check = args.no_digest = args.no_cpu_baseline = True
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: a solo-rank timing run computes no product (SFG_BENCH_SOLO)")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the HIP path has no CPU fallback")
     if args.backend == "gloo":
@@ -948,6 +1026,19 @@ def main_torch(args):
             digests = {"out1_sha256": hashlib.sha256(mine.tobytes()).hexdigest(),
                        "out2_sha256": hashlib.sha256(ct_hashes(out2).tobytes()).hexdigest(),
                        "of": "SHA-256 over the per-ciphertext SHA-256s in [i][j] order: Q*X (kp x m_ct) and Q'*X^T (kp x nbr); equal for every world size"}
+    # ---- --dump-outputs: the last timed step's products (rank 0 writes; Q*X's sampled ciphertexts are gathered from the ranks that own their block columns)
+    dumped = None
+    if args.dump_outputs:
+        idx1, idx2 = dump_sample(KP * mct_x, KP * nbr_x, outw)
+        cts1 = {int(f): out1[f // mct_x, f % mct_x - blk0].cpu().numpy() for f in idx1 if blk0 <= f % mct_x < blk1}
+        if use_dist and world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, cts1)
+            cts1 = {k: v for p in parts for k, v in p.items()}
+        if rank == 0:
+            dumped = write_dump(args.dump_outputs, {
+                "qx": (np.stack([cts1[int(f)] for f in idx1]).reshape(-1, 2, L, N), idx1, (KP, mct_x)),
+                "qtxt": (out2.view(KP * nbr_x, outw)[torch.from_numpy(idx2).to(dev)].cpu().numpy().reshape(-1, 2, L, N), idx2, (KP, nbr_x))})
 
     # ---- work accounting: useful ring-MACs = nrow*ncol*s*2 polys*L*(N/slots) per product
     macs_per_product = n_ind * m_snp * KP * 2 * L * (N // SLOTS)
@@ -992,6 +1083,8 @@ def main_torch(args):
         if digests is not None:
             res["digests"] = digests
             res["digests_match_pinned"] = digests_match_pinned(args.config, digests)
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         if world > 1:
             res["engine_fallback"] = bool(getattr(args, "engine_fallback", False))       # true: --allow-engine-fallback was given AND the library's engine could not be created
             res["rccl_ranks"] = dist.get_world_size() if use_dist and args.backend == "nccl" else 0
@@ -1054,8 +1147,11 @@ def main_torch(args):
                                     "what": "SURVEY §8(d): int8 genotypes once per product + ciphertexts in/out, divided by the WHOLE step time"}}
         res["phases_ms_per_step"] = {k: v[0] / args.steps for k, v in phase_tot.items()}
         if not args.no_cpu_baseline and world == 1:
-            res["cpu_baseline"] = cpu_baseline(args.cpu_seconds, L, N, D)
-            if not args.no_cpu_end_to_end:
+            try:
+                res["cpu_baseline"] = cpu_baseline(args.cpu_seconds, L, N, D)
+            except Exception as e:                           # noqa: BLE001 - a baseline leg must not lose the measured line
+                res["cpu_baseline"] = {"error": str(e)}
+            if not args.no_cpu_end_to_end and "error" not in res["cpu_baseline"]:
                 try:
                     res["cpu_baseline"]["end_to_end"] = cpu_end_to_end(ctx, P, res["cpu_baseline"]["cores"], res["cpu_baseline"]["cores_granted_vs_present"])
                 except Exception as e:                       # noqa: BLE001 - a baseline leg must not lose the measured line

@@ -6,8 +6,9 @@ into tests/golden/example_party1/ -
                                 (scripts/preprocessing/computeGenoCounts.py) - the expected output
   chrom_sizes.txt               SNPs per chromosome file
 
-and, for party 2, only the expected output (example_party2_gcount.bin) plus a SHA-256 of each of its .pgen inputs: its decoder check
-runs where the reference tree is present (tests/test_pgen.py skips it elsewhere).  Data only - no reference source text is copied."""
+and, for party 2, the expected output (example_party2_gcount.bin), a SHA-256 of each of its 22 .pgen inputs and, in example_party2/geno/, each
+distinct input once (4 files, named after the first chromosome that carries it; tests/test_pgen.py finds them by hash).  Data only - no reference
+source text is copied."""
 import hashlib
 import json
 import os
@@ -27,6 +28,13 @@ def main():
     shutil.copyfile(f"{REF}/party2/all.gcount.transpose.bin", os.path.join(HERE, "example_party2_gcount.bin"))
     sums = {f"chr{c}.pgen": hashlib.sha256(open(f"{REF}/party2/geno/chr{c}.pgen", "rb").read()).hexdigest() for c in range(1, 23)}
     json.dump(sums, open(os.path.join(HERE, "example_party2_pgen_sha256.json"), "w"), indent=1)
+    dst2 = os.path.join(HERE, "example_party2", "geno")
+    os.makedirs(dst2, exist_ok=True)
+    seen = set()
+    for c in range(1, 23):
+        if sums[f"chr{c}.pgen"] not in seen:
+            seen.add(sums[f"chr{c}.pgen"])
+            shutil.copyfile(f"{REF}/party2/geno/chr{c}.pgen", f"{dst2}/chr{c}.pgen")
 
 
 if __name__ == "__main__":

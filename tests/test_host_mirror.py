@@ -11,12 +11,20 @@ import oracle_lib as ol
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "sfgwas_amd", "lib")
+_PRIVATE = []
 
 
 def build(name, with_oracle=False):
     """with_oracle: the test program also links the CPU oracle (used as a key generator only)"""
     src = os.path.join(ROOT, "tests", "host", name + ".cpp")
-    exe = os.path.join(ROOT, "tests", "host", "_build_" + name)
+    out = os.path.join(ROOT, "tests", "host")
+    if not os.access(out, os.W_OK):                    # a tree this user may not write: a private directory of this session (removed at exit)
+        if not _PRIVATE:
+            import atexit, shutil, tempfile
+            _PRIVATE.append(tempfile.mkdtemp(prefix="sfg_host_tests_"))
+            atexit.register(shutil.rmtree, _PRIVATE[0], True)
+        out = _PRIVATE[0]
+    exe = os.path.join(out, "_build_" + name)
     hdr = os.path.join(ROOT, "sfgwas_amd", "host", "gwas.hpp")
     if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
         odir = os.path.join(ROOT, "oracle", "_build")

@@ -14,7 +14,8 @@ import oracle_lib as ol
 import pgen_writer as pw
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-REF2 = "/root/reference/example_data/party2"
+# party 2's 22 .pgen inputs are 4 distinct files: each is stored once, under the first chromosome that carries it, and found by its SHA-256
+PARTY2 = os.path.join(GOLD, "example_party2", "geno")
 
 
 def party1_images():
@@ -33,13 +34,16 @@ def test_oracle_geno_counts_of_party1_equal_the_reference_fixture_for_all_100000
 
 
 def test_oracle_geno_counts_of_party2_equal_the_reference_fixture():
-    if not os.path.isdir(REF2):
-        pytest.skip("party 2's .pgen inputs are read from the reference tree (build container only); its expected output is committed")
     ref = np.fromfile(os.path.join(GOLD, "example_party2_gcount.bin"), dtype=np.uint32).reshape(6, -1)
     sums = json.load(open(os.path.join(GOLD, "example_party2_pgen_sha256.json")))
+    stored = {}
+    for f in sorted(os.listdir(PARTY2)):
+        raw = open(os.path.join(PARTY2, f), "rb").read()
+        stored[hashlib.sha256(raw).hexdigest()] = raw
+    assert len(stored) == 4 and set(stored) == set(sums.values())
     cols = []
     for c in range(1, 23):
-        raw = open(f"{REF2}/geno/chr{c}.pgen", "rb").read()
+        raw = stored[sums[f"chr{c}.pgen"]]
         assert hashlib.sha256(raw).hexdigest() == sums[f"chr{c}.pgen"]
         cols.append(ol.pgen_geno_counts(np.frombuffer(raw, dtype=np.uint8).copy()))
     assert np.array_equal(np.concatenate(cols, axis=1), ref)
