@@ -133,7 +133,10 @@ int sfg_mac_i8_dev(sfg_ctx *ctx, const uint64_t *rot_dev, const uint64_t *pt_hal
 int sfg_encode_diags_dev(sfg_ctx *ctx, const int8_t *block_dev, size_t ld, int r, int c, int transposed,
                          int shift0, int nshift, int L, uint64_t *pt_dev);
 /* coefficient-domain result of the encoder for arbitrary real slot vectors (host convenience used by
- * Mask/MaskTrunc-style callers, basics.go:110-172): values_host[nvec][slots] -> coeffs_host[nvec][N] int64 */
+ * Mask/MaskTrunc-style callers, basics.go:110-172): values_host[nvec][slots] -> coeffs_host[nvec][N] int64.
+ * Domain (both real-slot entry points): finite slot values with |Delta w_c| < 2^53 for every coefficient - there every coefficient is the exactly
+ * rounded integer (half away from zero).  A NaN / inf value, or a coefficient of magnitude 2^53 or more, fails the call (the message names the
+ * cause) and leaves the output undefined; nothing is returned as words. */
 int sfg_encode_coeffs_host(sfg_ctx *ctx, const double *values_host, int nvec, int64_t *coeffs_host);
 /* Rounding audit of the encoder.  The reference rounds Delta * sigma^-1(v) computed with 256-bit big floats (NewEncoderBig(params, 256),
  * matmult.go:1019,1421); the device computes the same reals in double-double (better than 2^-58 absolute here).  The two can only round a
@@ -159,7 +162,8 @@ int sfg_ctx_encoder_unprovable(sfg_ctx *ctx, unsigned long long *count);
 int sfg_ctx_encoder_inject_unsafe_for_test(sfg_ctx *ctx, unsigned long long n);
 /* crypto.EncodeFloatVector (crypto.go:398-420; behind Mask / MaskTrunc / MaskWithScaling, basics.go:110-172, and
  * CPMult operands): nvec real slot vectors [nvec][slots] (host) -> NTT-domain plaintexts pt_dev[nvec][level+1][N]
- * at the context's default scale. The reference encodes at MaxLevel; a product at a lower level reads the first rows. */
+ * at the context's default scale. The reference encodes at MaxLevel; a product at a lower level reads the first rows.
+ * Same domain as sfg_encode_coeffs_host; out of it (or for a NaN / inf value) the call fails. */
 int sfg_encode_vectors_dev(sfg_ctx *ctx, const double *values_host, int nvec, int level, uint64_t *pt_dev);
 
 /* ---- C1/A8: rotations (crypto/basics.go:201-224 -> ckks.Evaluator.RotateNew) ----

@@ -372,16 +372,28 @@ __device__ __forceinline__ void dif_radix8(dd (&xr)[8], dd (&xi)[8], const doubl
 // A second, sticky counter takes the coefficients within 2^-50 of a tie (2^8 times the pipeline's error estimate, about once per 10^15
 // coefficients): while it is non-zero every synchronising entry point FAILS (sfg_encoder_check) - the contract is bit-exactness, and such a
 // coefficient has to be re-derived by a big-float encoder on the host before the product may be used.
+// Real slot vectors (F64IN) have no fixed magnitude: every intermediate of their transform, in units of p, is bounded by Sp = (Delta / n) sum_t |v_t|, the
+// pipeline's error by ~2^-96 Sp, so their band is max(2^-50, 2^-88 Sp) - the same 2^8 margin.  Their domain is a finite input and |Delta w_c| < 2^53 for every
+// coefficient (then the rounded integers are exact doubles, and Sp <= sqrt(N) 2^53); anything else sets a bit of tie_count[3] (ENC_DOM_*), the vector counts no
+// ties, and the calling entry point FAILS instead of returning words.
 template <bool EXACT_TIES>
 __device__ __forceinline__ double dd_round_away(dd x, unsigned &near_tie, double band, bool &inside) {                // integer-valued double
     double nn = __builtin_rint(x.hi);
     double diff = (x.hi - nn) + x.lo;                                                         // |diff| <= 1/2 + |x.lo|
-    const double tie_dist = __builtin_fabs(__builtin_fabs(diff) - 0.5);
-    inside = tie_dist < band;                                                                 // band (2^-50): the double-double value does not prove the rounding - re-derived exactly below, or the call FAILS
-    near_tie += (tie_dist < 0x1p-40 ? 1u : 0u);                                               // audit band
-    if (!EXACT_TIES) return nn + __builtin_rint(diff);      // = the rule below whenever |diff| != 1/2; an exact tie (impossible for integer slot values at Delta/n = 2^k) is counted above
-    const bool up = (diff > 0.5) | ((diff == 0.5) & (nn >= 0)), dn = (diff < -0.5) | ((diff == -0.5) & (nn <= 0));      // (no short-circuit: selects, not branches)
-    return nn + (up ? 1.0 : 0.0) - (dn ? 1.0 : 0.0);
+    if (!EXACT_TIES) {      // genotype rows (|p| < 2^42: |x.lo| is far below 1/2)
+        const double tie_dist = __builtin_fabs(__builtin_fabs(diff) - 0.5);
+        inside = tie_dist < band;                                                             // band (2^-50): the double-double value does not prove the rounding - re-derived exactly below, or the call FAILS
+        near_tie += (tie_dist < 0x1p-40 ? 1u : 0u);                                           // audit band
+        return nn + __builtin_rint(diff);                   // = half away from zero whenever |diff| != 1/2; an exact tie (impossible for integer slot values at Delta/n = 2^k) is counted above
+    }
+    // real slot vectors: above 2^51 ulp(x.hi) >= 1/2 and the unrenormalised x.lo may pass 1, so the integer part of diff is split off first: value = b + e, |e| <= 1/2
+    // (all exact: b is an integer below 2^53, e = diff - rint(diff))
+    const double k = __builtin_rint(diff), e = diff - k, b = nn + k;
+    const double tie_dist = __builtin_fabs(__builtin_fabs(e) - 0.5);
+    inside = tie_dist < band;
+    near_tie += (tie_dist < 0x1p-40 ? 1u : 0u);
+    const bool up = (e == 0.5) & (b >= 0), dn = (e == -0.5) & (b <= 0);                     // (no short-circuit: selects, not branches)
+    return b + (up ? 1.0 : 0.0) - (dn ? 1.0 : 0.0);
 }
 
 // Exact re-derivation of ONE coefficient of a genotype-row plaintext (Delta / n = 2^sexp).  p_j = (Delta / n) sum_t v_t cos(2 pi 5^t j / 2N): with 5^t = 4 m + 1
@@ -417,13 +429,14 @@ __device__ __noinline__ bool enc_tie_resolve(const int8_t *row, const uint16_t *
 
 // rows: diag-major int8 rows of length n; plaintext p encodes row (shift0 + p) right-rotated by d*((shift0+p)/d).
 // F64IN: rows are n doubles (arbitrary real slot vectors, no rotation) — the Mask / EncodeFloatVector use.
+constexpr unsigned long long ENC_DOM_NONFINITE = 1, ENC_DOM_RANGE = 2;      // tie_count[3]: a real slot vector outside the encoder's domain (see dd_round_away)
 constexpr size_t ENC_LDS_BYTES = (size_t)2 * ENC_H * 8;        // 65,536 B: two workgroups per CU
 // Every exchange moves the HIGH parts of all 4096 points through the 64 KiB image (re, im: 2 x 4096 doubles), then the LOW parts: the image
 // holds half of the double-double data at a time, every thread does the same work in both rounds (no divergent writers), and a thread carries
 // at most 8 high + 8 low complex parts across a round.  16 waves per CU.
 template <bool F64IN>
 __global__ void __launch_bounds__(512, 4) k_fft_encode(const void *Dv, int shift0, const double4 *tb, const uint16_t *tinv,
-                                                      double *pc_out, unsigned long long *tie_count, const double2 *costab, int sexp, double band) {
+                                                      double *pc_out, unsigned long long *tie_count, const double2 *costab, int sexp, double band, double band_rel) {
     unsigned near_tie = 0;
     extern __shared__ double lds[];
     double *RE = lds, *IM = lds + ENC_H;
@@ -466,6 +479,21 @@ __global__ void __launch_bounds__(512, 4) k_fft_encode(const void *Dv, int shift
         t0 += t0 < 0 ? n : 0; t1 += t1 < 0 ? n : 0;
         if (F64IN) { xr[a] = dd_make(rowd[t0], 0.0); xi[a] = dd_make(rowd[t1], 0.0); }
         else { xr[a] = dd_make((double)rowl[t0], 0.0); xi[a] = dd_make((double)rowl[t1], 0.0); }
+    }
+    bool out_of_domain = false;
+    if (F64IN) {        // Sp = (Delta / n) sum |v_t| widens the band (band_rel = 2^-88 Delta / n); a non-finite input makes the sum non-finite.  LDS is free until exchange 1.
+        double s = 0.0;
+#pragma unroll
+        for (int a = 0; a < 8; a++) s += __builtin_fabs(xr[a].hi) + __builtin_fabs(xi[a].hi);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if ((tid & 63) == 0) lds[tid >> 6] = s;
+        __syncthreads();
+        s = 0.0;
+#pragma unroll
+        for (int w = 0; w < 8; w++) s += lds[w];
+        if (!__builtin_isfinite(s)) { if (tid == 0) atomicOr(tie_count + 3, ENC_DOM_NONFINITE); }
+        else band = __builtin_fmax(band, s * band_rel);
     }
     dif_radix8<512, !F64IN>(xr, xi, tb + ENC_TB_P512, tid);
     {
@@ -534,6 +562,7 @@ __global__ void __launch_bounds__(512, 4) k_fft_encode(const void *Dv, int shift
             bool in0, in1 = false;
             pc[c] = dd_round_away<F64IN>(wr, near_tie, band, in0);
             if (c > 0) pc[n - c] = -dd_round_away<F64IN>(wi, near_tie, band, in1);
+            if (F64IN) out_of_domain |= !(__builtin_fabs(wr.hi) < 0x1p53) | !(__builtin_fabs(wi.hi) < 0x1p53);      // (NaN included)
             if (in0) note(c);
             if (in1) note(n - c);
         }
@@ -547,6 +576,7 @@ __global__ void __launch_bounds__(512, 4) k_fft_encode(const void *Dv, int shift
             bool in0, in1 = false;
             pc[cc] = dd_round_away<F64IN>(wr, near_tie, band, in0);
             if (cc < h) pc[n - cc] = -dd_round_away<F64IN>(wi, near_tie, band, in1);
+            if (F64IN) out_of_domain |= !(__builtin_fabs(wr.hi) < 0x1p53) | !(__builtin_fabs(wi.hi) < 0x1p53);
             if (in0) note(cc);
             if (in1) note(n - cc);
         }
@@ -554,6 +584,10 @@ __global__ void __launch_bounds__(512, 4) k_fft_encode(const void *Dv, int shift
 #pragma unroll
     for (int i = 0; i < 4; i++) recomb(tid + 512 * i, Ar[i], Ai[i], Br[i], Bi[i]);
     if (tid == 0) recomb(h / 2, Ar[4], Ai[4], Br[4], Bi[4]);
+    if (F64IN && __syncthreads_or(out_of_domain ? 1 : 0)) {     // (uniform: every thread gets here) the vector is outside the domain - the call fails on
+        if (tid == 0) atomicOr(tie_count + 3, ENC_DOM_RANGE);    // ENC_DOM_RANGE, and its coefficients count no ties
+        return;
+    }
     if (tie_n) {       // re-derived exactly by this lane (enc_tie_resolve), or counted as unproven (a second one in the same lane, real-valued slot rows, Delta / n not a
         unsigned unproven = tie_n - 1, resolved = 0;      // power of two, the A/B build -DSFG_ENC_NO_RESOLVE) - which makes the synchronising entry points fail
         double v;
@@ -565,6 +599,17 @@ __global__ void __launch_bounds__(512, 4) k_fft_encode(const void *Dv, int shift
         if (unproven) atomicAdd(tie_count + 1, (unsigned long long)unproven);
     }
     if (near_tie) atomicAdd(tie_count, (unsigned long long)near_tie);
+}
+
+// band_rel of the real-slot encoder (k_fft_encode<true>): 2^-88 Delta / n
+static double enc_band_rel(const sfg_ctx *ctx) { return std::ldexp(ctx->sh->scale / (double)SFG_SLOTS, -88); }
+// after the queue has drained: the domain bits the real-slot encoder set since the reset before its launch (tie_count[3]), as the caller's failure
+static int enc_domain_check(sfg_ctx *ctx, const char *who) {
+    unsigned long long f = 0;
+    SFG_HIP(ctx, hipMemcpy(&f, (unsigned long long *)ctx->tie_count_dev + 3, 8, hipMemcpyDeviceToHost));
+    if (f & ENC_DOM_NONFINITE) SFG_FAIL(ctx, "%s: a slot value is not finite (NaN or inf): outside the encoder's domain", who);
+    if (f & ENC_DOM_RANGE) SFG_FAIL(ctx, "%s: a coefficient |Delta * w_c| reaches 2^53: outside the encoder's domain (the rounded integers must be exact doubles)", who);
+    return 0;
 }
 
 static int enc_pc_scratch(sfg_ctx *ctx, size_t nplain, double **pc) {
@@ -599,7 +644,7 @@ int launch_encode_rows(sfg_ctx *ctx, const int8_t *D, int shift0, int nshift, in
         if (cmode == 1) pc = pcache->slot + (size_t)(shift0 + s0) * SFG_SLOTS;          // the coefficient rows of these shifts live in the cache slot
         if (cmode <= 1) {
             PhaseTimer t(ctx, "encode", false);
-            hipLaunchKernelGGL(k_fft_encode<false>, dim3(nb), dim3(512), lds_bytes, ctx->stream, (const void *)D, shift0 + s0, et->tb, et->tinv, pc, (unsigned long long *)ctx->tie_count_dev, et->costab, et->sexp, ctx->cfg.tie_band);
+            hipLaunchKernelGGL(k_fft_encode<false>, dim3(nb), dim3(512), lds_bytes, ctx->stream, (const void *)D, shift0 + s0, et->tb, et->tinv, pc, (unsigned long long *)ctx->tie_count_dev, et->costab, et->sexp, ctx->cfg.tie_band, 0.0);
             SFG_HIP(ctx, hipGetLastError());
         }
         if (cmode == 2) pc = pcache->slot + (size_t)(shift0 + s0) * SFG_SLOTS;
@@ -672,13 +717,15 @@ extern "C" int sfg_encode_coeffs_host(sfg_ctx *ctx, const double *values_host, i
     std::vector<double> pc((size_t)nvec * n);
     int rc = 0;
     if (hipMemcpyAsync(dv, values_host, (size_t)nvec * n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = 1;
+    if (!rc && hipMemsetAsync((unsigned long long *)ctx->tie_count_dev + 3, 0, 8, ctx->stream) != hipSuccess) rc = 1;
     if (!rc) {
-        hipLaunchKernelGGL(k_fft_encode<true>, dim3(nvec), dim3(512), lds_bytes, ctx->stream, (const void *)dv, 0, et->tb, et->tinv, dpc, (unsigned long long *)ctx->tie_count_dev, et->costab, -1, ctx->cfg.tie_band);
+        hipLaunchKernelGGL(k_fft_encode<true>, dim3(nvec), dim3(512), lds_bytes, ctx->stream, (const void *)dv, 0, et->tb, et->tinv, dpc, (unsigned long long *)ctx->tie_count_dev, et->costab, -1, ctx->cfg.tie_band, enc_band_rel(ctx));
         if (hipGetLastError() != hipSuccess) rc = 1;
     }
     if (!rc && hipMemcpyAsync(pc.data(), dpc, (size_t)nvec * n * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = 1;
     (void)hipStreamSynchronize(ctx->stream); (void)hipFree(dv); (void)hipFree(dpc);
     if (rc) SFG_FAIL(ctx, "encode_coeffs: device operation failed");
+    SFG_TRY(enc_domain_check(ctx, "encode_coeffs"));        // (the doubles are not converted: out of the domain they may be NaN or beyond int64)
     for (int v = 0; v < nvec; v++) {                       // expand p_n = 0, p_{n+c} = -p_{n-c}
         const double *h = pc.data() + (size_t)v * n; int64_t *o = coeffs_host + (size_t)v * SFG_N;
         for (size_t c = 0; c < n; c++) o[c] = (int64_t)h[c];
@@ -700,11 +747,12 @@ extern "C" int sfg_encode_vectors_dev(sfg_ctx *ctx, const double *values_host, i
     SFG_TRY(sfg_scratch(ctx, "enc.vectors", (size_t)nvec * n * 16, &p));
     double *dv = (double *)p; double *dpc = dv + (size_t)nvec * n;
     SFG_HIP(ctx, hipMemcpyAsync(dv, values_host, (size_t)nvec * n * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_fft_encode<true>, dim3(nvec), dim3(512), lds_bytes, ctx->stream, (const void *)dv, 0, et->tb, et->tinv, dpc, (unsigned long long *)ctx->tie_count_dev, et->costab, -1, ctx->cfg.tie_band);
+    SFG_HIP(ctx, hipMemsetAsync((unsigned long long *)ctx->tie_count_dev + 3, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(k_fft_encode<true>, dim3(nvec), dim3(512), lds_bytes, ctx->stream, (const void *)dv, 0, et->tb, et->tinv, dpc, (unsigned long long *)ctx->tie_count_dev, et->costab, -1, ctx->cfg.tie_band, enc_band_rel(ctx));
     SFG_HIP(ctx, hipGetLastError());
     SFG_TRY(launch_ntt_plain(ctx, dpc, (u64 *)pt_dev, (size_t)nvec, level + 1));
     SFG_HIP(ctx, hipStreamSynchronize(ctx->stream));          // values_host may be reused by the caller
-    return 0;
+    return enc_domain_check(ctx, "encode_vectors");           // (out of the domain pt_dev holds no defined words)
 }
 
 // encoder coefficients (since context creation / the last reset) whose double-double value lay within 2^-40 of a rounding tie

@@ -16,7 +16,9 @@
 #include "ntt_core.hpp"
 
 // IN_MODE 0: rows of canonical u64; 1: half-coefficient input (integer-valued doubles) of a real-slot plaintext
-// (pc[0..N/2): p_c, with p_{N/2} = 0 and p_{N-c} = -p_c, see encode.hip), rows = [plain][L]
+// (pc[0..N/2): p_c, with p_{N/2} = 0 and p_{N-c} = -p_c, see encode.hip), rows = [plain][L].  Those coefficients may
+// reach 2^53 (real slot vectors): they are reduced into (-q/2 - 1, q/2 + 1) first - exactly (pred: the remainder is an integer below q) - so that
+// the lazy stages see what they see for canonical input (|x| < 15 q < 2^51, the bound of canon).
 template <int IN_MODE>
 __global__ void __launch_bounds__(512) k_ntt_fwd(const void *in_, u64 *out_, ModPattern pat, RowMap rm, const double *tw_all, const double2 *pack_all, const ModConst *modc) {
     extern __shared__ double lds[];
@@ -42,11 +44,11 @@ __global__ void __launch_bounds__(512) k_ntt_fwd(const void *in_, u64 *out_, Mod
     } else {
         const double *pc = (const double *)in_ + (row / pat.period) * (size_t)(N / 2);
 #pragma unroll
-        for (int a = 0; a < 16; a++) v[a] = pc[a * 512 + tid];
+        for (int a = 0; a < 16; a++) v[a] = pred(pc[a * 512 + tid], q, qinv);
 #pragma unroll
         for (int a = 16; a < 32; a++) {                 // j = N/2 + x, x = (a-16)*512 + tid: p_j = -p_{N/2 - x}, p_{N/2} = 0
             int x = (a - 16) * 512 + tid;
-            v[a] = x == 0 ? 0.0 : -pc[N / 2 - x];
+            v[a] = x == 0 ? 0.0 : -pred(pc[N / 2 - x], q, qinv);
         }
     }
     ntt_fwd_phases(v, lds, tw, pack, q, qinv, tid);
