@@ -1,4 +1,4 @@
-// mac.hip — the hot loop of the hot path: lazy multiply-accumulate of rotated ciphertext rows with encoded
+// ab/mac_reg.hip — the register-staged MAC of round 1 (SFG_MAC_IMPL=reg, A/B build only): lazy multiply-accumulate of rotated ciphertext rows with encoded
 // diagonals (MulCoeffsAndAdd128 / CPMultAccWithoutMRedV2 / ReduceAndAddUint128, gwas/matmult.go:247-399).
 //
 // The reference walks diagonals outermost and keeps s*d*m_ct u128 accumulator polynomials in RAM (440 GB at
@@ -16,8 +16,8 @@
 // every product is < 2^48 so >= 24 terms add exactly below 2^53; accumulators are folded to (-q,q) every
 // `flush` terms, recombined and canonically reduced once at the end.  The canonical sum is what
 // MForm + u128 MAC + REDC + eval.Reduce produce in the reference, so outputs are bit-identical.
-#include "common.hpp"
-#include "kernels.hpp"
+#include "../common.hpp"
+#include "../kernels.hpp"
 
 constexpr int MAC_CL = 16;        // coefficients per workgroup (lanes 0..15 of each 16-lane group)
 constexpr int MAC_CG = 4;         // column groups per wave
@@ -45,7 +45,6 @@ struct MacArgs {
 // LDS image of one chunk: [kk][c][row] with the 2*RH rows of a coefficient contiguous, so a thread pulls its
 // rows with ds_read_b128 (two rows per read; 16 distinct 16-byte words per wave-read at a stride of 2*RH*8 B,
 // which spreads over all 64 banks) and every value read feeds 2 columns x 3..4 FMAs.
-#ifdef SFG_AB          // the register-staged kernel of round 1: A/B build only (make ab)
 template <bool BIG, int RH>
 __global__ void __launch_bounds__(MAC_THREADS, 2) k_mac(MacArgs a, const ModConst *modc) {
     constexpr int RW = BIG ? 2 : 1;                    // doubles per staged rot word
@@ -195,7 +194,6 @@ static int launch_mac_rt(sfg_ctx *ctx, MacArgs a, int rt) {
     SFG_HIP(ctx, hipGetLastError());
     return 0;
 }
-#endif
 
 int launch_mac(sfg_ctx *ctx, const u64 *rot, const u64 *pt, u64 *out, int K, int R, int Ncols, int L, int accumulate) {
     MacStrides st;
@@ -206,10 +204,6 @@ int launch_mac(sfg_ctx *ctx, const u64 *rot, const u64 *pt, u64 *out, int K, int
 }
 
 int launch_mac_strided(sfg_ctx *ctx, const u64 *rot, const u64 *pt, u64 *out, int K, int R, int Ncols, int L, int accumulate, const MacStrides &st) {
-#ifndef SFG_AB
-    (void)rot; (void)pt; (void)out; (void)K; (void)R; (void)Ncols; (void)L; (void)accumulate; (void)st;
-    SFG_FAIL(ctx, "the register-staged MAC kernel exists in the A/B build only (make ab)");
-#else
     if (K <= 0 || R <= 0 || Ncols <= 0) return 0;
     if (L < 1 || L > ctx->nq) SFG_FAIL(ctx, "sfg_mac: L out of range");
     for (int r0 = 0; r0 < R; r0 += MAC_RMAX) {
@@ -237,45 +231,4 @@ int launch_mac_strided(sfg_ctx *ctx, const u64 *rot, const u64 *pt, u64 *out, in
         }
     }
     return 0;
-#endif
-}
-
-// (A/B build: SFG_MAC_IMPL=reg selects the register-staged kernel of this file)
-bool mac_use_dma(const sfg_ctx *ctx) { return !ctx->cfg.mac_reg; }
-
-extern "C" int sfg_mac_dev(sfg_ctx *ctx, const uint64_t *rot, const uint64_t *pt, uint64_t *out, int K, int R, int Ncols, int L, int accumulate) {
-    SFG_HIP(ctx, hipSetDevice(ctx->device));
-    if (L < 1 || L > ctx->nq) SFG_FAIL(ctx, "sfg_mac: L out of range");
-    if (K < 1 || R < 1 || Ncols < 1) SFG_FAIL(ctx, "sfg_mac: K, R and Ncols must be positive (got %d, %d, %d)", K, R, Ncols);
-    PhaseTimer t(ctx, "mac");
-    int rc;
-    if (!mac_use_dma(ctx)) rc = launch_mac(ctx, (const u64 *)rot, (const u64 *)pt, (u64 *)out, K, R, Ncols, L, accumulate);
-    else {
-        std::vector<int> plane_of, is_big; const int nplanes = mac_dma_planes(ctx, L, plane_of, is_big);
-        if (nplanes < 0) return 1;
-        double *rotf = nullptr;
-        const size_t rows = (size_t)K * R;                       // rot is [K][R][L][N]
-        const size_t pad_rows = (size_t)((4 - K % 4) % 4) * R;       // k-slices read (against zero plaintexts) by the ragged last chunk
-        SFG_HIP(ctx, hipMalloc(&rotf, (rows + pad_rows) * (size_t)nplanes * SFG_N * 8));
-        if (pad_rows) SFG_HIP(ctx, hipMemsetAsync(rotf + rows * (size_t)nplanes * SFG_N, 0, pad_rows * (size_t)nplanes * SFG_N * 8, ctx->stream));
-        rc = launch_rot_to_f64(ctx, (const u64 *)rot, rows, L, L, rotf);
-        MacStrides st;
-        st.rot_k = (size_t)R * L * SFG_N; st.rot_r = (size_t)L * SFG_N;
-        st.pt_k = (size_t)Ncols * L * SFG_N; st.pt_n = (size_t)L * SFG_N;
-        st.out_n = (size_t)R * L * SFG_N; st.out_r = (size_t)L * SFG_N;
-        // default build: the small-modulus plaintext rows go through the packed-limb format the product path uses (A/B build, plain panel: as given)
-        const unsigned pmask = mac_dma_packed_mask(ctx, L);
-        u64 *ptp = nullptr; double *rsum = nullptr;
-        if (!rc && pmask) {
-            const size_t prows = (size_t)K * Ncols * L;
-            if (hipMalloc(&ptp, prows * SFG_N * 8) != hipSuccess || hipMalloc(&rsum, (size_t)R * nplanes * SFG_N * 8) != hipSuccess) { rc = 1; ctx->err = "sfg_mac: out of device memory"; }
-            if (!rc) rc = launch_pack_pt(ctx, (const u64 *)pt, ptp, prows, SFG_N, L, pmask);
-            if (!rc) rc = launch_rot_sum(ctx, rotf, (size_t)R, K, L, rsum);
-            st.pt_packed = true;
-        }
-        if (!rc) rc = launch_mac_dma(ctx, rotf, (size_t)R, pmask ? ptp : (const u64 *)pt, (u64 *)out, K, R, Ncols, L, accumulate, st, rsum);
-        (void)hipStreamSynchronize(ctx->stream); (void)hipFree(rotf); (void)hipFree(ptp); (void)hipFree(rsum);
-    }
-    t.stop(1);
-    return rc;
 }

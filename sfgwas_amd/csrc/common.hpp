@@ -51,50 +51,44 @@ struct sfg_geno {
     mutable size_t ptc_hits = 0, ptc_fills = 0;
 };
 
-// A/B and diagnostic switches: read ONCE from the environment by sfg_ctx_create (never on the launch path)
+// The configuration of a context: read ONCE from the caller's sfg_config and the environment by sfg_ctx_create (never on the launch path; ctx.hip read_config)
 struct SfgConfig {
-    bool mac_reg = false;          // SFG_MAC_IMPL=reg      register-staged MAC kernel (mac.hip)
-    bool mac_bc = true;            // SFG_MAC_IMPL=dma      the 8 x 3-tile LDS-DMA kernel (mac_dma.hip) instead of the DPP-broadcast kernel (mac_bc.hip)
-    bool mac_i8 = true;            // SFG_MAC_IMPL=bc       the DPP-broadcast fp64 kernel for every modulus (round 2's MAC) instead of: small moduli on the int8 matrix core (mac_i8.hip), the 46-bit one on the DPP-broadcast kernel
-    size_t i8_keep_reserve = 80ULL << 30;   // SFG_I8_KEEP_RESERVE_GB  HBM that must stay free beside the transposed copies of ALL groups of a caller's rotation cache (association scan) for the int8 MAC to take that call
-    bool mac_i8_big = true;        // SFG_MAC_I8_BIG=0      the 46-bit modulus on the fp64 DPP-broadcast kernel k_mac_bc<true> (round 3's default) instead of the int8 matrix core (six digits, 36 products, eleven sums; round 4, same box: 11.14 s against 11.85 s per power iteration - mac_big 0.53 s + 0.5 s of transposition against 1.83 s).  Forced off for a ciphertext modulus above SFG_I8_BIG_QMAX
-    bool mac_i8_nolds = true;      // SFG_MAC_I8_ROT=lds    int8 MAC: rot tiles of a coefficient pair staged through LDS (k_mac_i8_lds) instead of shared through the cache (measured at 100k x 1M: 3.31 s against 2.56 s per step - the barriers cost more than the re-fetches)
-    double tie_band = 0x1p-50;     // distance from a rounding tie inside which the encoder's double-double value does not prove the rounding (SFG_TEST_TIE_BAND_LOG2 widens it under the test switch)
-    bool test_hooks = false;       // SFG_ENABLE_TEST_HOOKS=1   sfg_ctx_encoder_inject_unsafe_for_test may be called (tests of the failure path only)
-    bool mac_i8_ring = true;       // SFG_MAC_I8_ROT=cache    int8 MAC without the LDS prefetch ring (k_mac_i8: operands straight from global memory, rot tiles shared through the L1)
-    bool stage_pack = false;       // SFG_MAC_I8_STAGE=1    int8 MAC: streamed transposition (StagePack, kernels.hpp) instead of the full plaintext panel and a transposition pass per MAC launch.  Built, bit-exact, and measured SLOWER at 100k x 1M (14.2 s against 12.5 s per step on one box: the small per-batch transposition launches run at 1.5 TB/s and slow the encode kernels they share the chip with)
-    int stage_giants = 11;         // SFG_STAGE_GIANTS=n     giant steps per batch of the streamed transposition (16: a batch completes whole 16-column tiles)
-    bool stage_same_queue = false; // SFG_STAGE_SAMEQ=1      the batch transposition on the product's own queue (behind its NTT) instead of the encode queue
-    int mac_i8_waves = 12;         // SFG_MAC_I8_WAVES=6     k_mac_i8_ring with six waves per coefficient pair (a wave = both coefficients x 16 columns) instead of twelve (one coefficient each)
-    int mac_i8_diag = 0;           // SFG_MAC_I8_DIAG=1 / 2   timing diagnostics of k_mac_i8_ring, results INVALID: 1 = one MFMA per rot tile, 2 = no DMA after the prologue
-    bool mac_i8_wg1 = false;       // SFG_MAC_I8_WG=1       int8 MAC diagnostic: one column wave per workgroup (no cache shared between the column waves of a coefficient pair); for the PMC re-fetch measurement
-    int mac_wc = 1;                // SFG_MAC_WC            column waves per small-modulus MAC workgroup
+    // ---- deployment (sfg_config, SFG_MM_GROUP, SFG_MM_ACC_BUDGET_MB, SFG_ASSOC_ROTCACHE_MB, SFG_KSW_BUDGET_MB, SFG_ENC_BATCH, SFG_UPLOAD_BLOCKING)
     int mm_group = 8;              // SFG_MM_GROUP          block rows per MAC launch
     bool mm_group_auto = true;     //                       (unset) 16 block rows per launch when the plaintext panel and the rotation operands of such a group fit the free HBM, else 8
     size_t acc_budget = 24ULL << 30;   // SFG_MM_ACC_BUDGET_MB
-    bool no_overlap = true;        // SFG_MM_OVERLAP=1      two queues: the key switching of the next block-row group / the giant-step alignment of the last column pass beside the encode + MAC.  Off since round 4 (single queue: 10.87 s against 10.91 s per step at 100k x 1M, 3.39 against 3.41 s at 50k x 500k - the fp64-issue-bound kernels only slow each other down beside the HBM-bound ones); SFG_MM_NO_OVERLAP=1 is still accepted
-    bool no_enc_overlap = true;    // SFG_MM_ENC_OVERLAP=1  the encode of MAC launch k + 1 on a third queue beside the transposition + MAC of launch k (two plaintext panels).  Built and measured at
-                                   // 100k x 1M: 12.24 s against 12.20 s - the kernels then share the machine in time, not in space: a MAC workgroup (6 waves x 240 VGPRs) leaves no SIMD
-                                   // with the 128 VGPRs a plaintext-NTT wave needs, so an encode workgroup cannot be resident beside it.  Off until the MAC leaves that room.
-    bool ntt_fwd_full = false;     // SFG_NTT_FWD_IMPL=full   one 512-thread workgroup per row for the general forward NTT (instead of two half-row workgroups)
-    bool ntt_half_full = false;    // SFG_NTT_HALF_IMPL=full
-    bool upload_blocking = false;  // SFG_UPLOAD_BLOCKING   blocking pointer-table uploads (rocprofv3 --pmc)
+    size_t assoc_cache_budget = 160ULL << 30;   // SFG_ASSOC_ROTCACHE_MB   largest baby-step rotation cache sfg_assoc_stream_bed keeps across the batches of a call (0: rebuild per batch)
     size_t ksw_budget = 4ULL << 30; // SFG_KSW_BUDGET_MB      key-switch scratch per input group / job chunk: more jobs per chunk = more reuse of a key (64 MB: +45 %, 1.5 GB: +2 %, 12 GB: -2 %)
-    std::string test_scratch_oom;  // SFG_TEST_SCRATCH_OOM=name:n  (test switch only) the n-th request of scratch buffer `name` inside a top-level call behaves as if the device were full: the eviction path of sfg_scratch runs
-    int i8_mover = 0;              // SFG_I8_MOVER=n (A/B build)  n workgroups of the plaintext transposition in its mover form (i8_move.hpp) instead of the pass k_i8_pack_pt_digits: 1280 is 3 % faster alone, nothing in a product (profiles/r06_mover_ubench.txt)
-    int i8_mover_depth = 3;        // SFG_I8_MOVER_DEPTH     units (32 KiB) a mover workgroup keeps in flight + 1
-    bool pt_compact = true;        // panel rows of an all-int8 product hold only their digit planes (208 KiB per plaintext instead of 320 KiB at L = 5).  SFG_PT_COMPACT=0 in the A/B build
-    bool pt_kmajor = true;         // the compact panel K-major: [column][plane][128-byte coefficient block][k][128 B] (2 KiB source runs for the transposition).  SFG_PT_KMAJOR=0 in the A/B build
-    int pt_ride = 192;             // mover workgroups of the riding transposition per plaintext-NTT launch (kernels.hpp PtRide; 0 = the transposition pass before every MAC launch).  SFG_PT_RIDE in the A/B build
-    int i8_mover_depth_ride = 1, i8_mover_nt_ride = 1;     // (A/B build: SFG_PT_RIDE_DEPTH, SFG_PT_RIDE_NT)
     int enc_batch = 2048;          // SFG_ENC_BATCH          diagonals per FFT / plaintext-NTT launch pair: 128 MB of coefficient rows stay cache resident between the two now that the NTT's digit planes leave by streaming stores (round 5: 2048 -3 % of a 50k x 500k step against 1024, 3072 the same, 4096 worse; with plain stores 1024 was best)
+    bool upload_blocking = false;  // SFG_UPLOAD_BLOCKING   blocking pointer-table uploads (rocprofv3 --pmc)
+    // ---- tests (SFG_ENABLE_TEST_HOOKS=1 and the switches it unlocks)
+    bool test_hooks = false;       // SFG_ENABLE_TEST_HOOKS=1   sfg_ctx_encoder_inject_unsafe_for_test may be called (tests of the failure path only)
+    std::string test_scratch_oom;  // SFG_TEST_SCRATCH_OOM=name:n  the n-th request of scratch buffer `name` inside a top-level call behaves as if the device were full: the eviction path of sfg_scratch runs
+    double tie_band = 0x1p-50;     // SFG_TEST_TIE_BAND_LOG2  distance from a rounding tie inside which the encoder's double-double value does not prove the rounding (the test switch widens it)
+    // ---- set from the moduli at context creation
+    bool mac_i8_big = true;        // the 46-bit modulus on the int8 matrix core (six digits, 36 products, eleven sums; round 4, same box: 11.14 s against 11.85 s per power iteration - mac_big 0.53 s
+                                   // + 0.5 s of transposition against 1.83 s) instead of the fp64 DPP-broadcast kernel k_mac_bc<true>.  Forced off for a ciphertext modulus above SFG_I8_BIG_QMAX; SFG_MAC_I8_BIG=0 in the A/B build
+    // ---- A/B build only; constant in the product (ab/config.hip reads them from the environment under -DSFG_AB; defaults = the measured configuration)
+    bool mac_reg = false;          // SFG_MAC_IMPL=reg      register-staged MAC kernel (ab/mac_reg.hip)
+    bool mac_bc = true;            // SFG_MAC_IMPL=dma      the 8 x 3-tile LDS-DMA kernel (ab/mac_dma_tiles.hip) instead of the DPP-broadcast kernel (mac_bc.hip)
+    bool mac_i8 = true;            // SFG_MAC_IMPL=bc       the DPP-broadcast fp64 kernel for every modulus (round 2's MAC) instead of: small moduli on the int8 matrix core (mac_i8.hip), the 46-bit one on the DPP-broadcast kernel
+    bool mac_i8_nolds = true;      // SFG_MAC_I8_ROT=lds    int8 MAC: rot tiles of a coefficient pair staged through LDS (k_mac_i8_lds) instead of shared through the cache (measured at 100k x 1M: 3.31 s against 2.56 s per step - the barriers cost more than the re-fetches)
+    bool mac_i8_ring = true;       // SFG_MAC_I8_ROT=cache    int8 MAC without the LDS prefetch ring (k_mac_i8: operands straight from global memory, rot tiles shared through the L1)
+    int mac_i8_waves = 12;         // SFG_MAC_I8_WAVES=6     k_mac_i8_ring with six waves per coefficient pair (a wave = both coefficients x 16 columns) instead of twelve (one coefficient each)
+    bool mac_i8_wg1 = false;       // SFG_MAC_I8_WG=1       int8 MAC diagnostic: one column wave per workgroup (no cache shared between the column waves of a coefficient pair); for the PMC re-fetch measurement
+    int mac_wc = 1;                // SFG_MAC_WC            column waves per small-modulus MAC workgroup
+    bool no_overlap = true;        // SFG_MM_OVERLAP=1      two queues: the key switching of the next block-row group / the giant-step alignment of the last column pass beside the encode + MAC.  Off since round 4 (single queue: 10.87 s against 10.91 s per step at 100k x 1M, 3.39 against 3.41 s at 50k x 500k - the fp64-issue-bound kernels only slow each other down beside the HBM-bound ones); SFG_MM_NO_OVERLAP=1 is still accepted
+    bool ntt_fwd_full = false;     // SFG_NTT_FWD_IMPL=full   one 512-thread workgroup per row for the general forward NTT (instead of two half-row workgroups)
+    bool ntt_half_full = false;    // SFG_NTT_HALF_IMPL=full  the full-image plaintext NTT (ab/ntt_full.hip)
+    bool pt_compact = true;        // SFG_PT_COMPACT=0      panel rows of an all-int8 product hold only their digit planes (208 KiB per plaintext instead of 320 KiB at L = 5)
+    bool pt_kmajor = true;         // SFG_PT_KMAJOR=0       the compact panel K-major: [column][plane][128-byte coefficient block][k][128 B] (2 KiB source runs for the transposition)
+    int pt_ride = 192;             // SFG_PT_RIDE           mover workgroups of the riding transposition per plaintext-NTT launch (kernels.hpp PtRide; 0 = the transposition pass before every MAC launch)
+    int i8_mover_depth_ride = 1, i8_mover_nt_ride = 1;     // SFG_PT_RIDE_DEPTH, SFG_PT_RIDE_NT
     bool mac_plain_pt = false;     // SFG_MAC_PT=plain      plaintext panel as plain u64 words (A/B of the packed-limb panel format)
-    // CU partitioning experiments (round 5): restrict a queue of the context to a set of compute units, "lo-hi[,lo-hi...]" over the bits of hipExtStreamCreateWithCUMask
-    // (bit i = CU i of the device's enumeration).  Empty = all CUs (the default).  A stream installed by sfg_ctx_set_stream is the caller's and keeps its own mask.
-    std::string cu_main, cu_enc, cu_aux;   // SFG_CU_MAIN / SFG_CU_ENC / SFG_CU_AUX
-    bool assoc_i8 = true;                   // SFG_ASSOC_I8=0           association scan: keep the rotation cache as fp64 operand rows (round 3) instead of the int8 MAC's rot tiles
-    size_t assoc_cache_budget = 160ULL << 30;   // SFG_ASSOC_ROTCACHE_MB   largest baby-step rotation cache sfg_assoc_stream_bed keeps across the batches of a call (0: rebuild per batch, the A/B switch)
+    bool assoc_trace = false;      // SFG_ASSOC_TRACE       the streamed association scan prints the wall times of its cache build and of every batch (each synchronised)
 };
+// HBM that must stay free beside the transposed copies of ALL groups of a caller's rotation cache (association scan) for the int8 MAC to take that call
+constexpr size_t SFG_I8_KEEP_RESERVE = 80ULL << 30;
 
 // Immutable after setup, shared by a context and its forks (sfg_ctx_fork): ring tables, encoder tables, key material.
 struct SfgShared {
@@ -144,8 +138,7 @@ struct sfg_ctx {
     hipStream_t aux_stream = nullptr;    // second queue: key switching of the next group / previous column pass runs beside encode + MAC
     // pinned host ring for small stream-ordered uploads (pointer tables): no blocking copies on the launch path
     unsigned char *pin = nullptr; size_t pin_bytes = 0, pin_head = 0;
-    hipStream_t enc_stream = nullptr;    // third queue: the encode (skew, FFT, NTT: fp64-issue bound) of MAC launch k + 1 beside the HBM-bound transposition + int8 MAC of launch k
-    hipEvent_t ev_enc[4] = {nullptr, nullptr, nullptr, nullptr};    // [0,1]: panel buffer encoded; [2,3]: panel buffer consumed by its MAC
+    hipStream_t coll_stream = nullptr;   // third queue: the multi-GPU engine's collectives (mgpu.hip)
     hipEvent_t ev_pipe[4] = {nullptr, nullptr, nullptr, nullptr};   // [0,1]: rotation cache of group parity ready; [2,3]: finalize of column pass parity done
     std::vector<hipEvent_t> ev_pool; size_t ev_next = 0;     // ordering events (no timing), reused round-robin
     std::map<int, void *> ksw_cache;   // per-level key-switch constants (device), rotate.hip
@@ -159,7 +152,6 @@ struct sfg_ctx {
     std::vector<PendingEvent> pending;                      // phase timers not yet read back (resolved by sfg_phases_resolve)
     std::string err;
     std::map<std::string, PhaseStat> phases;
-    int sp_shape = -1;                      // block rows per group the streamed tile buffers (mi8.Bs / mi8.Bb) were last cleared for
     std::set<const sfg_geno *> ptc_genos;   // matrices whose plaintext coefficient cache this context owns (dropped when an unprovable encoder rounding is reported / reset)
     bool test_hooks = false;                // SFG_ENABLE_TEST_HOOKS=1 at context creation: the failure-path test hook may be used
     void *tie_count_dev = nullptr;          // counters (+ a third: coefficients inside the band whose rounding the exact re-derivation proved): encoder coefficients within 2^-40 of a rounding tie (audit) and within 2^-50 (sticky failure, sfg_encoder_check)
@@ -180,14 +172,12 @@ void sfg_ptc_invalidate_all(sfg_ctx *ctx);     // matmul.hip: forget every cache
 extern thread_local std::string g_create_error;
 
 #define SFG_FAIL(ctx, ...) do { char _b[512]; snprintf(_b, sizeof _b, __VA_ARGS__); (ctx)->err = _b; return 1; } while (0)
-// (the A/B build names the failing call; the product names file and line only - its binary carries no expression text)
 #ifdef SFG_AB
-#define SFG_HIP(ctx, call) do { hipError_t _e = (call); if (_e != hipSuccess) { char _b[512]; \
-    snprintf(_b, sizeof _b, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); (ctx)->err = _b; return 1; } } while (0)
-#else
+#include "ab/ab.hpp"          // the A/B build's entry points (csrc/ab/)
+#endif
+// (file and line only: the binary carries no expression text)
 #define SFG_HIP(ctx, call) do { hipError_t _e = (call); if (_e != hipSuccess) { char _b[512]; \
     snprintf(_b, sizeof _b, "HIP call failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); (ctx)->err = _b; return 1; } } while (0)
-#endif
 #define SFG_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 
 // workspace (grow-only scratch owned by the context)

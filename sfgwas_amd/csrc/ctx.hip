@@ -19,7 +19,6 @@ static u64 derive_psi(u64 q, int logN) {
 int sfg_encoder_init(sfg_ctx *ctx);      // encode.hip (tables into ctx->sh)
 void sfg_encoder_destroy(SfgShared *sh);
 int sfg_kernel_attrs_init(sfg_ctx *ctx);  // raises the dynamic-LDS limits of every big-LDS kernel on ctx->device (mac_dma/ntt/encode)
-int mac_dma_set_attrs(sfg_ctx *ctx);
 int mac_bc_set_attrs(sfg_ctx *ctx);
 int ntt_set_attrs(sfg_ctx *ctx);
 int encode_set_attrs(sfg_ctx *ctx);
@@ -31,9 +30,9 @@ int mac_i8_set_attrs(sfg_ctx *ctx);
 //     SFG_ENC_BATCH, SFG_UPLOAD_BLOCKING (here) and SFG_MGPU_TRANSPORT, SFG_MGPU_CACHE_GB, SFG_RCCL_LIB (mgpu.hip), plus the test switch itself.
 //   * Three test-only switches exist in this build and are honoured only under SFG_ENABLE_TEST_HOOKS=1: SFG_TEST_SCRATCH_OOM, SFG_TEST_TIE_BAND_LOG2 and
 //     SFG_MGPU_FORCE_COLLECTIVES (the exchange at world size 1).
-//   * Every A/B and diagnostic switch of rounds 1 - 6 (which MAC kernel, which NTT form, queue schedules, CU masks, ...) and the superseded kernels they select exist
-//     only in the A/B build (`make ab` -> sfgwas_amd/lib_ab/libsfgwas_hip.so, -DSFG_AB): a party process that inherits a stray variable from its shell cannot change
-//     which kernels multiply.
+//   * The remaining A/B switches (which MAC kernel, which NTT form, panel layouts, the second queue, ...; the last block of SfgConfig) and the superseded kernels they
+//     select exist only in the A/B build (`make ab` -> sfgwas_amd/lib_ab/libsfgwas_hip.so, -DSFG_AB, with the sources of csrc/ab/): a party process that inherits a
+//     stray variable from its shell cannot change which kernels multiply.  The experiments measured and not kept are recorded in profiles/EXPERIMENTS.md.
 static void apply_public_config(SfgConfig &c, const sfg_config *pc) {
     if (!pc || pc->struct_size < sizeof(uint32_t) * 2) return;
     const size_t have = pc->struct_size;
@@ -63,36 +62,7 @@ static void read_config(SfgConfig &c, const sfg_config *pc) {
         if (const char *e = env("SFG_TEST_TIE_BAND_LOG2")) c.tie_band = ldexp(1.0, atoi(e));       // a wider band sends ordinary coefficients through the exact re-derivation
     }
 #ifdef SFG_AB
-    // ---- the A/B build only: experiment switches (defaults = the measured configuration; results identical words unless a line says INVALID)
-    if (const char *e = env("SFG_MAC_IMPL")) { c.mac_reg = !strcmp(e, "reg"); c.mac_bc = strcmp(e, "dma") != 0 && !c.mac_reg; c.mac_i8 = !strcmp(e, "i8"); }      // bc | dma | reg | i8
-    if (const char *e = env("SFG_I8_KEEP_RESERVE_GB")) c.i8_keep_reserve = (size_t)atoll(e) << 30;
-    if (const char *e = env("SFG_MAC_I8_BIG")) c.mac_i8_big = atoi(e) != 0;
-    if (const char *e = env("SFG_MAC_I8_ROT")) { c.mac_i8_nolds = strcmp(e, "lds") != 0; c.mac_i8_ring = !strcmp(e, "ring"); }      // ring (default) | cache | lds
-    if (env("SFG_MAC_I8_WG")) c.mac_i8_ring = false;
-    if (const char *e = env("SFG_MAC_I8_DIAG")) { if (c.test_hooks) c.mac_i8_diag = atoi(e); }       // timing diagnostics with INVALID results
-    if (const char *e = env("SFG_MAC_I8_WAVES")) c.mac_i8_waves = atoi(e) == 6 ? 6 : 12;
-    if (const char *e = env("SFG_MAC_I8_STAGE")) c.stage_pack = atoi(e) != 0;
-    if (const char *e = env("SFG_STAGE_GIANTS")) { c.stage_giants = atoi(e); if (c.stage_giants < 1) c.stage_giants = 1; if (c.stage_giants > 91) c.stage_giants = 91; }
-    if (const char *e = env("SFG_STAGE_SAMEQ")) c.stage_same_queue = atoi(e) != 0;
-    if (const char *e = env("SFG_MAC_I8_WG")) c.mac_i8_wg1 = atoi(e) == 1;
-    if (const char *e = env("SFG_MAC_WC")) c.mac_wc = atoi(e) == 2 ? 2 : 1;
-    if (const char *e = env("SFG_MM_OVERLAP")) c.no_overlap = atoi(e) == 0;
-    if (env("SFG_MM_NO_OVERLAP")) c.no_overlap = true;
-    if (const char *e = env("SFG_MM_ENC_OVERLAP")) c.no_enc_overlap = atoi(e) == 0;
-    if (const char *e = env("SFG_NTT_HALF_IMPL")) c.ntt_half_full = !strcmp(e, "full");
-    if (const char *e = env("SFG_NTT_FWD_IMPL")) c.ntt_fwd_full = !strcmp(e, "full");
-    if (const char *e = env("SFG_MAC_PT")) c.mac_plain_pt = !strcmp(e, "plain");
-    if (const char *e = env("SFG_CU_MAIN")) c.cu_main = e;
-    if (const char *e = env("SFG_CU_ENC")) c.cu_enc = e;
-    if (const char *e = env("SFG_CU_AUX")) c.cu_aux = e;
-    if (const char *e = env("SFG_ASSOC_I8")) c.assoc_i8 = atoi(e) != 0;
-    if (const char *e = env("SFG_I8_MOVER")) { c.i8_mover = atoi(e); if (c.i8_mover < 0) c.i8_mover = 0; c.i8_mover = c.i8_mover / 8 * 8; }
-    if (const char *e = env("SFG_PT_RIDE")) { c.pt_ride = atoi(e); if (c.pt_ride < 0) c.pt_ride = 0; c.pt_ride = c.pt_ride / 8 * 8; }
-    if (const char *e = env("SFG_PT_COMPACT")) c.pt_compact = atoi(e) != 0;
-    if (const char *e = env("SFG_PT_KMAJOR")) c.pt_kmajor = atoi(e) != 0;
-    if (const char *e = env("SFG_PT_RIDE_DEPTH")) { c.i8_mover_depth_ride = atoi(e); if (c.i8_mover_depth_ride < 1 || c.i8_mover_depth_ride > 3) c.i8_mover_depth_ride = 1; }
-    if (const char *e = env("SFG_PT_RIDE_NT")) c.i8_mover_nt_ride = atoi(e) != 0;
-    if (const char *e = env("SFG_I8_MOVER_DEPTH")) { c.i8_mover_depth = atoi(e); if (c.i8_mover_depth < 1 || c.i8_mover_depth > 3) c.i8_mover_depth = 3; }
+    ab_read_config(c);          // the A/B build's experiment switches (ab/config.hip)
 #endif
 }
 
@@ -103,45 +73,17 @@ static void ctx_bind_shared(sfg_ctx *ctx, SfgShared *sh) {
     memcpy(ctx->q, sh->q, sizeof sh->q); memcpy(ctx->psi, sh->psi, sizeof sh->psi); memcpy(ctx->modc_host, sh->modc_host, sizeof sh->modc_host);
     ctx->tw_fwd = sh->tw_fwd; ctx->tw_inv = sh->tw_inv; ctx->pack_fwd = sh->pack_fwd; ctx->pack_inv = sh->pack_inv; ctx->modc = sh->modc;
 }
-#ifdef SFG_AB
-// a queue restricted to the compute units named by `spec` ("lo-hi[,lo-hi...]", bits of hipExtStreamCreateWithCUMask); empty spec: nullptr (caller creates a plain queue)
-static hipStream_t stream_with_cu_mask(const std::string &spec) {
-    if (spec.empty()) return nullptr;
-    uint32_t mask[16] = {0};                                   // up to 512 CUs
-    const char *p = spec.c_str();
-    while (*p) {
-        char *e = nullptr; long lo = strtol(p, &e, 10), hi = lo + 1;
-        if (e == p) return nullptr;
-        if (*e == '-') { p = e + 1; hi = strtol(p, &e, 10); if (e == p) return nullptr; }
-        for (long i = lo; i < hi && i < 512; i++) if (i >= 0) mask[i >> 5] |= 1u << (i & 31);
-        p = *e == ',' ? e + 1 : e;
-        if (*e && *e != ',') return nullptr;
-    }
-    hipStream_t st = nullptr;
-    if (hipExtStreamCreateWithCUMask(&st, 16, mask) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    return st;
-}
-#endif
 // per-caller execution state: two queues, ordering events, the pinned staging ring
 static const char *ctx_exec_init(sfg_ctx *ctx) {
     if (hipSetDevice(ctx->device) != hipSuccess) return "hipSetDevice failed";
-    const SfgConfig &c = ctx->sh->cfg;
-#ifdef SFG_AB
-    if (!c.cu_main.empty() && !(ctx->own_stream = stream_with_cu_mask(c.cu_main))) return "SFG_CU_MAIN: bad CU list or hipExtStreamCreateWithCUMask failed";
-    if (!c.cu_aux.empty() && !(ctx->aux_stream = stream_with_cu_mask(c.cu_aux))) return "SFG_CU_AUX: bad CU list or hipExtStreamCreateWithCUMask failed";
-    if (!c.cu_enc.empty() && !(ctx->enc_stream = stream_with_cu_mask(c.cu_enc))) return "SFG_CU_ENC: bad CU list or hipExtStreamCreateWithCUMask failed";
-#else
-    (void)c;
-#endif
-    if (!ctx->own_stream && hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) return "hipStreamCreate failed";
+    if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) return "hipStreamCreate failed";
     ctx->stream = ctx->own_stream;
-    if (!ctx->aux_stream) {   // the auxiliary queue yields to the main one: its element-wise key-switch kernels fill gaps, they must not displace MAC workgroups
+    {   // the auxiliary queue yields to the main one: its element-wise key-switch kernels fill gaps, they must not displace MAC workgroups
         int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         if (hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, lo) != hipSuccess) return "hipStreamCreate failed";
     }
-    if (!ctx->enc_stream && hipStreamCreateWithFlags(&ctx->enc_stream, hipStreamNonBlocking) != hipSuccess) return "hipStreamCreate failed";
+    if (hipStreamCreateWithFlags(&ctx->coll_stream, hipStreamNonBlocking) != hipSuccess) return "hipStreamCreate failed";
     for (int i = 0; i < 4; i++) if (hipEventCreateWithFlags(&ctx->ev_pipe[i], hipEventDisableTiming) != hipSuccess) return "hipEventCreate failed";
-    for (int i = 0; i < 4; i++) if (hipEventCreateWithFlags(&ctx->ev_enc[i], hipEventDisableTiming) != hipSuccess) return "hipEventCreate failed";
     ctx->pin_bytes = 64u << 20;
     if (hipHostMalloc((void **)&ctx->pin, ctx->pin_bytes, hipHostMallocDefault) != hipSuccess) return "hipHostMalloc failed";
     if (hipMalloc(&ctx->tie_count_dev, 32) != hipSuccess || hipMemset(ctx->tie_count_dev, 0, 32) != hipSuccess) return "hipMalloc failed";
@@ -226,7 +168,7 @@ extern "C" int sfg_ctx_create_ex(sfg_ctx **out, int device, int logN, int nq, in
     ctx_bind_shared(ctx, sh);
     if (sfg_encoder_init(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
     // dynamic-LDS limits are per (function, device): set here for this context's device, not behind process-wide flags
-    if (mac_dma_set_attrs(ctx) || mac_bc_set_attrs(ctx) || ntt_set_attrs(ctx) || encode_set_attrs(ctx) || mac_i8_set_attrs(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
+    if (mac_bc_set_attrs(ctx) || ntt_set_attrs(ctx) || encode_set_attrs(ctx) || mac_i8_set_attrs(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
     *out = ctx;
     return 0;
 }
@@ -251,7 +193,7 @@ extern "C" void sfg_ctx_destroy(sfg_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
-    if (ctx->enc_stream) (void)hipStreamSynchronize(ctx->enc_stream);
+    if (ctx->coll_stream) (void)hipStreamSynchronize(ctx->coll_stream);
     if (ctx->user_stream) (void)hipStreamSynchronize(ctx->user_stream);
     sfg_phases_resolve(ctx);
     sfg_ptc_detach_all(ctx);           // matrices whose plaintext cache this context owns must not keep a pointer to it (their handles outlive a fork)
@@ -261,8 +203,7 @@ extern "C" void sfg_ctx_destroy(sfg_ctx *ctx) {
     (void)hipFree(ctx->ws); (void)hipFree(ctx->tie_count_dev);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
-    if (ctx->enc_stream) (void)hipStreamDestroy(ctx->enc_stream);
-    for (int i = 0; i < 4; i++) if (ctx->ev_enc[i]) (void)hipEventDestroy(ctx->ev_enc[i]);
+    if (ctx->coll_stream) (void)hipStreamDestroy(ctx->coll_stream);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     for (int i = 0; i < 4; i++) if (ctx->ev_pipe[i]) (void)hipEventDestroy(ctx->ev_pipe[i]);
@@ -295,7 +236,7 @@ int sfg_sync_all(sfg_ctx *ctx) {
     if (ctx->user_stream && ctx->user_stream != ctx->stream) SFG_HIP(ctx, hipStreamSynchronize(ctx->user_stream));
     if (ctx->own_stream && ctx->own_stream != ctx->stream) SFG_HIP(ctx, hipStreamSynchronize(ctx->own_stream));
     if (ctx->aux_stream && ctx->aux_stream != ctx->stream) SFG_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
-    if (ctx->enc_stream && ctx->enc_stream != ctx->stream) SFG_HIP(ctx, hipStreamSynchronize(ctx->enc_stream));
+    if (ctx->coll_stream && ctx->coll_stream != ctx->stream) SFG_HIP(ctx, hipStreamSynchronize(ctx->coll_stream));
     return 0;
 }
 
@@ -394,7 +335,6 @@ int sfg_scratch(sfg_ctx *ctx, const char *name, size_t bytes, void **out) {
                 } else ++it;
             }
             if (freed_rot_copy) { for (int b = 0; b < 2; b++) for (int i = 0; i < sfg_ctx::I8_SLOTS; i++) ctx->i8_slot[b][i] = sfg_ctx::I8Slot(); ctx->i8_gen++; }
-            ctx->sp_shape = -1;
             auto &e2 = ctx->pool[name];
             err = hipMalloc(&e2.first, bytes);
             if (err != hipSuccess) { e2.first = nullptr; e2.second = 0; SFG_FAIL(ctx, "out of device memory: %zu bytes for scratch buffer '%s' (after returning the buffers of earlier calls)", bytes, name); }
@@ -418,7 +358,7 @@ extern "C" int sfg_ctx_release_scratch(sfg_ctx *ctx) {
     for (auto &kv : ctx->host_pool) (void)hipHostFree(kv.second.first);
     ctx->host_pool.clear();
     for (int b = 0; b < 2; b++) for (int i = 0; i < sfg_ctx::I8_SLOTS; i++) ctx->i8_slot[b][i] = sfg_ctx::I8Slot();      // the kept transposed rot copies lived in the pool
-    ctx->i8_gen++; ctx->sp_shape = -1;
+    ctx->i8_gen++;
     return 0;
 }
 // pinned host scratch: a streamed scan reads its file through two slots of one batch each (1 GB at 500 000 samples x 8192 SNPs); pinning them costs ~0.2 s per

@@ -631,11 +631,10 @@ int launch_skew(sfg_ctx *ctx, const int8_t *blk, size_t ld, int r, int c, int tr
 // encode diagonals [shift0, shift0+nshift) of a skewed block D into pt[nshift][L][N]
 // half_rows + G > 0: `pt` is the base of a grouped panel and rows are scattered by PanelMap (half rows only)
 int encode_rows_launches(const sfg_ctx *ctx, int nshift) { const int B = ctx->cfg.enc_batch; return (nshift + B - 1) / B; }
-int launch_encode_rows(sfg_ctx *ctx, const int8_t *D, int shift0, int nshift, int L, u64 *pt, bool half_rows, int G, int g, unsigned packed_mask, const PcCache *pcache, StagePack *sp, PtRide *ride) {
+int launch_encode_rows(sfg_ctx *ctx, const int8_t *D, int shift0, int nshift, int L, u64 *pt, bool half_rows, int G, int g, unsigned packed_mask, const PcCache *pcache, PtRide *ride) {
     EncTables *et = (EncTables *)ctx->enc_tables();
     const size_t lds_bytes = ENC_LDS_BYTES;
-    if (sp && (shift0 % SFG_D || !half_rows || !(packed_mask >> 31))) SFG_FAIL(ctx, "encode: internal: the streamed transposition takes whole giant steps of digit-plane rows");
-    const int BATCH = sp ? ctx->cfg.stage_giants * SFG_D : ctx->cfg.enc_batch;                 // plaintexts per FFT / NTT launch pair (SFG_ENC_BATCH)
+    const int BATCH = ctx->cfg.enc_batch;                 // plaintexts per FFT / NTT launch pair (SFG_ENC_BATCH)
     const int cmode = pcache && pcache->slot && half_rows && G > 0 ? pcache->mode : 0;
     double *pc = nullptr;
     if (!cmode) SFG_TRY(enc_pc_scratch(ctx, (size_t)(nshift < BATCH ? nshift : BATCH), &pc));
@@ -651,21 +650,10 @@ int launch_encode_rows(sfg_ctx *ctx, const int8_t *D, int shift0, int nshift, in
         // the panel NTT is timed on a sample (every 16th launch carries an event pair: 50 000 launches per power iteration) and counted in full
         // (launches that carry mover workgroups of the riding transposition are timed and counted apart: phases ntt_plain_ride / ntt_ride_all, their mover bytes in pt_ride)
         const bool sampled = half_rows && G > 0 && (ctx->ntt_plain_seq++ & 15) == 0;
-        const bool riding = !sp && half_rows && G > 0 && ride && ride->on && ride->next < ride->total();
+        const bool riding = half_rows && G > 0 && ride && ride->on && ride->next < ride->total();
         PhaseTimer tn(ctx, riding ? "ntt_plain_ride" : "ntt_plain", sampled);
         if (half_rows && G > 0) { PhaseStat &all = ctx->phases[riding ? "ntt_ride_all" : "ntt_plain_all"]; all.launches += 1; }
-        if (sp) {
-            // the staging buffer is free once the previous batch has been transposed (that ran beside this batch's FFT)
-            if (sp->pending) SFG_HIP(ctx, hipStreamWaitEvent(ctx->stream, sp->ev_pack, 0));
-            PanelMap pm{0, 0, shift0 + s0, packed_mask};
-            SFG_TRY(launch_ntt_plain_half(ctx, cmode == 3 ? pcache->slot : pc, sp->stage, nb, L, pm, cmode == 3 ? pcache->perm : nullptr));
-            SFG_HIP(ctx, hipEventRecord(sp->ev_ntt, ctx->stream));
-            SFG_HIP(ctx, hipStreamWaitEvent(sp->q, sp->ev_ntt, 0));
-            SFG_TRY(launch_i8_pack_stage(ctx, *sp, shift0 + s0, nb, L));
-            SFG_HIP(ctx, hipEventRecord(sp->ev_pack, sp->q));
-            sp->pending = true;
-        }
-        else if (half_rows && G > 0) {
+        if (half_rows && G > 0) {
             // the riding transposition: this launch's share of the previous MAC launch's panel goes along as mover workgroups (k_ntt_half3_move)
             MoveJob mj; const MoveJob *mv = nullptr; double moved = 0;
             if (ride && ride->on && ride->next < ride->total()) {

@@ -16,7 +16,7 @@ struct I8Args {
     size_t pt_d_stride, pt_cb_stride;      // bytes between the digit planes of a modulus row / between its 128-byte coefficient blocks (N/2 and 128 unless the panel is K-major)
     size_t pt_l0_off;                      // words from a plaintext's start to the row of modulus l0; row of modulus l0 + m is pt_l_stride * m further (compact digit-plane panels: 5 or 6 planes apart)
     int K, R, Ncols, accumulate, r0, l0, nl, plane0, nch, njt, pt_digits;
-    int kb;                                // 0: k is the row of the rot operand; else k' = g * kb + baby with baby < 91 real (streamed plaintext tiles: block rows start on a dword)
+    int kb;                                // always 0 (k is the row of the rot operand): vestigial, left from the removed streamed transposition so that the kernels' code stays as measured
     int8_t *A, *B; u64 *T;
     int fake;                              // A/B build, microbenchmark only (results INVALID): bit 0 = the mover reads 32 KiB contiguous per unit, bit 1 = writes 32 KiB contiguous, bit 2 = sleeps instead of moving
 };
@@ -39,6 +39,37 @@ struct PtRide {
     unsigned total() const { return job.n5 + job.n6; }
     double item_bytes5 = 0, item_bytes6 = 0;      // bytes read + written per item (phase statistics)
 };
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+constexpr int I8_ND = 5;                   // digits per operand word of a 35-bit modulus (the 46-bit one: 6)
+
+// ND signed base-256 digits of an integer |v| < 2^(8 ND - 1) (two's complement arithmetic shift)
+template <int ND> __device__ __forceinline__ void i8_digits(long long v, int8_t d[ND]) {
+#pragma unroll
+    for (int i = 0; i < ND; i++) { const long long lo = ((v + 128) & 255) - 128; d[i] = (int8_t)lo; v = (v - lo) >> 8; }
+}
+// byte offset of element (row-or-column i < 16, kk < 64) inside a 1 KiB operand tile: lane = i + 16 (kk / 16), byte kk % 16
+__device__ __forceinline__ int i8_tile_off(int i, int kk) { return ((i + 16 * (kk >> 4)) << 4) + (kk & 15); }
+
+// sum_s D_s 256^s mod q by Horner on exact integers held in fp64: |r| <= q/2 and |D| < 2^31.  One step x = r 256 + D, r' = x - q rint(x / q) is exact while
+// 128 q + 2^31 < 2^53 (x itself AND the product q rint(x / q) <= 128 q), i.e. for q <= 2^46 - 2^24: PN14QP438's q0 = 0x200000440001 < 2^46 and every 35-bit prime.
+// A modulus in (2^46 - 2^24, 2^47) - accepted by sfg_ctx_create - takes the step as two multiplications by 16 with a reduction in between (8 q + 2^31 < 2^51).
+// `wide` is uniform over the launch's modulus (a scalar branch).
+constexpr double I8_WIDE_Q = 0x1p46 - 0x1p24;
+template <int NS> __device__ __forceinline__ double i8_horner(const v4i (&a)[NS], int e, double q, double qinv, bool wide) {
+    double r = (double)a[NS - 1][e];
+    if (!wide) {
+#pragma unroll
+        for (int s = NS - 2; s >= 0; s--) { const double x = r * 256.0 + (double)a[s][e]; r = x - q * __builtin_rint(x * qinv); }
+    } else {
+#pragma unroll
+        for (int s = NS - 2; s >= 0; s--) {
+            const double x1 = r * 16.0, r1 = x1 - q * __builtin_rint(x1 * qinv);
+            const double x = r1 * 16.0 + (double)a[s][e]; r = x - q * __builtin_rint(x * qinv);
+        }
+    }
+    return r < 0 ? r + q : r;
+}
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 struct I8MoveItem { const unsigned char *src; int8_t *dst; int kq, jt; };
@@ -69,6 +100,15 @@ __device__ __forceinline__ I8MoveLane i8_move_lane(const I8Args &a, int tid) {
     l.voff = (unsigned)l.cq8 * 16u + l.koff + l.joff;
     return l;
 }
+// the A/B build's microbenchmark read patterns (I8Args::fake, results INVALID): bit 0 = 32 KiB contiguous per unit; bit 3 = a panel laid out [column][plane][128-byte
+// coefficient block][k][128 B], the 16 k of a column one 2 KiB run
+template <int ND>
+__device__ __forceinline__ const v4u *i8_move_fake_src(const I8Args &a, const I8MoveLane &l, const I8MoveItem &t, unsigned item, int d, int it, int x) {
+    if (a.fake & 1) return reinterpret_cast<const v4u *>(reinterpret_cast<const unsigned char *>(a.pt) + ((size_t)item * ND + d) * 32768 + (size_t)((it * 4 + x) * 256 + l.wave * 64 + (int)(threadIdx.x & 63)) * 16);
+    const int m = (int)(item / ((unsigned)(a.nch * 4) * (unsigned)(SFG_N / 2 / I8_PD)) / (unsigned)a.njt), cb = (int)(item % (SFG_N / 2 / I8_PD));
+    const size_t pl = (ND == 6 ? 0 : 6 + m * 5) + d, n = (size_t)t.jt * 16 + it * 8 + l.wave * 2 + l.jb, k = (size_t)t.kq * 16 + 4 * l.k4 + x;
+    return reinterpret_cast<const v4u *>(reinterpret_cast<const unsigned char *>(a.pt) + (((n * 26 + pl) * 64 + cb) * ((size_t)a.nch * 64) + k) * 128 + l.cq8 * 16);
+}
 template <int ND, bool NT>
 __device__ __forceinline__ void i8_move_issue(const I8Args &a, const I8MoveLane &l, unsigned item, int d, v4u (&w)[8]) {
     const I8MoveItem t = i8_move_item<ND>(a, item);
@@ -86,12 +126,7 @@ __device__ __forceinline__ void i8_move_issue(const I8Args &a, const I8MoveLane 
             const size_t so = ok ? ((size_t)n0 * a.pt_n_stride + (size_t)k0 * a.pt_k_stride) * 8 : ((size_t)(t.jt * 16) * a.pt_n_stride + (size_t)(t.kq * 16) * a.pt_k_stride) * 8;
             const v4u *p = reinterpret_cast<const v4u *>(src + so + vo);
 #ifdef SFG_AB
-            if (a.fake & 1) p = reinterpret_cast<const v4u *>(reinterpret_cast<const unsigned char *>(a.pt) + ((size_t)item * ND + d) * 32768 + (size_t)((it * 4 + x) * 256 + l.wave * 64 + (int)(threadIdx.x & 63)) * 16);
-            if (a.fake & 8) {      // the read pattern of a panel laid out [column][plane][128-byte coefficient block][k][128 B]: the 16 k of a column are one 2 KiB run
-                const int m = (int)(item / ((unsigned)(a.nch * 4) * (unsigned)(SFG_N / 2 / I8_PD)) / (unsigned)a.njt), cb = (int)(item % (SFG_N / 2 / I8_PD));
-                const size_t pl = (ND == 6 ? 0 : 6 + m * 5) + d, n = (size_t)t.jt * 16 + it * 8 + l.wave * 2 + l.jb, k = (size_t)t.kq * 16 + 4 * l.k4 + x;
-                p = reinterpret_cast<const v4u *>(reinterpret_cast<const unsigned char *>(a.pt) + (((n * 26 + pl) * 64 + cb) * ((size_t)a.nch * 64) + k) * 128 + l.cq8 * 16);
-            }
+            if (a.fake & 9) p = i8_move_fake_src<ND>(a, l, t, item, d, it, x);          // the microbenchmarks' read patterns (ab/ubench.hip)
 #endif
             w[it * 4 + x] = NT ? __builtin_nontemporal_load(p) : *p;
         }

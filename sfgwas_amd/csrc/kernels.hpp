@@ -30,46 +30,34 @@ int launch_ntt_plain_half(sfg_ctx *ctx, const double *pc, u64 *out_half, size_t 
 int launch_expand_half(sfg_ctx *ctx, const u64 *half, u64 *full, size_t nrows);
 int launch_ntt_fwd_map(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat, const RowMap &rm);
 int launch_ntt_inv_map(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat, const RowMap &rm);
-// mac.hip
+// the MAC launches
 struct MacStrides { size_t rot_k, rot_r, pt_k, pt_n, out_n, out_r; bool pt_half = false; bool pt_packed = false; bool pt_digits = false; bool i8 = false; bool i8_big = false; bool pt_digits_big = false;
-                    const int8_t *B_small = nullptr, *B_big = nullptr; int kb = 0;
+                    const int8_t *B_small = nullptr, *B_big = nullptr;
                     int pt_layout = 0, pt_L = 0;  // 1: digit-plane panel rows packed - a plaintext is its pt_L moduli's 5 / 6 planes of N/2 bytes back to back (208 KiB at PN14QP438, L = 5) instead of L rows of N/2 words (320 KiB), PanelMap bit 29; 2: K-major, bits 29 + 28 (mac_i8.hip i8_panel_rows)
-                    int B_mode = 0;       // B_* given and B_mode 0: streamed tiles (k' = g * kb + baby); 1: the pass's layout, already transposed (riding mover): no pass; 2: the pass runs into these buffers
-                    const int8_t *A_small = nullptr, *A_big = nullptr; };   // A_*: the transposed rot tiles of this launch are given (I8RotPre): no copy to look up or make   // B_*: the int8 MAC's plaintext tiles are already in place (streamed transposition, StagePack): no panel, k' = g * kb + baby   // i8: small moduli on the int8 MAC (mac_i8.hip); pt_digits: their panel rows hold five digit planes   // in words; pt_half: pt rows hold N/2 words (mirror-symmetric plaintexts)
+                    int B_mode = 0;       // B_* given (the riding transposition's tile buffers) and B_mode 1: already transposed (riding mover): no pass; 2: the pass runs into these buffers
+                    const int8_t *A_small = nullptr, *A_big = nullptr; };   // A_*: the transposed rot tiles of this launch are given (I8RotPre): no copy to look up or make   // i8: small moduli on the int8 MAC (mac_i8.hip); pt_digits: their panel rows hold five digit planes   // in words; pt_half: pt rows hold N/2 words (mirror-symmetric plaintexts)
 int launch_mac_i8_small(sfg_ctx *ctx, const double *rotf, size_t rotf_k_stride, size_t rotf_r_stride, int plane0, const u64 *pt, u64 *out, int K, int R, int r0, int Ncols,
                         int l0, int nl, int accumulate, const MacStrides &st);       // mac_i8.hip
 int launch_mac_i8_big(sfg_ctx *ctx, const double *rotf, size_t rotf_k_stride, size_t rotf_r_stride, int plane0, const u64 *pt, u64 *out, int K, int R, int r0, int Ncols,
                       int l0, int accumulate, const MacStrides &st);
 size_t mac_i8_stream_bytes(int K, int nl, int ND, int copies_of_rot);
 size_t mac_i8_tile_bytes(int Kp, int nl, int ND);      // plaintext tile buffer of nl moduli with ND digits, K' contraction steps (mac_i8.hip)
-int launch_mac(sfg_ctx *ctx, const u64 *rot, const u64 *pt, u64 *out, int K, int R, int Ncols, int L, int accumulate);
-int launch_mac_strided(sfg_ctx *ctx, const u64 *rot, const u64 *pt, u64 *out, int K, int R, int Ncols, int L, int accumulate, const MacStrides &st);
 // encode.hip
 int launch_skew(sfg_ctx *ctx, const int8_t *blk, size_t ld, int r, int c, int transposed, int square, int8_t *D);
 // pcache (nullable): the block's slot of the plaintext coefficient cache, [8192 shifts][N/2] doubles.  mode 1: the FFT writes its rows there (and the NTT reads them);
 // 2: the rows are there already (no FFT; D unused); 3: they are there in the block's other orientation (no FFT; NTT through the permutation table)
 struct PcCache { double *slot = nullptr; int mode = 0; const uint32_t *perm = nullptr; };
-// Streamed transposition (round 4): the plaintext NTT of a batch writes its digit planes DENSE into one small staging buffer (reused by every batch, so it lives in
-// the Infinity Cache and never reaches HBM) and k_i8_pack_stage moves the batch into the int8 MAC's k-contiguous tiles on a second queue, beside the (fp64-issue
-// bound) FFT of the next batch.  The 21 - 43 GB plaintext panel and its read + write pass per MAC launch disappear.
-struct StagePack {
-    u64 *stage = nullptr;                  // [batch][L][N/2 words]
-    int8_t *Bs = nullptr, *Bb = nullptr;   // tiles of the small moduli [m][c][jt][ch][5][1 KiB] / of the 46-bit modulus [c][jt][ch][6][1 KiB]
-    int g = 0, kb = 92, njt = 6, nch = 0;  // block row inside the MAC group: k' = g * kb + baby
-    int l_big = -1, l_small0 = 0, n_small = 0;
-    hipStream_t q = nullptr; hipEvent_t ev_ntt = nullptr, ev_pack = nullptr; bool pending = false;
-    unsigned seq = 0;
-};
-// plaintexts per batch of the streamed transposition: cfg.stage_giants whole giant steps (default 11: 1001 plaintexts, 5005 NTT workgroups; SFG_STAGE_GIANTS)
-int launch_i8_pack_stage(sfg_ctx *ctx, StagePack &sp, int shift_lo, int nshift, int L);      // mac_i8.hip
 int launch_encode_rows(sfg_ctx *ctx, const int8_t *D, int shift0, int nshift, int L, u64 *pt, bool half_rows = false, int G = 0, int g = 0, unsigned packed_mask = 0, const PcCache *pcache = nullptr,
-                       StagePack *sp = nullptr, PtRide *ride = nullptr);
+                       PtRide *ride = nullptr);
 int encode_rows_launches(const sfg_ctx *ctx, int nshift);          // NTT launches launch_encode_rows makes for nshift diagonals (panel form)
 // mac_i8.hip: the riding transposition of one delayed MAC launch (panel of K = ng * 91 k-rows x 91 columns -> tile buffers mi8.Bs / mi8.Bb); ride.on stays false where the
 // moduli are not one run of 35-bit ones plus at most one 46-bit one
 int i8_ride_prepare(sfg_ctx *ctx, const u64 *panel, int K, int Ncols, size_t pt_k, size_t pt_n, int layout, int L, int launches, PtRide &ride);
 int i8_ride_finish(sfg_ctx *ctx, PtRide &ride);                     // items no NTT launch took: a launch of mover workgroups alone on the current stream
 int i8_ride_tiles(sfg_ctx *ctx, int K, int L, int8_t **Bs, int8_t **Bb);          // the two tile buffers (a launch that transposes by the pass uses them as well: B_mode 2)
+struct I8Args;                                                      // i8_move.hpp
+void launch_i8_pack_pt_digits(hipStream_t q, const I8Args &a, unsigned items, bool big);      // the transposition pass of digit-plane panel rows
+void launch_move_alone(hipStream_t q, const MoveJob &j);           // the same by mover workgroups alone on queue q
 // genoio.hip: dense int8 copy [nr][ld_out] of the stored sub-block (r0.., c0..) of a 2-bit packed matrix (c0 a multiple of 4)
 int launch_geno_unpack(sfg_ctx *ctx, const sfg_geno *g, size_t r0, size_t c0, size_t nr, size_t nc, int8_t *out, size_t ld_out);
 // rotate.hip

@@ -5,7 +5,7 @@
 // same canonical sums are produced block by block:
 //   for every block row bi of the operand:   rotCache[bi] = { RotateRight(A[i][bi], -baby) }      (rotate.hip)
 //   for every 8192x8192 block (bi, j):        P = encode(all 8192 diagonals of the block)           (encode.hip, ntt.hip)
-//                                             acc[j][giant][i] += sum_baby rotCache[bi][baby][i] * P[giant*d + baby]   (mac.hip)
+//                                             acc[j][giant][i] += sum_baby rotCache[bi][baby][i] * P[giant*d + baby]   (mac_i8.hip, mac_bc.hip)
 //   finalize:  out[i][j] = sum_giant RotateRight(acc[j][giant][i], -giant*d)                       (rotate.hip)
 // acc holds canonical residues (8 B per coefficient instead of the reference's 16 B lazy u128), and only for the
 // block columns of the current group, so 100k x 1M fits one GPU's HBM.  The genotype matrix is kept once in HBM
@@ -441,16 +441,14 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
                     const int G2 = std::min(cand, b1 - b0);
                     if (G2 <= G) break;
                     const bool pipe2 = !rotf_pre && b1 - b0 > G2 && !ctx->cfg.no_overlap;
-                    const bool enc2 = !ctx->cfg.no_overlap && !ctx->cfg.no_enc_overlap && (size_t)((b1 - b0 + G2 - 1) / G2) * (j1 - j0) >= 2;
-                    const bool streamable2 = ctx->cfg.mac_i8 && ctx->cfg.mac_i8_big && ctx->cfg.mac_i8_ring && ctx->cfg.stage_pack && !enc2;      // then the panel holds 4 block rows
-                    const bool ride2 = ctx->cfg.mac_i8 && ctx->cfg.pt_ride > 0 && !enc2 && !streamable2 && (j1 - j0 >= 2 || (pre8 && b1 - b0 > G2));      // (the riding transposition keeps two panels too)
+                    const bool ride2 = ctx->cfg.mac_i8 && ctx->cfg.pt_ride > 0 && (j1 - j0 >= 2 || (pre8 && b1 - b0 > G2));      // (the riding transposition keeps two panels)
                     size_t ptb = (size_t)L * ((size_t)N / 2) * 8;                    // bytes per plaintext: compact rows where every modulus is on the int8 MAC (as decided below)
-                    if (ctx->cfg.pt_compact && ctx->cfg.mac_i8 && !streamable2 && mac_dma_packed_mask(ctx, L)) {
+                    if (ctx->cfg.pt_compact && ctx->cfg.mac_i8 && mac_dma_packed_mask(ctx, L)) {
                         bool big_ok = true; size_t planes = 0;
                         for (int l = 0; l < L; l++) { const bool sm = ctx->q[l] < (1ULL << 36); planes += sm ? 5 : 6; if (!sm && !ctx->cfg.mac_i8_big) big_ok = false; }
                         if (big_ok && ((b1 - b0 + G2 - 1) / G2 <= 2 || j1 - j0 >= 4)) ptb = planes * ((size_t)N / 2);
                     }
-                    size_t need = (size_t)(streamable2 ? std::min(G2, 4) : G2) * nplain * ptb * (enc2 || ride2 ? 2 : 1);
+                    size_t need = (size_t)G2 * nplain * ptb * (ride2 ? 2 : 1);
                     if (!rotf_pre) need += ((size_t)G2 * d + 3) * s * 2 * (size_t)npl * N * 8 * (pipe2 ? 2 : 1);
                     if (ctx->cfg.mac_i8) {                         // + the two operand streams and the tile-ordered results of the int8 MAC (small moduli)
                         int nsm = 0; for (int l = 0; l < L; l++) nsm += ctx->q[l] < (1ULL << 36);
@@ -474,7 +472,7 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
         const size_t per = mac_i8_stream_bytes(G * d, nsm, 5, 1) - mac_i8_stream_bytes(G * d, nsm, 5, 0), ngr = (size_t)(b1 - b0 + G - 1) / G;
         size_t fr = 0, tot = 0, held = 0;
         for (const auto &kv : ctx->pool) if (kv.first.rfind("mi8.A", 0) == 0) held += kv.second.second;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess) keep_all = fr + held >= ngr * per + mac_i8_stream_bytes(G * d, nsm, 5, 0) + ctx->cfg.i8_keep_reserve;     // (the panel, accumulators and key-switch scratch of the call are still to be allocated the first time)
+        if (hipMemGetInfo(&fr, &tot) == hipSuccess) keep_all = fr + held >= ngr * per + mac_i8_stream_bytes(G * d, nsm, 5, 0) + SFG_I8_KEEP_RESERVE;     // (the panel, accumulators and key-switch scratch of the call are still to be allocated the first time)
     }
     const bool use_i8 = pre8 || (dma && ctx->cfg.mac_i8 && packed_mask && ((b1 - b0 + G - 1) / G <= 2 || j1 - j0 >= 4 || keep_all));
     const bool use_i8_big = pre8 || (use_i8 && ctx->cfg.mac_i8_big);                    // the 46-bit modulus too: six digit planes, its own pair of transposed rot copies
@@ -482,36 +480,31 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
     const bool pipelined = dma && !rot_ext && b1 - b0 > G && !ctx->cfg.no_overlap;
     SFG_TRY(sfg_scratch(ctx, "mm.a_row", (size_t)s * ctw * 8, (void **)&a_row));
     SFG_TRY(sfg_scratch(ctx, "mm.rotc", dma ? 8 : (size_t)d * s * ctw * 8, (void **)&rotc));     // u64 rotation cache: only the register-staged MAC reads one
-    // Two plaintext panels when the encode of launch k + 1 runs on its own queue beside the transposition + MAC of launch k (fp64-issue bound beside HBM bound)
-    const bool enc_ov = dma && !ctx->cfg.no_overlap && !ctx->cfg.no_enc_overlap && (size_t)((b1 - b0 + G - 1) / G) * (j1 - j0) >= 2;
-    // where every modulus multiplies on the int8 matrix core from streamed tiles, the panel serves only the rare launches that cannot stream: Gp block rows of it
-    const bool streamable = use_i8 && use_i8_big && ctx->cfg.mac_i8_ring && ctx->cfg.stage_pack && !enc_ov && !pre8;
-    const int Gp = streamable ? std::min(G, 4) : G;
     // Compact panel rows (round 6): where every modulus of the product multiplies on the int8 matrix core the panel holds nothing but digit planes - five (six) planes of
     // N/2 bytes per modulus, back to back: 208 KiB per plaintext at L = 5 instead of five rows of N/2 words (320 KiB).  Room for the second panel of the riding transposition.
     bool all_small = true; for (int l = 0; l < L; l++) if (ctx->q[l] >= (1ULL << 36)) all_small = false;
-    const bool compact = ctx->cfg.pt_compact && dma && use_i8 && (use_i8_big || all_small) && !streamable;
+    const bool compact = ctx->cfg.pt_compact && dma && use_i8 && (use_i8_big || all_small);
     size_t plw = (size_t)L * prow;                           // words per plaintext
     int pt_planes = 0;
     if (compact) { for (int l = 0; l < L; l++) pt_planes += ctx->q[l] < (1ULL << 36) ? 5 : 6; plw = (size_t)pt_planes * ((size_t)N / 2) / 8; }
     // K-major panel (round 6): the compact panel's bytes ordered [column][plane][128-byte coefficient block][k][128 B], so that the 16 k of a transposition unit's
-    // column are one 2 KiB run (the NTT's stores are 128-byte runs either way).  Whole-group launches only (a sub-launch would change K between encode and MAC).
-    const bool kmajor = compact && ctx->cfg.pt_kmajor && Gp == G && (size_t)G * d * 128 * 64 * 32 < (1ULL << 31);
+    // column are one 2 KiB run (the NTT's stores are 128-byte runs either way).
+    const bool kmajor = compact && ctx->cfg.pt_kmajor && (size_t)G * d * 128 * 64 * 32 < (1ULL << 31);
     const int pt_layout = kmajor ? 2 : compact ? 1 : 0;
-    const size_t panel_words = (size_t)Gp * nplain * plw;
+    const size_t panel_words = (size_t)G * nplain * plw;
     // The riding transposition (kernels.hpp PtRide): the panel of MAC launch k - 1 is transposed by mover workgroups inside the plaintext-NTT launches of launch k's
     // encode, which writes the OTHER panel; MAC launch k - 1 follows that encode on the same queue and finds its tiles in place.  Taken where every modulus multiplies
     // on the int8 matrix core from digit-plane panels; the first launch after a change of block-row group (its rot operand's buffer is about to be rebuilt) and the
     // call's last launch transpose by the pass as before.
     // (a launch rides in the encode of the NEXT block column of its group - or of the next group's first column where the rot tiles of every group are the caller's,
     //  I8RotPre: nothing is rebuilt between groups then, so the multi-GPU engine's one-column calls over several groups ride as well)
-    bool ride_want = use_i8 && !streamable && !enc_ov && ctx->cfg.pt_ride > 0 && (j1 - j0 >= 2 || (pre8 && b1 - b0 > G)) &&
+    bool ride_want = use_i8 && ctx->cfg.pt_ride > 0 && (j1 - j0 >= 2 || (pre8 && b1 - b0 > G)) &&
                      (use_i8_big || [&] { for (int l = 0; l < L; l++) if (ctx->q[l] >= (1ULL << 36)) return false; return true; }());
     // (+ 64 KiB: the transposition walks whole chunks of 64 k, and in the K-major panel the rows K .. K + 63 of the last column's last coefficient block - read, then
     //  masked - lie up to 8 KiB past the panel)
     // A caller's group size (SFG_MM_GROUP, sfg_config.mm_group) may leave room for one panel only: the product then transposes by the pass, as before round 6
     if (ride_want && sfg_scratch(ctx, "mm.pt", panel_words * 8 * 2 + 65536, (void **)&pt)) { ctx->err.clear(); ride_want = false; }
-    if (!ride_want) SFG_TRY(sfg_scratch(ctx, "mm.pt", panel_words * 8 * (enc_ov ? 2 : 1) + 65536, (void **)&pt));
+    if (!ride_want) SFG_TRY(sfg_scratch(ctx, "mm.pt", panel_words * 8 + 65536, (void **)&pt));
     u64 *const pt_base = pt;
     SFG_TRY(sfg_scratch(ctx, "mm.skew", (size_t)SFG_SLOTS * SFG_SLOTS, (void **)&skew));
     int8_t *unpacked = nullptr;
@@ -546,27 +539,28 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
     }
     int gi = 0, it = 0;
     // a MAC launch: the plaintext panel `ptp` of `gsn` block rows against the group's rot operand, into block column accumulator `accj`
-    struct MacJob { bool on = false; u64 *ptp = nullptr; int gsn = 0, sub0 = 0, gi = 0, acc_flag = 0; u64 *accj = nullptr; const double *rotf_grp = nullptr, *rotsum_grp = nullptr; StagePack *sp = nullptr; };
+    struct MacJob { bool on = false; u64 *ptp = nullptr; int gsn = 0, gi = 0, acc_flag = 0; u64 *accj = nullptr; const double *rotf_grp = nullptr, *rotsum_grp = nullptr; };
     int8_t *rideBs = nullptr, *rideBb = nullptr;               // the riding launches' tile buffers (a launch of the same call that transposes by the pass uses them too)
     auto run_mac = [&](const MacJob &m, int B_mode) -> int {
         PhaseTimer t(ctx, "mac");
         MacStrides st;
-        if (m.sp) { st.B_small = m.sp->Bs; st.B_big = m.sp->Bb; st.kb = m.sp->kb; }
-        else if (rideBs) { st.B_small = rideBs; st.B_big = rideBb; st.B_mode = B_mode; }
+        if (rideBs) { st.B_small = rideBs; st.B_big = rideBb; st.B_mode = B_mode; }
         if (pre8) { st.A_small = pre8->As[m.gi]; st.A_big = pre8->Ab[m.gi]; }
         st.rot_k = (size_t)s * ctw; st.rot_r = (size_t)nl * N;          // rotc[baby][i][poly][nl][N]: row r = i*2+poly
         st.pt_k = plw; st.pt_n = (size_t)m.gsn * d * plw; st.pt_half = dma; st.pt_packed = packed_mask != 0; st.pt_digits = st.i8 = use_i8; st.i8_big = st.pt_digits_big = use_i8_big;   // pt[giant][g][baby]: k = g*91 + baby
         st.pt_layout = pt_layout; st.pt_L = L;
         st.out_n = accw; st.out_r = (size_t)L * N;                      // acc[j][giant][r]
         int r2;
-        if (dma) r2 = launch_mac_dma(ctx, pre8 ? nullptr : m.rotf_grp + (size_t)m.sub0 * d * s * 2 * rowf, (size_t)s * 2, m.ptp, m.accj, m.gsn * d, 2 * s, d, L, m.acc_flag, st, m.rotsum_grp);
-        else r2 = launch_mac_strided(ctx, rotc, m.ptp, m.accj, d, 2 * s, d, L, m.acc_flag, st);
+        if (dma) r2 = launch_mac_dma(ctx, pre8 ? nullptr : m.rotf_grp, (size_t)s * 2, m.ptp, m.accj, m.gsn * d, 2 * s, d, L, m.acc_flag, st, m.rotsum_grp);
+#ifdef SFG_AB
+        else r2 = launch_mac_strided(ctx, rotc, m.ptp, m.accj, d, 2 * s, d, L, m.acc_flag, st);      // ab/mac_reg.hip
+#else
+        else { r2 = 1; ctx->err = "matmul: the register-staged MAC exists in the A/B build only (make ab)"; }
+#endif
         t.stop(1);
         return r2;
     };
     MacJob held;                                               // the delayed MAC launch whose panel the next encode's NTT launches transpose
-    struct StreamRestore { sfg_ctx *c; hipStream_t s; ~StreamRestore() { c->stream = s; } } restore_main{ctx, main_stream};       // whatever path leaves the loop
-    if (enc_ov) SFG_TRY(sfg_stream_after(ctx, ctx->enc_stream, main_stream));      // the genotypes, the cache slots and whatever the caller enqueued before
     for (int bg = b0; bg < b1 && !rc; bg += G, gi++) {
         const int ng = std::min(G, b1 - bg);
         // (the delayed launch of the previous group reads a rot operand buffer that is rebuilt below: it goes first, transposing by the pass - unless the rot tiles
@@ -591,62 +585,22 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
         }
         for (int bj = j0; bj < j1 && !rc; bj++, it++) {
             const int nc = sh.cols_of(bj);
-            // Streamed transposition (StagePack, kernels.hpp): when every block of this launch has all 8192 diagonals and every modulus multiplies on the int8
-            // matrix core, the NTT's digit planes go batch by batch through a cache-resident staging buffer into the MAC's tiles - no panel, no transposition pass
-            bool stream = streamable;
-            for (int g = 0; g < ng && stream; g++) stream = sh.rows_of(bg + g) + nc > SFG_SLOTS;
-            StagePack sp;
-            if (stream) {
-                std::vector<int> po, ib; (void)mac_dma_planes(ctx, L, po, ib);
-                int nbig = 0; sp.l_big = -1; sp.l_small0 = -1; sp.n_small = 0;
-                for (int l = 0; l < L; l++) { if (ib[l]) { nbig++; sp.l_big = l; } else { if (sp.l_small0 < 0) sp.l_small0 = l; sp.n_small++; } }
-                bool contiguous = nbig <= 1;
-                for (int l = 0; l < L && contiguous; l++) if (!ib[l] && (l < sp.l_small0 || l >= sp.l_small0 + sp.n_small)) contiguous = false;
-                if (!contiguous || !sp.n_small) stream = false;
-            }
-            if (stream) {
-                sp.kb = 92; sp.njt = 6; sp.nch = (ng * sp.kb + 63) / 64; sp.q = ctx->cfg.stage_same_queue ? ctx->stream : ctx->enc_stream; sp.ev_ntt = ctx->ev_enc[0]; sp.ev_pack = ctx->ev_enc[1];
-                const size_t nBs = mac_i8_tile_bytes(ng * sp.kb, sp.n_small, 5), nBb = sp.l_big >= 0 ? mac_i8_tile_bytes(ng * sp.kb, 1, 6) : 0;
-                const size_t had_s = ctx->pool.count("mi8.Bs") ? ctx->pool["mi8.Bs"].second : 0, had_b = ctx->pool.count("mi8.Bb") ? ctx->pool["mi8.Bb"].second : 0;
-                rc = sfg_scratch(ctx, "mi8.Bs", nBs, (void **)&sp.Bs); if (rc) break;
-                if (nBb) { rc = sfg_scratch(ctx, "mi8.Bb", nBb, (void **)&sp.Bb); if (rc) break; }
-                rc = sfg_scratch(ctx, "mi8.stage", (size_t)ctx->cfg.stage_giants * SFG_D * L * (N / 2) * 8, (void **)&sp.stage); if (rc) break;
-                // what no batch owns (columns 91..95, k' past the group's last block row) must read as zero: cleared when the buffers are new or the group shape changes
-                if (had_s < nBs || had_b < nBb || ctx->sp_shape != ng) {
-                    SFG_HIP(ctx, hipMemsetAsync(sp.Bs, 0, nBs, ctx->stream));
-                    if (nBb) SFG_HIP(ctx, hipMemsetAsync(sp.Bb, 0, nBb, ctx->stream));
-                    ctx->sp_shape = ng;
+            pt = pt_base + (size_t)(ride_want ? (it & 1) : 0) * panel_words;
+            // riding: this launch's encode carries the held launch's transposition; its own MAC is held in turn
+            PtRide ride;
+            if (ride_want && !rideBs) { rc = i8_ride_tiles(ctx, G * d, L, &rideBs, &rideBb); if (rc) break; }
+            if (held.on && ride_want && rideBs) {
+                int launches = 0;
+                for (int g = 0; g < ng; g++) {
+                    const int nr = sh.rows_of(bg + g);
+                    if (nr + nc > SFG_SLOTS) launches += encode_rows_launches(ctx, SFG_SLOTS);
+                    else launches += encode_rows_launches(ctx, nr) + (nc > 1 ? encode_rows_launches(ctx, nc - 1) : 0);
                 }
-                // the transposition queue starts behind everything this queue has done (the previous MAC launch read the tiles, the memsets above)
-                rc = sfg_stream_after(ctx, sp.q, ctx->stream); if (rc) break;
+                rc = i8_ride_prepare(ctx, held.ptp, held.gsn * d, d, plw, (size_t)held.gsn * d * plw, pt_layout, L, launches, ride); if (rc) break;
+                if (ride.on && (ride.job.a5.B != rideBs || (ride.job.n6 && ride.job.a6.B != rideBb))) { rc = 1; ctx->err = "matmul: internal: the riding transposition's tile buffers moved"; break; }
             }
-            const int pbuf = enc_ov || ride_want ? (it & 1) : 0;
-            pt = pt_base + (size_t)pbuf * panel_words;
-            if (enc_ov) {                                  // encode on its queue: after the MAC that last read this panel buffer
-                if (it >= 2) SFG_HIP(ctx, hipStreamWaitEvent(ctx->enc_stream, ctx->ev_enc[2 + pbuf], 0));
-                ctx->stream = ctx->enc_stream;
-            }
-          // A launch that cannot stream (a block with fewer than 8192 diagonals: the corner of a ragged matrix) goes through the plaintext panel.  Where streaming
-          // is the rule the panel holds only Gp block rows, and such a launch is multiplied in sub-launches of Gp rows that accumulate onto each other.
-          const int step = stream ? ng : std::min(ng, Gp);
-          // riding: this launch's encode carries the held launch's transposition; its own MAC is held in turn (whole-group launches only)
-          const bool ride_this = ride_want && !stream && step == ng;
-          PtRide ride;
-          if (ride_this && !rideBs) { rc = i8_ride_tiles(ctx, G * d, L, &rideBs, &rideBb); if (rc) break; }
-          if (held.on && ride_this && rideBs) {
-              int launches = 0;
-              for (int g = 0; g < ng; g++) {
-                  const int nr = sh.rows_of(bg + g);
-                  if (nr + nc > SFG_SLOTS) launches += encode_rows_launches(ctx, SFG_SLOTS);
-                  else launches += encode_rows_launches(ctx, nr) + (nc > 1 ? encode_rows_launches(ctx, nc - 1) : 0);
-              }
-              rc = i8_ride_prepare(ctx, held.ptp, held.gsn * d, d, plw, (size_t)held.gsn * d * plw, pt_layout, L, launches, ride); if (rc) break;
-              if (ride.on && (ride.job.a5.B != rideBs || (ride.job.n6 && ride.job.a6.B != rideBb))) { rc = 1; ctx->err = "matmul: internal: the riding transposition's tile buffers moved"; break; }
-          }
-          if (held.on && !ride.on) { rc = run_mac(held, rideBs ? 2 : 0); held.on = false; if (rc) break; }       // nothing to ride in: the held launch goes now, by the pass
-          for (int sub0 = 0; sub0 < ng && !rc; sub0 += step) {
-            const int gs = std::min(step, ng - sub0);
-            for (int g = sub0; g < sub0 + gs && !rc; g++) {
+            if (held.on && !ride.on) { rc = run_mac(held, rideBs ? 2 : 0); held.on = false; if (rc) break; }       // nothing to ride in: the held launch goes now, by the pass
+            for (int g = 0; g < ng && !rc; g++) {
                 const int bi = bg + g, nr = sh.rows_of(bi);
                 // plaintext coefficient cache of the stored block (sfg_geno_set_plaintext_cache)
                 PcCache pcc; uint64_t ptc_key = 0; bool ptc_new = false;
@@ -680,47 +634,37 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
                 else { runs[0][0] = 0; runs[0][1] = nr; runs[1][0] = SFG_SLOTS - nc + 1; runs[1][1] = SFG_SLOTS; nruns = runs[1][0] < runs[1][1] ? 2 : 1; }
                 const bool full = nruns == 1 && runs[0][1] - runs[0][0] == SFG_SLOTS;
                 // zero what the encoder will not write: plaintext slot of (giant, g, baby) is ((giant*ng + g)*91 + baby)
-                if (stream) {      // (the tiles' unowned positions are zero already, owned ones without a plaintext are written as zeros)
-                } else if (kmajor) {      // (K-major panel: rows of block row g in column 90 past shift 8191, or in every column)
-                    const int kb0 = (g - sub0) * d;
-                    if (full) rc = launch_pt_zero_kmajor(ctx, pt, gs * d, pt_planes, d - 1, d, kb0 + (SFG_SLOTS - (d - 1) * d), kb0 + d);
-                    else rc = launch_pt_zero_kmajor(ctx, pt, gs * d, pt_planes, 0, d, kb0, kb0 + d);
+                if (kmajor) {      // (K-major panel: rows of block row g in column 90 past shift 8191, or in every column)
+                    const int kb0 = g * d;
+                    if (full) rc = launch_pt_zero_kmajor(ctx, pt, ng * d, pt_planes, d - 1, d, kb0 + (SFG_SLOTS - (d - 1) * d), kb0 + d);
+                    else rc = launch_pt_zero_kmajor(ctx, pt, ng * d, pt_planes, 0, d, kb0, kb0 + d);
                 } else if (full) {        // only the 89 slots past shift 8191 (giant 90, baby 2..90)
-                    rc = launch_pt_zero(ctx, pt + (((size_t)(d - 1) * gs + (g - sub0)) * d + (SFG_SLOTS - (d - 1) * d)) * plw, 0, (nplain - SFG_SLOTS) * plw, 1, L, prow, packed_mask);
+                    rc = launch_pt_zero(ctx, pt + (((size_t)(d - 1) * ng + g) * d + (SFG_SLOTS - (d - 1) * d)) * plw, 0, (nplain - SFG_SLOTS) * plw, 1, L, prow, packed_mask);
                 } else {           // ragged block: all 91 x 91 slots of this block row
-                    rc = launch_pt_zero(ctx, pt + (size_t)(g - sub0) * d * plw, (size_t)gs * d * plw, (size_t)d * plw, d, L, prow, packed_mask);
+                    rc = launch_pt_zero(ctx, pt + (size_t)g * d * plw, (size_t)ng * d * plw, (size_t)d * plw, d, L, prow, packed_mask);
                 }
                 if (rc) { ptc_undo(); break; }
                 {
                     PhaseTimer t(ctx, "encode");
                     for (int r = 0; r < nruns && !rc; r++) {
-                        if (stream) sp.g = g;
-                        if (dma) rc = launch_encode_rows(ctx, skew, runs[r][0], runs[r][1] - runs[r][0], L, pt, true, gs, g - sub0, packed_mask | (use_i8 ? 0x80000000u : 0u) | (use_i8_big ? 0x40000000u : 0u) | (compact ? PT_COMPACT : 0u) | (kmajor ? PT_KMAJOR : 0u),
-                                                         pcc.mode ? &pcc : nullptr, stream ? &sp : nullptr, ride.on ? &ride : nullptr);
+                        if (dma) rc = launch_encode_rows(ctx, skew, runs[r][0], runs[r][1] - runs[r][0], L, pt, true, ng, g, packed_mask | (use_i8 ? 0x80000000u : 0u) | (use_i8_big ? 0x40000000u : 0u) | (compact ? PT_COMPACT : 0u) | (kmajor ? PT_KMAJOR : 0u),
+                                                         pcc.mode ? &pcc : nullptr, ride.on ? &ride : nullptr);
                         else rc = launch_encode_rows(ctx, skew, runs[r][0], runs[r][1] - runs[r][0], L, pt + (size_t)runs[r][0] * plw, false);
                     }
                     t.stop(nruns);
                 }
                 if (rc) ptc_undo();
             }
-            if (enc_ov) {
-                ctx->stream = main_stream;
-                if (!rc) { SFG_HIP(ctx, hipEventRecord(ctx->ev_enc[pbuf], ctx->enc_stream)); SFG_HIP(ctx, hipStreamWaitEvent(main_stream, ctx->ev_enc[pbuf], 0)); }
-            }
             if (rc) break;
-            if (!stream && streamable) ctx->sp_shape = -1;       // (this launch transposes through the tile buffers the streamed launches keep partly cleared)
-            if (stream && sp.pending) SFG_HIP(ctx, hipStreamWaitEvent(ctx->stream, sp.ev_pack, 0));       // the last batch is in the tiles
             // the held launch: whatever of its transposition no NTT launch of this encode took, then its MAC on the tiles
             if (held.on) { rc = i8_ride_finish(ctx, ride); if (!rc) rc = run_mac(held, 1); held.on = false; if (rc) break; }
             {
-                MacJob m; m.on = true; m.ptp = pt; m.gsn = gs; m.sub0 = sub0; m.gi = gi; m.sp = stream ? &sp : nullptr;
-                m.acc_flag = (accumulate || !first_group || sub0 > 0) ? 1 : 0;      // the first (sub-)launch of a fresh call overwrites
+                MacJob m; m.on = true; m.ptp = pt; m.gsn = ng; m.gi = gi;
+                m.acc_flag = (accumulate || !first_group) ? 1 : 0;      // the first launch of a fresh call overwrites
                 m.accj = acc + (size_t)(bj - j0) * acc_col; m.rotf_grp = rotf_grp; m.rotsum_grp = rotsum_grp;
-                if (ride_this && rideBs) held = m;                                 // multiplied after the next launch's encode has transposed this panel
+                if (ride_want && rideBs) held = m;                                 // multiplied after the next launch's encode has transposed this panel
                 else rc = run_mac(m, rideBs ? 2 : 0);
             }
-          }
-            if (enc_ov && !rc) SFG_HIP(ctx, hipEventRecord(ctx->ev_enc[2 + pbuf], main_stream));
         }
         first_group = false;
     }
@@ -981,7 +925,7 @@ int i8_rotpre_build(sfg_ctx *ctx, const u64 *A, int s, int in_level, int max_lev
     pre = I8RotPre();
     const int d = SFG_D, L = max_level;
     const auto &c = ctx->cfg;
-    if (!c.assoc_i8 || !mac_use_dma(ctx) || !c.mac_bc || c.mac_plain_pt || !c.mac_i8 || !c.mac_i8_big || 2 * s > 30 || L < 1 || L > ctx->nq || nbr < 1) return 0;
+    if (!mac_use_dma(ctx) || !c.mac_bc || c.mac_plain_pt || !c.mac_i8 || !c.mac_i8_big || 2 * s > 30 || L < 1 || L > ctx->nq || nbr < 1) return 0;
     if (!mac_dma_packed_mask(ctx, L)) return 0;
     std::vector<int> plane_of, is_big; const int nplanes = mac_dma_planes(ctx, L, plane_of, is_big);
     if (nplanes < 0) { ctx->err.clear(); return 0; }

@@ -62,9 +62,7 @@ struct MgRank {
     sfg_ctx *ctx = nullptr;
     int rank = 0, device = 0;
     ncclComm_t comm = nullptr;
-    hipStream_t coll = nullptr;             // the collectives' queue (RCCL kernels beside the MAC of the next column)
-    bool own_coll = false;                  // coll was created by the engine (else it is the context's encode queue)
-    hipStream_t spare = nullptr;            // SFG_MGPU_COLL_QUEUE=spare (diagnostics)
+    hipStream_t coll = nullptr;             // the collectives' queue (RCCL kernels beside the MAC of the next column): the context's third queue, coll_stream
     hipEvent_t ev_acc[2] = {nullptr, nullptr}, ev_rs[2] = {nullptr, nullptr}, ev_c = nullptr;
     uint64_t *status_dev = nullptr, *status_host = nullptr;      // the agreement word of a call (coll_agree): made with the rank, so that agreeing never allocates
     std::string err;
@@ -119,15 +117,10 @@ struct sfg_mgeno {
 thread_local std::string g_mgpu_create_error;
 #define MG_FAIL(mg, ...) do { char _b[640]; snprintf(_b, sizeof _b, __VA_ARGS__); (mg)->err = _b; return 1; } while (0)
 #define R_FAIL(R, ...) do { char _b[640]; snprintf(_b, sizeof _b, __VA_ARGS__); (R).err = _b; return 1; } while (0)
-#ifdef SFG_AB
-#define R_HIP(R, call) do { hipError_t _e = (call); if (_e != hipSuccess) R_FAIL(R, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); } while (0)
-#define R_CTX(R, call) do { if ((call)) { (R).err = std::string(#call).substr(0, std::string(#call).find('(')) + ": " + (R).ctx->err; return 1; } } while (0)
-#define R_NCCL(R, call) do { ncclResult_t _e = (call); if (_e != ncclSuccess) R_FAIL(R, "%s failed: %s", #call, g_rccl.GetErrorString(_e)); } while (0)
-#else         // (the product's binary carries no expression text: file and line, and the context's own message)
+// (the binary carries no expression text: file and line, and the context's own message)
 #define R_HIP(R, call) do { hipError_t _e = (call); if (_e != hipSuccess) R_FAIL(R, "HIP call failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); } while (0)
 #define R_CTX(R, call) do { if ((call)) { (R).err = "mgpu.hip:" + std::to_string(__LINE__) + ": " + (R).ctx->err; return 1; } } while (0)
 #define R_NCCL(R, call) do { ncclResult_t _e = (call); if (_e != ncclSuccess) R_FAIL(R, "RCCL call failed: %s (mgpu.hip:%d)", g_rccl.GetErrorString(_e), __LINE__); } while (0)
-#endif
 
 // one host thread per local rank (the library's rule: one thread drives a context at a time); first failure wins
 template <class F> static int run_ranks(sfg_mgpu *mg, F &&fn) {
@@ -174,21 +167,11 @@ static void mgpu_read_config(sfg_mgpu *mg, const sfg_config *pc) {
 }
 static const char *rank_exec_init(MgRank &R) {
     if (hipSetDevice(R.device) != hipSuccess) return "hipSetDevice failed";
-    // The collectives' queue is the context's encode queue (idle unless SFG_MM_ENC_OVERLAP=1 - then the engine makes its own).  Not a fourth queue by default: measured
-    // (tools/r5_order.sh, tools/r5_collq.sh, profiles/r05_mgpu_queue_count.txt), with a fourth library stream IN USE and the product on the context's own queue every
-    // kernel of the step starts 15 - 30 us later (a rank's step 1.65 s against 1.46 s); a stream that only exists costs nothing, and with GPU_MAX_HW_QUEUES <= 3, or with
-    // the product on a stream the caller made, the effect vanishes - it depends on which hardware queues the runtime hands the streams.
-#ifdef SFG_AB
-    const char *cq = getenv("SFG_MGPU_COLL_QUEUE");       // diagnostics (tools/r5_collq.sh): "own" = a queue of the engine's whatever the schedule, "spare" = made but not used
-    const bool own = cq && !strcmp(cq, "own"), spare = cq && !strcmp(cq, "spare");
-#else
-    const bool own = false, spare = false;
-#endif
-    const bool enc_busy = R.ctx->cfg.stage_pack && !R.ctx->cfg.stage_same_queue;      // (A/B build: the streamed transposition runs on the encode queue whatever the overlap switches say)
-    if (!own && !enc_busy && (spare || R.ctx->cfg.no_enc_overlap || R.ctx->cfg.no_overlap)) {
-        if (spare && hipStreamCreateWithFlags(&R.spare, hipStreamNonBlocking) != hipSuccess) return "hipStreamCreate failed";
-        R.coll = R.ctx->enc_stream; R.own_coll = false;
-    } else { if (hipStreamCreateWithFlags(&R.coll, hipStreamNonBlocking) != hipSuccess) return "hipStreamCreate failed"; R.own_coll = true; }
+    // The collectives' queue is the context's third queue, which nothing else uses.  Not a fourth queue: measured (profiles/r05_mgpu_queue_count.txt), with a fourth
+    // library stream IN USE and the product on the context's own queue every kernel of the step starts 15 - 30 us later (a rank's step 1.65 s against 1.46 s); a stream
+    // that only exists costs nothing, and with GPU_MAX_HW_QUEUES <= 3, or with the product on a stream the caller made, the effect vanishes - it depends on which
+    // hardware queues the runtime hands the streams.
+    R.coll = R.ctx->coll_stream;
     for (int i = 0; i < 2; i++) if (hipEventCreateWithFlags(&R.ev_acc[i], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&R.ev_rs[i], hipEventDisableTiming) != hipSuccess) return "hipEventCreate failed";
     if (hipEventCreateWithFlags(&R.ev_c, hipEventDisableTiming) != hipSuccess) return "hipEventCreate failed";
     if (hipMalloc((void **)&R.status_dev, 64) != hipSuccess || hipHostMalloc((void **)&R.status_host, 64, hipHostMallocDefault) != hipSuccess) return "status word allocation failed";
@@ -207,8 +190,6 @@ extern "C" void sfg_mgpu_destroy(sfg_mgpu *mg) {
     for (auto &R : mg->r) {
         if (!R.ctx) continue;
         (void)hipSetDevice(R.device);
-        if (R.coll && R.own_coll) (void)hipStreamDestroy(R.coll);
-        if (R.spare) (void)hipStreamDestroy(R.spare);
         for (int i = 0; i < 2; i++) { if (R.ev_acc[i]) (void)hipEventDestroy(R.ev_acc[i]); if (R.ev_rs[i]) (void)hipEventDestroy(R.ev_rs[i]); }
         if (R.ev_c) (void)hipEventDestroy(R.ev_c);
         if (R.status_dev) (void)hipFree(R.status_dev);
@@ -235,11 +216,7 @@ static int mgpu_create_common(sfg_mgpu **out, const int *devices, int n, int ran
     mgpu_read_config(mg, config);
     auto fail = [&](const std::string &m) { g_mgpu_create_error = m; sfg_mgpu_destroy(mg); return 1; };
 #ifdef SFG_AB
-    if (const char *e = getenv("SFG_MGPU_SOLO")) {
-        int r = 0, w = 0;
-        if (sscanf(e, "%d/%d", &r, &w) != 2 || w < 1 || r < 0 || r >= w || n != 1 || id128) return fail("SFG_MGPU_SOLO=r/w needs one local device and a single process");
-        mg->solo = true; mg->world = world = w; rank0 = r;
-    }
+    if (const char *e = ab_mgpu_solo(n, id128 != nullptr, mg->solo, world, rank0)) return fail(e); else mg->world = world;      // SFG_MGPU_SOLO=r/w (ab/mgpu_solo.hip)
 #endif
     bool dup = false;
     for (int i = 0; i < n; i++) for (int j = 0; j < i; j++) dup = dup || devices[i] == devices[j];

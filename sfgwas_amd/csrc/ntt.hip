@@ -144,104 +144,6 @@ __global__ void __launch_bounds__(512) k_ntt_inv(const u64 *in_, u64 *out_, ModP
 // Cooley-Tukey stage is redundant.  This kernel computes r_j = p_j + W p_{n+j} = p_j - W p_{n-j} (W = psi^(N/2),
 // r_0 = p_0) and runs stages 2..14 on those n = N/2 values only: half the butterflies, half the LDS (two
 // workgroups per CU), and it emits half rows P[0..n).  256 threads, j = a*512 + b*16 + c with a < 16.
-// Block -> (plaintext, modulus) for the plaintext NTT kernels.  The L workgroups of one plaintext read the same 64 KiB of coefficients; workgroups are
-// dealt round-robin over the 8 XCDs, each with its own L2, so they are numbered b, b + 8, ..., b + 8 (L - 1): same XCD, dispatched back to back -
-// the coefficients come from HBM once instead of once per modulus (measured with row = blockIdx.x: 4.6x the unique bytes).
-__device__ __forceinline__ bool plain_block_of(size_t b, size_t nplain, int L, size_t &row, int &m) {
-    const size_t per = (size_t)8 * L, plain = (b / per) * 8 + (b % per) % 8;
-    m = (int)((b % per) / 8); row = plain * L + m;
-    return plain < nplain;
-}
-__device__ __forceinline__ bool plain_block(size_t nplain, int L, size_t &row, int &m) { return plain_block_of(blockIdx.x, nplain, L, row, m); }
-#ifdef SFG_AB          // the full-image form of the plaintext NTT (round 1): A/B build only
-constexpr int HLDS_DOUBLES = 16 * LDS_ROW;   // 67,584 B
-__global__ void __launch_bounds__(256) k_ntt_half(const double *pc_all, u64 *out_, size_t nplain, int L, PanelMap pm, const double *tw_all, const double2 *pack_all, const ModConst *modc) {
-    extern __shared__ double lds[];
-    const int N = SFG_N, n = N / 2, tid = threadIdx.x;
-    size_t row; int m;
-    if (!plain_block(nplain, L, row, m)) return;
-    const double *tw = tw_all + (size_t)m * N;
-    const double2 *pack = pack_all + (size_t)m * (N / 2);
-    const double q = modc[m].q, qinv = modc[m].qinv;
-    const double *pc = pc_all + (row / L) * (size_t)n;
-    const double W = tw[1], Wq = W * qinv;
-    double v[32];
-    // ---- phase A: two (b,c) columns per thread, 16 values of a each; stages t = 4096, 2048, 1024, 512
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const int pp = tid + 256 * h;
-        double w[16];
-#pragma unroll
-        for (int a = 0; a < 16; a++) {
-            const int j = a * 512 + pp;
-            const double lo = pc[j];
-            const double hi = j == 0 ? 0.0 : pc[n - j];          // p_{n+j} = -p_{n-j}
-            w[a] = lo - mulmod_lazy(hi, W, Wq, q);
-        }
-        ct_stage<16, 8>(w, q, qinv, [&](int g) { return tw[2 + g]; });
-        ct_stage<16, 4>(w, q, qinv, [&](int g) { return tw[4 + g]; });
-        ct_stage<16, 2>(w, q, qinv, [&](int g) { return tw[8 + g]; });
-        ct_stage<16, 1>(w, q, qinv, [&](int g) { return tw[16 + g]; });
-#pragma unroll
-        for (int a = 0; a < 16; a++) lds[a * LDS_ROW + pp] = w[a];
-    }
-    __syncthreads();
-    // ---- phase B: thread (a, c), 32 values of b; stages t = 256 .. 16
-    {
-        const int a = tid >> 4, c = tid & 15;
-#pragma unroll
-        for (int b = 0; b < 32; b++) v[b] = lds[a * LDS_ROW + b * 16 + c];
-        ct_stage<32, 16>(v, q, qinv, [&](int g) { return tw[32 + a + g]; });
-        ct_stage<32, 8>(v, q, qinv, [&](int g) { return tw[64 + a * 2 + g]; });
-        ct_stage<32, 4>(v, q, qinv, [&](int g) { return tw[128 + a * 4 + g]; });
-        ct_stage<32, 2>(v, q, qinv, [&](int g) { return tw[256 + a * 8 + g]; });
-        ct_stage<32, 1>(v, q, qinv, [&](int g) { return tw[512 + a * 16 + g]; });
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < 32; b++) lds[a * LDS_ROW + c * 33 + b] = v[b];
-    }
-    __syncthreads();
-    // ---- phase C: two (a, b) groups per thread, 16 values of c; stages t = 8 .. 1 with the packed twiddles
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const int p = tid + 256 * h, a = p >> 5, b = p & 31;
-        double w[16];
-#pragma unroll
-        for (int c = 0; c < 16; c++) w[c] = lds[a * LDS_ROW + c * 33 + b];
-        double tl[16];
-        {
-            const double2 *pk = pack + (size_t)(p >> 6) * 512 + (p & 63);
-#pragma unroll
-            for (int i = 0; i < 8; i++) { const double2 e = pk[i * 64]; tl[2 * i] = e.x; tl[2 * i + 1] = e.y; }
-        }
-        ct_stage<16, 8>(w, q, qinv, [&](int g) { return tl[0 + g]; });
-        ct_stage<16, 4>(w, q, qinv, [&](int g) { return tl[1 + g]; });
-        ct_stage<16, 2>(w, q, qinv, [&](int g) { return tl[3 + g]; });
-        ct_stage<16, 1>(w, q, qinv, [&](int g) { return tl[7 + g]; });
-#pragma unroll
-        for (int c = 0; c < 16; c++) v[h * 16 + c] = w[c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const int p = tid + 256 * h, a = p >> 5, b = p & 31;
-#pragma unroll
-        for (int c = 0; c < 16; c++) lds[a * LDS_ROW + c * 33 + b] = v[h * 16 + c];
-    }
-    __syncthreads();
-    // destination plaintext slot inside a (possibly multi-block-row) panel: see PanelMap
-    const size_t plain = row / L; const int shift = pm.shift0 + (int)plain;
-    const size_t dst = pm.G ? ((size_t)(shift / SFG_D) * pm.G + pm.g) * SFG_D + (size_t)(shift % SFG_D) : plain;
-    u64 *out = out_ + (dst * L + m) * (size_t)n;
-    const bool packed = (pm.packed_mask >> m) & 1u;
-#pragma unroll
-    for (int k = 0; k < 32; k++) {
-        const int j = k * 256 + tid, a = j >> 9, x = j & 511, b = x >> 4, c = x & 15;
-        const u64 w = f64_to_u64(canon(lds[a * LDS_ROW + c * 33 + b], q, qinv));
-        out[j] = packed ? pack_limbs(w) : w;
-    }
-}
-#endif
 // Same transform with every exchange split in two rounds through a HALF image (33 KiB instead of 66 KiB): three
 // workgroups (12 waves) fit a CU instead of two.  Round structure:
 //   A->B  by column half h (pp = tid + 256 h  <=>  b < 16 or b >= 16): everyone writes its column h, (a, c) readers take 16 b's
@@ -284,19 +186,11 @@ __device__ __forceinline__ void ntt_half3_body(int hs, First first, Store store,
     }
     // ---- phase B: thread (a, c), 32 values of b; stages t = 256 .. 16
     const int ab = 16 * hs + a_b;
-#if defined(SFG_NTT_DIAG) && SFG_NTT_DIAG == 3          // timing only: no phase-B twiddle loads
-    ct_stage<32, 16>(v, q, qinv, [&](int g) { return (double)(ab + g + 3); });
-    ct_stage<32, 8>(v, q, qinv, [&](int g) { return (double)(ab * 2 + g + 5); });
-    ct_stage<32, 4>(v, q, qinv, [&](int g) { return (double)(ab * 4 + g + 7); });
-    ct_stage<32, 2>(v, q, qinv, [&](int g) { return (double)(ab * 8 + g + 9); });
-    ct_stage<32, 1>(v, q, qinv, [&](int g) { return (double)(ab * 16 + g + 11); });
-#else
     ct_stage<32, 16>(v, q, qinv, [&](int g) { return tw[32 + ab + g]; });
     ct_stage<32, 8>(v, q, qinv, [&](int g) { return tw[64 + ab * 2 + g]; });
     ct_stage<32, 4>(v, q, qinv, [&](int g) { return tw[128 + ab * 4 + g]; });
     ct_stage<32, 2>(v, q, qinv, [&](int g) { return tw[256 + ab * 8 + g]; });
     ct_stage<32, 1>(v, q, qinv, [&](int g) { return tw[512 + ab * 16 + g]; });
-#endif
     // ---- B->C, phase C and the output staging are WAVE-PRIVATE.  Thread (a_b, c_b) of phase B and the phase-C owner of group (a, b) with
     // a = tid >> 4 live in the same 16-lane quarter of a wave: the B->C exchange is a 16 x 16 transpose inside each quarter, and staging a wave's
     // results for coalesced stores needs only that wave's four `a` rows.  So each wave works in its own 8 KiB of the (dead) A->B image with
@@ -322,11 +216,7 @@ __device__ __forceinline__ void ntt_half3_body(int hs, First first, Store store,
                 const double2 *pk = pack + (size_t)((p >> 6) + 8 * hs) * 512 + (p & 63);
 #pragma unroll
                 for (int i = 0; i < 8; i++) {
-#if defined(SFG_NTT_DIAG) && SFG_NTT_DIAG == 4          // timing only: no phase-C twiddle loads
-                    const double2 e = make_double2((double)(p + 2 * i + 3), (double)(p + 2 * i + 4)); (void)pk;
-#else
                     const double2 e = pk[i * 64];
-#endif
                     tl[2 * i] = e.x; tl[2 * i + 1] = e.y;
                 }
             }
@@ -379,11 +269,7 @@ __device__ __forceinline__ void ntt_half3_wg(size_t vb, double *lds, const doubl
     if (PERM) { const uint32_t e = perm[pm.shift0 + (int)(row / L)]; pc = pc_all + (size_t)(e & 0xFFFFu) * n; gal = e >> 16; }
     const double W = tw[1], Wq = W * qinv;
     // stage 1 on the antisymmetric input: r_j = p_j + W p_{n+j} = p_j - W p_{n-j}, r_0 = p_0
-#if defined(SFG_NTT_DIAG) && SFG_NTT_DIAG == 5              // timing only: no coefficient-row loads
-    auto first = [&](int j) { const double lo = (double)(j + 7), hi = j == 0 ? 0.0 : (double)(n - j + 5); return lo - mulmod_lazy(hi, W, Wq, q); };
-#else
     auto first = [&](int j) { const double lo = pc[j], hi = j == 0 ? 0.0 : pc[n - j]; return lo - mulmod_lazy(hi, W, Wq, q); };
-#endif
     // PERM: source driven.  A thread reads the pairs (p_i, p_{n-i}), i = tid + 256 k < n/2, coalesced.  p_i is coefficient raw = i g mod 2N of the image, i.e.
     // +-coefficient J of its stored half (quadrants of raw: [0,n] J = raw, +; (n,N) J = N - raw, -; [N,N+n] J = raw - N, -; (N+n,2N) J = 2N - raw, +), and
     // because g = 1 mod 4 its partner p_{n-i} is coefficient n - J (signs +, +, -, -): the pair yields r_J and r_{n-J}.  The 8192 stage-1 values then go to
@@ -435,10 +321,6 @@ __device__ __forceinline__ void ntt_half3_wg(size_t vb, double *lds, const doubl
         } else out = reinterpret_cast<u64 *>(reinterpret_cast<uint8_t *>(out_) + dst * (planes_all * n) + planes_below * n);
     }
     // (the format test is hoisted: inside the store loop it costs a branch per word)
-#ifdef SFG_NTT_DIAG          // timing diagnostics only: 1 = no panel stores (kept alive by an impossible value), 2 = stores without canon / packing
-    if (SFG_NTT_DIAG == 1) { ntt_half3_body(0, first, [&](int j, double x) { if (x == 0.123) out[j] = pack_limbs_f64(canon_le(x, q, qinv)); }, lds, tw, pack, q, qinv, tid); return; }
-    if (SFG_NTT_DIAG == 2) { ntt_half3_body(0, first, [&](int j, double x) { out[j] = (u64)__double_as_longlong(x); }, lds, tw, pack, q, qinv, tid); return; }
-#endif
     // int8 MAC (mac_i8.hip; bit 31 of the mask): the packed rows leave as five planes of signed base-256 digits instead of words - 5 of the row's 8 bytes per word.
     // Balanced digits of v: the bytes of v + 0x8080808080 with their top bits flipped; the sum is read off the mantissa of v + 2^52 + 0x8080808080.
     if constexpr (DIG) if (!((pm.packed_mask >> m) & 1u) && ((pm.packed_mask >> 30) & 1u)) {        // the 46-bit row as SIX digit planes (48 KiB of its 64 KiB)
@@ -543,9 +425,6 @@ int ntt_set_attrs(sfg_ctx *ctx) {
     hipError_t e = hipFuncSetAttribute((const void *)k_ntt_fwd<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_fwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_inv, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
-#ifdef SFG_AB
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_half, hipFuncAttributeMaxDynamicSharedMemorySize, HLDS_DOUBLES * 8);
-#endif
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_half3<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_half3<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_half3<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
@@ -556,6 +435,7 @@ int ntt_set_attrs(sfg_ctx *ctx) {
 #ifdef SFG_AB
     SFG_MV_ATTR(false, 1, false); SFG_MV_ATTR(false, 2, false); SFG_MV_ATTR(false, 2, true); SFG_MV_ATTR(false, 3, false); SFG_MV_ATTR(false, 3, true);
     SFG_MV_ATTR(true, 1, false); SFG_MV_ATTR(true, 2, false); SFG_MV_ATTR(true, 2, true); SFG_MV_ATTR(true, 3, false); SFG_MV_ATTR(true, 3, true);
+    if (e == hipSuccess && ab_set_attrs(ctx)) return 1;          // and those of the A/B build's own kernels (csrc/ab/)
 #endif
 #undef SFG_MV_ATTR
     if (e != hipSuccess) SFG_FAIL(ctx, "cannot raise dynamic LDS limit for the NTT kernels");
@@ -584,15 +464,16 @@ int launch_ntt_plain(sfg_ctx *ctx, const double *pc, u64 *out, size_t nplain, in
 }
 // half rows [nplain][L][N/2] from half-coefficient plaintexts
 template <bool PERM>
-static void launch_half3_move(sfg_ctx *ctx, dim3 grid, const double *pc, u64 *out_half, size_t nplain, int L, PanelMap pm, const uint32_t *perm, const MoveJob &j) {
+static int launch_half3_move(sfg_ctx *ctx, dim3 grid, const double *pc, u64 *out_half, size_t nplain, int L, PanelMap pm, const uint32_t *perm, const MoveJob &j) {
 #define SFG_MV(D, T) hipLaunchKernelGGL((k_ntt_half3_move<PERM, D, T>), grid, dim3(256), H3_LDS_BYTES, ctx->stream, pc, out_half, nplain, L, pm, ctx->tw_fwd, ctx->pack_fwd, ctx->modc, perm, j)
+    if (j.depth == 1 && j.nt) { SFG_MV(1, true); return 0; }
 #ifdef SFG_AB
-    if (j.depth == 3) { if (j.nt) SFG_MV(3, true); else SFG_MV(3, false); return; }
-    if (j.depth == 2) { if (j.nt) SFG_MV(2, true); else SFG_MV(2, false); return; }
-    if (!j.nt) { SFG_MV(1, false); return; }
+    if (j.depth == 3) { if (j.nt) SFG_MV(3, true); else SFG_MV(3, false); return 0; }
+    if (j.depth == 2) { if (j.nt) SFG_MV(2, true); else SFG_MV(2, false); return 0; }
+    if (j.depth == 1) { SFG_MV(1, false); return 0; }
 #endif
-    SFG_MV(1, true);
 #undef SFG_MV
+    SFG_FAIL(ctx, "plaintext NTT: the product build holds the mover with one unit in flight and streaming accesses only (other forms: make ab)");
 }
 int launch_ntt_plain_half(sfg_ctx *ctx, const double *pc, u64 *out_half, size_t nplain, int L, PanelMap pm, const uint32_t *perm, const MoveJob *mv) {
     if (!nplain) return 0;
@@ -600,12 +481,9 @@ int launch_ntt_plain_half(sfg_ctx *ctx, const double *pc, u64 *out_half, size_t 
     const bool dig = pm.packed_mask >> 31;                 // digit planes for the int8 MAC (mac_i8.hip): its own instances, the default kernels are untouched
     if (mv && mv->count) {
         if (!dig || mv->nblocks % 8 || !mv->nblocks) SFG_FAIL(ctx, "plaintext NTT: mover workgroups need the digit-plane form and a multiple of 8 of them");
-#ifndef SFG_AB
-        if (mv->depth != 1 || !mv->nt) SFG_FAIL(ctx, "plaintext NTT: the product build holds the mover with one unit in flight and streaming accesses only (other forms: make ab)");
-#endif
         const dim3 g2(grid.x + mv->nblocks);
-        if (perm) launch_half3_move<true>(ctx, g2, pc, out_half, nplain, L, pm, perm, *mv);
-        else launch_half3_move<false>(ctx, g2, pc, out_half, nplain, L, pm, (const uint32_t *)nullptr, *mv);
+        if (perm) SFG_TRY(launch_half3_move<true>(ctx, g2, pc, out_half, nplain, L, pm, perm, *mv));
+        else SFG_TRY(launch_half3_move<false>(ctx, g2, pc, out_half, nplain, L, pm, (const uint32_t *)nullptr, *mv));
         SFG_HIP(ctx, hipGetLastError());
         return 0;
     }
@@ -613,7 +491,7 @@ int launch_ntt_plain_half(sfg_ctx *ctx, const double *pc, u64 *out_half, size_t 
     else if (perm) hipLaunchKernelGGL((k_ntt_half3<true, false>), grid, dim3(256), H3_LDS_BYTES, ctx->stream, pc, out_half, nplain, L, pm, ctx->tw_fwd, ctx->pack_fwd, ctx->modc, perm);
     else if (dig) hipLaunchKernelGGL((k_ntt_half3<false, true>), grid, dim3(256), H3_LDS_BYTES, ctx->stream, pc, out_half, nplain, L, pm, ctx->tw_fwd, ctx->pack_fwd, ctx->modc, (const uint32_t *)nullptr);
 #ifdef SFG_AB
-    else if (ctx->cfg.ntt_half_full) hipLaunchKernelGGL(k_ntt_half, grid, dim3(256), HLDS_DOUBLES * 8, ctx->stream, pc, out_half, nplain, L, pm, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
+    else if (ctx->cfg.ntt_half_full) ab_launch_ntt_half_full(ctx, pc, out_half, nplain, L, pm);          // ab/ntt_full.hip
 #endif
     else hipLaunchKernelGGL((k_ntt_half3<false, false>), grid, dim3(256), H3_LDS_BYTES, ctx->stream, pc, out_half, nplain, L, pm, ctx->tw_fwd, ctx->pack_fwd, ctx->modc, (const uint32_t *)nullptr);
     SFG_HIP(ctx, hipGetLastError());

@@ -102,7 +102,7 @@ int assoc_build_rotcache(sfg_ctx *ctx, const u64 *A_dev, int s, int in_level, in
 // fp64 kernel, the cache shrinks from 1.86 to 1.3 GB per block row at s = 13), else the fp64 operand rows, else nothing (every product rotates for itself).
 int assoc_build_rot(sfg_ctx *ctx, const u64 *A_dev, int s, int in_level, int max_level, size_t nr, const std::vector<size_t> &widths, AssocRot &out) {
     out = AssocRot();
-    if (ctx->cfg.assoc_cache_budget && ctx->cfg.assoc_i8) {
+    if (ctx->cfg.assoc_cache_budget) {
         std::vector<std::vector<uint8_t>> tabs; assoc_baby_tabs(nr, widths, tabs);
         SFG_TRY(i8_rotpre_build(ctx, A_dev, s, in_level, max_level, (int)tabs.size(), &tabs, ctx->cfg.assoc_cache_budget, "assoc.rot8", out.pre));
         if (out.pre.G) return 0;
@@ -219,11 +219,7 @@ int assoc_stream_part(sfg_ctx *ctx, int fmt, const char *path, size_t num_sample
         if (!rc) ST_HIP(hipEventCreateWithFlags(&ev_free[i], hipEventDisableTiming));
     }
     if (rc) { cleanup(); return rc; }
-#ifdef SFG_AB
-    const bool trace = getenv("SFG_ASSOC_TRACE") != nullptr;
-#else
-    const bool trace = false;
-#endif       // (debug: wall times of the cache build and of every batch's product, each synchronised)
+    const bool trace = ctx->cfg.assoc_trace;       // (A/B build, SFG_ASSOC_TRACE: wall times of the cache build and of every batch's product, each synchronised)
     if (trace) fprintf(stderr, "[assoc] buffers: %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
     // the reader fills the first two slots while the rotation cache is built
     Reader rd; rd.fd = fd; rd.bt = &bt; rd.slot[0] = hb[0]; rd.slot[1] = hb[1]; rd.direct = direct;
