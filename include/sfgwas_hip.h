@@ -458,6 +458,8 @@ int sfg_mgpu_geno_compare_rows(sfg_mgpu *mg, const sfg_mgeno *g, unsigned flags,
 int sfg_mgpu_matmul_dev(sfg_mgpu *mg, const uint64_t *const *A_dev, int s, int in_level, int max_level, const sfg_mgeno *g, unsigned flags,
                         uint64_t *const *out_dev);
 int sfg_mgpu_matmul(sfg_mgpu *mg, const uint64_t *A_host, int s, int in_level, int max_level, const sfg_mgeno *g, unsigned flags, uint64_t *out_host);
+/* test hook: local rank `local` fails ONCE in the next exchanging Q' * X^T call (phase 0: the host form's I/O pass, 1: before the agreement point); refused unless SFG_ENABLE_TEST_HOOKS=1 was set before sfg_mgpu_create */
+int sfg_mgpu_inject_failure_for_test(sfg_mgpu *mg, int local, int phase);
 /* GenoBlockMult's batch loop (gwas/assoc.go:340-420) on G GPUs: the reference hands the SNP batches of a chromosome file to assoc_num_blocks_parallel workers
  * (:360-408); here batch k goes to rank k % world.  Every rank streams its batches from the file (sfg_assoc_stream_bed / _pgen: reader thread, pinned slots, decode on
  * the device), multiplies them against its own call-wide rotation cache of `mat` and its output ciphertexts land at their positions of

@@ -192,6 +192,7 @@ def _sig(L):
         "sfg_mgpu_geno_set_plaintext_cache": (i, [vp, vp, sz]),
         "sfg_mgpu_matmul_dev": (i, [vp, C.POINTER(vp), i, i, i, vp, C.c_uint, C.POINTER(vp)]),
         "sfg_mgpu_matmul": (i, [vp, u64p, i, i, i, vp, C.c_uint, u64p]),
+        "sfg_mgpu_inject_failure_for_test": (i, [vp, i, i]),
         "sfg_mgpu_assoc_stream_bed": (i, [vp, C.c_char_p, sz, sz, vp, vp, sz, u64p, i, i, i, C.c_uint, u64p, sz, C.POINTER(sz), vp, vp]),
         "sfg_mgpu_assoc_stream_pgen": (i, [vp, C.c_char_p, vp, vp, sz, sz, u64p, i, i, i, C.c_uint, u64p, sz, C.POINTER(sz), vp, vp]),
         "sfg_ctx_clear_phases": (i, [vp]),
@@ -833,6 +834,10 @@ class MultiGpu:
         pa = (C.c_void_p * n)(*[a.p for a in A])
         po = (C.c_void_p * n)(*[o.p for o in out])
         self.check(lib().sfg_mgpu_matmul_dev(self.h, pa, s, in_level, max_level, g, flags, po), "sfg_mgpu_matmul_dev")
+
+    def inject_failure_for_test(self, local, phase):
+        """test hook (SFG_ENABLE_TEST_HOOKS=1 before the engine was made): local rank `local` fails once in the next exchanging Q'X^T call; phase 0 = I/O pass, 1 = prepare"""
+        self.check(lib().sfg_mgpu_inject_failure_for_test(self.h, local, phase), "sfg_mgpu_inject_failure_for_test")
 
     def matmul(self, A_host, s, in_level, max_level, g, flags=0):
         """host form: A_host [s][nbr or m_ct][2][in_level+1][N] -> out [s][m_ct or nbr][2][max_level][N]"""

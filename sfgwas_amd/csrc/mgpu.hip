@@ -20,10 +20,9 @@
 // tested on a one-GPU box; host-side rendezvous, no overlap).  Integer sums: both give identical words.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "rendezvous.hpp"      // the host-side meeting point of the rank threads (agreement point, direct transport)
 #include <rccl/rccl.h>          // types and prototypes only; the functions are resolved at run time (Rccl below)
 #include <dlfcn.h>
-#include <atomic>
-#include <condition_variable>
 #include <mutex>
 #include <thread>
 
@@ -65,22 +64,8 @@ struct MgRank {
     hipStream_t coll = nullptr;             // the collectives' queue (RCCL kernels beside the MAC of the next column): the context's third queue, coll_stream
     hipEvent_t ev_acc[2] = {nullptr, nullptr}, ev_rs[2] = {nullptr, nullptr}, ev_c = nullptr;
     uint64_t *status_dev = nullptr, *status_host = nullptr;      // the agreement word of a call (coll_agree): made with the rank, so that agreeing never allocates
+    int inject_phase = -1;                  // sfg_mgpu_inject_failure_for_test: this rank fails once in the next exchanging Q'X^T call (0: I/O pass, 1: prepare)
     std::string err;
-};
-
-// host-side meeting point of the rank threads of the direct transport
-struct Rendezvous {
-    std::mutex m; std::condition_variable cv; int n = 1, count = 0; unsigned long gen = 0; std::atomic<bool> failed{false};
-    const void *ptr[64];
-    bool barrier() {       // false: a peer has failed (nobody will arrive)
-        std::unique_lock<std::mutex> lk(m);
-        if (failed.load()) return false;
-        const unsigned long g = gen;
-        if (++count == n) { count = 0; gen++; cv.notify_all(); return true; }
-        cv.wait(lk, [&] { return gen != g || failed.load(); });
-        return gen != g;
-    }
-    void fail() { std::unique_lock<std::mutex> lk(m); failed.store(true); cv.notify_all(); }
 };
 
 // out[x] = sum_p src[p][x] over n peers' slices (uint64, wraps never: world * 2^47)
@@ -104,6 +89,7 @@ struct sfg_mgpu {
     std::string rccl_lib;                   // sfg_config.rccl_lib
     std::vector<MgRank> r;                  // local ranks
     bool broken = false;                    // a rank failed after a call's agreement point and its communicator was aborted: the engine refuses further exchanges
+    bool test_hooks = false;                // SFG_ENABLE_TEST_HOOKS=1 when the engine was made: sfg_mgpu_inject_failure_for_test may be called
     Rendezvous rv;
     std::string err;
 };
@@ -127,7 +113,7 @@ template <class F> static int run_ranks(sfg_mgpu *mg, F &&fn) {
     const int n = (int)mg->r.size();
     std::vector<int> rc((size_t)n, 0);
     for (auto &R : mg->r) R.err.clear();
-    mg->rv.failed.store(false);
+    mg->rv.reset();                                      // (no rank thread is running: a failed call of the past leaves no arrivals behind)
     auto body = [&](int i) { rc[(size_t)i] = fn(mg->r[(size_t)i], i); if (rc[(size_t)i]) mg->rv.fail(); };
     if (n == 1) body(0);
     else { std::vector<std::thread> th; for (int i = 0; i < n; i++) th.emplace_back(body, i); for (auto &t : th) t.join(); }
@@ -163,7 +149,8 @@ static void mgpu_read_config(sfg_mgpu *mg, const sfg_config *pc) {
     if (const char *e = getenv("SFG_MGPU_TRANSPORT")) mg->direct = !strcmp(e, "direct");
     if (const char *e = getenv("SFG_MGPU_CACHE_GB")) { double gb = atof(e); if (!(gb >= 0)) gb = 0; if (gb > 4096) gb = 4096; mg->cache_budget = (size_t)(gb * (double)(1ULL << 30)); }
     const char *hooks = getenv("SFG_ENABLE_TEST_HOOKS");
-    if (hooks && atoi(hooks) == 1) if (const char *e = getenv("SFG_MGPU_FORCE_COLLECTIVES")) mg->force_coll = atoi(e) != 0;
+    mg->test_hooks = hooks && atoi(hooks) == 1;
+    if (mg->test_hooks) if (const char *e = getenv("SFG_MGPU_FORCE_COLLECTIVES")) mg->force_coll = atoi(e) != 0;
 }
 static const char *rank_exec_init(MgRank &R) {
     if (hipSetDevice(R.device) != hipSuccess) return "hipSetDevice failed";
@@ -294,6 +281,24 @@ extern "C" int sfg_mgpu_comm_info(sfg_mgpu *mg, int local, int *nranks, int *ran
     if (g_rccl.CommCount(R.comm, &n) != ncclSuccess || g_rccl.CommUserRank(R.comm, &r) != ncclSuccess) MG_FAIL(mg, "sfg_mgpu_comm_info: ncclCommCount / ncclCommUserRank failed");
     if (nranks) *nranks = n; if (rank) *rank = r;
     return 0;
+}
+
+// test hook: local rank `local` fails ONCE, in the next Q'X^T product that exchanges (world > 1, or the forced exchange): phase 0 at the end of sfg_mgpu_matmul's I/O pass,
+// phase 1 at the end of rank_contract's prepare(), i.e. with the rank's work of the call enqueued and its peers on their way to the agreement point
+extern "C" int sfg_mgpu_inject_failure_for_test(sfg_mgpu *mg, int local, int phase) {
+    MG_NEED(mg, mg != nullptr, "null engine");
+    if (!mg->test_hooks) MG_FAIL(mg, "sfg_mgpu_inject_failure_for_test: test hook, enabled only in a process that set the test switch before creating the engine");
+    MG_NEED(mg, local >= 0 && local < (int)mg->r.size(), "local rank out of range");
+    MG_NEED(mg, phase == 0 || phase == 1, "phase must be 0 (I/O pass) or 1 (prepare)");
+    mg->r[(size_t)local].inject_phase = phase;
+    return 0;
+}
+// the injected failure of `phase`, if it is armed on this rank (and disarmed by firing)
+static int rank_injected(MgRank &R, int phase) {
+    if (R.inject_phase != phase) return 0;
+    R.inject_phase = -1;
+    R.err = std::string("injected test failure (") + (phase ? "prepare" : "I/O pass") + ")";
+    return 1;
 }
 
 extern "C" int sfg_mgpu_load_rotkey(sfg_mgpu *mg, uint64_t galois_el, const uint64_t *key_host, int montgomery_form) {
@@ -539,10 +544,11 @@ extern "C" int sfg_mgpu_preflight(sfg_mgpu *mg, size_t count_per_rank) {
 }
 
 // ---------------------------------------------------------------- the products
-// Q' * X^T of one rank: see the header of this file
-static int rank_contract(sfg_mgpu *mg, MgRank &R, int li, const uint64_t *A, int s, int in_level, int L, const sfg_mgeno *g, unsigned flags, uint64_t *out) {
+// Q' * X^T of one rank: see the header of this file.  pre_rc: the rank's status from the call's work before this (sfg_mgpu_matmul's I/O pass) - a rank that has
+// failed already still brings that status to the agreement point instead of returning before it (its peers would wait there for ever in a world of one rank per process)
+static int rank_contract(sfg_mgpu *mg, MgRank &R, int li, const uint64_t *A, int s, int in_level, int L, const sfg_mgeno *g, unsigned flags, uint64_t *out, int pre_rc) {
     sfg_ctx *ctx = R.ctx;
-    R_HIP(R, hipSetDevice(R.device));
+    if (!pre_rc && hipSetDevice(R.device) != hipSuccess) { R.err = "hipSetDevice failed (mgpu.hip:" + std::to_string(__LINE__) + ")"; pre_rc = 1; }
     ApiScope api_scope(ctx);                             // one top-level call for the scratch pools' bookkeeping
     const int world = mg->world, d = SFG_D, N = SFG_N;
     const sfg_geno *shard = g->shard[(size_t)li];
@@ -551,7 +557,7 @@ static int rank_contract(sfg_mgpu *mg, MgRank &R, int li, const uint64_t *A, int
     const size_t outw = (size_t)2 * L * N, accw = (size_t)s * outw;
     const int gpr = (d + world - 1) / world, g_lo = R.rank * gpr;
     const size_t col = (size_t)d * accw, colp = (size_t)world * gpr * accw, mine = (size_t)gpr * accw;
-    if (world == 1 && !mg->force_coll) { R_CTX(R, sfg_matmul_resident_dev(ctx, A, s, in_level, L, shard, fl, out)); return 0; }
+    if (world == 1 && !mg->force_coll) { if (pre_rc) return pre_rc; R_CTX(R, sfg_matmul_resident_dev(ctx, A, s, in_level, L, shard, fl, out)); return 0; }
     I8RotPre pre8;
     bool pipe = false;
     int PW = 1;                                          // block columns per multiply call of the pipeline: with int8 rot tiles TWO, so that the second column's encode carries the
@@ -594,9 +600,9 @@ static int rank_contract(sfg_mgpu *mg, MgRank &R, int li, const uint64_t *A, int
             R_HIP(R, hipMemsetAsync(acc2, 0, acc_w * 8, cs));
             if (nloc) R_CTX(R, sfg_matmul_accumulate_dev(ctx, A, s, in_level, L, shard, fl, 0, nloc, 0, nbr_x, 0, acc2));
         }
-        return 0;
+        return rank_injected(R, 1);
     };
-    if (coll_agree(mg, R, prepare())) { i8_rotpre_free(pre8); return 1; }
+    if (coll_agree(mg, R, pre_rc ? pre_rc : prepare())) { i8_rotpre_free(pre8); return 1; }
     // ---- from here on a failure aborts the communicator: the peers are inside (or about to enter) their collectives
     auto exchange = [&]() -> int {
         if (pipe) {
@@ -633,6 +639,15 @@ static int rank_contract(sfg_mgpu *mg, MgRank &R, int li, const uint64_t *A, int
     return rc;
 }
 
+// one rank's share of sfg_mgpu_matmul(_dev); pre_rc as for rank_contract (Q X has no exchange: a failed rank returns at once)
+static int rank_product(sfg_mgpu *mg, MgRank &R, int i, const uint64_t *A, int s, int in_level, int max_level, const sfg_mgeno *g, unsigned flags, uint64_t *out, int pre_rc) {
+    if (flags & SFG_TRANSPOSE) return rank_contract(mg, R, i, A, s, in_level, max_level, g, flags, out, pre_rc);
+    if (pre_rc) return pre_rc;
+    R_HIP(R, hipSetDevice(R.device));
+    if (g->shard[(size_t)i]) R_CTX(R, sfg_matmul_resident_dev(R.ctx, A, s, in_level, max_level, g->shard[(size_t)i], flags & SFG_SQUARE, out));
+    return 0;
+}
+
 // device-pointer form.  A_dev[i] / out_dev[i] belong to local rank i (device sfg_mgpu_ctx(mg, i)):
 //   flags without SFG_TRANSPOSE (Q * X):   A_dev[i] = the whole [s][ceil(nrow / 8192)] input grid (replicated); out_dev[i] = [s][blk1 - blk0] of the rank's block columns
 //   SFG_TRANSPOSE (Q' * X^T):              A_dev[i] = [s][blk1 - blk0] inputs of the rank's SNP blocks;          out_dev[i] = the whole [s][ceil(nrow / 8192)] result, on EVERY rank
@@ -648,12 +663,7 @@ extern "C" int sfg_mgpu_matmul_dev(sfg_mgpu *mg, const uint64_t *const *A_dev, i
         if ((has_in && has_out && !A_dev[i]) || (has_out && !out_dev[i])) MG_FAIL(mg, "sfg_mgpu_matmul_dev: null device pointer for local rank %zu", i);
     }
     MgApiScope scope(mg);
-    return run_ranks(mg, [&](MgRank &R, int i) {
-        R_HIP(R, hipSetDevice(R.device));
-        if (flags & SFG_TRANSPOSE) return rank_contract(mg, R, i, A_dev[i], s, in_level, max_level, g, flags, out_dev[i]);
-        if (g->shard[(size_t)i]) R_CTX(R, sfg_matmul_resident_dev(R.ctx, A_dev[i], s, in_level, max_level, g->shard[(size_t)i], flags & SFG_SQUARE, out_dev[i]));
-        return 0;
-    });
+    return run_ranks(mg, [&](MgRank &R, int i) { return rank_product(mg, R, i, A_dev[i], s, in_level, max_level, g, flags, out_dev[i], 0); });
 }
 
 // host-pointer form = MatMult4StreamCompute on the sharded resident matrix (what the Go shim calls):
@@ -669,19 +679,29 @@ extern "C" int sfg_mgpu_matmul(sfg_mgpu *mg, const uint64_t *A_host, int s, int 
     const size_t nbr_x = (g->nrow + SFG_SLOTS - 1) / SFG_SLOTS, mct = (g->ncol + SFG_SLOTS - 1) / SFG_SLOTS;
     const bool tr = flags & SFG_TRANSPOSE;
     const size_t n = mg->r.size();
+    if (s < 1 || max_level < 1) MG_FAIL(mg, "sfg_mgpu_matmul: bad s / max_level");
     std::vector<uint64_t *> A(n, nullptr), O(n, nullptr);
-    int rc = run_ranks(mg, [&](MgRank &R, int i) {
+    std::vector<int> io_rc(n, 0);
+    std::vector<std::string> io_err(n);
+    (void)run_ranks(mg, [&](MgRank &R, int i) {
         const size_t nloc = g->blk1[(size_t)i] - g->blk0[(size_t)i], na = tr ? nloc : nbr_x, no = tr ? nbr_x : nloc;
-        R_CTX(R, sfg_scratch(R.ctx, "mg.Ain", std::max<size_t>(na, 1) * s * ctw * 8, (void **)&A[(size_t)i]));
-        R_CTX(R, sfg_scratch(R.ctx, "mg.Oout", std::max<size_t>(no, 1) * s * outw * 8, (void **)&O[(size_t)i]));
-        if (!tr) { if (na) R_CTX(R, sfg_memcpy_h2d(R.ctx, A[(size_t)i], A_host, (size_t)s * nbr_x * ctw * 8)); }
-        else for (int r = 0; r < s && nloc; r++)      // row r of the input grid: the rank's block range
-            R_CTX(R, sfg_memcpy_h2d(R.ctx, A[(size_t)i] + (size_t)r * nloc * ctw, A_host + ((size_t)r * mct + g->blk0[(size_t)i]) * ctw, nloc * ctw * 8));
-        return 0;
+        auto upload = [&]() -> int {
+            R_CTX(R, sfg_scratch(R.ctx, "mg.Ain", std::max<size_t>(na, 1) * s * ctw * 8, (void **)&A[(size_t)i]));
+            R_CTX(R, sfg_scratch(R.ctx, "mg.Oout", std::max<size_t>(no, 1) * s * outw * 8, (void **)&O[(size_t)i]));
+            if (!tr) { if (na) R_CTX(R, sfg_memcpy_h2d(R.ctx, A[(size_t)i], A_host, (size_t)s * nbr_x * ctw * 8)); }
+            else for (int r = 0; r < s && nloc; r++)      // row r of the input grid: the rank's block range
+                R_CTX(R, sfg_memcpy_h2d(R.ctx, A[(size_t)i] + (size_t)r * nloc * ctw, A_host + ((size_t)r * mct + g->blk0[(size_t)i]) * ctw, nloc * ctw * 8));
+            return tr && !mg->solo && (mg->world > 1 || mg->force_coll) ? rank_injected(R, 0) : 0;
+        };
+        io_rc[(size_t)i] = upload(); io_err[(size_t)i] = R.err;
+        return 0;                                     // (a failed upload is not the end of the call: see below)
     });
-    if (rc) return rc;
-    std::vector<const uint64_t *> Ac(A.begin(), A.end());
-    rc = sfg_mgpu_matmul_dev(mg, Ac.data(), s, in_level, max_level, g, flags, O.data());
+    // the product; a rank whose I/O pass failed brings that status to Q'X^T's agreement point instead of staying away from it (in a world of one rank per process
+    // its peers would wait there for ever), and every rank fails the call with its message
+    int rc = run_ranks(mg, [&](MgRank &R, int i) {
+        if (io_rc[(size_t)i]) R.err = io_err[(size_t)i];
+        return rank_product(mg, R, i, A[(size_t)i], s, in_level, max_level, g, flags, O[(size_t)i], io_rc[(size_t)i]);
+    });
     if (rc) return rc;
     return run_ranks(mg, [&](MgRank &R, int i) {
         const size_t nloc = g->blk1[(size_t)i] - g->blk0[(size_t)i];

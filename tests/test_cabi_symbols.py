@@ -183,3 +183,18 @@ def test_multi_gpu_engine_fails_loudly_without_a_gpu():
     import oracle_lib as ol
     with pytest.raises(capi.SfgError, match="no HIP device|hip|device"):
         capi.MultiGpu(ol.Q_PN14, ol.P_PN14, devices=[0, 0])
+
+
+def test_every_test_hook_is_declared_as_refused_without_the_test_switch():
+    """an entry point named *_for_test exists for the failure-path tests only: its declaration must say that it is refused unless SFG_ENABLE_TEST_HOOKS=1, and the
+    library must carry that refusal in its text"""
+    hdr = open(os.path.join(ROOT, "include", "sfgwas_hip.h")).read()
+    hooks = sorted(set(re.findall(r"\b(sfg_[a-z0-9_]+_for_test)\s*\(", hdr)))
+    assert "sfg_mgpu_inject_failure_for_test" in hooks and "sfg_ctx_encoder_inject_unsafe_for_test" in hooks
+    for name in hooks:
+        decl = hdr.index(name + "(")
+        comment = hdr[hdr.rindex("/*", 0, decl):decl]
+        assert "SFG_ENABLE_TEST_HOOKS=1" in comment and "efused" in comment, f"{name}: the declaration does not say it is a refused-by-default test hook"
+    from sfgwas_amd import capi
+    blob = open(capi.LIB_PATH, "rb").read()
+    assert b"sfg_mgpu_inject_failure_for_test: test hook, enabled only" in blob
