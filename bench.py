@@ -4,7 +4,7 @@
    Q'*X^T (kp x m_snp)(m_snp x n_ind)  pca.go:352 -> MatMult4StreamCompute
 on synthetic data, through the C-ABI of libsfgwas_hip.so, one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--config c4|c3|c2|tiny]
+    python bench.py --gpus N --steps K --warmup W [--config c4|c3|c2|tiny] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Sharding (strong scaling, total work fixed): the genotype matrix is split by SNP block (8192 columns of X) across
@@ -20,8 +20,12 @@ matrix and the output digests in the JSON line are comparable between N = 1 and 
   --backend nccl (default: RCCL over xGMI, one GPU per rank) | gloo (collectives staged through host memory: a rehearsal of the
   N > 1 code path in which several ranks may share ONE GPU; its timings mean nothing).
 
-Before timing, rank 0 pushes a reduced problem (1 block row x 2 block columns, all 8192 diagonals, s = 2) through the
-CPU oracle and compares every output word with the HIP path ("parity_gate" in the JSON line; --no-check skips it).
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints its line: nothing the headline figure
+does not need.  --full adds the checks and the other measurements, each of which its --no-* switch still skips:
+  - before timing, rank 0 pushes a reduced problem (1 block row x 2 block columns, all 8192 diagonals, s = 2) through the
+    CPU oracle and compares every output word with the HIP path ("parity_gate"; --no-check);
+  - after timing, SHA-256 digests of both products and whether they are the pinned ones ("digests", "digests_match_pinned"; --no-digest);
+  - one GPU: the CPU baselines, built -O3 -march=native on this host ("cpu_baseline"; --no-cpu-baseline, --no-cpu-end-to-end).
 
 Prints ONE JSON line (rank 0).  PyTorch is plumbing here: device tensors, streams and torch.distributed.
 """
@@ -707,11 +711,14 @@ def main():
     ap.add_argument("--steps", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default=os.environ.get("SFG_BENCH_CONFIG", "c4"))
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bounded CPU-baseline sample (seconds of wall time)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cpu-end-to-end", action="store_true", help="skip the end-to-end CPU leg (one 8192 x 8192 block through the whole CPU restatement, ~ 30 s)")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle parity gate")
-    ap.add_argument("--no-digest", action="store_true", help="skip the SHA-256 digests of the outputs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run the oracle parity gate, the SHA-256 digests of the outputs against the pinned ones and (one GPU) the "
+                         "CPU baselines; a plain run does none of these")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: bounded CPU-baseline sample (seconds of wall time)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-cpu-end-to-end", action="store_true", help="--full: skip the end-to-end CPU leg (one 8192 x 8192 block through the whole CPU restatement, ~ 30 s)")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the oracle parity gate")
+    ap.add_argument("--no-digest", action="store_true", help="--full: skip the SHA-256 digests of the outputs")
     ap.add_argument("--backend", default=os.environ.get("SFG_BENCH_BACKEND", "nccl"), choices=("nccl", "gloo"),
                     help="nccl = RCCL, one GPU per rank (the measured path); gloo = host-staged collectives, ranks may share one GPU (rehearsal)")
     ap.add_argument("--packed-geno", action="store_true", help="keep the genotype matrix 2-bit packed in HBM (sfg_geno_pack: 4x smaller, blocks expanded on the fly)")
@@ -732,6 +739,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                     # a plain run: only what the headline figure needs
+        args.no_check = args.no_digest = args.no_cpu_baseline = True
     if args.dump_outputs:
         args.dump_outputs = os.path.abspath(args.dump_outputs)
     # switches of this script that need more than the product library offers: the timing-only solo rank and the kernel A/B switches live in the experimenters' build

@@ -19,7 +19,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--no-cpu-baseline", "--no-check", "--warmup", "0", "--steps", "1"]
+COMMON = ["--full", "--no-cpu-baseline", "--no-check", "--warmup", "0", "--steps", "1"]      # --full: the digests
 # ranks that share one GPU also share its 288 GB: smaller MAC groups / accumulator passes (results do not depend on either:
 # tests/test_gpu_properties.py), and Q'*X^T's rank-local rotation cache only when it is small
 SHARED_GPU_ENV = {"SFG_MM_GROUP": "4", "SFG_MM_ACC_BUDGET_MB": "4096", "SFG_BENCH_CACHE2_GB": "24"}

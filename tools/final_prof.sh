@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; TAG=${1:-r05final}; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 make -C oracle native > $O/make.log 2>&1
 ( while sleep 60; do echo "tick $(date +%T)"; done ) & TICK=$!
-timeout -k 10 700 python3 bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $O/bench_default.log 2>&1 || { tail -5 $O/bench_default.log; kill $TICK; exit 1; }
+timeout -k 10 700 python3 bench.py --full --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $O/bench_default.log 2>&1 || { tail -5 $O/bench_default.log; kill $TICK; exit 1; }
 grep '^{' $O/bench_default.log | tail -1 > $O/benchline.json
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-digest > $O/bench_prof.log 2>&1 || { tail -5 $O/bench_prof.log; kill $TICK; exit 1; }
 kill $TICK
