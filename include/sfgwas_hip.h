@@ -276,7 +276,7 @@ int sfg_geno_colsums(sfg_ctx *ctx, const sfg_geno *g, double *sum_host, double *
  * A: s x nbr ciphertexts [s][nbr][2][in_level+1][N] (nbr = ceil(rows/slots) of the operand orientation);
  * out: s x m_ct ciphertexts [s][m_ct][2][max_level][N] at level max_level-1, scale = A.scale * Params.Scale().
  * The result is the deterministic sum over giant steps; the reference adds it onto a fresh encryption of zero
- * (CZeroMat, matmult.go:1174,1443) which the Go shim keeps doing.
+ * (CZeroMat, matmult.go:1174,1443): sfg_ct_add_fresh_zero_dev does that on the device when a public key is loaded, else the Go shim keeps doing it.
  * flags: SFG_SQUARE squares genotypes after missing->0 (matmult.go:1301-1303); SFG_TRANSPOSE multiplies by X^T. */
 #define SFG_SQUARE 1u
 #define SFG_TRANSPOSE 2u
@@ -514,6 +514,38 @@ int sfg_ckks_to_ss_share_dev(sfg_ctx *ctx, const uint64_t *ct_dev, int nct, int 
 int sfg_ss_mask_dev(sfg_ctx *ctx, int limbs, const uint64_t *modulus_host, const uint64_t *bound_host, const uint64_t *rm_dev, const uint64_t *rand_dev,
                     uint64_t *rm_masked_dev, uint64_t *mask_dev, size_t n);
 int sfg_ss_hub_share_dev(sfg_ctx *ctx, int limbs, const uint64_t *modulus_host, const uint64_t *revealed_dev, const uint64_t *mask_dev, uint64_t *share_dev, size_t n);
+
+/* ---- C6 on the device: public-key encryption (crypto.CZeros / CZeroMat, basics.go:367-384; EncryptFloatVector / EncryptFloatMatrixRow, crypto.go:340-388;
+ * both end in lattigo's pkEncryptor.EncryptNew) ----
+ * PARITY UNPINNED: restated from the published lattigo v2.1 ckks/encryptor.go (the form that samples in R_QP and divides by P); with fresh randomness bit parity
+ * with the Go binary cannot exist.  What IS pinned (tests/test_gpu_encrypt.py): every word against a big-integer statement of the arithmetic below, the sampler
+ * against an independent Python ChaCha20 + table inversion, and decryption within the derived worst-case noise bound. */
+/* cryptoParams.Pk.Value (crypto.go:45, what crypto.go:355 NewEncryptorFromPk takes): [2][nq+np][N] words in the NTT domain; montgomery_form != 0 for lattigo's
+ * stored form.  Kept with the rotation keys: every fork sees it, it is freed with the root.  Every encrypting call without it fails and launches nothing. */
+int sfg_ctx_load_public_key(sfg_ctx *ctx, const uint64_t *pk_host, int montgomery_form);
+int sfg_ctx_has_public_key(const sfg_ctx *ctx);
+/* The deterministic core of EncryptNew (lattigo ckks/encryptor.go encrypt(), the ModDown branch); randomness stays with the caller: u int8 [nct][N] in {-1, 0, 1},
+ * e0, e1 int32 [nct][N], pt_dev NULL (zero) or [nct][level+1][N] NTT-domain plaintext rows, out_dev [nct][2][level+1][N] canonical words.
+ * For every modulus m of Q_0..Q_level and of P:  t_i = pk_i (.) NTT(u) + NTT(e_i);  c_i = ModDown_P(t_i), the key switch's (float-corrected basis extension);
+ * c_0 += pt.  Row j of the result depends on modulus j and the P rows only: level l gives rows 0..l of the MaxLevel encryption of the same u, e0, e1. */
+int sfg_encrypt_explicit_dev(sfg_ctx *ctx, const uint64_t *pt_dev, int nct, int level, const int8_t *u_dev, const int32_t *e0_dev, const int32_t *e1_dev,
+                             uint64_t *out_dev);
+/* The sampler's key (replaces the PRNG lattigo's NewEncryptorFromPk draws from crypto/rand, crypto.go:355): 32 bytes from the caller's CSPRNG.  There is no default and
+ * nothing is derived from time or addresses: unseeded, the sampling calls fail.  ChaCha20 (RFC 8439) with nonce = (64-bit encryption index, 32-bit polynomial id);
+ * the index is ONE atomic counter shared by the root and its forks, a call takes nct consecutive indices, seeding resets it to 0.  A key must never be seeded twice
+ * (after a restart: a fresh key).  Wiped from host and device memory with the root context; never part of an error string.  Setup-time call: not concurrent with
+ * encrypting calls of other forks. */
+int sfg_ctx_seed_encryptor(sfg_ctx *ctx, const uint8_t *key32);
+int sfg_ctx_encryptor_next_index(const sfg_ctx *ctx, uint64_t *next_index);
+/* crypto.CZeroMat + eval.Add (matmult.go:1174,1225,1443,1494; integration/go/gwas/matmult_hip.go finish()): ct += Enc(0) in place on [nct][2][level+1][N], each
+ * with fresh samples (nct indices).  Bit-identical to sfg_encrypt_explicit_dev on those samples, added. */
+int sfg_ct_add_fresh_zero_dev(sfg_ctx *ctx, uint64_t *ct_dev, int nct, int level);
+/* crypto.EncryptFloatVector (crypto.go:340-362) / one row of EncryptFloatMatrixRow (crypto.go:364-388): sfg_encode_vectors_dev's plaintext rows (same argument
+ * conventions, same bits), encrypted: values_host [nct][slots] -> out_dev [nct][2][level+1][N]. */
+int sfg_encrypt_vectors_dev(sfg_ctx *ctx, const double *values_host, int nct, int level, uint64_t *out_dev);
+/* test hook (replaces nothing in the reference): the samples u, e0, e1 ([nct][N] int8 / int32 / int32) of encryption indices first_index .. first_index + nct - 1
+ * under the seeded key, without advancing the counter.  Refused unless the process set SFG_ENABLE_TEST_HOOKS=1 before sfg_ctx_create. */
+int sfg_encrypt_transcript_for_test(sfg_ctx *ctx, uint64_t first_index, int nct, int8_t *u_dev, int32_t *e0_dev, int32_t *e1_dev);
 
 /* ---- B1-B3: Beaver local products (mpc/beavermult.go:94-147) over a prime field of `limbs` 64-bit LE limbs ---- */
 int sfg_beaver_elem_dev(sfg_ctx *ctx, int pid, int limbs, const uint64_t *modulus_host,

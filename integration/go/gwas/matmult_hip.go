@@ -46,7 +46,17 @@ func asRows(A crypto.CipherMatrix) [][]*ckks.Ciphertext {
 
 // finish: the reference starts from crypto.CZeroMat - fresh encryptions of zero - and adds the aggregated giant steps onto it
 // (matmult.go:1174,1225 / :1443,1494); the library returns the deterministic sum, level maxLevel-1, scale A.scale * Params.Scale (:1045,350).
+// With a public key on the device (hip.Ctx.LoadPublicKey) the zeros are made and added there; otherwise by lattigo, one ciphertext at a time.
 func finish(cps *crypto.CryptoParams, h *hip.Ctx, flat []uint64, s, mct, maxLevel int, outScale float64) crypto.CipherMatrix {
+	if h.CanEncrypt() {
+		done := h.AddFreshZero(flat, s*mct, maxLevel-1)
+		out := make(crypto.CipherMatrix, s)
+		w := h.CtWords(maxLevel - 1)
+		for i := range out {
+			out[i] = crypto.CipherVector(h.VecFromFlat(done[i*mct*w:(i+1)*mct*w], mct, maxLevel-1, outScale))
+		}
+		return out
+	}
 	out := crypto.CZeroMat(cps, mct, s) // s rows of mct ciphertexts (basics.go:378-384: CZeroMat(cryptoParams, nrows=mct, ncols=s) -> [s][mct])
 	cps.WithEvaluator(func(eval ckks.Evaluator) error {
 		h.AddFlatInto(eval, asRows(out), flat, maxLevel-1, outScale)

@@ -22,6 +22,7 @@ package hip
 import "C"
 
 import (
+	"crypto/rand"
 	"fmt"
 	"sync"
 	"unsafe"
@@ -113,6 +114,53 @@ func Init(params *ckks.Parameters, rotKs *ckks.RotationKeySet, rlk *ckks.Relinea
 	}
 	Default = h
 	return h
+}
+
+// LoadPublicKey gives the device cryptoParams.Pk (crypto/crypto.go:45: [2] polynomials over QP, NTT + Montgomery form) and seeds its sampler with 32 bytes of
+// crypto/rand - the source lattigo's own encryptor draws from (crypto.go:355 NewEncryptorFromPk).  Call it once per process right after Init (gwas/gwas.go:212);
+// Init keeps its four arguments.  A process that restarts MUST come through here again: the encryption index restarts at 0, and an index may be used only once
+// per key, so the key has to be fresh (INTEGRATION.md, "Encrypting on the device").  With several devices the products are finished on devices[0]'s context.
+func (h *Ctx) LoadPublicKey(pk *ckks.PublicKey) {
+	nmod := h.NQ + h.NP
+	flat := make([]uint64, 2*nmod*h.N)
+	for k := 0; k < 2; k++ {
+		for m := 0; m < nmod; m++ {
+			copy(flat[(k*nmod+m)*h.N:(k*nmod+m+1)*h.N], pk.Value[k].Coeffs[m])
+		}
+	}
+	h.check(C.sfg_ctx_load_public_key(h.p, (*C.uint64_t)(unsafe.Pointer(&flat[0])), 1), "load_public_key")
+	var key [32]byte
+	if _, err := rand.Read(key[:]); err != nil {
+		panic(err)
+	}
+	h.check(C.sfg_ctx_seed_encryptor(h.p, (*C.uint8_t)(unsafe.Pointer(&key[0]))), "seed_encryptor")
+	for i := range key {
+		key[i] = 0
+	}
+}
+
+// CanEncrypt: a public key is loaded (and with it, by LoadPublicKey, a sampler key): products are finished on the device.
+func (h *Ctx) CanEncrypt() bool { return C.sfg_ctx_has_public_key(h.p) != 0 }
+
+// AddFreshZero: crypto.CZeroMat + eval.Add (basics.go:367-384; matmult.go:1174,1225,1443,1494) on the device - every one of the nct ciphertexts of flat
+// ([nct][2][level+1][N]) gets a fresh encryption of zero added; the words never visit lattigo's Add.
+func (h *Ctx) AddFreshZero(flat []uint64, nct, level int) []uint64 {
+	d := h.Upload(flat)
+	defer d.Free()
+	h.check(C.sfg_ct_add_fresh_zero_dev(h.p, d.U64(), C.int(nct), C.int(level)), "add_fresh_zero")
+	return d.Download()
+}
+
+// EncryptFloatVector: crypto.EncryptFloatVector (crypto.go:340-362) - f packed into ceil(len/slots) ciphertexts at `level` (the reference: MaxLevel), default scale.
+func (h *Ctx) EncryptFloatVector(f []float64, level int) []*ckks.Ciphertext {
+	slots := h.N / 2
+	nvec := (len(f) + slots - 1) / slots
+	padded := make([]float64, nvec*slots)
+	copy(padded, f)
+	d := h.Alloc(nvec * h.CtWords(level) * 8)
+	defer d.Free()
+	h.check(C.sfg_encrypt_vectors_dev(h.p, (*C.double)(unsafe.Pointer(&padded[0])), C.int(nvec), C.int(level), d.U64()), "encrypt_vectors")
+	return h.VecFromFlat(d.Download(), nvec, level, h.Params.Scale())
 }
 
 // mcheck is check for the multi-GPU engine's calls (the failing rank is named in the message).

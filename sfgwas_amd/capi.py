@@ -77,6 +77,14 @@ def _sig(L):
         "sfg_ctx_encoder_unprovable": (i, [vp, C.POINTER(C.c_ulonglong)]),
         "sfg_ctx_load_rotkey": (i, [vp, u64, u64p, i]),
         "sfg_ctx_load_secret_key": (i, [vp, u64p, i]),
+        "sfg_ctx_load_public_key": (i, [vp, u64p, i]),
+        "sfg_ctx_has_public_key": (i, [vp]),
+        "sfg_ctx_seed_encryptor": (i, [vp, C.c_char_p]),
+        "sfg_ctx_encryptor_next_index": (i, [vp, C.POINTER(u64)]),
+        "sfg_encrypt_explicit_dev": (i, [vp, vp, i, i, vp, vp, vp, vp]),
+        "sfg_ct_add_fresh_zero_dev": (i, [vp, vp, i, i]),
+        "sfg_encrypt_vectors_dev": (i, [vp, C.POINTER(d), i, i, vp]),
+        "sfg_encrypt_transcript_for_test": (i, [vp, u64, i, vp, vp, vp]),
         "sfg_ct_galois_dev": (i, [vp, vp, vp, i, i, u64]),
         "sfg_ct_mul_scalar_add_dev": (i, [vp, vp, u64p, vp, i, i]),
         "sfg_refresh_gen_shares_dev": (i, [vp, vp, i, i, vp, vp, i, vp, vp, vp, vp]),
@@ -596,6 +604,93 @@ def _ctx_encode_vectors(self, values, level):
 
 
 Context.encode_vectors = _ctx_encode_vectors
+
+
+# ---- public-key encryption on the device (encrypt.hip)
+def _ctx_load_public_key(self, pk_rows, montgomery=False):
+    """pk_rows [2][nq+np][N] uint64, NTT domain (cryptoParams.Pk.Value)"""
+    pk_rows = np.ascontiguousarray(pk_rows, dtype=np.uint64)
+    assert pk_rows.shape == (2, self.nq + self.np_, self.N)
+    self.check(lib().sfg_ctx_load_public_key(self.h, p64(pk_rows), int(montgomery)), "load_public_key")
+
+
+def _ctx_has_public_key(self):
+    return bool(lib().sfg_ctx_has_public_key(self.h))
+
+
+def _ctx_seed_encryptor(self, key32):
+    """key32: 32 bytes from the caller's CSPRNG; resets the encryption index (shared with every fork) to 0"""
+    key32 = bytes(key32)
+    if len(key32) != 32:
+        raise ValueError("the encryptor key is 32 bytes")
+    self.check(lib().sfg_ctx_seed_encryptor(self.h, key32), "seed_encryptor")
+
+
+def _ctx_encryptor_next_index(self):
+    n = C.c_uint64()
+    self.check(lib().sfg_ctx_encryptor_next_index(self.h, C.byref(n)), "encryptor_next_index")
+    return n.value
+
+
+def _ctx_encrypt_explicit(self, pt, level, u, e0, e1):
+    """the deterministic core: pt None or [nct][level+1][N] uint64, u int8 [nct][N], e0/e1 int32 [nct][N] -> host [nct][2][level+1][N]"""
+    u, e0, e1 = (np.ascontiguousarray(u, dtype=np.int8), np.ascontiguousarray(e0, dtype=np.int32), np.ascontiguousarray(e1, dtype=np.int32))
+    nct = u.shape[0]
+    assert u.shape == e0.shape == e1.shape == (nct, self.N)
+    d = [DevArray.from_host(self, a) for a in (u, e0, e1)]
+    dpt = None
+    if pt is not None:
+        pt = np.ascontiguousarray(pt, dtype=np.uint64)
+        assert pt.shape == (nct, level + 1, self.N)
+        dpt = DevArray.from_host(self, pt)
+    out = DevArray(self, (nct, 2, level + 1, self.N))
+    try:
+        self.check(lib().sfg_encrypt_explicit_dev(self.h, None if dpt is None else dpt.p, nct, level, d[0].p, d[1].p, d[2].p, out.p), "encrypt_explicit")
+        return out.host()
+    finally:
+        for a in d + [out] + ([dpt] if dpt is not None else []):
+            a.free()
+
+
+def _ctx_add_fresh_zero(self, ct_dev, level):
+    """ct_dev: DevArray [...][2][level+1][N]; every ciphertext += a fresh encryption of zero, in place"""
+    nct = int(np.prod(ct_dev.shape[:-3])) if len(ct_dev.shape) > 3 else 1
+    assert ct_dev.shape[-3:] == (2, level + 1, self.N)
+    self.check(lib().sfg_ct_add_fresh_zero_dev(self.h, ct_dev.p, nct, level), "add_fresh_zero")
+    return ct_dev
+
+
+def _ctx_encrypt_vectors(self, values, level):
+    """values [nct][slots] float64 -> DevArray [nct][2][level+1][N] (EncryptFloatVector)"""
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    nct = values.shape[0]
+    out = DevArray(self, (max(nct, 1), 2, level + 1, self.N))
+    rc = lib().sfg_encrypt_vectors_dev(self.h, values.ctypes.data_as(C.POINTER(C.c_double)), nct, level, out.p)
+    if rc:
+        out.free()
+    self.check(rc, "encrypt_vectors")
+    return out
+
+
+def _ctx_encrypt_transcript(self, first_index, nct):
+    """test hook: (u int8, e0 int32, e1 int32), each [nct][N], of the given encryption indices; the counter does not move"""
+    d = [DevArray(self, (max(nct, 1), self.N), t) for t in (np.int8, np.int32, np.int32)]
+    try:
+        self.check(lib().sfg_encrypt_transcript_for_test(self.h, int(first_index), nct, d[0].p, d[1].p, d[2].p), "encrypt_transcript")
+        return tuple(a.host() for a in d)
+    finally:
+        for a in d:
+            a.free()
+
+
+Context.load_public_key = _ctx_load_public_key
+Context.has_public_key = _ctx_has_public_key
+Context.seed_encryptor = _ctx_seed_encryptor
+Context.encryptor_next_index = _ctx_encryptor_next_index
+Context.encrypt_explicit = _ctx_encrypt_explicit
+Context.add_fresh_zero = _ctx_add_fresh_zero
+Context.encrypt_vectors = _ctx_encrypt_vectors
+Context.encrypt_transcript = _ctx_encrypt_transcript
 
 
 # ---- resident products (device-level plumbing for the tests and bench.py)

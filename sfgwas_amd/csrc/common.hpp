@@ -105,6 +105,10 @@ struct SfgShared {
     void *enc_tables = nullptr;  // encoder tables (double-double twiddles), see encode.hip
     void *zeros_dev = nullptr;   // 256 B of zeros (DMA source for padded k-steps)
     u64 *sk_dev = nullptr;       // secret-key shard [nq][N], NTT domain, canonical (sfg_ctx_load_secret_key; collective bootstrap shares)
+    u64 *pk_dev = nullptr;       // public key [2][nmod][N], NTT domain, canonical (sfg_ctx_load_public_key; encrypt.hip)
+    // the encryptor's sampler (encrypt.hip): ChaCha20 key, host and device copy, wiped with the root; ONE encryption-index counter for the root and every fork
+    uint32_t enc_key[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint32_t *enc_key_dev = nullptr; bool enc_seeded = false;
+    u64 enc_next = 0;            // next unused encryption index (atomic: __atomic builtins only)
     std::map<u64, RotKey> rotkeys;      // written only by sfg_ctx_load_rotkey / _relinkey (setup time), read by every fork
     SfgConfig cfg;
     int refs = 1;                // the creating context + live forks
@@ -168,6 +172,10 @@ int sfg_sync_all(sfg_ctx *ctx);
 int sfg_encoder_check(sfg_ctx *ctx);
 void sfg_ptc_detach_all(sfg_ctx *ctx);         // matmul.hip: release every plaintext coefficient cache this context owns and clear the owner of its matrices (context destruction)
 void sfg_ptc_invalidate_all(sfg_ctx *ctx);     // matmul.hip: forget every cached coefficient row of the matrices this context owns a cache of (arenas kept)
+
+int encrypt_set_attrs(sfg_ctx *ctx);           // encrypt.hip: dynamic-LDS limits of its kernels
+int sfg_rows_from_montgomery(sfg_ctx *ctx, unsigned long long *rows_dev, size_t nrows, int nmod);   // ctx.hip: lattigo InvMForm of rows with modulus index row % nmod
+void sfg_encrypt_destroy(SfgShared *sh);       // encrypt.hip: wipe the sampler key (host and device), free it and the public key
 
 extern thread_local std::string g_create_error;
 

@@ -168,7 +168,7 @@ extern "C" int sfg_ctx_create_ex(sfg_ctx **out, int device, int logN, int nq, in
     ctx_bind_shared(ctx, sh);
     if (sfg_encoder_init(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
     // dynamic-LDS limits are per (function, device): set here for this context's device, not behind process-wide flags
-    if (mac_bc_set_attrs(ctx) || ntt_set_attrs(ctx) || encode_set_attrs(ctx) || mac_i8_set_attrs(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
+    if (mac_bc_set_attrs(ctx) || ntt_set_attrs(ctx) || encode_set_attrs(ctx) || mac_i8_set_attrs(ctx) || encrypt_set_attrs(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
     *out = ctx;
     return 0;
 }
@@ -211,6 +211,7 @@ extern "C" void sfg_ctx_destroy(sfg_ctx *ctx) {
     if (sh && __atomic_sub_fetch(&sh->refs, 1, __ATOMIC_ACQ_REL) == 0) {
         for (auto &kv : sh->rotkeys) { (void)hipFree(kv.second.key_dev); (void)hipFree(kv.second.index_dev); }
         sfg_encoder_destroy(sh);
+        sfg_encrypt_destroy(sh);
         (void)hipFree(sh->tw_fwd); (void)hipFree(sh->tw_inv); (void)hipFree(sh->pack_fwd); (void)hipFree(sh->pack_inv); (void)hipFree(sh->modc); (void)hipFree(sh->zeros_dev); (void)hipFree(sh->sk_dev);
         delete sh;
     }
@@ -432,6 +433,13 @@ __global__ void k_from_montgomery(u64 *rows, int nmod, const ModConst *modc, siz
     for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < SFG_N; x += gridDim.x * blockDim.x) p[x] = d_mulmod_u64(p[x], r64inv, q);
 }
 
+// rows [nrows][N] with modulus index row % nmod, on ctx->stream (the public key: encrypt.hip)
+int sfg_rows_from_montgomery(sfg_ctx *ctx, u64 *rows_dev, size_t nrows, int nmod) {
+    dim3 grid(8, (unsigned)nrows);
+    hipLaunchKernelGGL(k_from_montgomery, grid, dim3(256), 0, ctx->stream, rows_dev, nmod, ctx->modc, nrows);
+    SFG_HIP(ctx, hipGetLastError());
+    return 0;
+}
 // cryptoParams.Sk.Value (crypto.go:44): this party's secret-key shard, the Q rows [nq][N] in the NTT domain
 extern "C" int sfg_ctx_load_secret_key(sfg_ctx *ctx, const uint64_t *sk_host, int mont) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));

@@ -15,25 +15,8 @@
 // FastBasisExtender); the oracle mirrors it, so results agree bit for bit.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "ksw.hpp"
 
-constexpr int KSW_MAXA = 4;       // max primes per digit (= max np)
-constexpr int KSW_MAXDIG = 8;
-
-struct ExtConst {
-    int a;                                        // source moduli in this digit at this level
-    int src[KSW_MAXA];                            // their global modulus indices
-    double qhat_inv[KSW_MAXA], qhat_inv_q[KSW_MAXA];          // (D/q_m)^-1 mod q_m, and that / q_m
-    double qhat_t[SFG_MAXMOD][KSW_MAXA], qhat_t_q[SFG_MAXMOD][KSW_MAXA];   // (D/q_m) mod q_t, / q_t  (t = global modulus index)
-    double D_t[SFG_MAXMOD], D_t_q[SFG_MAXMOD];    // D mod q_t, / q_t
-};
-struct KswConst {
-    int level, nl, np, nt, beta, alpha;
-    int tmod[SFG_MAXMOD];                         // target slot -> global modulus index (Q_0..level then P)
-    int digit_of[SFG_MAXMOD];                     // target slot -> digit that contains it (or -1 for P targets)
-    ExtConst dig[KSW_MAXDIG];
-    ExtConst pq;                                  // special primes -> Q (ModDown)
-    double pinv[SFG_MAXMOD], pinv_q[SFG_MAXMOD];  // P^-1 mod q_t by global modulus index
-};
 
 static void fill_ext(const sfg_ctx *ctx, ExtConst &e, const std::vector<int> &src) {
     memset(&e, 0, sizeof e);
@@ -58,7 +41,7 @@ static void fill_ext(const sfg_ctx *ctx, ExtConst &e, const std::vector<int> &sr
 }
 
 
-static int get_ksw(sfg_ctx *ctx, int level, KswConst **dev, KswConst *host) {
+int get_ksw(sfg_ctx *ctx, int level, KswConst **dev, KswConst *host) {
     KswConst kc; memset(&kc, 0, sizeof kc);
     kc.level = level; kc.nl = level + 1; kc.np = ctx->np; kc.alpha = ctx->np; kc.nt = kc.nl + kc.np;
     kc.beta = (kc.nl + kc.alpha - 1) / kc.alpha;
@@ -89,34 +72,6 @@ static int get_ksw(sfg_ctx *ctx, int level, KswConst **dev, KswConst *host) {
     return 0;
 }
 
-// general modular product of two canonical residues held in fp64 (both variable): result in (-q, q)
-__device__ __forceinline__ double mulmod2(double a, double b, double q, double qinv) {
-    double h = a * b;
-    double l = __builtin_fma(a, b, -h);
-    double qh = __builtin_rint(h * qinv);
-    double r = __builtin_fma(-qh, q, h);
-    return r + l;
-}
-
-// y_m, v and the extension to one target modulus (lattigo reconstructRNS + multSum restated)
-__device__ __forceinline__ void ext_prepare(const ExtConst &e, const ModConst *modc, const double (&x)[KSW_MAXA], double (&y)[KSW_MAXA], double &v) {
-    double vf = 0.0;
-#pragma unroll
-    for (int m = 0; m < KSW_MAXA; m++) {
-        if (m < e.a) {
-            const ModConst mc = modc[e.src[m]];
-            y[m] = canon(mulmod_lazy(x[m], e.qhat_inv[m], e.qhat_inv_q[m], mc.q), mc.q, mc.qinv);
-            vf += y[m] / mc.q;                                  // IEEE division, accumulated in modulus order
-        }
-    }
-    v = (double)(u64)vf;
-}
-__device__ __forceinline__ double ext_target(const ExtConst &e, int tg, double qt, double qtinv, const double (&y)[KSW_MAXA], double v) {
-    double acc = -mulmod_lazy(v, e.D_t[tg], e.D_t_q[tg], qt);
-#pragma unroll
-    for (int m = 0; m < KSW_MAXA; m++) if (m < e.a) acc += mulmod_lazy(y[m], e.qhat_t[tg][m], e.qhat_t_q[tg][m], qt);
-    return canon(acc, qt, qtinv);
-}
 
 // grid (N/256, beta, B). c2: [B][nl][N] coefficient-domain c1; cx: original ct (c1 rows at +nl*N); ext: [B][beta][nt][N]
 __global__ void __launch_bounds__(256) k_ksw_extend(const u64 *c2, const u64 *ct_in, u64 *ext, const KswConst *kcp, const ModConst *modc) {

@@ -390,6 +390,56 @@ inline DevCipherMatrix ConcatCipherMatrixDev(CryptoParams *cps, const std::vecto
         for (const auto &p : parts) { cps->check(sfg_memcpy_d2d(cps->ctx, out.row(i).ptr(c0), p.row(i).ptr(), p.cols * w * 8), "d2d"); c0 += p.cols; } }
     return out;
 }
+// ---- public-key encryption on the device (encrypt.hip).  PARITY UNPINNED against lattigo's pkEncryptor.EncryptNew (see include/sfgwas_hip.h).
+// cryptoParams.Pk.Value (crypto.go:45): [2][nq+np][N], NTT domain
+inline void LoadPublicKey(CryptoParams *cps, const std::vector<uint64_t> &pk, bool montgomeryForm) {
+    if (pk.size() != (size_t)2 * (size_t)(cps->nq + cps->np) * cps->N()) throw std::runtime_error("LoadPublicKey: expected [2][nq+np][N] words");
+    cps->check(sfg_ctx_load_public_key(cps->ctx, pk.data(), montgomeryForm ? 1 : 0), "LoadPublicKey");
+}
+// the sampler's key: 32 bytes of the caller's CSPRNG (what NewEncryptorFromPk's PRNG draws from crypto/rand, crypto.go:355); never reuse a key
+inline void SeedEncryptor(CryptoParams *cps, const std::vector<uint8_t> &key32) {
+    if (key32.size() != 32) throw std::runtime_error("SeedEncryptor: the key is 32 bytes");
+    cps->check(sfg_ctx_seed_encryptor(cps->ctx, key32.data()), "SeedEncryptor");
+}
+inline bool HasPublicKey(const CryptoParams *cps) { return sfg_ctx_has_public_key(cps->ctx) != 0; }
+// CZeroMat + Add (basics.go:367-384; matmult.go:1174,1225): every ciphertext += a fresh encryption of zero, in place on the device
+inline DevCipherVector CAddFreshZeroDev(CryptoParams *cps, DevCipherVector X) {
+    if (X.n) cps->check(sfg_ct_add_fresh_zero_dev(cps->ctx, X.ptr(), (int)X.n, X.level), "CAddFreshZero");
+    return X;
+}
+inline DevCipherMatrix CAddFreshZeroDev(CryptoParams *cps, DevCipherMatrix M) {
+    if (M.rows * M.cols) cps->check(sfg_ct_add_fresh_zero_dev(cps->ctx, M.buf->u(), (int)(M.rows * M.cols), M.level), "CAddFreshZero");
+    return M;
+}
+// crypto.CZeros (basics.go:367-375): n fresh encryptions of zero at `level` (the reference: MaxLevel), default scale
+inline DevCipherVector CZerosDev(CryptoParams *cps, size_t n, int level) {
+    DevCipherVector o = NewDevCipherVector(cps, n, level, cps->scale);
+    const std::vector<uint64_t> z(detail::ctWords(cps, level), 0);
+    for (size_t i = 0; i < n; i++) cps->check(sfg_memcpy_h2d(cps->ctx, o.ptr(i), z.data(), z.size() * 8), "h2d");
+    return CAddFreshZeroDev(cps, o);
+}
+// crypto.EncryptFloatVector (crypto.go:340-362): f packed into ceil(len/slots) ciphertexts at `level` (the reference: MaxLevel), default scale
+inline DevCipherVector EncryptFloatVectorDev(CryptoParams *cps, const std::vector<double> &f, int level) {
+    const size_t slots = (size_t)cps->GetSlots(), nvec = (f.size() + slots - 1) / slots;
+    std::vector<double> padded(nvec * slots, 0.0);
+    std::copy(f.begin(), f.end(), padded.begin());
+    DevCipherVector o = NewDevCipherVector(cps, nvec, level, cps->scale);
+    cps->check(sfg_encrypt_vectors_dev(cps->ctx, padded.data(), (int)nvec, level, o.ptr()), "EncryptFloatVector");
+    return o;
+}
+// crypto.EncryptFloatMatrixRow (crypto.go:364-388): one EncryptFloatVector per row (rows of equal length), all rows in one call
+inline DevCipherMatrix EncryptFloatMatrixRowDev(CryptoParams *cps, const std::vector<std::vector<double>> &rows, int level) {
+    if (rows.empty()) throw std::runtime_error("EncryptFloatMatrixRow: no rows");
+    const size_t slots = (size_t)cps->GetSlots(), nvec = (rows[0].size() + slots - 1) / slots;
+    std::vector<double> padded(rows.size() * nvec * slots, 0.0);
+    for (size_t i = 0; i < rows.size(); i++) {
+        if (rows[i].size() != rows[0].size()) throw std::runtime_error("EncryptFloatMatrixRow: rows of different lengths");
+        std::copy(rows[i].begin(), rows[i].end(), padded.begin() + i * nvec * slots);
+    }
+    DevCipherMatrix m = NewDevCipherMatrix(cps, rows.size(), nvec, level, cps->scale);
+    cps->check(sfg_encrypt_vectors_dev(cps->ctx, padded.data(), (int)(rows.size() * nvec), level, m.buf->u()), "EncryptFloatMatrixRow");
+    return m;
+}
 namespace detail {
 // n copies of one ciphertext (the length-1 broadcast of CMult / CSub), device to device
 inline DevCipherVector broadcast(const DevCipherVector &x, size_t n) {
@@ -995,6 +1045,12 @@ inline crypto::DevCipherMatrix MatMult4StreamComputeDev(crypto::CryptoParams *cp
     crypto::DevCipherMatrix out = crypto::NewDevCipherMatrix(cps, A.rows, (size_t)m_ct, maxLevel - 1, A.scale * cps->scale);
     cps->check(sfg_matmul_resident_dev(cps->ctx, A.buf->u(), (int)A.rows, A.level, maxLevel, rg.g, rg.flags, out.buf->u()), "MatMult4StreamCompute");
     return out;
+}
+// The same, finished on the device: the deterministic sum added onto fresh encryptions of zero (CZeroMat + Add, matmult.go:1174,1225) before it leaves the call.
+// Needs LoadPublicKey + SeedEncryptor; the overload above keeps returning the deterministic sum.
+inline crypto::DevCipherMatrix MatMult4StreamComputeDev(crypto::CryptoParams *cps, const crypto::DevCipherMatrix &A, int maxLevel, const std::string &cacheFilePrefix, int m_ct, bool addFreshZero) {
+    crypto::DevCipherMatrix out = MatMult4StreamComputeDev(cps, A, maxLevel, cacheFilePrefix, m_ct);
+    return addFreshZero ? crypto::CAddFreshZeroDev(cps, out) : out;
 }
 // QXLazyNormStream (matmult.go:27-77) = local part 1, BootstrapMatAll (network, stays in Go), local part 2.
 //   part 1: QS[i] = CMult(Q[i], XStdInv);  out = MatMult4StreamCompute(QS, 5, Xcache)                         (:36-42)
