@@ -547,6 +547,43 @@ int sfg_encrypt_vectors_dev(sfg_ctx *ctx, const double *values_host, int nct, in
  * under the seeded key, without advancing the counter.  Refused unless the process set SFG_ENABLE_TEST_HOOKS=1 before sfg_ctx_create. */
 int sfg_encrypt_transcript_for_test(sfg_ctx *ctx, uint64_t first_index, int nct, int8_t *u_dev, int32_t *e0_dev, int32_t *e1_dev);
 
+/* ---- the way back out: collective decryption and decoding on the device (decrypt.hip) ----
+ * PARITY UNPINNED: the collective key switch is restated from the published lattigo v2.1 dckks/public_keyswitch.go (PCKSProtocol.GenShare / KeySwitch), the branch
+ * that samples in R_QP and divides by P; with the reference's all-zero public key (mpc/mhe.go:107-220) the ternary sample multiplies zero and drops out.  Neither bit
+ * parity with the Go binary nor the CPU cost these calls replace (lattigo's decoder) can be established without a Go toolchain.  What IS pinned
+ * (tests/test_gpu_decrypt.py): every share word against the big-integer statement, every decoded coefficient bit for bit, every slot against an exact decoder. */
+/* mpc/mhe.go:107-220 CollectiveDecrypt / CollectiveDecryptVec / CollectiveDecryptMat, the local half before the aggregation: PCKSProtocol.GenShare(skShard, zeroPk,
+ * ct, share) on nct ciphertexts [nct][2][level+1][N]:
+ *   h0 [nct][level+1][N] = ModDown_P(NTT_QP(e0)) + sk (.) c1,     h1 [nct][level+1][N] = ModDown_P(NTT_QP(e1))
+ * ModDown_P(NTT_QP(e)) is sfg_encrypt_explicit_dev's for u = 0 and no plaintext (the same code path).  Randomness stays with the caller: e0, e1 int32 [nct][N]
+ * (the reference draws them with sigma 6.36, bound 38: NewPCKSProtocol(parameters, 6.36)).  h1_dev may be NULL (then e1_dev is not read): the reference discards
+ * polynomial 1 after KeySwitch.  Fails without a loaded secret-key shard.  The aggregation over the network stays in Go (mpc/aggregate.go). */
+int sfg_pcks_gen_share_dev(sfg_ctx *ctx, const uint64_t *ct_dev, int nct, int level, const int32_t *e0_dev, const int32_t *e1_dev, uint64_t *h0_dev, uint64_t *h1_dev);
+/* the local half after the aggregation: PCKSProtocol.KeySwitch followed by .Plaintext(): pt [nct][level+1][N] = c0 + h0agg, NTT domain.  The scale is the
+ * ciphertext's; the caller carries it. */
+int sfg_pcks_finish_dev(sfg_ctx *ctx, const uint64_t *ct_dev, int nct, int level, const uint64_t *h0agg_dev, uint64_t *pt_dev);
+/* crypto.DecodeFloatVector (crypto/crypto.go:525-536 -> encoder.Decode; gwas/assoc.go:491,496,587, gwas/utilities.go:385-389): the inverse of sfg_encode_vectors_dev.
+ * pt_dev: NTT-domain plaintext rows [level+1][N] per plaintext, pt_stride words apart (>= (level+1) * N: polynomial 0 of resident ciphertexts can be read in place);
+ * scale: any finite double >= 1 (not a power of two after a rescale).  re_host [nct][slots]: the real parts in lattigo's slot order; im_host NULL (the common case,
+ * ConvertVectorComplexToFloat64 keeps the real parts only: one transform) or [nct][slots] (a second transform).  The real parts are the same bits either way.
+ * All on the device: INTT, CRT to the centred integer p_c in (-Q/2, Q/2] with lattigo's Cmp(QHalf) rule, p_c / scale in double-double, the forward embedding
+ * v_t = sum_c (p_c + i p_{c+n}) / scale * zeta^(5^t c) in double-double, rounded to double once.  Accuracy contract: every returned double d_t satisfies
+ *   |d_t - v_t| <= B max_t |v_t|,   B = 2^-53 + 2^-82    (derivation: decrypt.hip)
+ * for levels 0..11 (level + 1 <= 12 moduli).  Synchronising; like sfg_memcpy_d2h it fails - before anything is launched - while an encoder coefficient within
+ * 2^-50 of a rounding tie is outstanding.  nct == 0 returns 0; a bad level, scale or count is an error that launches nothing. */
+int sfg_decode_vectors(sfg_ctx *ctx, const uint64_t *pt_dev, size_t pt_stride, int nct, int level, double scale, double *re_host, double *im_host);
+/* the same with the doubles left in HBM (re_dev [nct][slots], im_dev NULL or [nct][slots]): stream-ordered, not synchronising */
+int sfg_decode_vectors_dev(sfg_ctx *ctx, const uint64_t *pt_dev, size_t pt_stride, int nct, int level, double scale, double *re_dev, double *im_dev);
+/* the counterpart of sfg_encode_coeffs_host: INTT, CRT and the division only; coeffs_host [nct][N] doubles, each p_c / scale rounded to nearest (half to even) from a
+ * double-double value that is exact for |p_c| < 2^106 and otherwise within 2^-100 relative (correctly rounded unless the quotient lies that close to a rounding boundary). */
+int sfg_decode_coeffs(sfg_ctx *ctx, const uint64_t *pt_dev, size_t pt_stride, int nct, int level, double scale, double *coeffs_host);
+/* gwas/gwas.go:385-386 (CollectiveDecryptVec, then DecodeFloatVector) after the aggregation, in one call: sfg_pcks_finish_dev + sfg_decode_vectors, same doubles,
+ * no plaintext rows returned to the caller */
+int sfg_pcks_finish_decode(sfg_ctx *ctx, const uint64_t *ct_dev, int nct, int level, double scale, const uint64_t *h0agg_dev, double *re_host, double *im_host);
+/* crypto.DecryptFloatVector (crypto/crypto.go:489-510; DecryptFloat / DecryptMultipleFloat / DecryptFloatMatrix, :446-523) with the loaded key as the WHOLE secret
+ * key: c0 + sk (.) c1, then sfg_decode_vectors.  Fails without a loaded secret key. */
+int sfg_decrypt_vectors(sfg_ctx *ctx, const uint64_t *ct_dev, int nct, int level, double scale, double *re_host, double *im_host);
+
 /* ---- B1-B3: Beaver local products (mpc/beavermult.go:94-147) over a prime field of `limbs` 64-bit LE limbs ---- */
 int sfg_beaver_elem_dev(sfg_ctx *ctx, int pid, int limbs, const uint64_t *modulus_host,
                         const uint64_t *ar_dev, const uint64_t *am_dev, const uint64_t *br_dev, const uint64_t *bm_dev,

@@ -228,3 +228,20 @@ func CRescale(cryptoParams *CryptoParams, X CipherVector) CipherVector {
 	}
 	return X
 }
+
+// DecryptFloatVector - crypto/crypto.go:489-510: decrypt under the loaded secret key and decode on the device; the first N values.  The ciphertexts of X are
+// read at their common (lowest) level and X[0]'s scale, as the reference decrypts one vector of one computation.
+func DecryptFloatVector(cryptoParams *CryptoParams, X CipherVector, N int) []float64 {
+	h := hip.Default
+	level := minLevel(X)
+	return h.DecryptFloatVector(h.FlattenVec(X, len(X), level), len(X), level, X[0].Scale())[:N]
+}
+
+// DecryptFloatMatrix - crypto/crypto.go:512-523: DecryptFloatVector per row.
+func DecryptFloatMatrix(cryptoParams *CryptoParams, X CipherMatrix, N int) [][]float64 {
+	out := make([][]float64, len(X))
+	for i := range X {
+		out[i] = DecryptFloatVector(cryptoParams, X[i], N)
+	}
+	return out
+}

@@ -163,6 +163,59 @@ func (h *Ctx) EncryptFloatVector(f []float64, level int) []*ckks.Ciphertext {
 	return h.VecFromFlat(d.Download(), nvec, level, h.Params.Scale())
 }
 
+// LoadSecretKey gives the device cryptoParams.Sk (crypto/crypto.go:44, NTT + Montgomery form): this party's shard for the collective calls, the whole key for
+// DecryptFloatVector.
+func (h *Ctx) LoadSecretKey(sk *ckks.SecretKey) {
+	flat := make([]uint64, h.NQ*h.N)
+	for m := 0; m < h.NQ; m++ {
+		copy(flat[m*h.N:(m+1)*h.N], sk.Value.Coeffs[m])
+	}
+	h.check(C.sfg_ctx_load_secret_key(h.p, (*C.uint64_t)(unsafe.Pointer(&flat[0])), 1), "load_secret_key")
+}
+
+// DecodeFloatVector: crypto.DecodeFloatVector (crypto.go:525-536) - the real parts of every slot of nvec NTT-domain plaintexts ([nvec][level+1][N] words).
+func (h *Ctx) DecodeFloatVector(flat []uint64, nvec, level int, scale float64) []float64 {
+	d := h.Upload(flat)
+	defer d.Free()
+	out := make([]float64, nvec*h.N/2)
+	h.check(C.sfg_decode_vectors(h.p, d.U64(), C.size_t((level+1)*h.N), C.int(nvec), C.int(level), C.double(scale), (*C.double)(unsafe.Pointer(&out[0])), nil), "decode_vectors")
+	return out
+}
+
+// DecryptFloatVector: crypto.DecryptFloatVector (crypto.go:489-510) under the loaded key - nct ciphertexts ([nct][2][level+1][N] words) to nct * slots reals.
+func (h *Ctx) DecryptFloatVector(flat []uint64, nct, level int, scale float64) []float64 {
+	d := h.Upload(flat)
+	defer d.Free()
+	out := make([]float64, nct*h.N/2)
+	h.check(C.sfg_decrypt_vectors(h.p, d.U64(), C.int(nct), C.int(level), C.double(scale), (*C.double)(unsafe.Pointer(&out[0])), nil), "decrypt_vectors")
+	return out
+}
+
+// PCKSGenShare: the local half of mpc.CollectiveDecrypt* before the aggregation (mhe.go:107-220: PCKSProtocol.GenShare with the zero public key); e0 holds the
+// caller's Gaussian draws, [nct][N].  Returns polynomial 0 of every share, [nct][level+1][N]; polynomial 1 is discarded by the reference and not computed.
+func (h *Ctx) PCKSGenShare(flat []uint64, nct, level int, e0 []int32) []uint64 {
+	d := h.Upload(flat)
+	defer d.Free()
+	de := h.Alloc(len(e0) * 4)
+	defer de.Free()
+	h.check(C.sfg_memcpy_h2d(h.p, de.Ptr(), unsafe.Pointer(&e0[0]), C.size_t(len(e0)*4)), "h2d")
+	dh := h.Alloc(nct * (level + 1) * h.N * 8)
+	defer dh.Free()
+	h.check(C.sfg_pcks_gen_share_dev(h.p, d.U64(), C.int(nct), C.int(level), (*C.int32_t)(de.Ptr()), nil, dh.U64(), nil), "pcks_gen_share")
+	return dh.Download()
+}
+
+// PCKSFinishDecode: the local half after the aggregation, fused with the decoding (gwas/gwas.go:385-386): KeySwitch, .Plaintext(), DecodeFloatVector.
+func (h *Ctx) PCKSFinishDecode(flat []uint64, nct, level int, scale float64, h0agg []uint64) []float64 {
+	d := h.Upload(flat)
+	defer d.Free()
+	dh := h.Upload(h0agg)
+	defer dh.Free()
+	out := make([]float64, nct*h.N/2)
+	h.check(C.sfg_pcks_finish_decode(h.p, d.U64(), C.int(nct), C.int(level), C.double(scale), dh.U64(), (*C.double)(unsafe.Pointer(&out[0])), nil), "pcks_finish_decode")
+	return out
+}
+
 // mcheck is check for the multi-GPU engine's calls (the failing rank is named in the message).
 func (h *Ctx) mcheck(rc C.int, what string) {
 	if rc != 0 {

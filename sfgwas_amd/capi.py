@@ -85,6 +85,13 @@ def _sig(L):
         "sfg_ct_add_fresh_zero_dev": (i, [vp, vp, i, i]),
         "sfg_encrypt_vectors_dev": (i, [vp, C.POINTER(d), i, i, vp]),
         "sfg_encrypt_transcript_for_test": (i, [vp, u64, i, vp, vp, vp]),
+        "sfg_pcks_gen_share_dev": (i, [vp, vp, i, i, vp, vp, vp, vp]),
+        "sfg_pcks_finish_dev": (i, [vp, vp, i, i, vp, vp]),
+        "sfg_decode_vectors": (i, [vp, vp, sz, i, i, d, vp, vp]),
+        "sfg_decode_vectors_dev": (i, [vp, vp, sz, i, i, d, vp, vp]),
+        "sfg_decode_coeffs": (i, [vp, vp, sz, i, i, d, vp]),
+        "sfg_pcks_finish_decode": (i, [vp, vp, i, i, d, vp, vp, vp]),
+        "sfg_decrypt_vectors": (i, [vp, vp, i, i, d, vp, vp]),
         "sfg_ct_galois_dev": (i, [vp, vp, vp, i, i, u64]),
         "sfg_ct_mul_scalar_add_dev": (i, [vp, vp, u64p, vp, i, i]),
         "sfg_refresh_gen_shares_dev": (i, [vp, vp, i, i, vp, vp, i, vp, vp, vp, vp]),
@@ -691,6 +698,108 @@ Context.encrypt_explicit = _ctx_encrypt_explicit
 Context.add_fresh_zero = _ctx_add_fresh_zero
 Context.encrypt_vectors = _ctx_encrypt_vectors
 Context.encrypt_transcript = _ctx_encrypt_transcript
+
+
+# ---- collective decryption and decoding on the device (decrypt.hip)
+def _dev_ptr(self, a, dtype, shape=None):
+    """(pointer, DevArray to free or None): a DevArray is used in place, a host array is uploaded"""
+    if isinstance(a, DevArray):
+        return a.p, None
+    a = np.ascontiguousarray(a, dtype=dtype)
+    assert shape is None or a.shape == shape, (a.shape, shape)
+    d = DevArray.from_host(self, a)
+    return d.p, d
+
+
+def _ctx_pcks_gen_share(self, cts, level, e0, e1=None):
+    """cts [nct][2][level+1][N] (DevArray or host), e0 / e1 int32 [nct][N] -> host (h0, h1) [nct][level+1][N]; e1 None: h1 is not computed (None)"""
+    nct = int(cts.shape[0])
+    keep = []
+    try:
+        pc, t = _dev_ptr(self, cts, np.uint64, (nct, 2, level + 1, self.N)); keep.append(t)
+        p0, t = _dev_ptr(self, e0, np.int32, (nct, self.N)); keep.append(t)
+        p1 = None
+        if e1 is not None:
+            p1, t = _dev_ptr(self, e1, np.int32, (nct, self.N)); keep.append(t)
+        h0 = DevArray(self, (nct, level + 1, self.N)); keep.append(h0)
+        h1 = None
+        if e1 is not None:
+            h1 = DevArray(self, (nct, level + 1, self.N)); keep.append(h1)
+        self.check(lib().sfg_pcks_gen_share_dev(self.h, pc, nct, level, p0, p1, h0.p, None if h1 is None else h1.p), "pcks_gen_share")
+        return h0.host(), (None if h1 is None else h1.host())
+    finally:
+        for a in keep:
+            if a is not None:
+                a.free()
+
+
+def _ctx_pcks_finish(self, cts, level, h0agg, scale=None, want_imag=False):
+    """scale None: the plaintext rows [nct][level+1][N] (host); else the fused finish + decode: real parts [nct][slots] (and the imaginary parts)"""
+    nct = int(cts.shape[0])
+    keep = []
+    try:
+        pc, t = _dev_ptr(self, cts, np.uint64, (nct, 2, level + 1, self.N)); keep.append(t)
+        ph, t = _dev_ptr(self, h0agg, np.uint64, (nct, level + 1, self.N)); keep.append(t)
+        if scale is None:
+            pt = DevArray(self, (nct, level + 1, self.N)); keep.append(pt)
+            self.check(lib().sfg_pcks_finish_dev(self.h, pc, nct, level, ph, pt.p), "pcks_finish")
+            return pt.host()
+        re = np.empty((nct, self.slots)); im = np.empty((nct, self.slots)) if want_imag else None
+        self.check(lib().sfg_pcks_finish_decode(self.h, pc, nct, level, float(scale), ph, re.ctypes.data_as(C.c_void_p),
+                                                None if im is None else im.ctypes.data_as(C.c_void_p)), "pcks_finish_decode")
+        return (re, im) if want_imag else re
+    finally:
+        for a in keep:
+            if a is not None:
+                a.free()
+
+
+def _ctx_decode_vectors(self, pt, level, scale, want_imag=False, stride=None):
+    """pt: DevArray or host rows; [nct][level+1][N] plaintexts, or (stride = 2 (level+1) N) ciphertexts whose polynomial 0 is read in place"""
+    nct = int(pt.shape[0])
+    p, t = _dev_ptr(self, pt, np.uint64)
+    try:
+        re = np.empty((nct, self.slots)); im = np.empty((nct, self.slots)) if want_imag else None
+        self.check(lib().sfg_decode_vectors(self.h, p, (level + 1) * self.N if stride is None else int(stride), nct, level, float(scale),
+                                            re.ctypes.data_as(C.c_void_p), None if im is None else im.ctypes.data_as(C.c_void_p)), "decode_vectors")
+        return (re, im) if want_imag else re
+    finally:
+        if t is not None:
+            t.free()
+
+
+def _ctx_decode_coeffs(self, pt, level, scale, stride=None):
+    nct = int(pt.shape[0])
+    p, t = _dev_ptr(self, pt, np.uint64)
+    try:
+        out = np.empty((nct, self.N))
+        self.check(lib().sfg_decode_coeffs(self.h, p, (level + 1) * self.N if stride is None else int(stride), nct, level, float(scale),
+                                           out.ctypes.data_as(C.c_void_p)), "decode_coeffs")
+        return out
+    finally:
+        if t is not None:
+            t.free()
+
+
+def _ctx_decrypt_vectors(self, cts, level, scale, want_imag=False):
+    """cts [nct][2][level+1][N] (DevArray or host) under the loaded secret key -> real parts [nct][slots] (and the imaginary parts)"""
+    nct = int(np.prod(cts.shape[:-3]))
+    p, t = _dev_ptr(self, cts, np.uint64)
+    try:
+        re = np.empty((nct, self.slots)); im = np.empty((nct, self.slots)) if want_imag else None
+        self.check(lib().sfg_decrypt_vectors(self.h, p, nct, level, float(scale), re.ctypes.data_as(C.c_void_p),
+                                             None if im is None else im.ctypes.data_as(C.c_void_p)), "decrypt_vectors")
+        return (re, im) if want_imag else re
+    finally:
+        if t is not None:
+            t.free()
+
+
+Context.pcks_gen_share = _ctx_pcks_gen_share
+Context.pcks_finish = _ctx_pcks_finish
+Context.decode_vectors = _ctx_decode_vectors
+Context.decode_coeffs = _ctx_decode_coeffs
+Context.decrypt_vectors = _ctx_decrypt_vectors
 
 
 # ---- resident products (device-level plumbing for the tests and bench.py)

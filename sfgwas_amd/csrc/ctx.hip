@@ -22,6 +22,7 @@ int sfg_kernel_attrs_init(sfg_ctx *ctx);  // raises the dynamic-LDS limits of ev
 int mac_bc_set_attrs(sfg_ctx *ctx);
 int ntt_set_attrs(sfg_ctx *ctx);
 int encode_set_attrs(sfg_ctx *ctx);
+int decrypt_set_attrs(sfg_ctx *ctx);   // decrypt.hip
 int mac_i8_set_attrs(sfg_ctx *ctx);
 
 // The configuration surface.
@@ -168,7 +169,7 @@ extern "C" int sfg_ctx_create_ex(sfg_ctx **out, int device, int logN, int nq, in
     ctx_bind_shared(ctx, sh);
     if (sfg_encoder_init(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
     // dynamic-LDS limits are per (function, device): set here for this context's device, not behind process-wide flags
-    if (mac_bc_set_attrs(ctx) || ntt_set_attrs(ctx) || encode_set_attrs(ctx) || mac_i8_set_attrs(ctx) || encrypt_set_attrs(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
+    if (mac_bc_set_attrs(ctx) || ntt_set_attrs(ctx) || encode_set_attrs(ctx) || mac_i8_set_attrs(ctx) || encrypt_set_attrs(ctx) || decrypt_set_attrs(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
     *out = ctx;
     return 0;
 }

@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(512) k_enc_fwd(EncSrc src, const u64 *pk, u64 
 #pragma unroll
         for (int i = 0; i < 8; i++) key[i] = src.key[i];
         enc_sample_thread(key, src.index0 + ct, tid, su, s0, s1);
-    } else { up = src.u + ct * N; e0p = src.e0 + ct * N; e1p = src.e1 + ct * N; }
+    } else { up = src.u ? src.u + ct * N : nullptr; e0p = src.e0 + ct * N; e1p = src.e1 + ct * N; }
     const int b = tid >> 4, c = tid & 15;
     for (int t = 0; t < nt; t++) {
         const int m = t < nl ? t : nq + (t - nl);
@@ -141,6 +141,7 @@ __global__ void __launch_bounds__(512) k_enc_fwd(EncSrc src, const u64 *pk, u64 
             __syncthreads();                                       // the image has been read
         }
         // NTT_m(u), and as its epilogue t_p = pk_p (.) u^ + e_p^
+        if (!SAMPLE && !pk) continue;                              // (uniform) the zero public key of a collective key switch (decrypt.hip): u drops out, t_p = e_p^ as written
 #pragma unroll
         for (int a = 0; a < 32; a++) v[a] = SAMPLE ? byte_of(su, a) : (double)up[a * 512 + tid];
         ntt_fwd_phases(v, lds, tw, pack, q, qinv, tid);
@@ -233,7 +234,7 @@ void sfg_encrypt_destroy(SfgShared *sh) {
 
 // ---------------------------------------------------------------- host side
 // the three steps for nct ciphertexts, in chunks whose T rows fit 1 GiB of scratch.  mode 0: out = Enc(pt) (pt nullable: zero); mode 1: out += Enc(0)
-static int encrypt_run(sfg_ctx *ctx, const EncSrc &src0, const u64 *pt, int nct, int level, int mode, u64 *out) {
+static int encrypt_run(sfg_ctx *ctx, const EncSrc &src0, const u64 *pk, const u64 *pt, int nct, int level, int mode, u64 *out) {
     const int N = SFG_N, nl = level + 1, np = ctx->np, nt = nl + np;
     KswConst *kcd; KswConst kc;
     SFG_TRY(get_ksw(ctx, level, &kcd, &kc));
@@ -251,9 +252,9 @@ static int encrypt_run(sfg_ctx *ctx, const EncSrc &src0, const u64 *pt, int nct,
         const int nb = nct - c0 < chunk ? nct - c0 : chunk;
         EncSrc src = src0;
         if (src.key) src.index0 += (u64)c0;
-        else { src.u += (size_t)c0 * N; src.e0 += (size_t)c0 * N; src.e1 += (size_t)c0 * N; }
-        if (src.key) hipLaunchKernelGGL(k_enc_fwd<true>, dim3(nb), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, ctx->sh->pk_dev, T, nl, np, ctx->nq, ctx->nmod, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
-        else hipLaunchKernelGGL(k_enc_fwd<false>, dim3(nb), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, ctx->sh->pk_dev, T, nl, np, ctx->nq, ctx->nmod, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
+        else { if (src.u) src.u += (size_t)c0 * N; src.e0 += (size_t)c0 * N; src.e1 += (size_t)c0 * N; }
+        if (src.key) hipLaunchKernelGGL(k_enc_fwd<true>, dim3(nb), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, pk, T, nl, np, ctx->nq, ctx->nmod, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
+        else hipLaunchKernelGGL(k_enc_fwd<false>, dim3(nb), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, pk, T, nl, np, ctx->nq, ctx->nmod, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
         SFG_HIP(ctx, hipGetLastError());
         SFG_TRY(launch_ntt_inv_map(ctx, T + (size_t)nl * N, T + (size_t)nl * N, (size_t)nb * 2 * np, pp, rm));
         u64 *o = out + (size_t)c0 * 2 * nl * N;
@@ -317,12 +318,19 @@ extern "C" int sfg_ctx_encryptor_next_index(const sfg_ctx *ctx, uint64_t *next) 
     return 0;
 }
 
+// decrypt.hip: (ModDown_P(NTT_QP(e0)), ModDown_P(NTT_QP(e1))) for nct pairs of error polynomials, out [nct][2][level+1][N] - sfg_encrypt_explicit_dev for the zero public
+// key (u multiplies zero and drops out) and no plaintext: the same three launches, the same ModDown
+int encrypt_errors_moddown(sfg_ctx *ctx, const int32_t *e0, const int32_t *e1, int nct, int level, u64 *out) {
+    if (ctx->np < 1 || ctx->np > KSW_MAXA) SFG_FAIL(ctx, "pcks_gen_share: needs 1..%d special primes", KSW_MAXA);
+    EncSrc src{nullptr, e0, e1, nullptr, 0};
+    return encrypt_run(ctx, src, nullptr, nullptr, nct, level, 0, out);
+}
 extern "C" int sfg_encrypt_explicit_dev(sfg_ctx *ctx, const uint64_t *pt, int nct, int level, const int8_t *u, const int32_t *e0, const int32_t *e1, uint64_t *out) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
     SFG_TRY(enc_check_common(ctx, "encrypt_explicit", nct, level));
     if (!u || !e0 || !e1 || !out) SFG_FAIL(ctx, "encrypt_explicit: NULL polynomial or output");
     EncSrc src{u, e0, e1, nullptr, 0};
-    return encrypt_run(ctx, src, (const u64 *)pt, nct, level, 0, (u64 *)out);
+    return encrypt_run(ctx, src, ctx->sh->pk_dev, (const u64 *)pt, nct, level, 0, (u64 *)out);
 }
 extern "C" int sfg_ct_add_fresh_zero_dev(sfg_ctx *ctx, uint64_t *ct, int nct, int level) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
@@ -330,7 +338,7 @@ extern "C" int sfg_ct_add_fresh_zero_dev(sfg_ctx *ctx, uint64_t *ct, int nct, in
     if (!ct) SFG_FAIL(ctx, "add_fresh_zero: NULL ciphertexts");
     u64 first; SFG_TRY(enc_take_indices(ctx, "add_fresh_zero", nct, &first));
     EncSrc src{nullptr, nullptr, nullptr, ctx->sh->enc_key_dev, first};
-    return encrypt_run(ctx, src, nullptr, nct, level, 1, (u64 *)ct);
+    return encrypt_run(ctx, src, ctx->sh->pk_dev, nullptr, nct, level, 1, (u64 *)ct);
 }
 extern "C" int sfg_encrypt_vectors_dev(sfg_ctx *ctx, const double *values_host, int nct, int level, uint64_t *out) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
@@ -343,7 +351,7 @@ extern "C" int sfg_encrypt_vectors_dev(sfg_ctx *ctx, const double *values_host, 
     SFG_TRY(sfg_encode_vectors_dev(ctx, values_host, nct, level, (uint64_t *)ptp));      // the encoder's own rows (and its domain / rounding checks), before an index is spent
     u64 first; SFG_TRY(enc_take_indices(ctx, "encrypt_vectors", nct, &first));
     EncSrc src{nullptr, nullptr, nullptr, ctx->sh->enc_key_dev, first};
-    return encrypt_run(ctx, src, (const u64 *)ptp, nct, level, 0, (u64 *)out);
+    return encrypt_run(ctx, src, ctx->sh->pk_dev, (const u64 *)ptp, nct, level, 0, (u64 *)out);
 }
 extern "C" int sfg_encrypt_transcript_for_test(sfg_ctx *ctx, uint64_t first_index, int nct, int8_t *u, int32_t *e0, int32_t *e1) {
     if (!ctx->test_hooks) SFG_FAIL(ctx, "sfg_encrypt_transcript_for_test: test hook, enabled only in a process that set the test switch before creating the context");

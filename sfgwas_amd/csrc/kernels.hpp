@@ -58,6 +58,11 @@ int i8_ride_tiles(sfg_ctx *ctx, int K, int L, int8_t **Bs, int8_t **Bb);        
 struct I8Args;                                                      // i8_move.hpp
 void launch_i8_pack_pt_digits(hipStream_t q, const I8Args &a, unsigned items, bool big);      // the transposition pass of digit-plane panel rows
 void launch_move_alone(hipStream_t q, const MoveJob &j);           // the same by mover workgroups alone on queue q
+// refresh.hip: h = rows + sk (.) xr and out = a + b over [nct][nl][N] rows taken from strided sources (the loaded secret-key shard)
+int launch_share(sfg_ctx *ctx, const u64 *rows, size_t rows_ct_stride, const u64 *xr, size_t x_ct_stride, u64 *h, int nl, int nct);
+int launch_add_rows(sfg_ctx *ctx, const u64 *a, size_t a_ct_stride, const u64 *b, size_t b_ct_stride, u64 *out, size_t out_ct_stride, int nl, int nct);
+// encrypt.hip: the deterministic encryption core for the zero public key: out [nct][2][level+1][N] = (ModDown_P(NTT_QP(e0)), ModDown_P(NTT_QP(e1)))
+int encrypt_errors_moddown(sfg_ctx *ctx, const int32_t *e0, const int32_t *e1, int nct, int level, u64 *out);
 // genoio.hip: dense int8 copy [nr][ld_out] of the stored sub-block (r0.., c0..) of a 2-bit packed matrix (c0 a multiple of 4)
 int launch_geno_unpack(sfg_ctx *ctx, const sfg_geno *g, size_t r0, size_t c0, size_t nr, size_t nc, int8_t *out, size_t ld_out);
 // rotate.hip

@@ -13,15 +13,7 @@
 //               c0' = NTT(x) + sum h1,  c1' = crs.
 #include "common.hpp"
 #include "kernels.hpp"
-
-constexpr int RF_MAXL = 12;       // moduli of the input level
-struct RecodeConst {
-    int nl, nq;
-    double inv[RF_MAXL][RF_MAXL];         // inv[i][t] = q_t^-1 mod q_i, t < i
-    double half[RF_MAXL];                 // mixed-radix digits of floor(Q_level / 2)
-    double qm[SFG_MAXMOD][RF_MAXL];       // q_i mod q_j for the new moduli j >= nl
-    double Qmod[SFG_MAXMOD];              // Q_level mod q_j
-};
+#include "recode.hpp"
 
 // rows[(ct, j)][x] = (mask + e)[ct][x] mod q_j, coefficient domain.  mask: [nct][N][W] two's-complement 64-bit limbs; e: [nct][N] int32.
 // Horner over 32-bit digits in exact fp64: acc * 2^32 + digit.  grid (N/256, nmod, nct)
@@ -48,15 +40,13 @@ __global__ void __launch_bounds__(256) k_small_rows(const int *e, u64 *rows, int
     const long long v = e[c * N + x];
     rows[(c * nmod + j) * (size_t)N + x] = v < 0 ? modc[j].qi - (u64)(-v) : (u64)v;
 }
-// h = rows + sk (.) xrow (mod q), negated if neg.  rows/h: [nct][nmod][N]; xrow: row (ct, j) at x + ct * x_ct_stride + j * N.  grid (N/256, nmod, nct)
-__global__ void __launch_bounds__(256) k_share(const u64 *rows, const u64 *sk, const u64 *xr, size_t x_ct_stride, u64 *h, int nmod, int neg, const ModConst *modc) {
+// h = rows + sk (.) xrow (mod q), negated if neg.  h: [nct][nmod][N]; rows: row (ct, j) at x + ct * rows_ct_stride + j * N; xrow: row (ct, j) at x + ct * x_ct_stride + j * N.  grid (N/256, nmod, nct)
+__global__ void __launch_bounds__(256) k_share(const u64 *rows, size_t rows_ct_stride, const u64 *sk, const u64 *xr, size_t x_ct_stride, u64 *h, int nmod, int neg, const ModConst *modc) {
     const int N = SFG_N, x = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y; const size_t c = blockIdx.z;
     const double q = modc[j].q, qinv = modc[j].qinv;
     const size_t i = (c * nmod + j) * (size_t)N + x;
     const double s = u64_to_f64(sk[(size_t)j * N + x]), v = u64_to_f64(xr[c * x_ct_stride + (size_t)j * N + x]);
-    const double hh = s * v, ll = __builtin_fma(s, v, -hh);
-    double r = canon(__builtin_fma(-__builtin_rint(hh * qinv), q, hh) + ll, q, qinv) + u64_to_f64(rows[i]);
-    r = r >= q ? r - q : r;
+    double r = share_word(s, v, u64_to_f64(rows[c * rows_ct_stride + (size_t)j * N + x]), q, qinv);
     if (neg) r = r == 0.0 ? 0.0 : q - r;
     h[i] = f64_to_u64(r);
 }
@@ -74,19 +64,8 @@ __global__ void __launch_bounds__(256) k_recode(const u64 *xin, u64 *out, Recode
     const int nl = rc.nl, nq = rc.nq;
     double v[RF_MAXL], r[RF_MAXL];
     for (int i = 0; i < nl; i++) r[i] = u64_to_f64(xin[(c * nl + i) * (size_t)N + x]);
-    // Garner: x = v0 + v1 q0 + v2 q0 q1 + ..., 0 <= v_i < q_i
-    for (int i = 0; i < nl; i++) {
-        const double q = modc[i].q, qinv = modc[i].qinv;
-        double t = r[i];
-        for (int s = 0; s < i; s++) {
-            const double d = t - canon(v[s], q, qinv);                         // (-q, q)
-            t = canon(mulmod_lazy(d, rc.inv[i][s], rc.inv[i][s] * qinv, q), q, qinv);
-        }
-        v[i] = t;
-    }
-    // x >= floor(Q/2)  (lattigo: Cmp(QHalf) is 1 or 0)  ->  the represented value is x - Q
-    bool neg = true;                                                           // all digits equal: x == QHalf counts as negative
-    for (int i = nl - 1; i >= 0; i--) if (v[i] != rc.half[i]) { neg = v[i] > rc.half[i]; break; }
+    garner_digits(r, v, nl, rc, modc);
+    const bool neg = garner_negative(v, nl, rc);
     u64 *o = out + c * 2 * nq * (size_t)N + x;
     for (int j = 0; j < nl; j++) o[(size_t)j * N] = f64_to_u64(r[j]);           // x and x - Q agree modulo the moduli of Q
     for (int j = nl; j < nq; j++) {
@@ -184,18 +163,10 @@ struct RecodeBig { u64 Q[BG]; u64 qi[RF_MAXL]; };
 __global__ void __launch_bounds__(256) k_recode_scaled(const u64 *xin, u64 *out, RecodeConst rc, RecodeBig rb, ScaleRatio sr, const ModConst *modc) {
     const int N = SFG_N, x = blockIdx.x * 256 + threadIdx.x; const size_t c = blockIdx.y;
     const int nl = rc.nl, nq = rc.nq;
-    double v[RF_MAXL];
-    for (int i = 0; i < nl; i++) {
-        const double q = modc[i].q, qinv = modc[i].qinv;
-        double t = u64_to_f64(xin[(c * nl + i) * (size_t)N + x]);
-        for (int s = 0; s < i; s++) {
-            const double d = t - canon(v[s], q, qinv);
-            t = canon(mulmod_lazy(d, rc.inv[i][s], rc.inv[i][s] * qinv, q), q, qinv);
-        }
-        v[i] = t;
-    }
-    bool neg = true;
-    for (int i = nl - 1; i >= 0; i--) if (v[i] != rc.half[i]) { neg = v[i] > rc.half[i]; break; }
+    double v[RF_MAXL], r[RF_MAXL];
+    for (int i = 0; i < nl; i++) r[i] = u64_to_f64(xin[(c * nl + i) * (size_t)N + x]);
+    garner_digits(r, v, nl, rc, modc);
+    const bool neg = garner_negative(v, nl, rc);
     u64 a[BG];
 #pragma unroll
     for (int i = 0; i < BG; i++) a[i] = 0;
@@ -266,14 +237,14 @@ static int refresh_gen_shares(sfg_ctx *ctx, const uint64_t *ct, int nct, int lev
     SFG_HIP(ctx, hipGetLastError());
     ModPattern p0; p0.period = nl; for (int j = 0; j < nl; j++) p0.m[j] = (int8_t)j;
     SFG_TRY(launch_ntt_fwd(ctx, (const u64 *)h0, (u64 *)h0, (size_t)nct * nl, p0));
-    hipLaunchKernelGGL(k_share, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const u64 *)h0, sk, (const u64 *)ct + (size_t)nl * N, (size_t)2 * nl * N, (u64 *)h0, nl, 0, ctx->modc);
+    hipLaunchKernelGGL(k_share, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const u64 *)h0, (size_t)nl * N, sk, (const u64 *)ct + (size_t)nl * N, (size_t)2 * nl * N, (u64 *)h0, nl, 0, ctx->modc);
     // h1: all nq moduli, against the common reference polynomial, negated
     if (sr) hipLaunchKernelGGL(k_bigint_rows_scaled, dim3(N / 256, nct), dim3(256), 0, ctx->stream, (const u64 *)mask, W, (const int *)e1, (u64 *)h1, nq, *sr, ctx->modc);
     else hipLaunchKernelGGL(k_bigint_rows, dim3(N / 256, nq, nct), dim3(256), 0, ctx->stream, (const u64 *)mask, W, (const int *)e1, (u64 *)h1, nq, ctx->modc);
     SFG_HIP(ctx, hipGetLastError());
     ModPattern p1; p1.period = nq; for (int j = 0; j < nq; j++) p1.m[j] = (int8_t)j;
     SFG_TRY(launch_ntt_fwd(ctx, (const u64 *)h1, (u64 *)h1, (size_t)nct * nq, p1));
-    hipLaunchKernelGGL(k_share, dim3(N / 256, nq, nct), dim3(256), 0, ctx->stream, (const u64 *)h1, sk, (const u64 *)crs, (size_t)nq * N, (u64 *)h1, nq, 1, ctx->modc);
+    hipLaunchKernelGGL(k_share, dim3(N / 256, nq, nct), dim3(256), 0, ctx->stream, (const u64 *)h1, (size_t)nq * N, sk, (const u64 *)crs, (size_t)nq * N, (u64 *)h1, nq, 1, ctx->modc);
     SFG_HIP(ctx, hipGetLastError());
     return 0;
 }
@@ -301,7 +272,7 @@ extern "C" int sfg_ckks_to_ss_share_dev(sfg_ctx *ctx, const uint64_t *ct, int nc
     SFG_HIP(ctx, hipGetLastError());
     SFG_TRY(launch_ntt_fwd(ctx, (const u64 *)h0, (u64 *)h0, (size_t)nct * nl, p0));
     hipLaunchKernelGGL(k_add_rows, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const u64 *)h0, (size_t)nl * N, (const u64 *)mask_ntt, (size_t)nl * N, (u64 *)h0, (size_t)nl * N, ctx->modc);
-    hipLaunchKernelGGL(k_share, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const u64 *)h0, ctx->sh->sk_dev, (const u64 *)ct + (size_t)nl * N, (size_t)2 * nl * N, (u64 *)h0, nl, 0, ctx->modc);
+    hipLaunchKernelGGL(k_share, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const u64 *)h0, (size_t)nl * N, ctx->sh->sk_dev, (const u64 *)ct + (size_t)nl * N, (size_t)2 * nl * N, (u64 *)h0, nl, 0, ctx->modc);
     SFG_HIP(ctx, hipGetLastError());
     return 0;
 }
@@ -316,7 +287,7 @@ struct HBig {
     void shr1() { for (size_t i = 0; i < w.size(); i++) w[i] = (w[i] >> 1) | (i + 1 < w.size() ? w[i + 1] << 63 : 0); }
 };
 }
-static void recode_constants(const sfg_ctx *ctx, int level, RecodeConst &rc) {
+void recode_constants(const sfg_ctx *ctx, int level, RecodeConst &rc) {
     const int nl = level + 1, nq = ctx->nq;
     memset(&rc, 0, sizeof rc); rc.nl = nl; rc.nq = nq;
     for (int i = 0; i < nl; i++) for (int t = 0; t < i; t++) rc.inv[i][t] = (double)h_invmod(ctx->q[t] % ctx->q[i], ctx->q[i]);
@@ -370,6 +341,18 @@ static int refresh_finish(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, 
     SFG_TRY(launch_ntt_fwd_map(ctx, (const u64 *)out, (u64 *)out, (size_t)nct * nq, p1, rm));
     // Recrypt
     hipLaunchKernelGGL(k_recrypt, dim3(N / 256, nq, nct), dim3(256), 0, ctx->stream, (u64 *)out, (const u64 *)h1agg, (const u64 *)crs, nq, ctx->modc);
+    SFG_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// ---- launch interface for decrypt.hip (the kernels above, strided)
+int launch_share(sfg_ctx *ctx, const u64 *rows, size_t rows_ct_stride, const u64 *xr, size_t x_ct_stride, u64 *h, int nl, int nct) {
+    hipLaunchKernelGGL(k_share, dim3(SFG_N / 256, nl, nct), dim3(256), 0, ctx->stream, rows, rows_ct_stride, (const u64 *)ctx->sh->sk_dev, xr, x_ct_stride, h, nl, 0, ctx->modc);
+    SFG_HIP(ctx, hipGetLastError());
+    return 0;
+}
+int launch_add_rows(sfg_ctx *ctx, const u64 *a, size_t a_ct_stride, const u64 *b, size_t b_ct_stride, u64 *out, size_t out_ct_stride, int nl, int nct) {
+    hipLaunchKernelGGL(k_add_rows, dim3(SFG_N / 256, nl, nct), dim3(256), 0, ctx->stream, a, a_ct_stride, b, b_ct_stride, out, out_ct_stride, ctx->modc);
     SFG_HIP(ctx, hipGetLastError());
     return 0;
 }

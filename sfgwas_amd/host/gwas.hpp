@@ -440,6 +440,44 @@ inline DevCipherMatrix EncryptFloatMatrixRowDev(CryptoParams *cps, const std::ve
     cps->check(sfg_encrypt_vectors_dev(cps->ctx, padded.data(), (int)(rows.size() * nvec), level, m.buf->u()), "EncryptFloatMatrixRow");
     return m;
 }
+// ---- decryption and decoding on the device (decrypt.hip).  PARITY UNPINNED against lattigo's decryptor / encoder.Decode (see include/sfgwas_hip.h).
+// cryptoParams.Sk.Value (crypto.go:44): [nq][N], NTT domain; for DecryptFloat* the WHOLE secret key, for the collective calls this party's shard
+inline void LoadSecretKey(CryptoParams *cps, const std::vector<uint64_t> &sk, bool montgomeryForm) {
+    if (sk.size() != (size_t)cps->nq * cps->N()) throw std::runtime_error("LoadSecretKey: expected [nq][N] words");
+    cps->check(sfg_ctx_load_secret_key(cps->ctx, sk.data(), montgomeryForm ? 1 : 0), "LoadSecretKey");
+}
+// crypto.DecodeFloatVector (crypto.go:525-536): the real parts of every slot of every plaintext, concatenated
+inline std::vector<double> DecodeFloatVector(CryptoParams *cps, const PlainVector &X) {
+    if (X.empty()) return {};
+    const int level = X[0].level; const size_t pw = (size_t)(level + 1) * cps->N(), slots = (size_t)cps->GetSlots();
+    detail::DevBuf d(cps, X.size() * pw * 8);
+    for (size_t i = 0; i < X.size(); i++) {
+        if (X[i].level != level || X[i].scale != X[0].scale) throw std::runtime_error("DecodeFloatVector: plaintexts of different levels or scales");
+        cps->check(sfg_memcpy_h2d(cps->ctx, d.u() + i * pw, X[i].data.data(), pw * 8), "h2d");
+    }
+    std::vector<double> out(X.size() * slots);
+    cps->check(sfg_decode_vectors(cps->ctx, d.u(), pw, (int)X.size(), level, X[0].scale, out.data(), nullptr), "DecodeFloatVector");
+    return out;
+}
+// crypto.DecryptFloatVector (crypto.go:489-510): the first n values of the vector's slots, decrypted under the loaded key and decoded on the device
+inline std::vector<double> DecryptFloatVectorDev(CryptoParams *cps, const DevCipherVector &X, size_t n) {
+    const size_t slots = (size_t)cps->GetSlots();
+    if (n > X.n * slots) throw std::runtime_error("DecryptFloatVector: more values asked for than the vector holds");
+    std::vector<double> out(X.n * slots);
+    if (X.n) cps->check(sfg_decrypt_vectors(cps->ctx, X.ptr(), (int)X.n, X.level, X.scale, out.data(), nullptr), "DecryptFloatVector");
+    out.resize(n);
+    return out;
+}
+// crypto.DecryptFloatMatrix (crypto.go:512-523): one DecryptFloatVector per row, all rows in one call
+inline std::vector<std::vector<double>> DecryptFloatMatrixDev(CryptoParams *cps, const DevCipherMatrix &M, size_t n) {
+    const size_t slots = (size_t)cps->GetSlots();
+    if (n > M.cols * slots) throw std::runtime_error("DecryptFloatMatrix: more values asked for than a row holds");
+    std::vector<double> all(M.rows * M.cols * slots);
+    if (M.rows * M.cols) cps->check(sfg_decrypt_vectors(cps->ctx, M.buf->u(), (int)(M.rows * M.cols), M.level, M.scale, all.data(), nullptr), "DecryptFloatMatrix");
+    std::vector<std::vector<double>> out(M.rows);
+    for (size_t i = 0; i < M.rows; i++) out[i].assign(all.begin() + i * M.cols * slots, all.begin() + i * M.cols * slots + n);
+    return out;
+}
 namespace detail {
 // n copies of one ciphertext (the length-1 broadcast of CMult / CSub), device to device
 inline DevCipherVector broadcast(const DevCipherVector &x, size_t n) {
@@ -1250,6 +1288,25 @@ inline crypto::DevCipherMatrix CollectiveBootstrapFinish(crypto::CryptoParams *c
     crypto::DevCipherMatrix out = crypto::NewDevCipherMatrix(cps, cm.rows, cm.cols, cps->nq - 1, cps->scale);
     cps->check(sfg_refresh_finish_scaled_dev(cps->ctx, cm.buf->u(), (int)(cm.rows * cm.cols), cm.level, cm.scale, cps->scale, h0agg, h1agg, crs, out.buf->u()),
                "RefreshProtocol.Decrypt/Recode/Recrypt");
+    return out;
+}
+// ---- collective decryption, local halves (mpc/mhe.go:107-220 CollectiveDecryptMat; gwas/utilities.go:385-389, gwas/gwas.go:385-386).  The network step between
+//      them stays in Go: the aggregation of the shares (mpc/aggregate.go).  PARITY UNPINNED (see include/sfgwas_hip.h).
+// Per-ciphertext randomness is drawn by the caller, as the reference draws it (the PCKS protocol's Gaussian sampler, sigma 6.36): e0 [nct][N], device resident
+struct PCKSShares { std::shared_ptr<crypto::detail::DevBuf> h0; size_t nct = 0; int level = 0; };     // [nct][level+1][N]; polynomial 1 of the switched ciphertext is discarded by the reference and not computed
+inline PCKSShares CollectiveDecryptGenShares(crypto::CryptoParams *cps, const crypto::DevCipherMatrix &cm, const int32_t *e0_dev) {
+    PCKSShares sh; sh.nct = cm.rows * cm.cols; sh.level = cm.level;
+    sh.h0 = std::make_shared<crypto::detail::DevBuf>(cps, sh.nct * (cm.level + 1) * (size_t)cps->N() * 8);
+    cps->check(sfg_pcks_gen_share_dev(cps->ctx, cm.buf->u(), (int)sh.nct, cm.level, e0_dev, nullptr, sh.h0->u(), nullptr), "PCKSProtocol.GenShare");
+    return sh;
+}
+// KeySwitch + .Plaintext() + DecodeFloatVector per row with the aggregated shares: rows x (cols * slots) doubles
+inline std::vector<std::vector<double>> CollectiveDecryptFinish(crypto::CryptoParams *cps, const crypto::DevCipherMatrix &cm, const uint64_t *h0agg_dev) {
+    const size_t slots = (size_t)cps->GetSlots(), nct = cm.rows * cm.cols;
+    std::vector<double> all(nct * slots);
+    if (nct) cps->check(sfg_pcks_finish_decode(cps->ctx, cm.buf->u(), (int)nct, cm.level, cm.scale, h0agg_dev, all.data(), nullptr), "PCKSProtocol.KeySwitch/Decode");
+    std::vector<std::vector<double>> out(cm.rows);
+    for (size_t i = 0; i < cm.rows; i++) out[i].assign(all.begin() + i * cm.cols * slots, all.begin() + (i + 1) * cm.cols * slots);
     return out;
 }
 }  // namespace mpc
