@@ -58,7 +58,7 @@ extern "C" int ubench_ntt_move(sfg_ctx *ctx, int mode, int G, int nblocks, int d
     MoveJob pj; SFG_TRY(move_job_for(ctx, panel, G, L, Bs, Bb, pj));
     pj.nblocks = (unsigned)nblocks; pj.depth = depth; pj.nt = nt;
     if (const char *e = getenv("SFG_UB_MOVER_FAKE")) pj.a5.fake = pj.a6.fake = atoi(e);          // timing experiments with INVALID results (i8_move.hpp)
-    PanelMap pm; pm.G = 0; pm.g = 0; pm.shift0 = 0; pm.packed_mask = mac_dma_packed_mask(ctx, L) | 0x80000000u | 0x40000000u;
+    PanelMap pm; pm.G = 0; pm.g = 0; pm.shift0 = 0; pm.packed_mask = mac_dma_packed_mask(ctx, L) | PT_DIGITS | PT_DIGITS_BIG;
     if (pj.a5.fake & 16) { pm.packed_mask |= PT_COMPACT | PT_KMAJOR; pm.K = K; }                  // the NTTs write the K-major panel pattern (the launch's plaintexts: column p / K, row p % K)
     auto pack_alone = [&](const MoveJob &j) { launch_i8_pack_pt_digits(ctx->stream, j.a5, j.n5, false); launch_i8_pack_pt_digits(ctx->stream, j.a6, j.n6, true); };
     // NTT launches (into ntt_out) with the job's items spread evenly over them

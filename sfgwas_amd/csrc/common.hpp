@@ -9,15 +9,11 @@
 #include <map>
 #include <set>
 #include "../../include/sfgwas_hip.h"
+#include "consts.hpp"          // SFG_N, SFG_SLOTS, SFG_D, SFG_MAXMOD, SFG_I8_KEEP_RESERVE, the PT_* panel flags
 
 typedef unsigned long long u64;
 typedef unsigned __int128 u128;
 
-constexpr int SFG_LOGN = 14;
-constexpr int SFG_N = 1 << SFG_LOGN;      // ring degree (PN14QP438, gwas.go:169)
-constexpr int SFG_SLOTS = SFG_N / 2;
-constexpr int SFG_D = 91;                 // ceil(sqrt(8192)), matmult.go:1047
-constexpr int SFG_MAXMOD = 16;
 constexpr unsigned long long SFG_I8_BIG_QMAX = 0x7F7F7F7F7F80ULL;   // largest modulus whose canonical words (<= q - 1) fit six signed base-256 digits (mac_i8.hip, the NTT's six digit planes)
 
 // per-modulus constants, device copy
@@ -87,8 +83,6 @@ struct SfgConfig {
     bool mac_plain_pt = false;     // SFG_MAC_PT=plain      plaintext panel as plain u64 words (A/B of the packed-limb panel format)
     bool assoc_trace = false;      // SFG_ASSOC_TRACE       the streamed association scan prints the wall times of its cache build and of every batch (each synchronised)
 };
-// HBM that must stay free beside the transposed copies of ALL groups of a caller's rotation cache (association scan) for the int8 MAC to take that call
-constexpr size_t SFG_I8_KEEP_RESERVE = 80ULL << 30;
 
 // Immutable after setup, shared by a context and its forks (sfg_ctx_fork): ring tables, encoder tables, key material.
 struct SfgShared {

@@ -1,6 +1,7 @@
 // kernels.hpp — internal launch interface between the translation units of libsfgwas_hip.
 #pragma once
 #include "common.hpp"
+#include "mm_plan.hpp"            // the product's launch plan; the byte models mac_i8_stream_bytes / mac_i8_tile_bytes / mac_i8_rot_tile_bytes
 
 // row r of a batch uses modulus m[r % period] (ciphertext rows, plaintext rows, key-switch rows are all periodic)
 // m < 0 marks a row the kernel must leave untouched
@@ -11,11 +12,7 @@ struct RowMap { int rpg; size_t gstride_in, gstride_out; };
 // where the plaintext of diagonal `shift` (= shift0 + index in the batch) of block row g lands inside a panel that holds G
 // block rows: slot ((shift / 91) * G + g) * 91 + shift % 91, i.e. [giant][g][baby] so that k = g*91 + baby is contiguous.
 // G == 0: dense (slot = index in the batch)
-struct PanelMap { int G, g, shift0; unsigned packed_mask = 0; int K = 0; };   // packed_mask bit l: rows of modulus l are written as packed-limb words (mac_dma.hip); bit 31: as digit planes instead (mac_i8.hip); bit 30: the 46-bit modulus too (six planes); bit 29: compact rows (every modulus in planes, a plaintext's planes back to back)
-constexpr unsigned PT_COMPACT = 1u << 29;
-// bit 28 (with bit 29): K-MAJOR panel - [column][plane][128-byte coefficient block][k < K][128 B]: the k rows of a column's coefficient block are adjacent, so a transposition
-// unit reads 16 runs of 2 KiB instead of 256 runs of 128 B (PanelMap::K = rows per column; G == 0: plaintext p of the launch is column p / K, row p % K)
-constexpr unsigned PT_KMAJOR = 1u << 28;
+struct PanelMap { int G, g, shift0; unsigned packed_mask = 0; int K = 0; };   // packed_mask: the panel's flag word - bit l: rows of modulus l are written as packed-limb words (mac_dma.hip); PT_DIGITS, PT_DIGITS_BIG, PT_COMPACT, PT_KMAJOR (consts.hpp); K: rows per column of a K-major panel
 
 // ntt.hip
 int launch_ntt_fwd(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat);
@@ -40,8 +37,6 @@ int launch_mac_i8_small(sfg_ctx *ctx, const double *rotf, size_t rotf_k_stride, 
                         int l0, int nl, int accumulate, const MacStrides &st);       // mac_i8.hip
 int launch_mac_i8_big(sfg_ctx *ctx, const double *rotf, size_t rotf_k_stride, size_t rotf_r_stride, int plane0, const u64 *pt, u64 *out, int K, int R, int r0, int Ncols,
                       int l0, int accumulate, const MacStrides &st);
-size_t mac_i8_stream_bytes(int K, int nl, int ND, int copies_of_rot);
-size_t mac_i8_tile_bytes(int Kp, int nl, int ND);      // plaintext tile buffer of nl moduli with ND digits, K' contraction steps (mac_i8.hip)
 // encode.hip
 int launch_skew(sfg_ctx *ctx, const int8_t *blk, size_t ld, int r, int c, int transposed, int square, int8_t *D);
 // pcache (nullable): the block's slot of the plaintext coefficient cache, [8192 shifts][N/2] doubles.  mode 1: the FFT writes its rows there (and the NTT reads them);
@@ -100,7 +95,6 @@ int matmul_resident_range_i8pre(sfg_ctx *ctx, const I8RotPre &pre, int s, int ma
 int matmul_accumulate_i8pre(sfg_ctx *ctx, const I8RotPre &pre, int s, int max_level, const sfg_geno *g, unsigned flags, int j0, int j1, int accumulate, uint64_t *acc,
                             size_t acc_col_words = 0);        // acc_col_words: words between consecutive block columns' accumulators (0: dense [column][91 giants]...)
 int launch_i8_pack_rot_to(sfg_ctx *ctx, const double *rotf, size_t rotf_k_stride, size_t rotf_r_stride, int plane0, int K, int R, int l0, int nl, bool big, int8_t *A_out);      // mac_i8.hip
-size_t mac_i8_rot_tile_bytes(int K, int nl, int ND);
 // the rotation cache of an association scan in whichever form the context multiplies with
 struct AssocRot { double *f64 = nullptr; I8RotPre pre; };
 int assoc_build_rot(sfg_ctx *ctx, const u64 *A_dev, int s, int in_level, int max_level, size_t nr, const std::vector<size_t> &widths, AssocRot &out);

@@ -37,20 +37,17 @@ __global__ void __launch_bounds__(256) k_pack_pt(const u64 *in, u64 *out, size_t
 // bit l set: the plaintext rows of modulus l use the packed-limb format (small moduli with the default broadcast kernel; not with the A/B build's plain panel / dma / reg kernels)
 unsigned mac_dma_packed_mask(sfg_ctx *ctx, int L) {
     if (ctx->cfg.mac_plain_pt || ctx->cfg.mac_reg || !ctx->cfg.mac_bc) return 0u;       // the packed format is the broadcast kernel's
-    unsigned m = 0; for (int l = 0; l < L; l++) if (ctx->q[l] < (1ULL << 36)) m |= 1u << l;
-    return m;
+    return ModSplit(ctx->q, L).packed_mask_all;
 }
 
 // 46/47-bit moduli: rot words are centred and split into signed halves (k_rot_to_f64: |lo| <= 2^22, |hi| <= (q >> 24) + 1), plaintext words into
 // unsigned halves (p_lo < 2^23, p_hi <= q >> 23).  The largest product of a k-step is the Karatsuba middle term.
 double mac_big_maxterm(u64 q) { return (4194304.0 + (double)((q >> 24) + 1)) * (8388608.0 + (double)((q >> 23) + 1)); }
 int mac_dma_planes(sfg_ctx *ctx, int L, std::vector<int> &plane_of, std::vector<int> &is_big) {
-    plane_of.assign(L, 0); is_big.assign(L, 0); int nplanes = 0;
-    for (int l = 0; l < L; l++) {
-        if (ctx->q[l] >= (1ULL << 47)) { ctx->err = "sfg_mac: modulus >= 2^47 unsupported by the fp64 limb schedule"; return -1; }
-        is_big[l] = ctx->q[l] >= (1ULL << 36); plane_of[l] = nplanes; nplanes += is_big[l] ? 2 : 1;
-    }
-    return nplanes;
+    const ModSplit m(ctx->q, L);
+    if (m.too_big) { ctx->err = "sfg_mac: modulus >= 2^47 unsupported by the fp64 limb schedule"; return -1; }
+    plane_of.assign(m.plane_of, m.plane_of + L); is_big.assign(m.is_big, m.is_big + L);
+    return m.fp64_planes;
 }
 
 // convert nrows polynomial rows [nrows][nl_rot][N] (ciphertexts are two consecutive rows) to the fp64 operand form rotf[nrows][nplanes*N]

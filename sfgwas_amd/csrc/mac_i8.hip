@@ -365,13 +365,7 @@ int mac_i8_set_attrs(sfg_ctx *ctx) {       // per device, at context creation (c
     SFG_HIP(ctx, hipFuncSetAttribute((const void *)k_mac_i8_ring<6, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 10 * 6 * 1024));
     return 0;
 }
-// bytes of the two operand streams and the tile-ordered results of one launch (for the group-size choice in matmul.hip)
-size_t mac_i8_stream_bytes(int K, int nl, int ND, int copies_of_rot) {
-    const size_t N = SFG_N, H = N / 2, nch = ((size_t)K + 63) / 64;
-    return (size_t)nl * (N * nch * 2 * ND * 1024 * copies_of_rot + H * 6 * nch * ND * 1024 + H * 2 * 6 * 2 * 256 * 8);
-}
-// bytes of the tile buffer of `nl` moduli with ND digits for K' contraction steps
-size_t mac_i8_tile_bytes(int Kp, int nl, int ND) { return (size_t)nl * (SFG_N / 2) * 6 * (((size_t)Kp + 63) / 64) * ND * 1024; }
+// (the byte models of the operand streams, the tile buffers and the rot tiles: mm_plan.hpp)
 // the transposition pass over `items` items of digit-plane panel rows (k_i8_pack_pt_digits<5>, or <6> for the 46-bit modulus)
 void launch_i8_pack_pt_digits(hipStream_t q, const I8Args &a, unsigned items, bool big) {
     if (big) hipLaunchKernelGGL(k_i8_pack_pt_digits<6>, dim3(items), dim3(256), 0, q, a);
@@ -546,7 +540,6 @@ static int launch_mac_i8_nd(sfg_ctx *ctx, const double *rotf, size_t rotf_k_stri
     return 0;
 }
 // the transposed rot tiles of one MAC group into a caller's buffer (mac_i8_rot_tile_bytes(K, nl, ND) bytes): rows [0, R) of every k-slice, R <= 32
-size_t mac_i8_rot_tile_bytes(int K, int nl, int ND) { return (size_t)nl * SFG_N * (((size_t)K + 63) / 64) * 2 * ND * 1024; }
 int launch_i8_pack_rot_to(sfg_ctx *ctx, const double *rotf, size_t rotf_k_stride, size_t rotf_r_stride, int plane0, int K, int R, int l0, int nl, bool big, int8_t *A_out) {
     if (R > 32 || (big && nl != 1)) SFG_FAIL(ctx, "i8 rot tiles: internal: at most 32 rows, one 46-bit modulus per buffer");
     I8Args a; memset(&a, 0, sizeof a);

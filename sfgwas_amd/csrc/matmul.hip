@@ -398,6 +398,146 @@ static int build_rot_row_tab(sfg_ctx *ctx, const u64 *A, int s, int nl_in, int n
 }
 
 // ---------------------------------------------------------------- phase 1: accumulate
+// The decisions of a call are mm_plan's (mm_plan.hpp); here are its impure inputs, its buffers and its launches.
+static MmPlanIn plan_input(sfg_ctx *ctx, int s, int L, int nblockrows, int ncolb, RotSrc rot, int pre_G) {
+    const SfgConfig &c = ctx->cfg;
+    MmPlanIn in;
+    in.mm_group = c.mm_group; in.mm_group_auto = c.mm_group_auto; in.mac_i8 = c.mac_i8; in.mac_i8_big = c.mac_i8_big;
+    in.pt_compact = c.pt_compact; in.pt_kmajor = c.pt_kmajor; in.pt_ride = c.pt_ride; in.no_overlap = c.no_overlap;
+    in.dma = mac_use_dma(ctx); in.packed_mask = in.dma ? mac_dma_packed_mask(ctx, L) : 0u; in.mods = ModSplit(ctx->q, L);
+    in.s = s; in.L = L; in.nblockrows = nblockrows; in.ncolb = ncolb; in.rot = rot; in.pre_G = pre_G;
+    if (mm_plan_reads_memory(in)) {
+        size_t fr = 0, tot = 0;
+        in.mem_failed = hipMemGetInfo(&fr, &tot) != hipSuccess;
+        in.mem_search = in.mem_keep = fr;
+        for (const auto &kv : ctx->pool) {
+            if (kv.first == "mm.pt" || kv.first == "mm.rotf" || kv.first.rfind("mi8.", 0) == 0) in.mem_search += kv.second.second;   // regrown in place
+            if (kv.first.rfind("mi8.A", 0) == 0) in.mem_keep += kv.second.second;
+        }
+    }
+    return in;
+}
+// what the launches of one call share
+struct MmCall {
+    sfg_ctx *ctx; const Shape &sh; unsigned flags; const u64 *A; const I8RotPre *pre8;
+    int s, L, lev, nl, nl_in; bool dma; unsigned packed_mask; size_t ctw, accw, rowf = 0;
+    MmPlan plan;
+    u64 *a_row = nullptr, *rotc = nullptr; int8_t *skew = nullptr, *unpacked = nullptr; double *rotf = nullptr, *rotsum = nullptr;
+    int8_t *rideBs = nullptr, *rideBb = nullptr;               // the riding launches' tile buffers (a launch of the same call that transposes by the pass uses them too)
+};
+// a MAC launch: the plaintext panel `ptp` of `gsn` block rows against the group's rot operand, into block column accumulator `accj`
+struct MacJob { bool on = false; u64 *ptp = nullptr; int gsn = 0, gi = 0, acc_flag = 0; u64 *accj = nullptr; const double *rotf_grp = nullptr, *rotsum_grp = nullptr; };
+
+// rotation cache of the group that starts at block row bg into half `buf` of mm.rotf (on whatever stream is current)
+static int build_group(const MmCall &c, int bg, int b1, int buf) {
+    sfg_ctx *ctx = c.ctx; const int d = SFG_D, s = c.s, ng = std::min(c.plan.G, b1 - bg);
+    ctx->i8_gen++;                                          // (the int8 MAC keeps a transposed copy per rot operand: this one changes now)
+    double *dst = c.rotf + (size_t)buf * c.plan.grp_slices * s * 2 * c.rowf;
+    for (int g = 0; g < ng; g++) SFG_TRY(build_rot_row(ctx, c.A, s, c.nl_in, c.nl, c.lev, c.L, c.sh, bg + g, c.a_row, c.rotc, c.dma, c.dma ? dst + (size_t)g * d * s * 2 * c.rowf : nullptr));
+    if (c.dma && (ng * d) % 4)            // the ragged last MAC chunk reads up to 3 k-slices past the group against zero plaintexts: keep them finite
+        SFG_HIP(ctx, hipMemsetAsync(dst + (size_t)ng * d * s * 2 * c.rowf, 0, (size_t)3 * s * 2 * c.rowf * 8, ctx->stream));
+    if (c.packed_mask) SFG_TRY(launch_rot_sum(ctx, dst, (size_t)s * 2, ng * d, c.L, c.rotsum + (size_t)buf * s * 2 * c.rowf));
+    return 0;
+}
+// B_mode (MacStrides): 0: the launch transposes its panel by the pass into the MAC's own buffers; 1: the riding movers have transposed it into the ride's tile
+// buffers already; 2: the pass runs into the ride's tile buffers
+static int run_mac(const MmCall &c, const MacJob &m, int B_mode) {
+    sfg_ctx *ctx = c.ctx; const MmPlan &p = c.plan; const int N = SFG_N, d = SFG_D;
+    PhaseTimer t(ctx, "mac");
+    MacStrides st;
+    if (c.rideBs) { st.B_small = c.rideBs; st.B_big = c.rideBb; st.B_mode = B_mode; }
+    if (c.pre8) { st.A_small = c.pre8->As[m.gi]; st.A_big = c.pre8->Ab[m.gi]; }
+    st.rot_k = (size_t)c.s * c.ctw; st.rot_r = (size_t)c.nl * N;          // rotc[baby][i][poly][nl][N]: row r = i*2+poly
+    st.pt_k = p.plw; st.pt_n = (size_t)m.gsn * d * p.plw; st.pt_half = c.dma; st.pt_packed = c.packed_mask != 0; st.pt_digits = st.i8 = p.use_i8; st.i8_big = st.pt_digits_big = p.use_i8_big;   // pt[giant][g][baby]: k = g*91 + baby
+    st.pt_layout = p.pt_layout; st.pt_L = c.L;
+    st.out_n = c.accw; st.out_r = (size_t)c.L * N;                        // acc[j][giant][r]
+    int rc;
+    if (c.dma) rc = launch_mac_dma(ctx, c.pre8 ? nullptr : m.rotf_grp, (size_t)c.s * 2, m.ptp, m.accj, m.gsn * d, 2 * c.s, d, c.L, m.acc_flag, st, m.rotsum_grp);
+#ifdef SFG_AB
+    else rc = launch_mac_strided(ctx, c.rotc, m.ptp, m.accj, d, 2 * c.s, d, c.L, m.acc_flag, st);      // ab/mac_reg.hip
+#else
+    else { rc = 1; ctx->err = "matmul: the register-staged MAC exists in the A/B build only (make ab)"; }
+#endif
+    t.stop(1);
+    return rc;
+}
+// The slot of logical block (bi, bj) in the plaintext coefficient cache of the stored matrix (sfg_geno_set_plaintext_cache): found (pcc.mode 2, or 3 in the other
+// orientation), taken now for this encode to fill (mode 1), or none (mode 0)
+struct PtcSlot {
+    static constexpr size_t slot_bytes = (size_t)SFG_SLOTS * SFG_SLOTS * 8;
+    PcCache pcc; const sfg_geno *g; uint64_t key = 0; bool fresh = false;
+    PtcSlot(const MmCall &c, int bi, int bj) : g(c.sh.g) {
+        if (!c.dma || !g->ptc_budget || g->ptc_owner != (const void *)c.ctx) return;
+        const uint64_t sr = c.sh.transposed ? bj : bi, sc = c.sh.transposed ? bi : bj;
+        key = sr << 33 | sc << 1 | ((c.flags & SFG_SQUARE) ? 1u : 0u);
+        auto it = g->ptc.find(key);
+        if (it != g->ptc.end()) { pcc.slot = it->second.slot; pcc.mode = it->second.transposed == c.sh.transposed ? 2 : 3; pcc.perm = g->ptc_perm; g->ptc_hits++; }
+        else if (g->ptc_used + slot_bytes <= g->ptc_budget) {
+            double *slot = g->ptc_arena + g->ptc_used / 8;
+            g->ptc[key] = sfg_geno::PtcEntry{slot, c.sh.transposed}; g->ptc_used += slot_bytes; g->ptc_fills++;
+            pcc.slot = slot; pcc.mode = 1; fresh = true;
+        }
+    }
+    void undo() {              // a failed fill is the newest slot of the arena: give it back
+        if (!fresh) return;
+        auto it = g->ptc.find(key);
+        if (it != g->ptc.end()) { g->ptc.erase(it); g->ptc_used -= slot_bytes; }
+        fresh = false;
+    }
+};
+// the plaintexts of block (bi, bj) - block row g of ng in the panel `pt`: skew (unless cached), zeros where the encoder will not write, the encode launches
+static int encode_block(const MmCall &c, int bi, int bj, int g, int ng, u64 *pt, PtRide *ride) {
+    sfg_ctx *ctx = c.ctx; const Shape &sh = c.sh; const MmPlan &p = c.plan;
+    const int d = SFG_D, L = c.L, nr = sh.rows_of(bi), nc = sh.cols_of(bj), tr = sh.transposed ? 1 : 0, sq = (c.flags & SFG_SQUARE) ? 1 : 0;
+    const size_t plw = p.plw, nplain = (size_t)d * d;
+    PtcSlot ptc(c, bi, bj);
+    int rc = 0;
+    if (ptc.pcc.mode < 2) {
+        PhaseTimer t(ctx, "skew");
+        if (sh.g->packed) {        // expand the stored block (rows x cols as stored) into the int8 staging block, then skew as usual
+            const size_t sr0 = (size_t)(tr ? bj : bi) * SFG_SLOTS, sc0 = (size_t)(tr ? bi : bj) * SFG_SLOTS;
+            rc = launch_geno_unpack(ctx, sh.g, sr0, sc0, tr ? nc : nr, tr ? nr : nc, c.unpacked, SFG_SLOTS);
+            if (!rc) rc = launch_skew(ctx, c.unpacked, SFG_SLOTS, nr, nc, tr, sq, c.skew);
+        } else rc = launch_skew(ctx, sh.block(bi, bj), sh.ld, nr, nc, tr, sq, c.skew);
+        t.stop(1);
+    }
+    if (rc) { ptc.undo(); return rc; }
+    // existing diagonals of this block form at most two runs of shifts: [0, nr) and (n - nc, n)  (GetDiagBool)
+    int runs[2][2]; int nruns = 0;
+    if (nr + nc > SFG_SLOTS) { runs[0][0] = 0; runs[0][1] = SFG_SLOTS; nruns = 1; }
+    else { runs[0][0] = 0; runs[0][1] = nr; runs[1][0] = SFG_SLOTS - nc + 1; runs[1][1] = SFG_SLOTS; nruns = runs[1][0] < runs[1][1] ? 2 : 1; }
+    const bool full = nruns == 1 && runs[0][1] - runs[0][0] == SFG_SLOTS;
+    // zero what the encoder will not write: plaintext slot of (giant, g, baby) is ((giant*ng + g)*91 + baby)
+    if (p.kmajor) {      // (K-major panel: rows of block row g in column 90 past shift 8191, or in every column)
+        const int kb0 = g * d;
+        if (full) rc = launch_pt_zero_kmajor(ctx, pt, ng * d, p.pt_planes, d - 1, d, kb0 + (SFG_SLOTS - (d - 1) * d), kb0 + d);
+        else rc = launch_pt_zero_kmajor(ctx, pt, ng * d, p.pt_planes, 0, d, kb0, kb0 + d);
+    } else if (full) {        // only the 89 slots past shift 8191 (giant 90, baby 2..90)
+        rc = launch_pt_zero(ctx, pt + (((size_t)(d - 1) * ng + g) * d + (SFG_SLOTS - (d - 1) * d)) * plw, 0, (nplain - SFG_SLOTS) * plw, 1, L, p.prow, c.packed_mask);
+    } else {           // ragged block: all 91 x 91 slots of this block row
+        rc = launch_pt_zero(ctx, pt + (size_t)g * d * plw, (size_t)ng * d * plw, (size_t)d * plw, d, L, p.prow, c.packed_mask);
+    }
+    if (rc) { ptc.undo(); return rc; }
+    PhaseTimer t(ctx, "encode");
+    for (int r = 0; r < nruns && !rc; r++) {
+        if (c.dma) rc = launch_encode_rows(ctx, c.skew, runs[r][0], runs[r][1] - runs[r][0], L, pt, true, ng, g, p.enc_flags, ptc.pcc.mode ? &ptc.pcc : nullptr, ride);
+        else rc = launch_encode_rows(ctx, c.skew, runs[r][0], runs[r][1] - runs[r][0], L, pt + (size_t)runs[r][0] * plw, false);      // (register-staged MAC, A/B build: dense full rows)
+    }
+    t.stop(nruns);
+    if (rc) ptc.undo();
+    return rc;
+}
+// plaintext-NTT launches of the encodes of block rows [bg, bg + ng) in a block column of nc columns (encode_block's runs)
+static int ride_launch_count(const MmCall &c, int bg, int ng, int nc) {
+    int launches = 0;
+    for (int g = 0; g < ng; g++) {
+        const int nr = c.sh.rows_of(bg + g);
+        if (nr + nc > SFG_SLOTS) launches += encode_rows_launches(c.ctx, SFG_SLOTS);
+        else launches += encode_rows_launches(c.ctx, nr) + (nc > 1 ? encode_rows_launches(c.ctx, nc - 1) : 0);
+    }
+    return launches;
+}
+
 // acc_dev: [(j - j0)][giant < d][i < s][2][L][N] canonical residues (zero-initialised here unless accumulate != 0)
 // for operand block rows [b0, b1) and block columns [j0, j1).
 static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, int max_level, const Shape &sh, unsigned flags,
@@ -406,7 +546,6 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
     const int N = SFG_N, d = SFG_D, L = max_level;
     if (pre8 && (rotf_pre || !mac_use_dma(ctx) || b0 != 0 || b1 != pre8->nbr || sh.nbr != pre8->nbr || s != pre8->s || L != pre8->L))
         SFG_FAIL(ctx, "matmul: internal: the int8 rot tiles were built for another product (block rows %d, s = %d, level %d)", pre8->nbr, pre8->s, pre8->L);
-    const bool rot_ext = rotf_pre || pre8;                  // the caller holds the rotations of every block row
     const int lev = in_level > max_level ? max_level : in_level, nl = lev + 1, nl_in = in_level + 1;
     if (L < 1 || L > ctx->nq) SFG_FAIL(ctx, "matmul: max_level out of range");
     if (nl < L) SFG_FAIL(ctx, "matmul: input level %d has fewer than max_level = %d moduli", in_level, max_level);
@@ -419,256 +558,85 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
         if (!accumulate) for (int c = 0; c < ncolb; c++) SFG_HIP(ctx, hipMemsetAsync(acc + (size_t)c * acc_col, 0, (size_t)d * accw * 8, ctx->stream));
         return 0;
     }
-    const bool dma = mac_use_dma(ctx);                          // LDS-DMA MAC: half-row plaintexts, fp64 rot operand, block-row groups
-    const size_t prow = dma ? (size_t)N / 2 : (size_t)N;     // words per plaintext modulus row
-    // G block rows share one MAC launch (K = G*91): accumulators are written once per group instead of
-    // read-modify-written per block.  Bounded by scratch: ~4.9 GB per block row at s = 15.
-    int G = 1;
-    const size_t nplain = (size_t)d * d;                     // 8281 >= 8192 slots per block row: the tail stays zero
-    if (dma) {
-        G = ctx->cfg.mm_group;
-        // 16 (24) block rows per launch halve (third) the accumulator read-modify-writes and the per-launch prologues (16: -1.7 % at 100k x 1M, identical bits) but
-        // need a 43 (65) GB plaintext panel and, for the pipelined rotation caches, 2 x 34.5 (52) GB of operands: taken only when that fits beside what is resident
-        // (not for a single block column against a caller's rotation cache - the association scan: fewer launches save a few accumulator passes there, and the
-        //  larger panel competes with the 115 GB cache for HBM: measured 0.49 s instead of 0.31 s per batch)
-        if (pre8) G = pre8->G;
-        else if (ctx->cfg.mm_group_auto && b1 - b0 > G && (j1 - j0 >= 4 || !rotf_pre)) {
-            std::vector<int> po, ib; const int npl = mac_dma_planes(ctx, L, po, ib);
-            size_t have = 0, total = 0;
-            if (npl > 0 && hipMemGetInfo(&have, &total) == hipSuccess) {
-                for (const auto &kv : ctx->pool) if (kv.first == "mm.pt" || kv.first == "mm.rotf" || kv.first.rfind("mi8.", 0) == 0) have += kv.second.second;   // regrown in place
-                for (int cand : {24, 20, 16, 14, 12, 10}) {
-                    const int G2 = std::min(cand, b1 - b0);
-                    if (G2 <= G) break;
-                    const bool pipe2 = !rotf_pre && b1 - b0 > G2 && !ctx->cfg.no_overlap;
-                    const bool ride2 = ctx->cfg.mac_i8 && ctx->cfg.pt_ride > 0 && (j1 - j0 >= 2 || (pre8 && b1 - b0 > G2));      // (the riding transposition keeps two panels)
-                    size_t ptb = (size_t)L * ((size_t)N / 2) * 8;                    // bytes per plaintext: compact rows where every modulus is on the int8 MAC (as decided below)
-                    if (ctx->cfg.pt_compact && ctx->cfg.mac_i8 && mac_dma_packed_mask(ctx, L)) {
-                        bool big_ok = true; size_t planes = 0;
-                        for (int l = 0; l < L; l++) { const bool sm = ctx->q[l] < (1ULL << 36); planes += sm ? 5 : 6; if (!sm && !ctx->cfg.mac_i8_big) big_ok = false; }
-                        if (big_ok && ((b1 - b0 + G2 - 1) / G2 <= 2 || j1 - j0 >= 4)) ptb = planes * ((size_t)N / 2);
-                    }
-                    size_t need = (size_t)G2 * nplain * ptb * (ride2 ? 2 : 1);
-                    if (!rotf_pre) need += ((size_t)G2 * d + 3) * s * 2 * (size_t)npl * N * 8 * (pipe2 ? 2 : 1);
-                    if (ctx->cfg.mac_i8) {                         // + the two operand streams and the tile-ordered results of the int8 MAC (small moduli)
-                        int nsm = 0; for (int l = 0; l < L; l++) nsm += ctx->q[l] < (1ULL << 36);
-                        need += mac_i8_stream_bytes(G2 * d, nsm, 5, 1);          // (one transposed rot copy: a group's copy is recycled for the next group, in stream order)
-                        if (ctx->cfg.mac_i8_big && nsm < L) need += mac_i8_stream_bytes(G2 * d, 1, 6, 1);
-                    }
-                    if (need + (12ULL << 30) <= have) { G = G2; break; }
-                }
-            }
-        }
-        if (G > b1 - b0) G = b1 - b0;
-    }
-    u64 *a_row = nullptr, *rotc = nullptr, *pt = nullptr; int8_t *skew = nullptr; double *rotf = nullptr, *rotsum = nullptr; size_t rowf = 0;
-    const unsigned packed_mask = dma ? mac_dma_packed_mask(ctx, L) : 0u;      // small-modulus plaintext rows in the packed-limb format
-    // The int8 MAC multiplies with a k-contiguous copy of a group's rot operand, transposed when the operand changes and kept for two operands.  That pays when
-    // the copy is reused: several block columns in this call, or so few groups that the copies survive from call to call (a caller's rotation cache multiplied one
-    // block column at a time).  The association scan - one block column per batch against a 62-block-row cache - takes the fp64 kernel.
-    bool keep_all = false;                                  // a caller's rotation cache of up to 16 groups whose transposed copies all fit: the association scan
-    if (dma && ctx->cfg.mac_i8 && packed_mask && rotf_pre && (b1 - b0 + G - 1) / G <= 16) {
-        int nsm = 0; for (int l = 0; l < L; l++) nsm += ctx->q[l] < (1ULL << 36);
-        const size_t per = mac_i8_stream_bytes(G * d, nsm, 5, 1) - mac_i8_stream_bytes(G * d, nsm, 5, 0), ngr = (size_t)(b1 - b0 + G - 1) / G;
-        size_t fr = 0, tot = 0, held = 0;
-        for (const auto &kv : ctx->pool) if (kv.first.rfind("mi8.A", 0) == 0) held += kv.second.second;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess) keep_all = fr + held >= ngr * per + mac_i8_stream_bytes(G * d, nsm, 5, 0) + SFG_I8_KEEP_RESERVE;     // (the panel, accumulators and key-switch scratch of the call are still to be allocated the first time)
-    }
-    const bool use_i8 = pre8 || (dma && ctx->cfg.mac_i8 && packed_mask && ((b1 - b0 + G - 1) / G <= 2 || j1 - j0 >= 4 || keep_all));
-    const bool use_i8_big = pre8 || (use_i8 && ctx->cfg.mac_i8_big);                    // the 46-bit modulus too: six digit planes, its own pair of transposed rot copies
-    const size_t grp_slices = (size_t)G * d + 3;            // k-slices of one group's fp64 rotation cache (+ 3: see launch_mac_dma)
-    const bool pipelined = dma && !rot_ext && b1 - b0 > G && !ctx->cfg.no_overlap;
-    SFG_TRY(sfg_scratch(ctx, "mm.a_row", (size_t)s * ctw * 8, (void **)&a_row));
-    SFG_TRY(sfg_scratch(ctx, "mm.rotc", dma ? 8 : (size_t)d * s * ctw * 8, (void **)&rotc));     // u64 rotation cache: only the register-staged MAC reads one
-    // Compact panel rows (round 6): where every modulus of the product multiplies on the int8 matrix core the panel holds nothing but digit planes - five (six) planes of
-    // N/2 bytes per modulus, back to back: 208 KiB per plaintext at L = 5 instead of five rows of N/2 words (320 KiB).  Room for the second panel of the riding transposition.
-    bool all_small = true; for (int l = 0; l < L; l++) if (ctx->q[l] >= (1ULL << 36)) all_small = false;
-    const bool compact = ctx->cfg.pt_compact && dma && use_i8 && (use_i8_big || all_small);
-    size_t plw = (size_t)L * prow;                           // words per plaintext
-    int pt_planes = 0;
-    if (compact) { for (int l = 0; l < L; l++) pt_planes += ctx->q[l] < (1ULL << 36) ? 5 : 6; plw = (size_t)pt_planes * ((size_t)N / 2) / 8; }
-    // K-major panel (round 6): the compact panel's bytes ordered [column][plane][128-byte coefficient block][k][128 B], so that the 16 k of a transposition unit's
-    // column are one 2 KiB run (the NTT's stores are 128-byte runs either way).
-    const bool kmajor = compact && ctx->cfg.pt_kmajor && (size_t)G * d * 128 * 64 * 32 < (1ULL << 31);
-    const int pt_layout = kmajor ? 2 : compact ? 1 : 0;
-    const size_t panel_words = (size_t)G * nplain * plw;
-    // The riding transposition (kernels.hpp PtRide): the panel of MAC launch k - 1 is transposed by mover workgroups inside the plaintext-NTT launches of launch k's
-    // encode, which writes the OTHER panel; MAC launch k - 1 follows that encode on the same queue and finds its tiles in place.  Taken where every modulus multiplies
-    // on the int8 matrix core from digit-plane panels; the first launch after a change of block-row group (its rot operand's buffer is about to be rebuilt) and the
-    // call's last launch transpose by the pass as before.
-    // (a launch rides in the encode of the NEXT block column of its group - or of the next group's first column where the rot tiles of every group are the caller's,
-    //  I8RotPre: nothing is rebuilt between groups then, so the multi-GPU engine's one-column calls over several groups ride as well)
-    bool ride_want = use_i8 && ctx->cfg.pt_ride > 0 && (j1 - j0 >= 2 || (pre8 && b1 - b0 > G)) &&
-                     (use_i8_big || [&] { for (int l = 0; l < L; l++) if (ctx->q[l] >= (1ULL << 36)) return false; return true; }());
+    // ---- the plan
+    const MmPlanIn in = plan_input(ctx, s, L, b1 - b0, ncolb, rotf_pre ? RotSrc::f64_cache : pre8 ? RotSrc::i8_tiles : RotSrc::own, pre8 ? pre8->G : 0);
+    if (in.dma && in.mods.too_big) SFG_FAIL(ctx, "sfg_mac: modulus >= 2^47 unsupported by the fp64 limb schedule");
+    MmCall c{ctx, sh, flags, A, pre8, s, L, lev, nl, nl_in, in.dma, in.packed_mask, ctw, accw};
+    c.plan = mm_plan(in);
+    MmPlan &plan = c.plan;
+    const int G = plan.G; const bool dma = in.dma, rot_ext = in.rot != RotSrc::own;        // rot_ext: the caller holds the rotations of every block row
+    if (rotsum_pre && G < rotsum_group_size(in.mm_group, in.nblockrows)) SFG_FAIL(ctx, "matmul: internal: fewer rot-sum groups than MAC groups");      // (see rotsum_group_size)
+    // ---- the buffers
+    u64 *pt = nullptr;
+    SFG_TRY(sfg_scratch(ctx, "mm.a_row", (size_t)s * ctw * 8, (void **)&c.a_row));
+    SFG_TRY(sfg_scratch(ctx, "mm.rotc", dma ? 8 : (size_t)d * s * ctw * 8, (void **)&c.rotc));     // u64 rotation cache: only the register-staged MAC reads one
+    // The riding transposition keeps two panels: the panel of MAC launch k - 1 is transposed by mover workgroups inside the plaintext-NTT launches of launch k's
+    // encode, which writes the OTHER panel.  A caller's group size (SFG_MM_GROUP, sfg_config.mm_group) may leave room for one panel only: the product then
+    // transposes by the pass.
     // (+ 64 KiB: the transposition walks whole chunks of 64 k, and in the K-major panel the rows K .. K + 63 of the last column's last coefficient block - read, then
     //  masked - lie up to 8 KiB past the panel)
-    // A caller's group size (SFG_MM_GROUP, sfg_config.mm_group) may leave room for one panel only: the product then transposes by the pass, as before round 6
-    if (ride_want && sfg_scratch(ctx, "mm.pt", panel_words * 8 * 2 + 65536, (void **)&pt)) { ctx->err.clear(); ride_want = false; }
-    if (!ride_want) SFG_TRY(sfg_scratch(ctx, "mm.pt", panel_words * 8 + 65536, (void **)&pt));
+    if (plan.ride_want && sfg_scratch(ctx, "mm.pt", plan.panel_words * 8 * 2 + 65536, (void **)&pt)) { ctx->err.clear(); plan.ride_want = false; }
+    if (!plan.ride_want) SFG_TRY(sfg_scratch(ctx, "mm.pt", plan.panel_words * 8 + 65536, (void **)&pt));
     u64 *const pt_base = pt;
-    SFG_TRY(sfg_scratch(ctx, "mm.skew", (size_t)SFG_SLOTS * SFG_SLOTS, (void **)&skew));
-    int8_t *unpacked = nullptr;
-    if (sh.g->packed) SFG_TRY(sfg_scratch(ctx, "mm.unpack", (size_t)SFG_SLOTS * SFG_SLOTS, (void **)&unpacked));
+    SFG_TRY(sfg_scratch(ctx, "mm.skew", (size_t)SFG_SLOTS * SFG_SLOTS, (void **)&c.skew));
+    if (sh.g->packed) SFG_TRY(sfg_scratch(ctx, "mm.unpack", (size_t)SFG_SLOTS * SFG_SLOTS, (void **)&c.unpacked));
     if (dma) {
-        std::vector<int> plane_of, is_big; const int nplanes = mac_dma_planes(ctx, L, plane_of, is_big);
-        if (nplanes < 0) return 1;
-        rowf = (size_t)nplanes * N;
-        if (!rot_ext) SFG_TRY(sfg_scratch(ctx, "mm.rotf", grp_slices * s * 2 * rowf * 8 * (pipelined ? 2 : 1), (void **)&rotf));
-        if (!rot_ext && packed_mask) SFG_TRY(sfg_scratch(ctx, "mm.rotsum", (size_t)2 * s * 2 * rowf * 8, (void **)&rotsum));     // one per ring half
+        c.rowf = (size_t)in.mods.fp64_planes * N;
+        if (!rot_ext) SFG_TRY(sfg_scratch(ctx, "mm.rotf", plan.grp_slices * s * 2 * c.rowf * 8 * (plan.pipelined ? 2 : 1), (void **)&c.rotf));
+        if (!rot_ext && in.packed_mask) SFG_TRY(sfg_scratch(ctx, "mm.rotsum", (size_t)2 * s * 2 * c.rowf * 8, (void **)&c.rotsum));     // one per ring half
     }
-    int rc = 0;
-    bool first_group = true;
-    // rotation cache of one group into half `buf` of mm.rotf (on whatever stream is current)
-    auto build_group = [&](int bg, int buf) -> int {
-        const int ng = std::min(G, b1 - bg);
-        ctx->i8_gen++;                                          // (the int8 MAC keeps a transposed copy per rot operand: this one changes now)
-        double *dst = rotf + (size_t)buf * grp_slices * s * 2 * rowf;
-        for (int g = 0; g < ng; g++) SFG_TRY(build_rot_row(ctx, A, s, nl_in, nl, lev, L, sh, bg + g, a_row, rotc, dma, dma ? dst + (size_t)g * d * s * 2 * rowf : nullptr));
-        if (dma && (ng * d) % 4)          // the ragged last MAC chunk reads up to 3 k-slices past the group against zero plaintexts: keep them finite
-            SFG_HIP(ctx, hipMemsetAsync(dst + (size_t)ng * d * s * 2 * rowf, 0, (size_t)3 * s * 2 * rowf * 8, ctx->stream));
-        if (packed_mask) SFG_TRY(launch_rot_sum(ctx, dst, (size_t)s * 2, ng * d, L, rotsum + (size_t)buf * s * 2 * rowf));
-        return 0;
-    };
+    const size_t rot_half = plan.grp_slices * s * 2 * c.rowf, rotsum_half = (size_t)s * 2 * c.rowf;
+    // ---- the schedule
     // With several groups the key switching of group k+1 runs on the auxiliary stream beside the encode + MAC of group k
     // (those kernels leave registers and wave slots free; the MAC does not, so nothing overlaps it).
     hipStream_t main_stream = ctx->stream;
-    if (pipelined) {
+    if (plan.pipelined) {
         SFG_TRY(sfg_stream_after(ctx, ctx->aux_stream, main_stream));            // inputs and scratch as the main stream left them
-        { AuxScope aux(ctx); SFG_TRY(build_group(b0, 0)); }
+        { AuxScope aux(ctx); SFG_TRY(build_group(c, b0, b1, 0)); }
         SFG_HIP(ctx, hipEventRecord(ctx->ev_pipe[0], ctx->aux_stream));
     }
-    int gi = 0, it = 0;
-    // a MAC launch: the plaintext panel `ptp` of `gsn` block rows against the group's rot operand, into block column accumulator `accj`
-    struct MacJob { bool on = false; u64 *ptp = nullptr; int gsn = 0, gi = 0, acc_flag = 0; u64 *accj = nullptr; const double *rotf_grp = nullptr, *rotsum_grp = nullptr; };
-    int8_t *rideBs = nullptr, *rideBb = nullptr;               // the riding launches' tile buffers (a launch of the same call that transposes by the pass uses them too)
-    auto run_mac = [&](const MacJob &m, int B_mode) -> int {
-        PhaseTimer t(ctx, "mac");
-        MacStrides st;
-        if (rideBs) { st.B_small = rideBs; st.B_big = rideBb; st.B_mode = B_mode; }
-        if (pre8) { st.A_small = pre8->As[m.gi]; st.A_big = pre8->Ab[m.gi]; }
-        st.rot_k = (size_t)s * ctw; st.rot_r = (size_t)nl * N;          // rotc[baby][i][poly][nl][N]: row r = i*2+poly
-        st.pt_k = plw; st.pt_n = (size_t)m.gsn * d * plw; st.pt_half = dma; st.pt_packed = packed_mask != 0; st.pt_digits = st.i8 = use_i8; st.i8_big = st.pt_digits_big = use_i8_big;   // pt[giant][g][baby]: k = g*91 + baby
-        st.pt_layout = pt_layout; st.pt_L = L;
-        st.out_n = accw; st.out_r = (size_t)L * N;                      // acc[j][giant][r]
-        int r2;
-        if (dma) r2 = launch_mac_dma(ctx, pre8 ? nullptr : m.rotf_grp, (size_t)s * 2, m.ptp, m.accj, m.gsn * d, 2 * s, d, L, m.acc_flag, st, m.rotsum_grp);
-#ifdef SFG_AB
-        else r2 = launch_mac_strided(ctx, rotc, m.ptp, m.accj, d, 2 * s, d, L, m.acc_flag, st);      // ab/mac_reg.hip
-#else
-        else { r2 = 1; ctx->err = "matmul: the register-staged MAC exists in the A/B build only (make ab)"; }
-#endif
-        t.stop(1);
-        return r2;
-    };
+    int rc = 0, gi = 0, it = 0;
     MacJob held;                                               // the delayed MAC launch whose panel the next encode's NTT launches transpose
-    for (int bg = b0; bg < b1 && !rc; bg += G, gi++) {
+    for (int bg = b0; bg < b1; bg += G, gi++) {
         const int ng = std::min(G, b1 - bg);
         // (the delayed launch of the previous group reads a rot operand buffer that is rebuilt below: it goes first, transposing by the pass - unless the rot tiles
         //  of all groups are the caller's)
-        if (held.on && !pre8) { rc = run_mac(held, 2); held.on = false; if (rc) break; }
+        if (held.on && !pre8) { SFG_TRY(run_mac(c, held, 2)); held.on = false; }
         // ---- rotation caches of the group's block rows (or the product-wide cache built by the caller)
-        const double *rotf_grp = rotf, *rotsum_grp = rotsum;
-        if (rotf_pre) { rotf_grp = rotf_pre + (size_t)(bg - b0) * d * s * 2 * rowf; rotsum_grp = rotsum_pre ? rotsum_pre + (size_t)gi * s * 2 * rowf : nullptr; }
+        const double *rotf_grp = c.rotf, *rotsum_grp = c.rotsum;
+        if (rotf_pre) { rotf_grp = rotf_pre + (size_t)(bg - b0) * d * s * 2 * c.rowf; rotsum_grp = rotsum_pre ? rotsum_pre + (size_t)gi * rotsum_half : nullptr; }
         else if (pre8) { rotf_grp = nullptr; rotsum_grp = nullptr; }            // group gi multiplies from pre8->As[gi] / Ab[gi]
-        else if (pipelined) {
+        else if (plan.pipelined) {
             if (bg + G < b1) {                                                   // next group: its half was last read by group gi-1
                 SFG_TRY(sfg_stream_after(ctx, ctx->aux_stream, main_stream));
-                { AuxScope aux(ctx); SFG_TRY(build_group(bg + G, (gi + 1) & 1)); }
+                { AuxScope aux(ctx); SFG_TRY(build_group(c, bg + G, b1, (gi + 1) & 1)); }
                 SFG_HIP(ctx, hipEventRecord(ctx->ev_pipe[(gi + 1) & 1], ctx->aux_stream));
             }
             SFG_HIP(ctx, hipStreamWaitEvent(main_stream, ctx->ev_pipe[gi & 1], 0));
-            rotf_grp = rotf + (size_t)(gi & 1) * grp_slices * s * 2 * rowf;
-            if (rotsum) rotsum_grp = rotsum + (size_t)(gi & 1) * s * 2 * rowf;
-        } else {
-            rc = build_group(bg, 0);
-            if (rc) break;
-        }
-        for (int bj = j0; bj < j1 && !rc; bj++, it++) {
-            const int nc = sh.cols_of(bj);
-            pt = pt_base + (size_t)(ride_want ? (it & 1) : 0) * panel_words;
+            rotf_grp = c.rotf + (size_t)(gi & 1) * rot_half;
+            if (c.rotsum) rotsum_grp = c.rotsum + (size_t)(gi & 1) * rotsum_half;
+        } else SFG_TRY(build_group(c, bg, b1, 0));
+        for (int bj = j0; bj < j1; bj++, it++) {
+            pt = pt_base + (size_t)(plan.ride_want ? (it & 1) : 0) * plan.panel_words;
             // riding: this launch's encode carries the held launch's transposition; its own MAC is held in turn
             PtRide ride;
-            if (ride_want && !rideBs) { rc = i8_ride_tiles(ctx, G * d, L, &rideBs, &rideBb); if (rc) break; }
-            if (held.on && ride_want && rideBs) {
-                int launches = 0;
-                for (int g = 0; g < ng; g++) {
-                    const int nr = sh.rows_of(bg + g);
-                    if (nr + nc > SFG_SLOTS) launches += encode_rows_launches(ctx, SFG_SLOTS);
-                    else launches += encode_rows_launches(ctx, nr) + (nc > 1 ? encode_rows_launches(ctx, nc - 1) : 0);
-                }
-                rc = i8_ride_prepare(ctx, held.ptp, held.gsn * d, d, plw, (size_t)held.gsn * d * plw, pt_layout, L, launches, ride); if (rc) break;
-                if (ride.on && (ride.job.a5.B != rideBs || (ride.job.n6 && ride.job.a6.B != rideBb))) { rc = 1; ctx->err = "matmul: internal: the riding transposition's tile buffers moved"; break; }
+            if (plan.ride_want && !c.rideBs) SFG_TRY(i8_ride_tiles(ctx, G * d, L, &c.rideBs, &c.rideBb));
+            if (held.on && plan.ride_want && c.rideBs) {
+                SFG_TRY(i8_ride_prepare(ctx, held.ptp, held.gsn * d, d, plan.plw, (size_t)held.gsn * d * plan.plw, plan.pt_layout, L, ride_launch_count(c, bg, ng, sh.cols_of(bj)), ride));
+                if (ride.on && (ride.job.a5.B != c.rideBs || (ride.job.n6 && ride.job.a6.B != c.rideBb))) SFG_FAIL(ctx, "matmul: internal: the riding transposition's tile buffers moved");
             }
-            if (held.on && !ride.on) { rc = run_mac(held, rideBs ? 2 : 0); held.on = false; if (rc) break; }       // nothing to ride in: the held launch goes now, by the pass
-            for (int g = 0; g < ng && !rc; g++) {
-                const int bi = bg + g, nr = sh.rows_of(bi);
-                // plaintext coefficient cache of the stored block (sfg_geno_set_plaintext_cache)
-                PcCache pcc; uint64_t ptc_key = 0; bool ptc_new = false;
-                if (dma && sh.g->ptc_budget && sh.g->ptc_owner == (const void *)ctx) {
-                    const uint64_t sr = sh.transposed ? bj : bi, sc = sh.transposed ? bi : bj;
-                    ptc_key = sr << 33 | sc << 1 | ((flags & SFG_SQUARE) ? 1u : 0u);
-                    const size_t slot_bytes = (size_t)SFG_SLOTS * SFG_SLOTS * 8;
-                    auto it = sh.g->ptc.find(ptc_key);
-                    if (it != sh.g->ptc.end()) { pcc.slot = it->second.slot; pcc.mode = it->second.transposed == sh.transposed ? 2 : 3; pcc.perm = sh.g->ptc_perm; sh.g->ptc_hits++; }
-                    else if (sh.g->ptc_used + slot_bytes <= sh.g->ptc_budget) {
-                        double *slot = sh.g->ptc_arena + sh.g->ptc_used / 8;
-                        sh.g->ptc[ptc_key] = sfg_geno::PtcEntry{slot, sh.transposed}; sh.g->ptc_used += slot_bytes; sh.g->ptc_fills++;
-                        pcc.slot = slot; pcc.mode = 1; ptc_new = true;
-                    }
-                }
-                // (a failed fill is the newest slot of the arena: give it back)
-                auto ptc_undo = [&]() { if (ptc_new) { auto it = sh.g->ptc.find(ptc_key); if (it != sh.g->ptc.end()) { sh.g->ptc.erase(it); sh.g->ptc_used -= (size_t)SFG_SLOTS * SFG_SLOTS * 8; } ptc_new = false; } };
-                if (pcc.mode < 2) {
-                    PhaseTimer t(ctx, "skew");
-                    if (sh.g->packed) {        // expand the stored block (rows x cols as stored) into the int8 staging block, then skew as usual
-                        const size_t sr0 = (size_t)(sh.transposed ? bj : bi) * SFG_SLOTS, sc0 = (size_t)(sh.transposed ? bi : bj) * SFG_SLOTS;
-                        rc = launch_geno_unpack(ctx, sh.g, sr0, sc0, sh.transposed ? nc : nr, sh.transposed ? nr : nc, unpacked, SFG_SLOTS);
-                        if (!rc) rc = launch_skew(ctx, unpacked, SFG_SLOTS, nr, nc, sh.transposed ? 1 : 0, (flags & SFG_SQUARE) ? 1 : 0, skew);
-                    } else rc = launch_skew(ctx, sh.block(bi, bj), sh.ld, nr, nc, sh.transposed ? 1 : 0, (flags & SFG_SQUARE) ? 1 : 0, skew);
-                    t.stop(1);
-                }
-                if (rc) { ptc_undo(); break; }
-                // existing diagonals of this block form at most two runs of shifts: [0, nr) and (n - nc, n)  (GetDiagBool)
-                int runs[2][2]; int nruns = 0;
-                if (nr + nc > SFG_SLOTS) { runs[0][0] = 0; runs[0][1] = SFG_SLOTS; nruns = 1; }
-                else { runs[0][0] = 0; runs[0][1] = nr; runs[1][0] = SFG_SLOTS - nc + 1; runs[1][1] = SFG_SLOTS; nruns = runs[1][0] < runs[1][1] ? 2 : 1; }
-                const bool full = nruns == 1 && runs[0][1] - runs[0][0] == SFG_SLOTS;
-                // zero what the encoder will not write: plaintext slot of (giant, g, baby) is ((giant*ng + g)*91 + baby)
-                if (kmajor) {      // (K-major panel: rows of block row g in column 90 past shift 8191, or in every column)
-                    const int kb0 = g * d;
-                    if (full) rc = launch_pt_zero_kmajor(ctx, pt, ng * d, pt_planes, d - 1, d, kb0 + (SFG_SLOTS - (d - 1) * d), kb0 + d);
-                    else rc = launch_pt_zero_kmajor(ctx, pt, ng * d, pt_planes, 0, d, kb0, kb0 + d);
-                } else if (full) {        // only the 89 slots past shift 8191 (giant 90, baby 2..90)
-                    rc = launch_pt_zero(ctx, pt + (((size_t)(d - 1) * ng + g) * d + (SFG_SLOTS - (d - 1) * d)) * plw, 0, (nplain - SFG_SLOTS) * plw, 1, L, prow, packed_mask);
-                } else {           // ragged block: all 91 x 91 slots of this block row
-                    rc = launch_pt_zero(ctx, pt + (size_t)g * d * plw, (size_t)ng * d * plw, (size_t)d * plw, d, L, prow, packed_mask);
-                }
-                if (rc) { ptc_undo(); break; }
-                {
-                    PhaseTimer t(ctx, "encode");
-                    for (int r = 0; r < nruns && !rc; r++) {
-                        if (dma) rc = launch_encode_rows(ctx, skew, runs[r][0], runs[r][1] - runs[r][0], L, pt, true, ng, g, packed_mask | (use_i8 ? 0x80000000u : 0u) | (use_i8_big ? 0x40000000u : 0u) | (compact ? PT_COMPACT : 0u) | (kmajor ? PT_KMAJOR : 0u),
-                                                         pcc.mode ? &pcc : nullptr, ride.on ? &ride : nullptr);
-                        else rc = launch_encode_rows(ctx, skew, runs[r][0], runs[r][1] - runs[r][0], L, pt + (size_t)runs[r][0] * plw, false);
-                    }
-                    t.stop(nruns);
-                }
-                if (rc) ptc_undo();
-            }
-            if (rc) break;
+            if (held.on && !ride.on) { SFG_TRY(run_mac(c, held, c.rideBs ? 2 : 0)); held.on = false; }       // nothing to ride in: the held launch goes now, by the pass
+            for (int g = 0; g < ng; g++) SFG_TRY(encode_block(c, bg + g, bj, g, ng, pt, ride.on ? &ride : nullptr));
             // the held launch: whatever of its transposition no NTT launch of this encode took, then its MAC on the tiles
-            if (held.on) { rc = i8_ride_finish(ctx, ride); if (!rc) rc = run_mac(held, 1); held.on = false; if (rc) break; }
-            {
-                MacJob m; m.on = true; m.ptp = pt; m.gsn = ng; m.gi = gi;
-                m.acc_flag = (accumulate || !first_group) ? 1 : 0;      // the first launch of a fresh call overwrites
-                m.accj = acc + (size_t)(bj - j0) * acc_col; m.rotf_grp = rotf_grp; m.rotsum_grp = rotsum_grp;
-                if (ride_want && rideBs) held = m;                                 // multiplied after the next launch's encode has transposed this panel
-                else rc = run_mac(m, rideBs ? 2 : 0);
-            }
+            if (held.on) { SFG_TRY(i8_ride_finish(ctx, ride)); SFG_TRY(run_mac(c, held, 1)); held.on = false; }
+            MacJob m; m.on = true; m.ptp = pt; m.gsn = ng; m.gi = gi;
+            m.acc_flag = (accumulate || bg != b0) ? 1 : 0;              // the first launch of a fresh call overwrites
+            m.accj = acc + (size_t)(bj - j0) * acc_col; m.rotf_grp = rotf_grp; m.rotsum_grp = rotsum_grp;
+            if (plan.ride_want && c.rideBs) held = m;                                 // multiplied after the next launch's encode has transposed this panel
+            else SFG_TRY(run_mac(c, m, c.rideBs ? 2 : 0));
         }
-        first_group = false;
     }
-    if (held.on && !rc) rc = run_mac(held, 2);                  // the call's last launch: nothing follows to ride in
+    if (held.on) rc = run_mac(c, held, 2);                      // the call's last launch: nothing follows to ride in
     return rc;
 }
 
@@ -777,8 +745,8 @@ static int matmul_resident_range(sfg_ctx *ctx, const uint64_t *A, int s, int in_
             for (int bi = b0; bi < b1; bi++) SFG_TRY(build_rot_row(ctx, (const u64 *)A, s, in_level + 1, nl, lev, L, sh, bi, a_row, rotc, true, buf + (size_t)(bi - b0) * per_row));
             SFG_HIP(ctx, hipMemsetAsync(buf + (size_t)(b1 - b0) * per_row, 0, 3 * (size_t)s * 2 * rowf * 8, ctx->stream));   // k-slices read by a ragged last chunk
             rotf_all = buf;
-            if (mac_dma_packed_mask(ctx, L)) {             // per MAC group (as matmul_accumulate forms them): sum of its k-slices
-                const int G = std::min(ctx->cfg.mm_group, b1 - b0), ngrp = (b1 - b0 + G - 1) / G;
+            if (mac_dma_packed_mask(ctx, L)) {             // per group of rotsum_group_size (mm_plan.hpp) block rows: sum of its k-slices
+                const int G = rotsum_group_size(ctx->cfg.mm_group, b1 - b0), ngrp = (b1 - b0 + G - 1) / G;
                 double *rs = nullptr;
                 SFG_TRY(sfg_scratch(ctx, "mm.rotsum_all", (size_t)ngrp * s * 2 * rowf * 8, (void **)&rs));
                 for (int gi = 0; gi < ngrp; gi++) {
@@ -927,35 +895,17 @@ int i8_rotpre_build(sfg_ctx *ctx, const u64 *A, int s, int in_level, int max_lev
     const auto &c = ctx->cfg;
     if (!mac_use_dma(ctx) || !c.mac_bc || c.mac_plain_pt || !c.mac_i8 || !c.mac_i8_big || 2 * s > 30 || L < 1 || L > ctx->nq || nbr < 1) return 0;
     if (!mac_dma_packed_mask(ctx, L)) return 0;
-    std::vector<int> plane_of, is_big; const int nplanes = mac_dma_planes(ctx, L, plane_of, is_big);
-    if (nplanes < 0) { ctx->err.clear(); return 0; }
     // launch_mac_bc multiplies run by run of like moduli: one run of 35-bit moduli and at most one 46-bit modulus have one tile buffer each
-    int l_big = -1, l_s0 = -1, n_s = 0, runs = 0;
-    for (int l = 0; l < L; l++) {
-        if (is_big[l]) { if (l_big >= 0) return 0; l_big = l; }
-        else { if (l_s0 < 0) l_s0 = l; n_s++; if (l == 0 || is_big[l - 1]) runs++; }
+    const ModSplit m(ctx->q, L);
+    const int l_big = m.l_big, l_s0 = m.l_small0, n_s = m.nsmall; const int *plane_of = m.plane_of;
+    const size_t rowf = (size_t)m.fp64_planes * SFG_N;
+    size_t have = 0, tot = 0; bool mem_failed = false;
+    if (c.mm_group_auto && nbr > c.mm_group) {
+        mem_failed = hipMemGetInfo(&have, &tot) != hipSuccess;
+        for (const auto &kv : ctx->pool) if (kv.first.rfind(prefix, 0) == 0 || kv.first == "mm.pt" || kv.first == "mm.rotf" || kv.first.rfind("mi8.", 0) == 0) have += kv.second.second;
     }
-    if (runs != 1) return 0;
-    const size_t rowf = (size_t)nplanes * SFG_N;
-    auto tiles_of = [&](int Gc) { size_t t = 0; for (int b = 0; b < nbr; b += Gc) { const int ng = std::min(Gc, nbr - b); t += mac_i8_rot_tile_bytes(ng * d, n_s, 5) + (l_big >= 0 ? mac_i8_rot_tile_bytes(ng * d, 1, 6) : 0); } return t; };
-    int G = std::min(c.mm_group, nbr);
-    // 16 (12) block rows per MAC group where the HBM takes the larger plaintext panel (two of them: the encode of a launch runs beside the previous launch's
-    // MAC) and plaintext tiles: half the launches, half the accumulator read-modify-writes (0.256 against 0.272 s per batch at 500 000 samples, 8 batches)
-    if (c.mm_group_auto && nbr > G) {
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
-            size_t have = fr;
-            for (const auto &kv : ctx->pool) if (kv.first.rfind(prefix, 0) == 0 || kv.first == "mm.pt" || kv.first == "mm.rotf" || kv.first.rfind("mi8.", 0) == 0) have += kv.second.second;
-            for (int cand : {16, 12}) {
-                const int G2 = std::min(cand, nbr);
-                if (G2 <= G) break;
-                const size_t panel = (size_t)G2 * d * d * L * (SFG_N / 2) * 8 * 2, rotf = ((size_t)G2 * d + 3) * s * 2 * rowf * 8;
-                const size_t need = tiles_of(G2) + panel + rotf + mac_i8_stream_bytes(G2 * d, n_s, 5, 0) + (l_big >= 0 ? mac_i8_stream_bytes(G2 * d, 1, 6, 0) : 0) + (24ULL << 30);
-                if (need <= have && tiles_of(G2) <= budget_bytes) { G = G2; break; }
-            }
-        }
-    }
-    if ((long long)G * d * 6 >= 131072 || tiles_of(G) > budget_bytes) return 0;
+    int G = i8pre_group_size(m, c.mm_group, c.mm_group_auto, s, nbr, mem_failed, have, budget_bytes);
+    if (!G) return 0;
     // every buffer first (the fp64 rows of one group in the product's own mm.rotf, the tile buffers of all groups); where the larger groups do not fit after
     // all - another context on the device - the default group size is tried before the caller is told to fall back
     double *tmp = nullptr;

@@ -321,9 +321,9 @@ __device__ __forceinline__ void ntt_half3_wg(size_t vb, double *lds, const doubl
         } else out = reinterpret_cast<u64 *>(reinterpret_cast<uint8_t *>(out_) + dst * (planes_all * n) + planes_below * n);
     }
     // (the format test is hoisted: inside the store loop it costs a branch per word)
-    // int8 MAC (mac_i8.hip; bit 31 of the mask): the packed rows leave as five planes of signed base-256 digits instead of words - 5 of the row's 8 bytes per word.
+    // int8 MAC (mac_i8.hip; PT_DIGITS): the packed rows leave as five planes of signed base-256 digits instead of words - 5 of the row's 8 bytes per word.
     // Balanced digits of v: the bytes of v + 0x8080808080 with their top bits flipped; the sum is read off the mantissa of v + 2^52 + 0x8080808080.
-    if constexpr (DIG) if (!((pm.packed_mask >> m) & 1u) && ((pm.packed_mask >> 30) & 1u)) {        // the 46-bit row as SIX digit planes (48 KiB of its 64 KiB)
+    if constexpr (DIG) if (!((pm.packed_mask >> m) & 1u) && (pm.packed_mask & PT_DIGITS_BIG)) {        // the 46-bit row as SIX digit planes (48 KiB of its 64 KiB)
         uint8_t *o8 = reinterpret_cast<uint8_t *>(out);
         auto dig6 = [&](double x, unsigned &lo, unsigned &hi) {
             const u64 b = (u64)__double_as_longlong(canon(x, q, qinv) + (4503599627370496.0 + 141289400074368.0));       // + 2^52 + 0x808080808080
@@ -478,7 +478,7 @@ static int launch_half3_move(sfg_ctx *ctx, dim3 grid, const double *pc, u64 *out
 int launch_ntt_plain_half(sfg_ctx *ctx, const double *pc, u64 *out_half, size_t nplain, int L, PanelMap pm, const uint32_t *perm, const MoveJob *mv) {
     if (!nplain) return 0;
     const dim3 grid((unsigned)((nplain + 7) / 8 * 8 * L));
-    const bool dig = pm.packed_mask >> 31;                 // digit planes for the int8 MAC (mac_i8.hip): its own instances, the default kernels are untouched
+    const bool dig = pm.packed_mask & PT_DIGITS;                 // digit planes for the int8 MAC (mac_i8.hip): its own instances, the default kernels are untouched
     if (mv && mv->count) {
         if (!dig || mv->nblocks % 8 || !mv->nblocks) SFG_FAIL(ctx, "plaintext NTT: mover workgroups need the digit-plane form and a multiple of 8 of them");
         const dim3 g2(grid.x + mv->nblocks);
