@@ -271,6 +271,25 @@ int sfg_geno_transpose(sfg_ctx *ctx, const sfg_geno *g, sfg_geno **out);
 int sfg_geno_concat_cols(sfg_ctx *ctx, const sfg_geno *const *parts, int k, sfg_geno **out);
 /* P2: per-column sum / sum of squares after missing->0 (matmult.go:1292-1300); either may be NULL */
 int sfg_geno_colsums(sfg_ctx *ctx, const sfg_geno *g, double *sum_host, double *sqsum_host);
+/* ---- quality control on the resident matrix (qcscan.hip): the three local passes of gwas/qualcontrol.go in ONE pass over the matrix bytes ----
+ * replaces the genotype loops of SNPMissFilter (qualcontrol.go:339-378), IndividualMissAndHetFilters (qualcontrol.go:36-81) and SNPMAFAndHWEFilters
+ * (qualcontrol.go:416-463); their secure comparisons stay in Go.  Only entries (i, j) with row_filter[i] != 0 and col_filter[j] != 0 are looked at (a NULL
+ * filter keeps all); row_ctrl[i] != 0 marks the control cohort (the reference's pheno < 1), NULL = no controls.  Outputs, any of which may be NULL (not all):
+ *   col_counts_host [2][4][ncol] uint32: [c][k][j] = kept rows of cohort c (0: all kept rows, 1: the kept controls) whose entry in column j is k = 0, 1, 2
+ *                                        or (k = 3) missing: any negative int8 / packed code 3
+ *   row_miss_host / row_het_host [nrow]: missing entries / entries equal to 1 of row i over the kept columns
+ * indexed by ORIGINAL position; a dropped row or column has zeros.  Per cohort the reference's xCount = 2 (n0 + n1 + n2), xSum = n1 + 2 n2,
+ * genoObservedCtrl[k] = n_k of cohort 1, and SNPMissFilter's count is n0 + n1 + n2 of cohort 0.  An int8 value above 2 at a kept position fails the call (the
+ * message names how many; the reference would panic at genoObservedCtrl[snp]); at a dropped position it is not looked at.  A packed handle is scanned in place.
+ * The matrix is read once whichever outputs are asked for; temporaries are O(nrow + ncol) ("qc." scratch).  Synchronising.  g == NULL or no output: an error that
+ * launches nothing. */
+int sfg_geno_qc_scan(sfg_ctx *ctx, const sfg_geno *g, const uint8_t *row_filter, const uint8_t *col_filter, const uint8_t *row_ctrl,
+                     uint32_t *col_counts_host, uint32_t *row_miss_host, uint32_t *row_het_host);
+/* the filtered matrix as a new owned resident handle: replaces FilterMatrixFile (gwas/utilities.go:154 -> scripts/filterMatrix.py) and the lazy row / column
+ * filters of the GenoFileStreams (gwas/gwas.go:545 GeneratePCAInput reads through them) for a matrix that is already in HBM.  Kept rows and columns in order;
+ * int8 in -> int8 out, packed in -> packed out (codes re-packed across the dropped columns, padding codes 0, no int8 intermediate).  Both filters NULL: a copy.
+ * Filters that keep nothing: an error that allocates nothing. */
+int sfg_geno_filter(sfg_ctx *ctx, const sfg_geno *g, const uint8_t *row_filter, const uint8_t *col_filter, sfg_geno **out);
 
 /* ---- A9/A10: the full product (MatMult4Stream matmult.go:1238-1505, MatMult4StreamCompute :1043-1236) ----
  * A: s x nbr ciphertexts [s][nbr][2][in_level+1][N] (nbr = ceil(rows/slots) of the operand orientation);
@@ -443,6 +462,13 @@ const sfg_geno *sfg_mgpu_geno_shard(const sfg_mgeno *g, int local);
 int sfg_mgpu_geno_dims(const sfg_mgeno *g, size_t *nrow, size_t *ncol);
 int sfg_mgpu_geno_blocks(const sfg_mgeno *g, int local, size_t *blk0, size_t *blk1);
 int sfg_mgpu_geno_set_plaintext_cache(sfg_mgpu *mg, const sfg_mgeno *g, size_t max_bytes_per_rank);
+/* sfg_geno_qc_scan on the sharded matrix (gwas/qualcontrol.go:36-81, 339-378, 416-463): filters and outputs span the WHOLE matrix; every local rank scans its
+ * column window, column counts land at the window's columns, the row counts of the local ranks are summed on the host.  No collective: in a one-process-per-GPU
+ * world the column counts outside this process's windows are zero and the row counts are the PARTIAL sums of this process's ranks - the caller adds them across
+ * processes.  (There is no sharded counterpart of sfg_geno_filter: a filtered window is no longer a whole number of 8192-column blocks, which is what sfg_mgeno
+ * windows are; filter per rank with sfg_geno_filter on sfg_mgpu_geno_shard's handles, or before sharding.) */
+int sfg_mgpu_geno_qc_scan(sfg_mgpu *mg, const sfg_mgeno *g, const uint8_t *row_filter, const uint8_t *col_filter, const uint8_t *row_ctrl,
+                          uint32_t *col_counts_host, uint32_t *row_miss_host, uint32_t *row_het_host);
 /* The row-streamed forms of sfg_geno_create / _write_rows / _compare_rows on the sharded matrix (MatMult4StreamPreprocess, gwas/matmult.go:914-1041, reads one row
  * at a time: gwas/filestream.go:414-426): a chunk of whole-matrix rows is scattered to the ranks' column windows; a chunk of the rows of the TRANSPOSE is compared by
  * the ranks whose windows hold those columns.  *ndiff accumulates over the local ranks. */

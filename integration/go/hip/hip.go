@@ -507,6 +507,81 @@ func LookupGeno(prefix string) *Geno {
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// Quality control on a resident matrix (gwas/qualcontrol.go:36-81, 339-378, 416-463; include/sfgwas_hip.h: sfg_geno_qc_scan, sfg_geno_filter).
+
+// QCCounts is what one scan returns, indexed by the matrix's own rows and columns (a dropped row or column holds zeros).
+// Col[c][k][j]: kept rows of cohort c (0 = all kept rows, 1 = kept controls) whose call at SNP j is k = 0, 1, 2 or 3 (missing).
+type QCCounts struct {
+	Col     [2][4][]uint32
+	RowMiss []uint32
+	RowHet  []uint32
+}
+
+func filterPtr(f []bool, n int, store *[]byte) *C.uint8_t {
+	if f == nil {
+		return nil
+	}
+	if len(f) != n {
+		panic("Invalid length of input array")
+	}
+	*store = make([]byte, n)
+	for i, keep := range f {
+		if keep {
+			(*store)[i] = 1
+		}
+	}
+	return (*C.uint8_t)(unsafe.Pointer(&(*store)[0]))
+}
+
+// QCScan counts, in one pass over the resident matrix, what the three loops of gwas/qualcontrol.go count: rowFilt / colFilt (nil = keep all) say which
+// individuals and SNPs are looked at, ctrl (nil = none) marks the control cohort (pheno < 1).  wantCols / wantRows choose the outputs.
+// On the multi-GPU engine the row counts are those of this process's ranks.
+func (h *Ctx) QCScan(g *Geno, rowFilt, colFilt, ctrl []bool, wantCols, wantRows bool) *QCCounts {
+	if g.Flags&FlagTranspose != 0 {
+		panic("QCScan: pass the stored matrix (individuals x SNPs), not its transposed view")
+	}
+	var rs, cs, ts []byte
+	pr, pc, pt := filterPtr(rowFilt, g.NRow, &rs), filterPtr(colFilt, g.NCol, &cs), filterPtr(ctrl, g.NRow, &ts)
+	out := &QCCounts{}
+	var pcol, pmiss, phet *C.uint32_t
+	var flat []uint32
+	if wantCols {
+		flat = make([]uint32, 8*g.NCol)
+		pcol = (*C.uint32_t)(unsafe.Pointer(&flat[0]))
+		for c := 0; c < 2; c++ {
+			for k := 0; k < 4; k++ {
+				out.Col[c][k] = flat[(c*4+k)*g.NCol : (c*4+k+1)*g.NCol]
+			}
+		}
+	}
+	if wantRows {
+		out.RowMiss, out.RowHet = make([]uint32, g.NRow), make([]uint32, g.NRow)
+		pmiss, phet = (*C.uint32_t)(unsafe.Pointer(&out.RowMiss[0])), (*C.uint32_t)(unsafe.Pointer(&out.RowHet[0]))
+	}
+	if g.mg != nil {
+		Default.mcheck(C.sfg_mgpu_geno_qc_scan(Default.mg, g.mg, pr, pc, pt, pcol, pmiss, phet), "mgpu_geno_qc_scan")
+	} else {
+		h.check(C.sfg_geno_qc_scan(h.p, g.g, pr, pc, pt, pcol, pmiss, phet), "geno_qc_scan")
+	}
+	return out
+}
+
+// FilterGeno returns the kept rows and columns of a single-device resident matrix as a new resident matrix (int8 stays int8, packed stays packed):
+// FilterMatrixFile (gwas/utilities.go:154) without the files.  The caller registers or frees the result.
+func (h *Ctx) FilterGeno(g *Geno, rowFilt, colFilt []bool) *Geno {
+	if g.mg != nil || g.Flags&FlagTranspose != 0 {
+		panic("FilterGeno: needs the stored single-device matrix (filter a sharded matrix per rank, or before sharding)")
+	}
+	var rs, cs []byte
+	pr, pc := filterPtr(rowFilt, g.NRow, &rs), filterPtr(colFilt, g.NCol, &cs)
+	var f *C.sfg_geno
+	h.check(C.sfg_geno_filter(h.p, g.g, pr, pc, &f), "geno_filter")
+	var nr, nc C.size_t
+	C.sfg_geno_dims(f, &nr, &nc)
+	return &Geno{f, nil, 0, int(nr), int(nc)}
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // The calls the sibling files make.
 
 // MatmulStream = MatMult4Stream on host buffers (include/sfgwas_hip.h: sfg_matmul_stream).

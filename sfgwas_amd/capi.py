@@ -151,6 +151,9 @@ def _sig(L):
         "sfg_geno_transpose": (i, [vp, vp, C.POINTER(vp)]),
         "sfg_geno_concat_cols": (i, [vp, C.POINTER(vp), i, C.POINTER(vp)]),
         "sfg_geno_colsums": (i, [vp, vp, C.POINTER(d), C.POINTER(d)]),
+        "sfg_geno_qc_scan": (i, [vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sfg_geno_filter": (i, [vp, vp, vp, vp, C.POINTER(vp)]),
+        "sfg_mgpu_geno_qc_scan": (i, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "sfg_matmul_resident_dev": (i, [vp, vp, i, i, i, vp, C.c_uint, vp]),
         "sfg_matmul_from_cache": (i, [vp, vp, i, i, i, C.c_char_p, i, vp]),
         "sfg_diagcache_header": (i, [vp, C.c_char_p, i, u64p]),
@@ -916,6 +919,49 @@ def _ctx_matmul_finalize(self, acc, s, max_level, ncolb, g0, g1, out=None):
     return out
 
 
+def _filter_arg(f, n, what):
+    """a row / column filter or cohort mask as the uint8 array the library reads (None stays None)"""
+    if f is None:
+        return None, None
+    f = np.ascontiguousarray(np.asarray(f) != 0, dtype=np.uint8)
+    if f.shape != (n,):
+        raise ValueError(f"{what}: expected {n} entries, got {f.shape}")
+    return f, f.ctypes.data_as(C.c_void_p)
+
+
+def _qc_scan(check, fn, h, g, nrow, ncol, row_filter, col_filter, row_ctrl, cols, rows):
+    rf, prf = _filter_arg(row_filter, nrow, "row_filter")
+    cf, pcf = _filter_arg(col_filter, ncol, "col_filter")
+    rc, prc = _filter_arg(row_ctrl, nrow, "row_ctrl")
+    cc = np.empty((2, 4, ncol), dtype=np.uint32) if cols else None
+    rm = np.empty(nrow, dtype=np.uint32) if rows else None
+    rh = np.empty(nrow, dtype=np.uint32) if rows else None
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    check(fn(h, g, prf, pcf, prc, ptr(cc), ptr(rm), ptr(rh)), "geno_qc_scan")
+    return cc, rm, rh
+
+
+def _ctx_geno_qc_scan(self, g, row_filter=None, col_filter=None, row_ctrl=None, cols=True, rows=True):
+    """one pass over a resident matrix (sfg_geno_qc_scan): (col_counts [2][4][ncol], row_miss [nrow], row_het [nrow]) as uint32; cols / rows = False leaves that
+    output out (None is returned in its place)"""
+    nr, nc = C.c_size_t(), C.c_size_t()
+    lib().sfg_geno_dims(g, C.byref(nr), C.byref(nc))
+    return _qc_scan(self.check, lib().sfg_geno_qc_scan, self.h, g, nr.value, nc.value, row_filter, col_filter, row_ctrl, cols, rows)
+
+
+def _ctx_geno_filter(self, g, row_filter=None, col_filter=None):
+    """the kept rows / columns of a resident matrix as a new resident handle of the same layout (sfg_geno_filter)"""
+    nr, nc = C.c_size_t(), C.c_size_t()
+    lib().sfg_geno_dims(g, C.byref(nr), C.byref(nc))
+    rf, prf = _filter_arg(row_filter, nr.value, "row_filter")
+    cf, pcf = _filter_arg(col_filter, nc.value, "col_filter")
+    out = C.c_void_p()
+    self.check(lib().sfg_geno_filter(self.h, g, prf, pcf, C.byref(out)), "geno_filter")
+    return out
+
+
+Context.geno_qc_scan = _ctx_geno_qc_scan
+Context.geno_filter = _ctx_geno_filter
 Context.geno_upload = _ctx_geno_upload
 Context.geno_free = _ctx_geno_free
 Context.geno_create = _ctx_geno_create
@@ -1026,6 +1072,13 @@ class MultiGpu:
 
     def geno_free(self, g):
         lib().sfg_mgpu_geno_free(self.h, g)
+
+    def geno_qc_scan(self, g, row_filter=None, col_filter=None, row_ctrl=None, cols=True, rows=True):
+        """Context.geno_qc_scan on the sharded matrix (sfg_mgpu_geno_qc_scan): filters and outputs span the whole matrix; the row counts are those of this
+        process's ranks"""
+        nr, nc = C.c_size_t(), C.c_size_t()
+        lib().sfg_mgpu_geno_dims(g, C.byref(nr), C.byref(nc))
+        return _qc_scan(self.check, lib().sfg_mgpu_geno_qc_scan, self.h, g, nr.value, nc.value, row_filter, col_filter, row_ctrl, cols, rows)
 
     def geno_blocks(self, g, local):
         b0, b1 = C.c_size_t(), C.c_size_t()

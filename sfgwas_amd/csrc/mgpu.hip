@@ -447,6 +447,41 @@ extern "C" int sfg_mgpu_geno_set_plaintext_cache(sfg_mgpu *mg, const sfg_mgeno *
     MG_NEED(mg, g && g->shard.size() == mg->r.size(), "the matrix belongs to another engine");
     return run_ranks(mg, [&](MgRank &R, int i) { if (g->shard[(size_t)i]) R_CTX(R, sfg_geno_set_plaintext_cache(R.ctx, g->shard[(size_t)i], max_bytes_per_rank)); return 0; });
 }
+// The quality-control scan (qcscan.hip) on the sharded matrix: every local rank scans its own column window with the whole-matrix row filter and its slice of the
+// column filter.  Column counts land at the window's columns; the row counts of the local ranks are summed on the host (in a one-process-per-GPU world: the partial
+// sums of this process's ranks).  No collective.
+extern "C" int sfg_mgpu_geno_qc_scan(sfg_mgpu *mg, const sfg_mgeno *g, const uint8_t *row_filter, const uint8_t *col_filter, const uint8_t *row_ctrl,
+                                     uint32_t *col_counts_host, uint32_t *row_miss_host, uint32_t *row_het_host) {
+    MG_NEED(mg, mg != nullptr, "null engine");
+    MG_NEED(mg, g && g->shard.size() == mg->r.size(), "the matrix belongs to another engine");
+    if (!col_counts_host && !row_miss_host && !row_het_host) MG_FAIL(mg, "sfg_mgpu_geno_qc_scan: no output requested");
+    const size_t n = mg->r.size(), nrow = g->nrow, ncol = g->ncol;
+    const bool want_rows = row_miss_host || row_het_host;
+    std::vector<std::vector<uint32_t>> cc(n), rm(n), rh(n);
+    const int rc = run_ranks(mg, [&](MgRank &R, int i) {
+        const sfg_geno *sh = g->shard[(size_t)i];
+        if (!sh) return 0;
+        const size_t c0 = g->blk0[(size_t)i] * SFG_SLOTS;
+        if (col_counts_host) cc[(size_t)i].resize(8 * sh->ncol);
+        if (want_rows) { rm[(size_t)i].resize(nrow); rh[(size_t)i].resize(nrow); }
+        R_CTX(R, sfg_geno_qc_scan(R.ctx, sh, row_filter, col_filter ? col_filter + c0 : nullptr, row_ctrl, col_counts_host ? cc[(size_t)i].data() : nullptr,
+                                  want_rows ? rm[(size_t)i].data() : nullptr, want_rows ? rh[(size_t)i].data() : nullptr));
+        return 0;
+    });
+    if (rc) return rc;
+    if (col_counts_host) std::fill(col_counts_host, col_counts_host + 8 * ncol, 0u);
+    if (row_miss_host) std::fill(row_miss_host, row_miss_host + nrow, 0u);
+    if (row_het_host) std::fill(row_het_host, row_het_host + nrow, 0u);
+    for (size_t i = 0; i < n; i++) {
+        const sfg_geno *sh = g->shard[i];
+        if (!sh) continue;
+        const size_t c0 = g->blk0[i] * SFG_SLOTS, w = sh->ncol;
+        if (col_counts_host) for (int k = 0; k < 8; k++) std::copy(cc[i].begin() + (size_t)k * w, cc[i].begin() + (size_t)(k + 1) * w, col_counts_host + (size_t)k * ncol + c0);
+        if (row_miss_host) for (size_t r = 0; r < nrow; r++) row_miss_host[r] += rm[i][r];
+        if (row_het_host) for (size_t r = 0; r < nrow; r++) row_het_host[r] += rh[i][r];
+    }
+    return 0;
+}
 
 // ---------------------------------------------------------------- collectives (enqueued on `st` of the calling rank, in order with it)
 static int coll_reduce_scatter(sfg_mgpu *mg, MgRank &R, const uint64_t *send, uint64_t *recv, size_t recv_count, hipStream_t st) {

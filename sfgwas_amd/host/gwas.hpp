@@ -1243,6 +1243,74 @@ inline std::vector<crypto::DevCipherVector> CMultMatColTimesToColDev(crypto::Cry
     }
     return result;
 }
+
+// ---------------------------------------------------------------- quality control on a resident matrix (qualcontrol.go)
+// The three passes over the genotype bytes that the reference makes with single-threaded loops, each served by ONE sfg_geno_qc_scan over the matrix in HBM; the
+// secure comparisons that follow them stay with the MPC layer.  g: a single-device resident matrix (ResidentGeno::g), stored orientation individuals x SNPs.
+namespace qc {
+struct FilterParams { double IndMissBound = 0, HetLowerBound = 0, HetUpperBound = 0; };        // the three fields of qualcontrol.go's FilterParams these loops read
+inline std::vector<uint8_t> toBytes(const std::vector<bool> &f) { std::vector<uint8_t> b(f.size()); for (size_t i = 0; i < f.size(); i++) b[i] = f[i] ? 1 : 0; return b; }
+inline void dims(const sfg_geno *g, size_t &nrow, size_t &ncol) { if (sfg_geno_dims(g, &nrow, &ncol)) throw std::runtime_error("qc: null matrix"); }
+inline const uint8_t *filterArg(const std::vector<bool> &f, size_t n, std::vector<uint8_t> &store, const char *what) {   // empty = no filter
+    if (f.empty()) return nullptr;
+    if (f.size() != n) throw std::runtime_error(std::string(what) + ": Invalid length of input array");
+    store = toBytes(f); return store.data();
+}
+// SNPMissFilter (:339-378): xCount[snp] = the individuals whose call is not missing
+inline std::vector<int> SNPMissCounts(crypto::CryptoParams *cps, const sfg_geno *g) {
+    size_t nrow, ncol; dims(g, nrow, ncol);
+    std::vector<uint32_t> cc(8 * ncol);
+    cps->check(sfg_geno_qc_scan(cps->ctx, g, nullptr, nullptr, nullptr, cc.data(), nullptr, nullptr), "SNPMissFilter");
+    std::vector<int> xCount(ncol);
+    for (size_t j = 0; j < ncol; j++) xCount[j] = (int)(cc[j] + cc[ncol + j] + cc[2 * ncol + j]);
+    return xCount;
+}
+// IndividualMissAndHetFilters (:36-81) over the SNPs colFilt keeps (the streams' column filter after SNPMissFilter); numSnps = qc.filtNumSnps.  The ikeep rule in
+// float64 exactly as written there: 0 / 0 is NaN, every comparison with it is false, the individual is dropped
+inline std::vector<bool> IndividualMissAndHetFilters(crypto::CryptoParams *cps, const sfg_geno *g, const std::vector<bool> &colFilt, int numSnps, const FilterParams &fp) {
+    size_t nrow, ncol; dims(g, nrow, ncol);
+    std::vector<uint8_t> cf; const uint8_t *pcf = filterArg(colFilt, ncol, cf, "IndividualMissAndHetFilters");
+    std::vector<uint32_t> miss(nrow), het(nrow);
+    cps->check(sfg_geno_qc_scan(cps->ctx, g, nullptr, pcf, nullptr, nullptr, miss.data(), het.data()), "IndividualMissAndHetFilters");
+    std::vector<bool> ikeep(nrow);
+    for (size_t i = 0; i < nrow; i++) {
+        const double missRate = (double)(int)miss[i] / (double)numSnps;
+        const double hetRate = (double)(int)het[i] / (double)(numSnps - (int)miss[i]);
+        ikeep[i] = missRate < fp.IndMissBound && hetRate < fp.HetUpperBound && hetRate > fp.HetLowerBound;
+    }
+    return ikeep;
+}
+// SNPMAFAndHWEFilters' scan (:416-463) over the rows rowFilt keeps and the SNPs colFilt keeps; pheno: one value per row of the STORED matrix (controls: pheno < 1).
+// The five results are compacted to the kept SNPs, as the Go slices of length filtNumSnps are
+struct MAFAndHWECounts { std::vector<int> xSum, xCount, xSumCtrl, xCountCtrl; std::vector<std::vector<int>> genoObservedCtrl; };
+inline MAFAndHWECounts SNPMAFAndHWECounts(crypto::CryptoParams *cps, const sfg_geno *g, const std::vector<bool> &rowFilt, const std::vector<bool> &colFilt, const std::vector<double> &pheno) {
+    size_t nrow, ncol; dims(g, nrow, ncol);
+    if (pheno.size() != nrow) throw std::runtime_error("SNPMAFAndHWEFilters: one phenotype per stored row expected");
+    std::vector<uint8_t> rf, cf, ctrl(nrow);
+    const uint8_t *prf = filterArg(rowFilt, nrow, rf, "SNPMAFAndHWEFilters"), *pcf = filterArg(colFilt, ncol, cf, "SNPMAFAndHWEFilters");
+    for (size_t i = 0; i < nrow; i++) ctrl[i] = (int)pheno[i] < 1 ? 1 : 0;                      // yi := int(phenoF.At(rowIndex, 0)); yi < 1
+    std::vector<uint32_t> cc(8 * ncol);
+    cps->check(sfg_geno_qc_scan(cps->ctx, g, prf, pcf, ctrl.data(), cc.data(), nullptr, nullptr), "SNPMAFAndHWEFilters");
+    MAFAndHWECounts r; r.genoObservedCtrl.resize(3);
+    for (size_t j = 0; j < ncol; j++) {
+        if (pcf && !pcf[j]) continue;
+        const uint32_t *a = cc.data() + j, *c = cc.data() + 4 * ncol + j;                        // [k][j] at k * ncol
+        r.xSum.push_back((int)(a[ncol] + 2 * a[2 * ncol])); r.xCount.push_back((int)(2 * (a[0] + a[ncol] + a[2 * ncol])));
+        r.xSumCtrl.push_back((int)(c[ncol] + 2 * c[2 * ncol])); r.xCountCtrl.push_back((int)(2 * (c[0] + c[ncol] + c[2 * ncol])));
+        for (int k = 0; k < 3; k++) r.genoObservedCtrl[k].push_back((int)c[(size_t)k * ncol]);
+    }
+    return r;
+}
+// FilterMatrixFile (utilities.go:154) for a matrix that is already resident: the kept rows and columns as a new resident matrix the caller owns (sfg_geno_free)
+inline sfg_geno *FilterResident(crypto::CryptoParams *cps, const sfg_geno *g, const std::vector<bool> &rowFilt, const std::vector<bool> &colFilt) {
+    size_t nrow, ncol; dims(g, nrow, ncol);
+    std::vector<uint8_t> rf, cf;
+    const uint8_t *prf = filterArg(rowFilt, nrow, rf, "FilterResident"), *pcf = filterArg(colFilt, ncol, cf, "FilterResident");
+    sfg_geno *out = nullptr;
+    cps->check(sfg_geno_filter(cps->ctx, g, prf, pcf, &out), "FilterResident");
+    return out;
+}
+}  // namespace qc
 }  // namespace gwas
 
 namespace mpc {
