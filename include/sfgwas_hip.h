@@ -263,6 +263,11 @@ int sfg_pgen_geno_counts(sfg_ctx *ctx, const uint8_t *pgen_host, size_t pgen_byt
 int sfg_geno_pack(sfg_ctx *ctx, const sfg_geno *g, sfg_geno **out);
 int sfg_geno_unpack(sfg_ctx *ctx, const sfg_geno *g, sfg_geno **out);
 int sfg_geno_dims(const sfg_geno *g, size_t *nrow, size_t *ncol);
+/* how a handle lies in device memory: *dev = its first byte, *ld = the row stride in BYTES (int8: >= ncol; packed: 4 columns per byte, a multiple of 4),
+ * *packed = 1 for 2-bit codes (any pointer may be NULL).  For INSPECTION and interoperability only - a test that reads the padding of a row, a caller that hands
+ * the matrix to a kernel of its own: the memory stays the library's (or, for sfg_geno_from_device, the caller's, as before), it is read-only to the caller, the
+ * pointer dies with the handle, and no library call takes such a pointer back as a matrix (sfg_geno_from_device wants memory the caller owns). */
+int sfg_geno_layout(const sfg_geno *g, const void **dev, size_t *ld, int *packed);
 /* host [nrow][ncol] copy of a resident matrix (interoperability with CPU-only parties, tests) */
 int sfg_geno_download(sfg_ctx *ctx, const sfg_geno *g, int8_t *host);
 /* scripts/transposeMatrix.py as a materialised copy (the products themselves use SFG_TRANSPOSE on the one copy) */
@@ -465,10 +470,32 @@ int sfg_mgpu_geno_set_plaintext_cache(sfg_mgpu *mg, const sfg_mgeno *g, size_t m
 /* sfg_geno_qc_scan on the sharded matrix (gwas/qualcontrol.go:36-81, 339-378, 416-463): filters and outputs span the WHOLE matrix; every local rank scans its
  * column window, column counts land at the window's columns, the row counts of the local ranks are summed on the host.  No collective: in a one-process-per-GPU
  * world the column counts outside this process's windows are zero and the row counts are the PARTIAL sums of this process's ranks - the caller adds them across
- * processes.  (There is no sharded counterpart of sfg_geno_filter: a filtered window is no longer a whole number of 8192-column blocks, which is what sfg_mgeno
- * windows are; filter per rank with sfg_geno_filter on sfg_mgpu_geno_shard's handles, or before sharding.) */
+ * processes.  (The sharded counterpart of sfg_geno_filter is sfg_mgpu_geno_filter below: it re-shards, because a rank's filtered window is no longer a whole
+ * number of 8192-column blocks, which is what sfg_mgeno windows are.  It exists inside one process only; in a one-process-per-GPU world filter before sharding.) */
 int sfg_mgpu_geno_qc_scan(sfg_mgpu *mg, const sfg_mgeno *g, const uint8_t *row_filter, const uint8_t *col_filter, const uint8_t *row_ctrl,
                           uint32_t *col_counts_host, uint32_t *row_miss_host, uint32_t *row_het_host);
+/* sfg_geno_filter on the sharded matrix, re-sharding (reshard.hip): what lies between quality control and the PCA in the reference - GeneratePCAInput
+ * (gwas/gwas.go:545) reads through the row and column filters, FilterMatrixFile (gwas/utilities.go:154) materialises the filtered matrix.  The filters span the
+ * WHOLE matrix (one byte per row, one per global column; zero drops, NULL keeps all; kept rows and columns stay in order).  *out is a new owned sfg_mgeno of
+ * kept_rows x kept_cols whose windows are those of sfg_mgpu_shard(world, kept_cols, rank): every rank gathers its new window straight out of the old windows of
+ * the ranks that hold its columns (plain loads between ranks that share a device, peer access between devices - enabled here on first use; devices that cannot
+ * reach each other fail the call before anything is allocated and are named).  int8 in -> int8 out, with the row stride of a shard rounded up to a multiple of
+ * 16 bytes and zero padding bytes (sfg_geno_layout tells; every product and scan takes a row stride); packed in -> packed out, codes re-packed across dropped
+ * columns and old rank boundaries, padding codes 0, no int8 intermediate.  Temporaries are the index tables, O(kept_rows + window columns) per rank ("qc."
+ * scratch).  The source is not changed and no collective is used; the call returns after every rank's queue has drained, so the source may be freed at once.  The
+ * result has no plaintext cache.  Both filters NULL: a copy with the same windows.  Filters that keep nothing, a NULL g or out, a dimension of 2^32 or more: an
+ * error that allocates and launches nothing.  If a rank fails, every new buffer is freed, *out is NULL and sfg_mgpu_last_error names the rank.  In a world of one
+ * rank per process a peer's memory is not addressable: the call is refused, and the matrix is filtered before it is sharded (sfg_geno_filter, or the filters of
+ * sfg_geno_from_bed / _from_pgen on each rank's window). */
+int sfg_mgpu_geno_filter(sfg_mgpu *mg, const sfg_mgeno *g, const uint8_t *row_filter, const uint8_t *col_filter, sfg_mgeno **out);
+/* sfg_sketch (gwas/pca.go:152-162) on the sharded matrix (SURVEY 8e "SNP-sharded, independent"): every local rank sketches its own window with the same per-row
+ * bucket_host / sgn_host; sketch_host [kp][ncol] and xsum_host / x2sum_host [ncol] are in the GLOBAL column layout, any of them may be NULL.  No collective: in a
+ * one-process-per-GPU world the entries outside this process's windows are zero.  A packed matrix is refused as by sfg_sketch, before anything is launched. */
+int sfg_mgpu_sketch(sfg_mgpu *mg, const sfg_mgeno *g, const int32_t *bucket_host, const int8_t *sgn_host, int kp,
+                    double *sketch_host, uint64_t *xsum_host, uint64_t *x2sum_host);
+/* sfg_geno_colsums (gwas/matmult.go:1292-1300) on the sharded matrix: sum_host / sqsum_host [ncol] in the global column layout, either may be NULL; entries
+ * outside this process's windows are zero. */
+int sfg_mgpu_geno_colsums(sfg_mgpu *mg, const sfg_mgeno *g, double *sum_host, double *sqsum_host);
 /* The row-streamed forms of sfg_geno_create / _write_rows / _compare_rows on the sharded matrix (MatMult4StreamPreprocess, gwas/matmult.go:914-1041, reads one row
  * at a time: gwas/filestream.go:414-426): a chunk of whole-matrix rows is scattered to the ranks' column windows; a chunk of the rows of the TRANSPOSE is compared by
  * the ranks whose windows hold those columns.  *ndiff accumulates over the local ranks. */

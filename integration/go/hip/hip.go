@@ -566,19 +566,71 @@ func (h *Ctx) QCScan(g *Geno, rowFilt, colFilt, ctrl []bool, wantCols, wantRows 
 	return out
 }
 
-// FilterGeno returns the kept rows and columns of a single-device resident matrix as a new resident matrix (int8 stays int8, packed stays packed):
-// FilterMatrixFile (gwas/utilities.go:154) without the files.  The caller registers or frees the result.
+// FilterGeno returns the kept rows and columns of a resident matrix as a new resident matrix (int8 stays int8, packed stays packed):
+// FilterMatrixFile (gwas/utilities.go:154) without the files.  A matrix sharded over the multi-GPU engine is re-sharded over the kept SNPs
+// (sfg_mgpu_geno_filter): the result multiplies, scans and sketches like any sharded matrix.  The caller registers or frees the result.
 func (h *Ctx) FilterGeno(g *Geno, rowFilt, colFilt []bool) *Geno {
-	if g.mg != nil || g.Flags&FlagTranspose != 0 {
-		panic("FilterGeno: needs the stored single-device matrix (filter a sharded matrix per rank, or before sharding)")
+	if g.Flags&FlagTranspose != 0 {
+		panic("FilterGeno: pass the stored matrix (individuals x SNPs), not its transposed view")
 	}
 	var rs, cs []byte
 	pr, pc := filterPtr(rowFilt, g.NRow, &rs), filterPtr(colFilt, g.NCol, &cs)
+	if g.mg != nil {
+		var m *C.sfg_mgeno
+		Default.mcheck(C.sfg_mgpu_geno_filter(Default.mg, g.mg, pr, pc, &m), "mgpu_geno_filter")
+		var mr, mc C.size_t
+		C.sfg_mgpu_geno_dims(m, &mr, &mc)
+		return &Geno{nil, m, 0, int(mr), int(mc)}
+	}
 	var f *C.sfg_geno
 	h.check(C.sfg_geno_filter(h.p, g.g, pr, pc, &f), "geno_filter")
 	var nr, nc C.size_t
 	C.sfg_geno_dims(f, &nr, &nc)
 	return &Geno{f, nil, 0, int(nr), int(nc)}
+}
+
+// FreeGeno returns the device memory of a matrix FilterGeno made (or of any matrix the caller holds unregistered).  g must not be used afterwards.
+func (h *Ctx) FreeGeno(g *Geno) {
+	if g.mg != nil {
+		C.sfg_mgpu_geno_free(Default.mg, g.mg)
+	} else if g.g != nil {
+		C.sfg_geno_free(h.p, g.g)
+	}
+	g.g, g.mg = nil, nil
+}
+
+// SketchGeno is the plaintext pass of the randomized PCA over the local genotypes (gwas/pca.go:152-162): sketch[k*NCol+j] = sum over the rows i of bucket k of
+// sgn[i] * x[i][j] (exact integers in float64), xsum / x2sum the column sums of x and x*x with Go's integer semantics.  On the multi-GPU engine every rank
+// sketches its own SNP window (sfg_mgpu_sketch).  A 2-bit packed matrix is refused.
+func (h *Ctx) SketchGeno(g *Geno, bucket []int32, sgn []int8, kp int) (sketch []float64, xsum, x2sum []uint64) {
+	if g.Flags&FlagTranspose != 0 || len(bucket) != g.NRow || len(sgn) != g.NRow {
+		panic("SketchGeno: needs the stored matrix (individuals x SNPs) and one bucket and sign per individual")
+	}
+	sketch, xsum, x2sum = make([]float64, kp*g.NCol), make([]uint64, g.NCol), make([]uint64, g.NCol)
+	pb, ps := (*C.int32_t)(unsafe.Pointer(&bucket[0])), (*C.int8_t)(unsafe.Pointer(&sgn[0]))
+	pk, px, px2 := (*C.double)(unsafe.Pointer(&sketch[0])), (*C.uint64_t)(unsafe.Pointer(&xsum[0])), (*C.uint64_t)(unsafe.Pointer(&x2sum[0]))
+	if g.mg != nil {
+		Default.mcheck(C.sfg_mgpu_sketch(Default.mg, g.mg, pb, ps, C.int(kp), pk, px, px2), "mgpu_sketch")
+	} else {
+		h.check(C.sfg_sketch(h.p, g.g, pb, ps, C.int(kp), pk, px, px2), "sketch")
+	}
+	return
+}
+
+// ColSumsGeno returns the per-SNP sum and sum of squares after missing -> 0 (gwas/matmult.go:1292-1300); on the multi-GPU engine every rank sums its own
+// SNP window (sfg_mgpu_geno_colsums).
+func (h *Ctx) ColSumsGeno(g *Geno) (sum, sqsum []float64) {
+	if g.Flags&FlagTranspose != 0 {
+		panic("ColSumsGeno: pass the stored matrix (individuals x SNPs), not its transposed view")
+	}
+	sum, sqsum = make([]float64, g.NCol), make([]float64, g.NCol)
+	ps, pq := (*C.double)(unsafe.Pointer(&sum[0])), (*C.double)(unsafe.Pointer(&sqsum[0]))
+	if g.mg != nil {
+		Default.mcheck(C.sfg_mgpu_geno_colsums(Default.mg, g.mg, ps, pq), "mgpu_geno_colsums")
+	} else {
+		h.check(C.sfg_geno_colsums(h.p, g.g, ps, pq), "geno_colsums")
+	}
+	return
 }
 
 // ----------------------------------------------------------------------------------------------------------------

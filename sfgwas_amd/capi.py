@@ -144,6 +144,7 @@ def _sig(L):
         "sfg_geno_plaintext_cache_stats": (i, [vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
         "sfg_geno_from_bed": (i, [vp, vp, sz, sz, sz, vp, vp, C.POINTER(vp)]),
         "sfg_geno_dims": (i, [vp, C.POINTER(sz), C.POINTER(sz)]),
+        "sfg_geno_layout": (i, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(i)]),
         "sfg_pgen_dims": (i, [vp, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
         "sfg_geno_from_pgen": (i, [vp, vp, sz, sz, sz, vp, vp, C.POINTER(vp)]),
         "sfg_pgen_geno_counts": (i, [vp, vp, sz, vp, vp]),
@@ -154,6 +155,9 @@ def _sig(L):
         "sfg_geno_qc_scan": (i, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "sfg_geno_filter": (i, [vp, vp, vp, vp, C.POINTER(vp)]),
         "sfg_mgpu_geno_qc_scan": (i, [vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sfg_mgpu_geno_filter": (i, [vp, vp, vp, vp, C.POINTER(vp)]),
+        "sfg_mgpu_sketch": (i, [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int8), i, C.POINTER(d), u64p, u64p]),
+        "sfg_mgpu_geno_colsums": (i, [vp, vp, C.POINTER(d), C.POINTER(d)]),
         "sfg_matmul_resident_dev": (i, [vp, vp, i, i, i, vp, C.c_uint, vp]),
         "sfg_matmul_from_cache": (i, [vp, vp, i, i, i, C.c_char_p, i, vp]),
         "sfg_diagcache_header": (i, [vp, C.c_char_p, i, u64p]),
@@ -960,6 +964,50 @@ def _ctx_geno_filter(self, g, row_filter=None, col_filter=None):
     return out
 
 
+def _sketch(check, fn, h, g, nrow, ncol, bucket, sgn, kp, sketch, sums):
+    """sfg_sketch / sfg_mgpu_sketch: (sketch [kp][ncol] fp64, xsum [ncol], x2sum [ncol] uint64); sketch / sums = False leaves that output out (None in its place)"""
+    bucket, sgn = np.ascontiguousarray(bucket, dtype=np.int32), np.ascontiguousarray(sgn, dtype=np.int8)
+    if bucket.shape != (nrow,) or sgn.shape != (nrow,):
+        raise ValueError(f"sketch: expected {nrow} buckets and signs")
+    sk = np.empty((kp, ncol), dtype=np.float64) if sketch else None
+    xs = np.empty(ncol, dtype=np.uint64) if sums else None
+    x2 = np.empty(ncol, dtype=np.uint64) if sums else None
+    check(fn(h, g, bucket.ctypes.data_as(C.POINTER(C.c_int32)), sgn.ctypes.data_as(C.POINTER(C.c_int8)), kp,
+             None if sk is None else sk.ctypes.data_as(C.POINTER(C.c_double)), None if xs is None else p64(xs), None if x2 is None else p64(x2)), "sketch")
+    return sk, xs, x2
+
+
+def _colsums(check, fn, h, g, ncol, sums, sqsums):
+    """sfg_geno_colsums / sfg_mgpu_geno_colsums: (sum [ncol], sqsum [ncol]) as fp64 after missing -> 0"""
+    a = np.empty(ncol, dtype=np.float64) if sums else None
+    b = np.empty(ncol, dtype=np.float64) if sqsums else None
+    ptr = lambda x: None if x is None else x.ctypes.data_as(C.POINTER(C.c_double))   # noqa: E731
+    check(fn(h, g, ptr(a), ptr(b)), "geno_colsums")
+    return a, b
+
+
+def _ctx_sketch(self, g, bucket, sgn, kp, sketch=True, sums=True):
+    nr, nc = C.c_size_t(), C.c_size_t()
+    lib().sfg_geno_dims(g, C.byref(nr), C.byref(nc))
+    return _sketch(self.check, lib().sfg_sketch, self.h, g, nr.value, nc.value, bucket, sgn, kp, sketch, sums)
+
+
+def _ctx_geno_colsums(self, g, sums=True, sqsums=True):
+    nr, nc = C.c_size_t(), C.c_size_t()
+    lib().sfg_geno_dims(g, C.byref(nr), C.byref(nc))
+    return _colsums(self.check, lib().sfg_geno_colsums, self.h, g, nc.value, sums, sqsums)
+
+
+def geno_layout(g):
+    """(device address, row stride in bytes, packed) of a resident handle (sfg_geno_layout)"""
+    dev, ld, pk = C.c_void_p(), C.c_size_t(), C.c_int()
+    if lib().sfg_geno_layout(g, C.byref(dev), C.byref(ld), C.byref(pk)):
+        raise SfgError("geno_layout: null matrix")
+    return dev.value, ld.value, bool(pk.value)
+
+
+Context.sketch = _ctx_sketch
+Context.geno_colsums = _ctx_geno_colsums
 Context.geno_qc_scan = _ctx_geno_qc_scan
 Context.geno_filter = _ctx_geno_filter
 Context.geno_upload = _ctx_geno_upload
@@ -1079,6 +1127,34 @@ class MultiGpu:
         nr, nc = C.c_size_t(), C.c_size_t()
         lib().sfg_mgpu_geno_dims(g, C.byref(nr), C.byref(nc))
         return _qc_scan(self.check, lib().sfg_mgpu_geno_qc_scan, self.h, g, nr.value, nc.value, row_filter, col_filter, row_ctrl, cols, rows)
+
+    def geno_dims(self, g):
+        nr, nc = C.c_size_t(), C.c_size_t()
+        lib().sfg_mgpu_geno_dims(g, C.byref(nr), C.byref(nc))
+        return nr.value, nc.value
+
+    def geno_shard(self, g, local):
+        """the borrowed handle of local rank `local`'s window on self.ctx[local] (None: the rank owns no block)"""
+        h = lib().sfg_mgpu_geno_shard(g, local)
+        return C.c_void_p(h) if h else None
+
+    def geno_filter(self, g, row_filter=None, col_filter=None):
+        """the kept rows / columns of a sharded matrix as a new sharded matrix over the kept columns (sfg_mgpu_geno_filter: re-sharding, single process only)"""
+        nr, nc = (0, 0) if g is None else self.geno_dims(g)
+        rf, prf = _filter_arg(row_filter, nr, "row_filter")
+        cf, pcf = _filter_arg(col_filter, nc, "col_filter")
+        out = C.c_void_p()
+        self.check(lib().sfg_mgpu_geno_filter(self.h, g, prf, pcf, C.byref(out)), "sfg_mgpu_geno_filter")
+        return out
+
+    def sketch(self, g, bucket, sgn, kp, sketch=True, sums=True):
+        """Context.sketch on the sharded matrix (sfg_mgpu_sketch): outputs in the global column layout"""
+        nr, nc = self.geno_dims(g)
+        return _sketch(self.check, lib().sfg_mgpu_sketch, self.h, g, nr, nc, bucket, sgn, kp, sketch, sums)
+
+    def geno_colsums(self, g, sums=True, sqsums=True):
+        """Context.geno_colsums on the sharded matrix (sfg_mgpu_geno_colsums): outputs in the global column layout"""
+        return _colsums(self.check, lib().sfg_mgpu_geno_colsums, self.h, g, self.geno_dims(g)[1], sums, sqsums)
 
     def geno_blocks(self, g, local):
         b0, b1 = C.c_size_t(), C.c_size_t()

@@ -183,6 +183,13 @@ extern "C" int sfg_geno_dims(const sfg_geno *g, size_t *nrow, size_t *ncol) {
     if (ncol) *ncol = g->ncol;
     return 0;
 }
+extern "C" int sfg_geno_layout(const sfg_geno *g, const void **dev, size_t *ld, int *packed) {
+    if (!g) return 1;
+    if (dev) *dev = g->dev;
+    if (ld) *ld = g->ld;
+    if (packed) *packed = g->packed ? 1 : 0;
+    return 0;
+}
 extern "C" int sfg_geno_download(sfg_ctx *ctx, const sfg_geno *g, int8_t *host) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
     if (g->packed) { sfg_geno *u = nullptr; SFG_TRY(sfg_geno_unpack(ctx, g, &u)); int rc = sfg_geno_download(ctx, u, host); sfg_geno_free(ctx, u); return rc; }

@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "rendezvous.hpp"      // the host-side meeting point of the rank threads (agreement point, direct transport)
+#include "reshard.hpp"         // a rank's share of the re-sharding filter
 #include <rccl/rccl.h>          // types and prototypes only; the functions are resolved at run time (Rccl below)
 #include <dlfcn.h>
 #include <mutex>
@@ -90,6 +91,7 @@ struct sfg_mgpu {
     std::vector<MgRank> r;                  // local ranks
     bool broken = false;                    // a rank failed after a call's agreement point and its communicator was aborted: the engine refuses further exchanges
     bool test_hooks = false;                // SFG_ENABLE_TEST_HOOKS=1 when the engine was made: sfg_mgpu_inject_failure_for_test may be called
+    bool peer_access = false;               // every local device reads every other's memory: enabled with the direct transport, else by the first sfg_mgpu_geno_filter
     Rendezvous rv;
     std::string err;
 };
@@ -194,6 +196,21 @@ extern "C" int sfg_mgpu_unique_id(uint8_t *id128) {
     memcpy(id128, &id, 128); return 0;
 }
 
+// every local device may read every other's memory (ranks that share a device need nothing); "" or what failed.  Allocates nothing.
+static std::string mgpu_enable_peer_access(sfg_mgpu *mg, const char *who) {
+    if (mg->peer_access) return "";
+    for (const MgRank &A : mg->r) for (const MgRank &B : mg->r) if (A.device != B.device) {
+        int can = 0; (void)hipDeviceCanAccessPeer(&can, A.device, B.device);
+        if (!can) return std::string(who) + ": devices " + std::to_string(A.device) + " and " + std::to_string(B.device) + " cannot access each other's memory";
+        (void)hipSetDevice(A.device);
+        const hipError_t e = hipDeviceEnablePeerAccess(B.device, 0);
+        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e);
+        (void)hipGetLastError();
+    }
+    mg->peer_access = true;
+    return "";
+}
+
 static int mgpu_create_common(sfg_mgpu **out, const int *devices, int n, int rank0, int world, const uint8_t *id128, int logN, int nq, int np, const uint64_t *moduli,
                               const uint64_t *psi, double scale, const sfg_config *config) {
     *out = nullptr;
@@ -230,14 +247,7 @@ static int mgpu_create_common(sfg_mgpu **out, const int *devices, int n, int ran
             if (rc != ncclSuccess) return fail(std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(rc));
         }
     }
-    if (mg->direct) for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) if (devices[i] != devices[j]) {
-        int can = 0; (void)hipDeviceCanAccessPeer(&can, devices[i], devices[j]);
-        if (!can) return fail("sfg_mgpu_create: direct transport: devices " + std::to_string(devices[i]) + " and " + std::to_string(devices[j]) + " cannot access each other's memory");
-        (void)hipSetDevice(devices[i]);
-        const hipError_t e = hipDeviceEnablePeerAccess(devices[j], 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return fail(std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
-        (void)hipGetLastError();
-    }
+    if (mg->direct) { const std::string e = mgpu_enable_peer_access(mg, "sfg_mgpu_create: direct transport"); if (!e.empty()) return fail(e); }
     *out = mg;
     return 0;
 }
@@ -481,6 +491,112 @@ extern "C" int sfg_mgpu_geno_qc_scan(sfg_mgpu *mg, const sfg_mgeno *g, const uin
         if (row_het_host) for (size_t r = 0; r < nrow; r++) row_het_host[r] += rh[i][r];
     }
     return 0;
+}
+
+// The re-sharding filter (reshard.hip has the kernels): the result's windows are sfg_mgpu_shard's over the KEPT columns, and local rank i gathers its window out of
+// the old windows of the ranks that hold its columns - a contiguous run of them, because kept columns stay in order.  All tables are host arithmetic made before
+// anything is allocated; the old shards are only read, so the ranks never meet: one pass drains every queue first (a shard filled by stream-ordered work, as
+// sfg_mgpu_geno_synthetic's, is complete before a peer reads it), the second gathers and ends with every queue drained again.
+extern "C" int sfg_mgpu_geno_filter(sfg_mgpu *mg, const sfg_mgeno *g, const uint8_t *row_filter, const uint8_t *col_filter, sfg_mgeno **out) {
+    MG_NEED(mg, mg != nullptr, "null engine");
+    if (out) *out = nullptr;
+    if (!g || !out) MG_FAIL(mg, "sfg_mgpu_geno_filter: null matrix / result pointer");
+    MG_NEED(mg, g->shard.size() == mg->r.size(), "the matrix belongs to another engine");
+    if (g->nrow >= (1ULL << 32) || g->ncol >= (1ULL << 32)) MG_FAIL(mg, "sfg_mgpu_geno_filter: dimension too large");
+    const size_t n = mg->r.size();
+    if (n < (size_t)mg->world) MG_FAIL(mg, "sfg_mgpu_geno_filter: a world of one rank per process cannot re-shard (a rank's new window draws on its peers' windows, and their "
+                                            "memory is not addressable from this process): filter before sharding");
+    std::vector<unsigned> rows, cols;                            // kept rows; kept global columns
+    for (size_t i = 0; i < g->nrow; i++) if (!row_filter || row_filter[i]) rows.push_back((unsigned)i);
+    for (size_t j = 0; j < g->ncol; j++) if (!col_filter || col_filter[j]) cols.push_back((unsigned)j);
+    const size_t nr = rows.size(), nc = cols.size();
+    if (!nr || !nc) MG_FAIL(mg, "sfg_mgpu_geno_filter: filters keep nothing (%zu rows, %zu columns)", nr, nc);
+    bool packed = false, first = true;
+    for (const sfg_geno *sh : g->shard) if (sh) {
+        if (first) { packed = sh->packed; first = false; }
+        if (sh->packed != packed) MG_FAIL(mg, "sfg_mgpu_geno_filter: int8 and packed shards in one matrix");
+    }
+    // per local rank: its new window [c0, c1) of the kept columns and the old shards that serve it
+    std::vector<size_t> c0(n, 0), c1(n, 0), b0(n, 0), b1(n, 0);
+    std::vector<ReshardSegs> segs(n);
+    for (size_t i = 0; i < n; i++) {
+        (void)sfg_mgpu_shard(mg->world, nc, mg->r[i].rank, &b0[i], &b1[i], &c0[i], &c1[i]);
+        ReshardSegs &t = segs[i]; t.n = 0;
+        size_t served = 0;
+        for (size_t j = 0; j < n && c1[i] > c0[i]; j++) {
+            const sfg_geno *sh = g->shard[j];
+            if (!sh) continue;
+            const size_t o0 = g->blk0[j] * SFG_SLOTS, o1 = o0 + sh->ncol;                  // the old window of local rank j
+            const auto wb = cols.begin() + (ptrdiff_t)c0[i], we = cols.begin() + (ptrdiff_t)c1[i];
+            const size_t lo = (size_t)(std::lower_bound(wb, we, o0) - wb), hi = (size_t)(std::lower_bound(wb, we, o1) - wb);
+            if (hi == lo) continue;
+            if (lo != served) break;                                                       // (the old windows leave a hole: caught below)
+            t.s[t.n].base = (const uint8_t *)sh->dev; t.s[t.n].ld = sh->ld; t.s[t.n].gcol0 = (unsigned)o0; t.s[t.n].out0 = (unsigned)lo; t.n++;
+            served = hi;
+        }
+        if (served != c1[i] - c0[i]) MG_FAIL(mg, "sfg_mgpu_geno_filter: the shards of this matrix do not cover the columns of rank %d's new window", mg->r[i].rank);
+    }
+    { const std::string e = mgpu_enable_peer_access(mg, "sfg_mgpu_geno_filter"); if (!e.empty()) MG_FAIL(mg, "%s", e.c_str()); }
+    sfg_mgeno *f = mgeno_new(mg, nr, nc);                        // (nothing below returns without handing it on or freeing it)
+    f->blk0 = b0; f->blk1 = b1;
+    int rc = run_ranks(mg, [&](MgRank &R, int) { R_HIP(R, hipSetDevice(R.device)); R_CTX(R, sfg_ctx_synchronize(R.ctx)); return 0; });
+    if (!rc) rc = run_ranks(mg, [&](MgRank &R, int i) {
+        const size_t k = (size_t)i;
+        if (c1[k] > c0[k]) R_CTX(R, sfg_reshard_window(R.ctx, segs[k], cols.data() + c0[k], c1[k] - c0[k], rows.data(), nr, packed, &f->shard[k]));
+        return 0;
+    });
+    if (rc) { sfg_mgpu_geno_free(mg, f); return 1; }
+    *out = f; return 0;
+}
+// The count sketch and the column moments of the PCA input (gwas/pca.go:152-162, gwas/matmult.go:1292-1300) on the sharded matrix: SNP-sharded and independent
+//  - every local rank runs the single-GPU call on its window and the host lays the results out at the window's columns.  No collective.
+extern "C" int sfg_mgpu_sketch(sfg_mgpu *mg, const sfg_mgeno *g, const int32_t *bucket_host, const int8_t *sgn_host, int kp,
+                               double *sketch_host, uint64_t *xsum_host, uint64_t *x2sum_host) {
+    MG_NEED(mg, mg != nullptr, "null engine");
+    MG_NEED(mg, g && g->shard.size() == mg->r.size(), "the matrix belongs to another engine");
+    MG_NEED(mg, bucket_host && sgn_host, "null bucket / sign table");
+    for (const sfg_geno *sh : g->shard) if (sh && sh->packed) MG_FAIL(mg, "sfg_sketch: 2-bit packed matrix (sketch before sfg_geno_pack, or sfg_geno_unpack first)");
+    if (kp < 1 || kp > 16) MG_FAIL(mg, "sfg_sketch: kp must be in 1..16 (one MFMA tile of buckets)");
+    const size_t n = mg->r.size(), ncol = g->ncol;
+    std::vector<std::vector<double>> sk(n);
+    std::vector<std::vector<uint64_t>> xs(n), x2(n);
+    const int rc = run_ranks(mg, [&](MgRank &R, int i) {
+        const sfg_geno *sh = g->shard[(size_t)i];
+        if (!sh) return 0;
+        if (sketch_host) sk[(size_t)i].resize((size_t)kp * sh->ncol);
+        if (xsum_host) xs[(size_t)i].resize(sh->ncol);
+        if (x2sum_host) x2[(size_t)i].resize(sh->ncol);
+        R_CTX(R, sfg_sketch(R.ctx, sh, bucket_host, sgn_host, kp, sketch_host ? sk[(size_t)i].data() : nullptr, xsum_host ? xs[(size_t)i].data() : nullptr,
+                            x2sum_host ? x2[(size_t)i].data() : nullptr));
+        return 0;
+    });
+    if (rc) return rc;
+    if (sketch_host) std::fill(sketch_host, sketch_host + (size_t)kp * ncol, 0.0);
+    if (xsum_host) std::fill(xsum_host, xsum_host + ncol, (uint64_t)0);
+    if (x2sum_host) std::fill(x2sum_host, x2sum_host + ncol, (uint64_t)0);
+    for (size_t i = 0; i < n; i++) {
+        const sfg_geno *sh = g->shard[i];
+        if (!sh) continue;
+        const size_t c0 = g->blk0[i] * SFG_SLOTS, w = sh->ncol;
+        if (sketch_host) for (int k = 0; k < kp; k++) std::copy(sk[i].begin() + (ptrdiff_t)((size_t)k * w), sk[i].begin() + (ptrdiff_t)((size_t)(k + 1) * w), sketch_host + (size_t)k * ncol + c0);
+        if (xsum_host) std::copy(xs[i].begin(), xs[i].end(), xsum_host + c0);
+        if (x2sum_host) std::copy(x2[i].begin(), x2[i].end(), x2sum_host + c0);
+    }
+    return 0;
+}
+extern "C" int sfg_mgpu_geno_colsums(sfg_mgpu *mg, const sfg_mgeno *g, double *sum_host, double *sqsum_host) {
+    MG_NEED(mg, mg != nullptr, "null engine");
+    MG_NEED(mg, g && g->shard.size() == mg->r.size(), "the matrix belongs to another engine");
+    // a rank's window is a slice of the global layout: it writes there itself (the windows are disjoint)
+    if (sum_host) std::fill(sum_host, sum_host + g->ncol, 0.0);
+    if (sqsum_host) std::fill(sqsum_host, sqsum_host + g->ncol, 0.0);
+    return run_ranks(mg, [&](MgRank &R, int i) {
+        const sfg_geno *sh = g->shard[(size_t)i];
+        if (!sh) return 0;
+        const size_t c0 = g->blk0[(size_t)i] * SFG_SLOTS;
+        R_CTX(R, sfg_geno_colsums(R.ctx, sh, sum_host ? sum_host + c0 : nullptr, sqsum_host ? sqsum_host + c0 : nullptr));
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------- collectives (enqueued on `st` of the calling rank, in order with it)

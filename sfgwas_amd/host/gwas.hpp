@@ -1310,6 +1310,41 @@ inline sfg_geno *FilterResident(crypto::CryptoParams *cps, const sfg_geno *g, co
     cps->check(sfg_geno_filter(cps->ctx, g, prf, pcf, &out), "FilterResident");
     return out;
 }
+// ---- the same step on a party's node (NewCryptoParamsMulti): g is a sharded matrix (ResidentGeno::mg) of the engine cps->mg
+inline sfg_mgpu *engineOf(crypto::CryptoParams *cps, const char *what) {
+    sfg_mgpu *eng = cps->mg ? cps->mg : cps->mg_root;
+    if (!eng) throw std::runtime_error(std::string(what) + ": these CryptoParams drive one device (NewCryptoParamsMulti makes the node's engine)");
+    return eng;
+}
+inline void mgFail(sfg_mgpu *eng, const char *what) { throw std::runtime_error(std::string(what) + ": " + sfg_mgpu_last_error(eng)); }
+// FilterMatrixFile (utilities.go:154) / the filters GeneratePCAInput reads through (gwas.go:545) for a sharded resident matrix: a new sharded matrix over the kept
+// columns, re-sharded by 8192-column blocks (sfg_mgpu_geno_filter); the caller owns it (sfg_mgpu_geno_free) and may free g at once
+inline sfg_mgeno *FilterResidentSharded(crypto::CryptoParams *cps, const sfg_mgeno *g, const std::vector<bool> &rowFilt, const std::vector<bool> &colFilt) {
+    sfg_mgpu *eng = engineOf(cps, "FilterResidentSharded");
+    size_t nrow, ncol; if (sfg_mgpu_geno_dims(g, &nrow, &ncol)) throw std::runtime_error("FilterResidentSharded: null matrix");
+    std::vector<uint8_t> rf, cf;
+    const uint8_t *prf = filterArg(rowFilt, nrow, rf, "FilterResidentSharded"), *pcf = filterArg(colFilt, ncol, cf, "FilterResidentSharded");
+    sfg_mgeno *out = nullptr;
+    if (sfg_mgpu_geno_filter(eng, g, prf, pcf, &out)) mgFail(eng, "FilterResidentSharded");
+    return out;
+}
+// the count sketch of the PCA input and its column sums (pca.go:152-162): sketch [kp][ncol] row-major (exact integers), xsum / x2sum [ncol]
+struct SketchResult { std::vector<double> sketch; std::vector<uint64_t> xsum, x2sum; };
+inline SketchResult SketchSharded(crypto::CryptoParams *cps, const sfg_mgeno *g, const std::vector<int32_t> &bucket, const std::vector<int8_t> &sgn, int kp) {
+    sfg_mgpu *eng = engineOf(cps, "SketchSharded");
+    size_t nrow, ncol; if (sfg_mgpu_geno_dims(g, &nrow, &ncol)) throw std::runtime_error("SketchSharded: null matrix");
+    if (bucket.size() != nrow || sgn.size() != nrow || kp < 1) throw std::runtime_error("SketchSharded: one bucket and one sign per row expected");
+    SketchResult r; r.sketch.resize((size_t)kp * ncol); r.xsum.resize(ncol); r.x2sum.resize(ncol);
+    if (sfg_mgpu_sketch(eng, g, bucket.data(), sgn.data(), kp, r.sketch.data(), r.xsum.data(), r.x2sum.data())) mgFail(eng, "SketchSharded");
+    return r;
+}
+// the per-SNP sum and sum of squares after missing -> 0 (matmult.go:1292-1300)
+inline void ColSumsSharded(crypto::CryptoParams *cps, const sfg_mgeno *g, std::vector<double> &sum, std::vector<double> &sqsum) {
+    sfg_mgpu *eng = engineOf(cps, "ColSumsSharded");
+    size_t nrow, ncol; if (sfg_mgpu_geno_dims(g, &nrow, &ncol)) throw std::runtime_error("ColSumsSharded: null matrix");
+    sum.resize(ncol); sqsum.resize(ncol);
+    if (sfg_mgpu_geno_colsums(eng, g, sum.data(), sqsum.data())) mgFail(eng, "ColSumsSharded");
+}
 }  // namespace qc
 }  // namespace gwas
 
