@@ -637,6 +637,53 @@ int sfg_pcks_finish_decode(sfg_ctx *ctx, const uint64_t *ct_dev, int nct, int le
  * key: c0 + sk (.) c1, then sfg_decode_vectors.  Fails without a loaded secret key. */
 int sfg_decrypt_vectors(sfg_ctx *ctx, const uint64_t *ct_dev, int nct, int level, double scale, double *re_host, double *im_host);
 
+/* ---- collective key generation on the device: the local halves of mpc.CollectiveInit (mpc/mhe.go:24-81; keygen.hip) ----
+ * PARITY UNPINNED: restated from the published lattigo v2.1 dckks / drlwe (CKGProtocol.GenShare, RTGProtocol.GenShare, RKGProtocol.GenShareRoundOne / RoundTwo);
+ * with fresh randomness bit parity with the Go binary cannot exist.  What IS pinned (tests/test_gpu_keygen.py): every share word against the Python-integer statement
+ * tests/keygen_ref.py, the sampled forms against the explicit cores, and keys made here carrying a ciphertext through a rotation and a relinearisation within the
+ * noise bound DESIGN.md derives.  The aggregation over the network stays in Go (mpc/aggregate.go:121-240); drawing the secret key stays with the caller.
+ * All polynomials are rows [nmod = nq + np][N], NTT domain, canonical words, in device memory.  beta = ceil(nq / np) digits; g_i at modulus m is P mod q_m when
+ * m < nq && m / np == i, else 0 (the convention the library's key switch consumes); a rotation key for Galois element g switches from phi_{g^-1}(s). */
+/* cryptoParams.Sk.Value over Q and P: sk_host [nq+np][N], NTT domain; montgomery_form != 0 for lattigo's stored form.  Also provides the Q rows that
+ * sfg_ctx_load_secret_key provides, stored identically.  Wiped from device memory with the root context.  Every key-generation call below fails, launching
+ * nothing, without it. */
+int sfg_ctx_load_secret_key_qp(sfg_ctx *ctx, const uint64_t *sk_host, int montgomery_form);
+/* CKGProtocol.GenShare (CollectivePubKeyGen, mhe.go:83-105): share [nmod][N] = -crp (.) sk + NTT(e); crp [nmod][N], e int32 [N] */
+int sfg_ckg_gen_share_dev(sfg_ctx *ctx, const uint64_t *crp_dev, const int32_t *e_dev, uint64_t *share_dev);
+/* RTGProtocol.GenShare for nkeys Galois elements at once (CollectiveRotKeyGen, mhe.go:381-476): shares [nkeys][beta][nmod][N],
+ *   h_{k,i} = -crp_{k,i} (.) phi_{g_k^-1}(sk) + NTT(e_{k,i}) + g_i sk;   crp [nkeys][beta][nmod][N], e int32 [nkeys][beta][N].
+ * nkeys is the caller's batching knob: the only scratch is 32 KiB of automorphism index per key.  An even Galois element or nkeys < 0 is an error that launches
+ * nothing; nkeys == 0 returns 0. */
+int sfg_rtg_gen_shares_dev(sfg_ctx *ctx, const uint64_t *galois_host, int nkeys, const uint64_t *crp_dev, const int32_t *e_dev, uint64_t *shares_dev);
+/* RKGProtocol.GenShareRoundOne (CollectiveRelinKeyGen, mhe.go:478-502): u int8 [N] the party's ephemeral ternary secret, e0, e1 int32 [beta][N], crp, h0, h1 [beta][nmod][N]:
+ *   h0_i = -NTT(u) (.) crp_i + g_i sk + NTT(e0_i),     h1_i = sk (.) crp_i + NTT(e1_i) */
+int sfg_rkg_round1_dev(sfg_ctx *ctx, const uint64_t *crp_dev, const int8_t *u_dev, const int32_t *e0_dev, const int32_t *e1_dev, uint64_t *h0_dev, uint64_t *h1_dev);
+/* RKGProtocol.GenShareRoundTwo on the aggregated round-one shares:  out_i = sk (.) H0agg_i + NTT(e2_i) + (NTT(u) - sk) (.) H1agg_i + NTT(e3_i) */
+int sfg_rkg_round2_dev(sfg_ctx *ctx, const uint64_t *h0agg_dev, const uint64_t *h1agg_dev, const int8_t *u_dev, const int32_t *e2_dev, const int32_t *e3_dev, uint64_t *out_dev);
+/* The sampled forms: the same shares with the errors (and the ephemeral u) drawn in the same kernel from the encryptor's keyed stream (sfg_ctx_seed_encryptor; the
+ * byte-to-sample map of sfg_encrypt_* unchanged), no host randomness.  Each polynomial pair takes one encryption index from the counter the root and its forks share:
+ *   public key share: 1 index, e = its polynomial id 1;   rotation shares: nkeys * beta indices, (k, i) takes first + k beta + i, e = id 1;
+ *   round 1: beta + 1 indices, digit i takes first + i (e0, e1 = ids 1, 2), u = id 0 of index first + beta, returned in *u_index;
+ *   round 2: beta indices, digit i takes first + i (e2, e3 = ids 1, 2); u is redrawn from u_index, never stored.
+ * *first_index (may be NULL) states the first index taken: sfg_encrypt_transcript_for_test reproduces every sample from it.  Each call is bit-identical to its
+ * explicit core on those samples.  Unseeded, they fail and launch nothing. */
+int sfg_ckg_gen_share_sampled_dev(sfg_ctx *ctx, const uint64_t *crp_dev, uint64_t *share_dev, uint64_t *first_index);
+int sfg_rtg_gen_shares_sampled_dev(sfg_ctx *ctx, const uint64_t *galois_host, int nkeys, const uint64_t *crp_dev, uint64_t *shares_dev, uint64_t *first_index);
+int sfg_rkg_round1_sampled_dev(sfg_ctx *ctx, const uint64_t *crp_dev, uint64_t *h0_dev, uint64_t *h1_dev, uint64_t *first_index, uint64_t *u_index);
+int sfg_rkg_round2_sampled_dev(sfg_ctx *ctx, const uint64_t *h0agg_dev, const uint64_t *h1agg_dev, uint64_t u_index, uint64_t *out_dev, uint64_t *first_index);
+/* Installation of the aggregated keys straight from device memory (no host copy; the words are kept as sfg_ctx_load_* keeps non-Montgomery input):
+ *   public key = (agg, crp);   rotation key k = (agg_{k,i}, crp_{k,i}) under galois_host[k];   relinearisation key = (round2agg_i, H1agg_i).
+ * Setup-time calls like the loads; forks see the installed keys as they see loaded ones; sfg_ctx_export_rotkey returns exactly (agg, crp). */
+int sfg_ctx_install_public_key_dev(sfg_ctx *ctx, const uint64_t *agg_dev, const uint64_t *crp_dev);
+int sfg_ctx_install_rotkeys_dev(sfg_ctx *ctx, const uint64_t *galois_host, int nkeys, const uint64_t *agg_dev, const uint64_t *crp_dev);
+int sfg_ctx_install_relinkey_dev(sfg_ctx *ctx, const uint64_t *round2agg_dev, const uint64_t *h1agg_dev);
+/* The common reference polynomials from a 32-byte seed all parties share (replaces ring.UniformSampler over the fork's frand, mhe.go:49-59, whose bytes cannot be
+ * reproduced here: a CPU-only party must implement this map).  Row r of the call is global row first_row + r at modulus mod_idx_host[r]; coefficient j comes from
+ * the ChaCha20 block (RFC 8439) under key32 with block counter j and nonce (64-bit global row number, 32-bit try counter t = 0): its sixteen words form eight
+ * 64-bit candidates (word 2k low, 2k + 1 high), each masked to bitlen(q) bits; the coefficient is the first candidate < q, and if none is, the same with t + 1.
+ * out_dev [nrows][N].  The key is not retained by the context. */
+int sfg_crp_fill_dev(sfg_ctx *ctx, const uint8_t *key32_host, uint64_t first_row, size_t nrows, const int *mod_idx_host, uint64_t *out_dev);
+
 /* ---- B1-B3: Beaver local products (mpc/beavermult.go:94-147) over a prime field of `limbs` 64-bit LE limbs ---- */
 int sfg_beaver_elem_dev(sfg_ctx *ctx, int pid, int limbs, const uint64_t *modulus_host,
                         const uint64_t *ar_dev, const uint64_t *am_dev, const uint64_t *br_dev, const uint64_t *bm_dev,

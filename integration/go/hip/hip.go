@@ -216,6 +216,105 @@ func (h *Ctx) PCKSFinishDecode(flat []uint64, nct, level int, scale float64, h0a
 	return out
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// Collective key generation, local halves (mpc/mhe.go:24-105, 381-502; keygen.hip).  PARITY UNPINNED against lattigo's dckks / drlwe protocols.  Shares come back
+// as host words for mpc/aggregate.go (AggregatePubKeyShares / AggregateRotKeyShare / AggregateRelinKeyShare sum them modulus by modulus); the aggregated words
+// go back in as host words and are installed from device memory.  The errors and the ephemeral secret are drawn on the device from the encryptor's stream
+// (SeedEncryptor first); the common reference polynomials come from a seed every party shares (INTEGRATION.md: NOT the bytes of the reference's frand).
+
+// LoadSecretKeyQP gives the device skShard.Value over Q and P (mhe.go:31-46, NTT + Montgomery form); it also serves as LoadSecretKey.
+func (h *Ctx) LoadSecretKeyQP(sk *ckks.SecretKey) {
+	nmod := h.NQ + h.NP
+	flat := make([]uint64, nmod*h.N)
+	for m := 0; m < nmod; m++ {
+		copy(flat[m*h.N:(m+1)*h.N], sk.Value.Coeffs[m])
+	}
+	h.check(C.sfg_ctx_load_secret_key_qp(h.p, (*C.uint64_t)(unsafe.Pointer(&flat[0])), 1), "load_secret_key_qp")
+}
+
+// SeedEncryptor keys the device sampler from crypto/rand (what LoadPublicKey does once a public key exists; key generation needs it before).
+func (h *Ctx) SeedEncryptor() {
+	var key [32]byte
+	if _, err := rand.Read(key[:]); err != nil {
+		panic(err)
+	}
+	h.check(C.sfg_ctx_seed_encryptor(h.p, (*C.uint8_t)(unsafe.Pointer(&key[0]))), "seed_encryptor")
+	for i := range key {
+		key[i] = 0
+	}
+}
+
+// CommonReferencePolys: crpGen.ReadNew() for npoly consecutive polynomials over Q and P, starting at polynomial firstPoly of the stream under seed32.
+func (h *Ctx) CommonReferencePolys(seed32 []byte, firstPoly uint64, npoly int) *DevBuf {
+	nmod := h.NQ + h.NP
+	mod := make([]int32, npoly*nmod)
+	for r := range mod {
+		mod[r] = int32(r % nmod)
+	}
+	d := h.Alloc(npoly * nmod * h.N * 8)
+	h.check(C.sfg_crp_fill_dev(h.p, (*C.uint8_t)(unsafe.Pointer(&seed32[0])), C.uint64_t(firstPoly*uint64(nmod)), C.size_t(len(mod)), (*C.int)(unsafe.Pointer(&mod[0])), d.U64()), "crp_fill")
+	return d
+}
+
+// CollectivePubKeyGenShare: ckgProtocol.GenShare(sk, crp, pkShare) (mhe.go:91).
+func (h *Ctx) CollectivePubKeyGenShare(crp *DevBuf) []uint64 {
+	d := h.Alloc((h.NQ + h.NP) * h.N * 8)
+	defer d.Free()
+	h.check(C.sfg_ckg_gen_share_sampled_dev(h.p, crp.U64(), d.U64(), nil), "ckg_gen_share")
+	return d.Download()
+}
+
+// CollectivePubKeyGenFinish: ckgProtocol.GenPublicKey(pkAgg, crp, pk) (mhe.go:103); the key stays on the device.
+func (h *Ctx) CollectivePubKeyGenFinish(agg []uint64, crp *DevBuf) {
+	d := h.Upload(agg)
+	defer d.Free()
+	h.check(C.sfg_ctx_install_public_key_dev(h.p, d.U64(), crp.U64()), "install_public_key")
+}
+
+// CollectiveRotKeyGenShares: rtgProtocol.GenShare for a batch of Galois elements (mhe.go:457-465); crp and the result are [len(gElems)][beta][nq+np][N].
+func (h *Ctx) CollectiveRotKeyGenShares(gElems []uint64, crp *DevBuf) []uint64 {
+	d := h.Alloc(crp.Bytes)
+	defer d.Free()
+	h.check(C.sfg_rtg_gen_shares_sampled_dev(h.p, (*C.uint64_t)(unsafe.Pointer(&gElems[0])), C.int(len(gElems)), crp.U64(), d.U64(), nil), "rtg_gen_shares")
+	return d.Download()
+}
+
+// CollectiveRotKeyGenFinish: rtgProtocol.GenRotationKey for the batch (mhe.go:469).
+func (h *Ctx) CollectiveRotKeyGenFinish(gElems []uint64, agg []uint64, crp *DevBuf) {
+	d := h.Upload(agg)
+	defer d.Free()
+	h.check(C.sfg_ctx_install_rotkeys_dev(h.p, (*C.uint64_t)(unsafe.Pointer(&gElems[0])), C.int(len(gElems)), d.U64(), crp.U64()), "install_rotkeys")
+}
+
+// CollectiveRelinKeyGenRound1: prot.GenShareRoundOne (mhe.go:492); uIndex names the ephemeral secret for round 2 (it is never stored).
+func (h *Ctx) CollectiveRelinKeyGenRound1(crp *DevBuf) (h0, h1 []uint64, uIndex uint64) {
+	d0, d1 := h.Alloc(crp.Bytes), h.Alloc(crp.Bytes)
+	defer d0.Free()
+	defer d1.Free()
+	var ui C.uint64_t
+	h.check(C.sfg_rkg_round1_sampled_dev(h.p, crp.U64(), d0.U64(), d1.U64(), nil, &ui), "rkg_round1")
+	return d0.Download(), d1.Download(), uint64(ui)
+}
+
+// CollectiveRelinKeyGenRound2: prot.GenShareRoundTwo on the aggregated round-one shares (mhe.go:495).
+func (h *Ctx) CollectiveRelinKeyGenRound2(h0agg, h1agg []uint64, uIndex uint64) []uint64 {
+	a, b := h.Upload(h0agg), h.Upload(h1agg)
+	defer a.Free()
+	defer b.Free()
+	d := h.Alloc(a.Bytes)
+	defer d.Free()
+	h.check(C.sfg_rkg_round2_sampled_dev(h.p, a.U64(), b.U64(), C.uint64_t(uIndex), d.U64(), nil), "rkg_round2")
+	return d.Download()
+}
+
+// CollectiveRelinKeyGenFinish: prot.GenRelinearizationKey(outRound1, outRound2, evk) (mhe.go:498).
+func (h *Ctx) CollectiveRelinKeyGenFinish(round2agg, h1agg []uint64) {
+	a, b := h.Upload(round2agg), h.Upload(h1agg)
+	defer a.Free()
+	defer b.Free()
+	h.check(C.sfg_ctx_install_relinkey_dev(h.p, a.U64(), b.U64()), "install_relinkey")
+}
+
 // mcheck is check for the multi-GPU engine's calls (the failing rank is named in the message).
 func (h *Ctx) mcheck(rc C.int, what string) {
 	if rc != 0 {

@@ -85,6 +85,19 @@ def _sig(L):
         "sfg_ct_add_fresh_zero_dev": (i, [vp, vp, i, i]),
         "sfg_encrypt_vectors_dev": (i, [vp, C.POINTER(d), i, i, vp]),
         "sfg_encrypt_transcript_for_test": (i, [vp, u64, i, vp, vp, vp]),
+        "sfg_ctx_load_secret_key_qp": (i, [vp, u64p, i]),
+        "sfg_ckg_gen_share_dev": (i, [vp, vp, vp, vp]),
+        "sfg_rtg_gen_shares_dev": (i, [vp, u64p, i, vp, vp, vp]),
+        "sfg_rkg_round1_dev": (i, [vp, vp, vp, vp, vp, vp, vp]),
+        "sfg_rkg_round2_dev": (i, [vp, vp, vp, vp, vp, vp, vp]),
+        "sfg_ckg_gen_share_sampled_dev": (i, [vp, vp, vp, C.POINTER(u64)]),
+        "sfg_rtg_gen_shares_sampled_dev": (i, [vp, u64p, i, vp, vp, C.POINTER(u64)]),
+        "sfg_rkg_round1_sampled_dev": (i, [vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]),
+        "sfg_rkg_round2_sampled_dev": (i, [vp, vp, vp, u64, vp, C.POINTER(u64)]),
+        "sfg_ctx_install_public_key_dev": (i, [vp, vp, vp]),
+        "sfg_ctx_install_rotkeys_dev": (i, [vp, u64p, i, vp, vp]),
+        "sfg_ctx_install_relinkey_dev": (i, [vp, vp, vp]),
+        "sfg_crp_fill_dev": (i, [vp, C.c_char_p, u64, sz, C.POINTER(i), vp]),
         "sfg_pcks_gen_share_dev": (i, [vp, vp, i, i, vp, vp, vp, vp]),
         "sfg_pcks_finish_dev": (i, [vp, vp, i, i, vp, vp]),
         "sfg_decode_vectors": (i, [vp, vp, sz, i, i, d, vp, vp]),
@@ -1181,3 +1194,127 @@ class MultiGpu:
         out = np.zeros((s, ncols, 2, max_level, self.N), dtype=np.uint64)
         self.check(lib().sfg_mgpu_matmul(self.h, p64(A_host), s, in_level, max_level, g, flags, p64(out)), "sfg_mgpu_matmul")
         return out
+
+
+# ---- collective key generation on the device (keygen.hip).  Every polynomial argument is a DevArray (used in place) or a host array (uploaded); results are
+# DevArrays the caller frees.  nmod = nq + np rows per polynomial.
+def _kg_call(self, what, fn, ins, outs):
+    """ins: [(array, dtype, shape)] -> device pointers; outs: [shape] -> fresh DevArrays; fn(*in pointers, *out pointers) -> rc"""
+    keep, res = [], []
+    try:
+        ptrs = []
+        for a, dt, shp in ins:
+            ptr, tmp = _dev_ptr(self, a, dt, None if isinstance(a, DevArray) else shp); keep.append(tmp); ptrs.append(ptr)
+        res = [DevArray(self, s) for s in outs]
+        rc = fn(*ptrs, *[o.p for o in res])
+        if rc:
+            for o in res:
+                o.free()
+        self.check(rc, what)
+        return res
+    finally:
+        for a in keep:
+            if a is not None:
+                a.free()
+
+
+def _galois_arr(galois):
+    g = np.ascontiguousarray(galois, dtype=np.uint64)
+    return g, (p64(g) if g.size else None)
+
+
+def _ctx_load_secret_key_qp(self, sk_rows, montgomery=False):
+    sk_rows = np.ascontiguousarray(sk_rows, dtype=np.uint64)
+    assert sk_rows.shape == (self.nq + self.np_, self.N)
+    self.check(lib().sfg_ctx_load_secret_key_qp(self.h, p64(sk_rows), int(montgomery)), "load_secret_key_qp")
+
+
+def _ctx_ckg_gen_share(self, crp, e=None):
+    """crp [nmod][N]; e int32 [N] (the explicit core) or None (sampled: returns (share, first index))"""
+    nm, L = self.nq + self.np_, lib()
+    if e is not None:
+        return _kg_call(self, "ckg_gen_share", lambda c, ee, o: L.sfg_ckg_gen_share_dev(self.h, c, ee, o), [(crp, np.uint64, (nm, self.N)), (e, np.int32, (self.N,))], [(nm, self.N)])[0]
+    first = C.c_uint64()
+    out = _kg_call(self, "ckg_gen_share_sampled", lambda c, o: L.sfg_ckg_gen_share_sampled_dev(self.h, c, o, C.byref(first)), [(crp, np.uint64, (nm, self.N))], [(nm, self.N)])[0]
+    return out, first.value
+
+
+def _ctx_rtg_gen_shares(self, galois, crp, e=None):
+    """galois: nkeys Galois elements; crp [nkeys][beta][nmod][N]; e int32 [nkeys][beta][N] or None (sampled: returns (shares, first index))"""
+    nm, L = self.nq + self.np_, lib()
+    g, gp = _galois_arr(galois); nk = int(g.size)
+    shp = (max(nk, 1), self.beta, nm, self.N)
+    if e is not None:
+        return _kg_call(self, "rtg_gen_shares", lambda c, ee, o: L.sfg_rtg_gen_shares_dev(self.h, gp, nk, c, ee, o),
+                        [(crp, np.uint64, shp), (e, np.int32, (max(nk, 1), self.beta, self.N))], [shp])[0]
+    first = C.c_uint64()
+    out = _kg_call(self, "rtg_gen_shares_sampled", lambda c, o: L.sfg_rtg_gen_shares_sampled_dev(self.h, gp, nk, c, o, C.byref(first)), [(crp, np.uint64, shp)], [shp])[0]
+    return out, first.value
+
+
+def _ctx_rkg_round1(self, crp, u=None, e0=None, e1=None):
+    """crp [beta][nmod][N]; u int8 [N], e0, e1 int32 [beta][N] -> (h0, h1); all None: sampled, returns (h0, h1, first index, u index)"""
+    nm, L = self.nq + self.np_, lib()
+    shp = (self.beta, nm, self.N)
+    if u is not None:
+        return tuple(_kg_call(self, "rkg_round1", lambda c, uu, a, b, h0, h1: L.sfg_rkg_round1_dev(self.h, c, uu, a, b, h0, h1),
+                              [(crp, np.uint64, shp), (u, np.int8, (self.N,)), (e0, np.int32, (self.beta, self.N)), (e1, np.int32, (self.beta, self.N))], [shp, shp]))
+    first, ui = C.c_uint64(), C.c_uint64()
+    h0, h1 = _kg_call(self, "rkg_round1_sampled", lambda c, a, b: L.sfg_rkg_round1_sampled_dev(self.h, c, a, b, C.byref(first), C.byref(ui)), [(crp, np.uint64, shp)], [shp, shp])
+    return h0, h1, first.value, ui.value
+
+
+def _ctx_rkg_round2(self, h0agg, h1agg, u=None, e2=None, e3=None, u_index=None):
+    """H0agg, H1agg [beta][nmod][N]; explicit (u, e2, e3) -> share; or u_index (from round 1) -> (share, first index)"""
+    nm, L = self.nq + self.np_, lib()
+    shp = (self.beta, nm, self.N)
+    if u is not None:
+        return _kg_call(self, "rkg_round2", lambda a, b, uu, x, y, o: L.sfg_rkg_round2_dev(self.h, a, b, uu, x, y, o),
+                        [(h0agg, np.uint64, shp), (h1agg, np.uint64, shp), (u, np.int8, (self.N,)), (e2, np.int32, (self.beta, self.N)), (e3, np.int32, (self.beta, self.N))], [shp])[0]
+    first = C.c_uint64()
+    out = _kg_call(self, "rkg_round2_sampled", lambda a, b, o: L.sfg_rkg_round2_sampled_dev(self.h, a, b, int(u_index), o, C.byref(first)),
+                   [(h0agg, np.uint64, shp), (h1agg, np.uint64, shp)], [shp])[0]
+    return out, first.value
+
+
+def _ctx_install_public_key(self, agg, crp):
+    nm = self.nq + self.np_
+    _kg_call(self, "install_public_key", lambda a, c: lib().sfg_ctx_install_public_key_dev(self.h, a, c), [(agg, np.uint64, (nm, self.N)), (crp, np.uint64, (nm, self.N))], [])
+
+
+def _ctx_install_rotkeys(self, galois, agg, crp):
+    nm = self.nq + self.np_
+    g, gp = _galois_arr(galois); nk = int(g.size)
+    shp = (max(nk, 1), self.beta, nm, self.N)
+    _kg_call(self, "install_rotkeys", lambda a, c: lib().sfg_ctx_install_rotkeys_dev(self.h, gp, nk, a, c), [(agg, np.uint64, shp), (crp, np.uint64, shp)], [])
+
+
+def _ctx_install_relinkey(self, round2agg, h1agg):
+    shp = (self.beta, self.nq + self.np_, self.N)
+    _kg_call(self, "install_relinkey", lambda a, c: lib().sfg_ctx_install_relinkey_dev(self.h, a, c), [(round2agg, np.uint64, shp), (h1agg, np.uint64, shp)], [])
+
+
+def _ctx_crp_fill(self, key32, first_row, mod_idx, out=None):
+    """rows first_row .. first_row + len(mod_idx) - 1 of the common reference stream under the 32-byte seed -> DevArray [nrows][N] (or into `out`)"""
+    key32 = bytes(key32)
+    if len(key32) != 32:
+        raise ValueError("the common reference seed is 32 bytes")
+    n = len(mod_idx)
+    mi = (C.c_int * max(n, 1))(*[int(x) for x in mod_idx])
+    dst = out if out is not None else DevArray(self, (max(n, 1), self.N))
+    rc = lib().sfg_crp_fill_dev(self.h, key32, int(first_row), n, mi, dst.p)
+    if rc and out is None:
+        dst.free()
+    self.check(rc, "crp_fill")
+    return dst
+
+
+Context.load_secret_key_qp = _ctx_load_secret_key_qp
+Context.ckg_gen_share = _ctx_ckg_gen_share
+Context.rtg_gen_shares = _ctx_rtg_gen_shares
+Context.rkg_round1 = _ctx_rkg_round1
+Context.rkg_round2 = _ctx_rkg_round2
+Context.install_public_key = _ctx_install_public_key
+Context.install_rotkeys = _ctx_install_rotkeys
+Context.install_relinkey = _ctx_install_relinkey
+Context.crp_fill = _ctx_crp_fill

@@ -100,6 +100,7 @@ struct SfgShared {
     void *zeros_dev = nullptr;   // 256 B of zeros (DMA source for padded k-steps)
     u64 *sk_dev = nullptr;       // secret-key shard [nq][N], NTT domain, canonical (sfg_ctx_load_secret_key; collective bootstrap shares)
     u64 *pk_dev = nullptr;       // public key [2][nmod][N], NTT domain, canonical (sfg_ctx_load_public_key; encrypt.hip)
+    u64 *skqp_dev = nullptr;     // secret-key shard over Q and P [nmod][N], NTT domain, canonical (sfg_ctx_load_secret_key_qp; keygen.hip); wiped with the root
     // the encryptor's sampler (encrypt.hip): ChaCha20 key, host and device copy, wiped with the root; ONE encryption-index counter for the root and every fork
     uint32_t enc_key[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint32_t *enc_key_dev = nullptr; bool enc_seeded = false;
     u64 enc_next = 0;            // next unused encryption index (atomic: __atomic builtins only)
@@ -170,6 +171,9 @@ void sfg_ptc_invalidate_all(sfg_ctx *ctx);     // matmul.hip: forget every cache
 int encrypt_set_attrs(sfg_ctx *ctx);           // encrypt.hip: dynamic-LDS limits of its kernels
 int sfg_rows_from_montgomery(sfg_ctx *ctx, unsigned long long *rows_dev, size_t nrows, int nmod);   // ctx.hip: lattigo InvMForm of rows with modulus index row % nmod
 void sfg_encrypt_destroy(SfgShared *sh);       // encrypt.hip: wipe the sampler key (host and device), free it and the public key
+int enc_take_indices(sfg_ctx *ctx, const char *what, int nct, unsigned long long *first);   // encrypt.hip: nct consecutive encryption indices from the counter the root and its forks share
+int keygen_set_attrs(sfg_ctx *ctx);            // keygen.hip: dynamic-LDS limits of its kernels
+void sfg_keygen_destroy(SfgShared *sh);        // keygen.hip: wipe and free the QP secret key
 
 extern thread_local std::string g_create_error;
 

@@ -12,6 +12,7 @@
 //   gwas::DiagCacheStream (reader + writer, reference byte format)       gwas/filestream.go:19-282
 //   gwas::MatMult4Stream / MatMult4StreamPreprocess / MatMult4StreamCompute   gwas/matmult.go:914,1043,1238
 //   mpc::BeaverMultElemVec / BeaverMultMat                               mpc/beavermult.go:108-147
+//   mpc::CollectivePubKeyGen / RotKeyGen / RelinKeyGen Share(s) / Round / Finish, crypto::GenerateRotKeys   mpc/mhe.go:24-105, 381-502, crypto/crypto.go:232-275
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -1411,5 +1412,98 @@ inline std::vector<std::vector<double>> CollectiveDecryptFinish(crypto::CryptoPa
     std::vector<std::vector<double>> out(cm.rows);
     for (size_t i = 0; i < cm.rows; i++) out[i].assign(all.begin() + i * cm.cols * slots, all.begin() + (i + 1) * cm.cols * slots);
     return out;
+}
+}  // namespace mpc
+
+// ---- collective key generation, local halves (mpc/mhe.go:24-105, 381-502 CollectiveInit; keygen.hip).  PARITY UNPINNED (see include/sfgwas_hip.h).  The network
+//      step between Share / Round and Finish stays in Go: the aggregation of the shares (mpc/aggregate.go:121-240), which hands the sums back as device rows.
+//      A multi-GPU party generates its shares on sfg_mgpu_ctx(mg, 0) (cps->ctx) and gives the finished keys to the other ranks through the existing
+//      sfg_mgpu_load_*: there is no device-to-device key broadcast (out of scope).  Drawing the secret key stays with the caller, as in mhe.go:31-46.
+namespace crypto {
+struct RotationType { int Value = 0; bool Side = false; };          // crypto.go:72-79
+constexpr bool SideRight = true, SideLeft = false;
+inline int FindClosestPow2(int n) { int b = 1; while (b < n) b *= 2; return b; }      // crypto.go:753-759
+// crypto.go:232-275: both sides of every power of two below the slot count, the baby and giant steps of the streamed products, right shifts below smallDim
+inline std::vector<RotationType> GenerateRotKeys(int slots, int smallDim, bool babyFlag) {
+    std::vector<RotationType> rotations;
+    const int l = FindClosestPow2(slots);
+    int rot = 1;
+    for (int i = 0; i < (int)std::ceil(std::log2((double)l)); i++) { rotations.push_back({rot, SideLeft}); rotations.push_back({rot, SideRight}); rot *= 2; }
+    if (babyFlag) {
+        const int rootl = (int)std::ceil(std::sqrt((double)slots));
+        for (int i = 1; i < rootl; i++) { rotations.push_back({i, SideLeft}); rotations.push_back({i * rootl, SideLeft}); }
+    }
+    for (int i = 1; i < smallDim; i++) rotations.push_back({i, SideRight});
+    return rotations;
+}
+// mhe.go:384-411: the distinct left shifts, their Galois elements, the conjugate (GaloisElementForRowRotation = 2N - 1), sorted so that every party agrees on the order
+inline std::vector<uint64_t> GaloisElementsForRotKeys(const CryptoParams *cps, const std::vector<RotationType> &rotTypes) {
+    const int slots = cps->GetSlots();
+    std::map<int, bool> shiftMap;
+    for (const RotationType &r : rotTypes) shiftMap[r.Side == SideRight ? slots - r.Value : r.Value] = true;
+    std::vector<uint64_t> gElems;
+    for (const auto &kv : shiftMap) gElems.push_back(sfg_galois_for_rotation(cps->ctx, kv.first));
+    gElems.push_back(2ULL * (uint64_t)cps->N() - 1);
+    std::sort(gElems.begin(), gElems.end());
+    return gElems;
+}
+// skShard.Value over Q and P (mhe.go:31-46): [nq+np][N], NTT domain; also what LoadSecretKey stores
+inline void LoadSecretKeyQP(CryptoParams *cps, const std::vector<uint64_t> &sk, bool montgomeryForm) {
+    if (sk.size() != (size_t)(cps->nq + cps->np) * cps->N()) throw std::runtime_error("LoadSecretKeyQP: expected [nq+np][N] words");
+    cps->check(sfg_ctx_load_secret_key_qp(cps->ctx, sk.data(), montgomeryForm ? 1 : 0), "LoadSecretKeyQP");
+}
+}  // namespace crypto
+namespace mpc {
+using KeyBuf = std::shared_ptr<crypto::detail::DevBuf>;
+inline size_t keyPolyWords(const crypto::CryptoParams *cps) { return (size_t)(cps->nq + cps->np) * cps->N(); }       // one polynomial over Q and P
+inline int keyBeta(const crypto::CryptoParams *cps) { return (cps->nq + cps->np - 1) / cps->np; }
+// crpGen.ReadNew() (mhe.go:49-59, 90, 419-421, 484-487) for npoly consecutive polynomials: global rows firstPoly (nq+np) .. of the stream every party expands
+// from the shared 32-byte seed (the map of sfg_crp_fill_dev; NOT the reference's frand bytes)
+inline KeyBuf CommonReferencePolys(crypto::CryptoParams *cps, const std::vector<uint8_t> &seed32, uint64_t firstPoly, size_t npoly) {
+    if (seed32.size() != 32) throw std::runtime_error("CommonReferencePolys: the seed is 32 bytes");
+    const int nmod = cps->nq + cps->np;
+    std::vector<int> mod(npoly * nmod); for (size_t r = 0; r < mod.size(); r++) mod[r] = (int)(r % nmod);
+    KeyBuf out = std::make_shared<crypto::detail::DevBuf>(cps, npoly * keyPolyWords(cps) * 8);
+    cps->check(sfg_crp_fill_dev(cps->ctx, seed32.data(), firstPoly * (uint64_t)nmod, mod.size(), mod.data(), out->u()), "CommonReferencePolys");
+    return out;
+}
+struct KeyShares { KeyBuf h; uint64_t firstIndex = 0; };            // the shares and the first sampler index the call took
+// mhe.go:83-105 CollectivePubKeyGen up to the aggregation: ckgProtocol.GenShare(sk, crp, pkShare), the error drawn on the device.  crp [nq+np][N]
+inline KeyShares CollectivePubKeyGenShare(crypto::CryptoParams *cps, const uint64_t *crp_dev) {
+    KeyShares s; s.h = std::make_shared<crypto::detail::DevBuf>(cps, keyPolyWords(cps) * 8);
+    cps->check(sfg_ckg_gen_share_sampled_dev(cps->ctx, crp_dev, s.h->u(), &s.firstIndex), "CKGProtocol.GenShare");
+    return s;
+}
+// ckgProtocol.GenPublicKey(pkAgg, crp, pk): the encryptor's key from now on
+inline void CollectivePubKeyGenFinish(crypto::CryptoParams *cps, const uint64_t *agg_dev, const uint64_t *crp_dev) {
+    cps->check(sfg_ctx_install_public_key_dev(cps->ctx, agg_dev, crp_dev), "CKGProtocol.GenPublicKey");
+}
+// mhe.go:381-476 CollectiveRotKeyGen for a batch of Galois elements (any slice of GaloisElementsForRotKeys: the batch size is the caller's memory knob),
+// rtgProtocol.GenShare for each.  crp, shares [len][beta][nq+np][N]
+inline KeyShares CollectiveRotKeyGenShares(crypto::CryptoParams *cps, const std::vector<uint64_t> &gElems, const uint64_t *crp_dev) {
+    KeyShares s; s.h = std::make_shared<crypto::detail::DevBuf>(cps, gElems.size() * keyBeta(cps) * keyPolyWords(cps) * 8);
+    cps->check(sfg_rtg_gen_shares_sampled_dev(cps->ctx, gElems.data(), (int)gElems.size(), crp_dev, s.h->u(), &s.firstIndex), "RTGProtocol.GenShare");
+    return s;
+}
+// rtgProtocol.GenRotationKey(rtgAgg, rtgCrp, rotKeys.Keys[galEl]) for the batch
+inline void CollectiveRotKeyGenFinish(crypto::CryptoParams *cps, const std::vector<uint64_t> &gElems, const uint64_t *agg_dev, const uint64_t *crp_dev) {
+    cps->check(sfg_ctx_install_rotkeys_dev(cps->ctx, gElems.data(), (int)gElems.size(), agg_dev, crp_dev), "RTGProtocol.GenRotationKey");
+}
+// mhe.go:478-502 CollectiveRelinKeyGen: GenShareRoundOne -> aggregation -> GenShareRoundTwo -> aggregation -> GenRelinearizationKey.  crp, shares [beta][nq+np][N];
+// the ephemeral secret is never stored: round 2 redraws it from uIndex
+struct RelinRound1Shares { KeyBuf h0, h1; uint64_t firstIndex = 0, uIndex = 0; };
+inline RelinRound1Shares CollectiveRelinKeyGenRound1(crypto::CryptoParams *cps, const uint64_t *crp_dev) {
+    RelinRound1Shares s; const size_t bytes = keyBeta(cps) * keyPolyWords(cps) * 8;
+    s.h0 = std::make_shared<crypto::detail::DevBuf>(cps, bytes); s.h1 = std::make_shared<crypto::detail::DevBuf>(cps, bytes);
+    cps->check(sfg_rkg_round1_sampled_dev(cps->ctx, crp_dev, s.h0->u(), s.h1->u(), &s.firstIndex, &s.uIndex), "RKGProtocol.GenShareRoundOne");
+    return s;
+}
+inline KeyShares CollectiveRelinKeyGenRound2(crypto::CryptoParams *cps, const RelinRound1Shares &round1, const uint64_t *h0agg_dev, const uint64_t *h1agg_dev) {
+    KeyShares s; s.h = std::make_shared<crypto::detail::DevBuf>(cps, keyBeta(cps) * keyPolyWords(cps) * 8);
+    cps->check(sfg_rkg_round2_sampled_dev(cps->ctx, h0agg_dev, h1agg_dev, round1.uIndex, s.h->u(), &s.firstIndex), "RKGProtocol.GenShareRoundTwo");
+    return s;
+}
+inline void CollectiveRelinKeyGenFinish(crypto::CryptoParams *cps, const uint64_t *round2agg_dev, const uint64_t *h1agg_dev) {
+    cps->check(sfg_ctx_install_relinkey_dev(cps->ctx, round2agg_dev, h1agg_dev), "RKGProtocol.GenRelinearizationKey");
 }
 }  // namespace mpc
