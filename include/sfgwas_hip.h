@@ -554,19 +554,52 @@ int sfg_refresh_gen_shares_scaled_dev(sfg_ctx *ctx, const uint64_t *ct_dev, int 
 int sfg_refresh_finish_scaled_dev(sfg_ctx *ctx, const uint64_t *ct_dev, int nct, int level, double ct_scale, double target_scale, const uint64_t *h0agg_dev,
                                   const uint64_t *h1agg_dev, const uint64_t *crs_dev, uint64_t *out_dev);
 
-/* f-4 (partial): ring work of MPC.CMatToSS (mpc/ss.go:146-281): the masked decryption share of each ciphertext and NTT(mask), which the Go side
- * turns into the additive share with the fork's DecodeRVec (ss.go:253-262; fork-only encoder API, stays in Go).
+/* f-4: ring work of MPC.CMatToSS (mpc/ss.go:146-281): the masked decryption share of each ciphertext and NTT(mask), which sfg_ckks_to_ss_finish_dev
+ * (below) turns into the additive share after the aggregation (ss.go:239-279).
  *   h0 [nct][level+1][N] = NTT(mask) + sk (.) c1 + NTT(e0)   (ss.go:222-236)      mask_ntt [nct][level+1][N] = NTT(mask)   (ctMask, ss.go:226) */
 int sfg_ckks_to_ss_share_dev(sfg_ctx *ctx, const uint64_t *ct_dev, int nct, int level, const uint64_t *mask_dev, int mask_limbs, const int32_t *e0_dev,
                              uint64_t *h0_dev, uint64_t *mask_ntt_dev);
 
-/* f-4: the share algebra of MPC.SSToCMat that does not need the fork (mpc/ss.go:84-110; EncodeRVecNew, :125, and the encryption stay in Go).
+/* f-4: the share algebra of MPC.SSToCMat (mpc/ss.go:84-110; EncodeRVecNew, :125, is sfg_rvec_encode_dev below, the encryption sfg_encrypt_explicit_dev).
  * Field elements as in the Beaver products.  rand_dev: the ring.RandInt(bound) draws of the caller (< bound), bound_host = Modulus / (4 (nParty - 1)):
  *   mask = rand >= bound / 2 ? rand - bound : rand  (mod p, :90-99);   rm_masked = rm - mask (:101-102, what RevealSymMat then opens)
  * and, on the hub party after the reveal, share = revealed + mask (:104-106). */
 int sfg_ss_mask_dev(sfg_ctx *ctx, int limbs, const uint64_t *modulus_host, const uint64_t *bound_host, const uint64_t *rm_dev, const uint64_t *rand_dev,
                     uint64_t *rm_masked_dev, uint64_t *mask_dev, size_t n);
 int sfg_ss_hub_share_dev(sfg_ctx *ctx, int limbs, const uint64_t *modulus_host, const uint64_t *revealed_dev, const uint64_t *mask_dev, uint64_t *share_dev, size_t n);
+
+/* ---- f-4: secret shares to CKKS plaintexts and back on the device (rvec.hip) ----
+ * PARITY UNPINNED against the lattigo fork's encoder.EncodeRVecNew / DecodeRVec, whose source is not published: what they compute is fixed by their call sites and
+ * by linearity, stated here exactly and pinned against that statement (tests/rvec_ref.py, tests/test_gpu_rvec.py; derivations: DESIGN.md section 12).
+ * N = 2^14, n = N/2 slots, zeta = exp(2 pi i / 2N), slot order and the 5^t rotation group of sfg_encode_vectors_dev / sfg_decode_vectors.  A field element is
+ * `limbs` (2 or 4) little-endian 64-bit words holding a canonical residue in [0, p) of the odd modulus p = modulus_host, plain (not Montgomery), as sfg_ss_mask_dev
+ * takes and returns it; centre(x) = x for x <= (p - 1)/2, else x - p.  scale: a finite double >= 1 taken as the exact rational it is; 0 <= frac_bits = f <= 62;
+ * round() is to nearest.
+ *   encode:  s_t = centre(x_t) for t < n_elem, 0 beyond;  w_c = (1/n) sum_t s_t zeta^(-5^t c);  p_c = round(scale 2^-f Re w_c),  p_{c+n} = round(scale 2^-f Im w_c);
+ *            pt = the NTT-domain rows [level+1][N] of p mod q_0..q_level, canonical words (what sfg_encrypt_explicit_dev takes as pt_dev)
+ *   decode:  p_c = the centred CRT integer of the INTT of the rows (lattigo's Cmp(QHalf) rule, as sfg_decode_vectors);  v_t = sum_c (p_c + i p_{c+n}) zeta^(5^t c);
+ *            r_t = round(2^f / scale Re v_t) mod p in [0, p), t < n_elem
+ * Accuracy contract, both directions: the transform is W-word fixed point (no floating point between the input words and the output words); before the final
+ * rounding the device value is within 2^-32 of the exact real value, in units of the output.  Every output is therefore the exact nearest integer, except where
+ * the exact value lies within 2^-32 of a rounding tie: there either neighbour may come out (exact ties round away from zero).
+ * Refused, with an error string and nothing launched: limbs not 2 or 4, an even modulus, n_elem outside 1..8192, a bad level, a scale that is not finite or below 1,
+ * frac_bits outside 0..62, a (scale, frac_bits) pair that needs more than 8 words of precision, and for the encoder a level too small for the field:
+ *   bitlen(p) - 1 - f + ceil(log2 scale) + 1 < bitlen(Q_level) - 1   must hold   (PN14QP438, f = 30, scale 2^34: limbs 2 from level 3, limbs 4 from level 7).
+ * Stream-ordered, not synchronising.  Scratch from the context's pool, per ciphertext of a chunk of at most 64: 2 W 65,536 bytes + (level + 1) 131,072 bytes, W <= 8
+ * the word count of the call (sfgwas_amd/csrc/rvec_host.hpp: 3 / 5 for the encoder at limbs 2 / 4, 2..7 for the decoder at levels 0..9, with f = 30, scale 2^34). */
+/* encoder.EncodeRVecNew (mpc/ss.go:125): share_dev [nct][n_elem][limbs] -> pt_dev [nct][level+1][N] */
+int sfg_rvec_encode_dev(sfg_ctx *ctx, int limbs, const uint64_t *modulus_host, const uint64_t *share_dev, int n_elem, int nct, int level, double scale, int frac_bits,
+                        uint64_t *pt_dev);
+/* encoder.DecodeRVec (mpc/ss.go:260,264): plaintext rows pt_stride words apart (>= (level+1) * N: polynomial 0 of a resident ciphertext can be read in place)
+ * -> out_dev [nct][n_elem][limbs] */
+int sfg_rvec_decode_dev(sfg_ctx *ctx, int limbs, const uint64_t *modulus_host, const uint64_t *pt_dev, size_t pt_stride, int nct, int level, double scale, int frac_bits,
+                        int n_elem, uint64_t *out_dev);
+/* mpc/ss.go:239-279 in one call, after the aggregation of the sfg_ckks_to_ss_share_dev shares: on the hub (is_hub != 0; ct_dev [nct][2][level+1][N], h0agg_dev
+ * [nct][level+1][N]) out = decode(c0 + h0agg) - decode(mask_ntt) mod p, on every other party out = -decode(mask_ntt) mod p (ct_dev and h0agg_dev not read).
+ * Every output word equals sfg_pcks_finish_dev, two sfg_rvec_decode_dev calls and the field subtraction.  out_dev [nct][n_elem][limbs]; additionally 2 * nct *
+ * n_elem * limbs * 8 bytes of scratch. */
+int sfg_ckks_to_ss_finish_dev(sfg_ctx *ctx, int limbs, const uint64_t *modulus_host, const uint64_t *ct_dev, int nct, int level, double scale, int frac_bits,
+                              const uint64_t *h0agg_dev, const uint64_t *mask_ntt_dev, int is_hub, int n_elem, uint64_t *out_dev);
 
 /* ---- C6 on the device: public-key encryption (crypto.CZeros / CZeroMat, basics.go:367-384; EncryptFloatVector / EncryptFloatMatrixRow, crypto.go:340-388;
  * both end in lattigo's pkEncryptor.EncryptNew) ----

@@ -217,6 +217,48 @@ func (h *Ctx) PCKSFinishDecode(flat []uint64, nct, level int, scale float64, h0a
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// Secret shares <-> CKKS plaintexts (mpc/ss.go:114-134, 239-279; rvec.hip).  PARITY UNPINNED against the lattigo fork's encoder.EncodeRVecNew / DecodeRVec.
+// Field elements are `limbs` little-endian 64-bit words (mpc/ss_hip.go converts); scale is the plaintext's, fracBits mpcObj.GetFracBits().
+
+// EncodeRVec: encoder.EncodeRVecNew (ss.go:125) for nct plaintexts of nElem elements each ([nct][nElem][limbs] words) -> [nct][level+1][N] NTT-domain words.
+func (h *Ctx) EncodeRVec(limbs int, modulus, shares []uint64, nElem, nct, level int, scale float64, fracBits int) []uint64 {
+	d := h.Upload(shares)
+	defer d.Free()
+	o := h.Alloc(nct * (level + 1) * h.N * 8)
+	defer o.Free()
+	h.check(C.sfg_rvec_encode_dev(h.p, C.int(limbs), (*C.uint64_t)(unsafe.Pointer(&modulus[0])), d.U64(), C.int(nElem), C.int(nct), C.int(level), C.double(scale), C.int(fracBits), o.U64()), "rvec_encode")
+	return o.Download()
+}
+
+// DecodeRVec: encoder.DecodeRVec (ss.go:260,264) of nct plaintexts ([nct][level+1][N] words) -> [nct][nElem][limbs] words.
+func (h *Ctx) DecodeRVec(limbs int, modulus, pts []uint64, nct, level int, scale float64, fracBits, nElem int) []uint64 {
+	d := h.Upload(pts)
+	defer d.Free()
+	o := h.Alloc(nct * nElem * limbs * 8)
+	defer o.Free()
+	h.check(C.sfg_rvec_decode_dev(h.p, C.int(limbs), (*C.uint64_t)(unsafe.Pointer(&modulus[0])), d.U64(), C.size_t((level+1)*h.N), C.int(nct), C.int(level), C.double(scale), C.int(fracBits), C.int(nElem), o.U64()), "rvec_decode")
+	return o.Download()
+}
+
+// CKKSToSSFinish: ss.go:239-279 after the aggregation - on the hub decode(c0 + h0agg) - decode(maskNTT), elsewhere -decode(maskNTT) (cts and h0agg nil there).
+func (h *Ctx) CKKSToSSFinish(limbs int, modulus, cts []uint64, nct, level int, scale float64, fracBits int, h0agg, maskNTT []uint64, isHub bool, nElem int) []uint64 {
+	dm := h.Upload(maskNTT)
+	defer dm.Free()
+	o := h.Alloc(nct * nElem * limbs * 8)
+	defer o.Free()
+	var pc, ph *C.uint64_t
+	hub := 0
+	if isHub {
+		dc, dh := h.Upload(cts), h.Upload(h0agg)
+		defer dc.Free()
+		defer dh.Free()
+		pc, ph, hub = dc.U64(), dh.U64(), 1
+	}
+	h.check(C.sfg_ckks_to_ss_finish_dev(h.p, C.int(limbs), (*C.uint64_t)(unsafe.Pointer(&modulus[0])), pc, C.int(nct), C.int(level), C.double(scale), C.int(fracBits), ph, dm.U64(), C.int(hub), C.int(nElem), o.U64()), "ckks_to_ss_finish")
+	return o.Download()
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // Collective key generation, local halves (mpc/mhe.go:24-105, 381-502; keygen.hip).  PARITY UNPINNED against lattigo's dckks / drlwe protocols.  Shares come back
 // as host words for mpc/aggregate.go (AggregatePubKeyShares / AggregateRotKeyShare / AggregateRelinKeyShare sum them modulus by modulus); the aggregated words
 // go back in as host words and are installed from device memory.  The errors and the ephemeral secret are drawn on the device from the encryptor's stream

@@ -112,6 +112,9 @@ def _sig(L):
         "sfg_refresh_gen_shares_scaled_dev": (i, [vp, vp, i, i, d, d, vp, vp, i, vp, vp, vp, vp]),
         "sfg_refresh_finish_scaled_dev": (i, [vp, vp, i, i, d, d, vp, vp, vp, vp]),
         "sfg_ckks_to_ss_share_dev": (i, [vp, vp, i, i, vp, i, vp, vp, vp]),
+        "sfg_rvec_encode_dev": (i, [vp, i, u64p, vp, i, i, i, d, i, vp]),
+        "sfg_rvec_decode_dev": (i, [vp, i, u64p, vp, sz, i, i, d, i, i, vp]),
+        "sfg_ckks_to_ss_finish_dev": (i, [vp, i, u64p, vp, i, i, d, i, vp, vp, i, i, vp]),
         "sfg_geno_pack": (i, [vp, vp, C.POINTER(vp)]),
         "sfg_geno_unpack": (i, [vp, vp, C.POINTER(vp)]),
         "sfg_assoc_stream_bed": (i, [vp, C.c_char_p, sz, sz, vp, vp, sz, vp, i, i, i, C.c_uint, vp, sz, C.POINTER(sz), vp, vp]),
@@ -371,6 +374,42 @@ class Context:
         for p_ in d + [h0, mk]:
             self.free(p_)
         return out
+
+    def rvec_encode(self, modulus, shares, level, scale, frac_bits):
+        """sfg_rvec_encode_dev: shares uint64 [nct][n_elem][limbs] -> plaintext rows uint64 [nct][level+1][N]"""
+        nct, n_elem, limbs = shares.shape
+        d_in, o = self.to_device(np.ascontiguousarray(shares, dtype=np.uint64)), self.malloc(nct * (level + 1) * self.N * 8)
+        try:
+            self.check(lib().sfg_rvec_encode_dev(self.h, limbs, p64(modulus), d_in, n_elem, nct, level, float(scale), frac_bits, o), "rvec_encode")
+            return self.to_host(o, (nct, level + 1, self.N), np.uint64)
+        finally:
+            self.free(d_in)
+            self.free(o)
+
+    def rvec_decode(self, modulus, pts, level, scale, frac_bits, n_elem):
+        """sfg_rvec_decode_dev: plaintext rows uint64 [nct][>= level+1][N] (the row blocks one pts.shape[1] * N apart) -> field elements uint64 [nct][n_elem][limbs]"""
+        nct, limbs = pts.shape[0], len(modulus)
+        d_in, o = self.to_device(np.ascontiguousarray(pts, dtype=np.uint64)), self.malloc(nct * n_elem * limbs * 8)
+        try:
+            self.check(lib().sfg_rvec_decode_dev(self.h, limbs, p64(modulus), d_in, pts.shape[1] * self.N, nct, level, float(scale), frac_bits, n_elem, o), "rvec_decode")
+            return self.to_host(o, (nct, n_elem, limbs), np.uint64)
+        finally:
+            self.free(d_in)
+            self.free(o)
+
+    def ckks_to_ss_finish(self, modulus, cts, level, scale, frac_bits, h0agg, mask_ntt, is_hub, n_elem):
+        """sfg_ckks_to_ss_finish_dev: the additive share [nct][n_elem][limbs] of this party after the aggregation (cts, h0agg: None off the hub)"""
+        nct, limbs = mask_ntt.shape[0], len(modulus)
+        d = [None if a is None else self.to_device(np.ascontiguousarray(a, dtype=np.uint64)) for a in (cts, h0agg, mask_ntt)]
+        o = self.malloc(nct * n_elem * limbs * 8)
+        try:
+            self.check(lib().sfg_ckks_to_ss_finish_dev(self.h, limbs, p64(modulus), d[0], nct, level, float(scale), frac_bits, d[1], d[2], 1 if is_hub else 0, n_elem, o),
+                       "ckks_to_ss_finish")
+            return self.to_host(o, (nct, n_elem, limbs), np.uint64)
+        finally:
+            for p_ in d + [o]:
+                if p_ is not None:
+                    self.free(p_)
 
     def refresh_finish(self, cts, level, h0agg, h1agg, crs, scales=None):
         nct = cts.shape[0]

@@ -97,6 +97,7 @@ struct SfgShared {
     ModConst *modc = nullptr;    // [nmod]
     ModConst modc_host[SFG_MAXMOD];
     void *enc_tables = nullptr;  // encoder tables (double-double twiddles), see encode.hip
+    void *rvec_tables = nullptr; // ring-vector encoder / decoder tables (fixed-point roots of unity, slot map), see rvec.hip
     void *zeros_dev = nullptr;   // 256 B of zeros (DMA source for padded k-steps)
     u64 *sk_dev = nullptr;       // secret-key shard [nq][N], NTT domain, canonical (sfg_ctx_load_secret_key; collective bootstrap shares)
     u64 *pk_dev = nullptr;       // public key [2][nmod][N], NTT domain, canonical (sfg_ctx_load_public_key; encrypt.hip)
@@ -174,6 +175,8 @@ void sfg_encrypt_destroy(SfgShared *sh);       // encrypt.hip: wipe the sampler 
 int enc_take_indices(sfg_ctx *ctx, const char *what, int nct, unsigned long long *first);   // encrypt.hip: nct consecutive encryption indices from the counter the root and its forks share
 int keygen_set_attrs(sfg_ctx *ctx);            // keygen.hip: dynamic-LDS limits of its kernels
 void sfg_keygen_destroy(SfgShared *sh);        // keygen.hip: wipe and free the QP secret key
+int sfg_rvec_init(sfg_ctx *ctx);               // rvec.hip: the fixed-point table zeta^j of the root context, built on the device from the committed base roots
+void sfg_rvec_destroy(SfgShared *sh);          // rvec.hip: free it
 
 extern thread_local std::string g_create_error;
 

@@ -168,6 +168,7 @@ extern "C" int sfg_ctx_create_ex(sfg_ctx **out, int device, int logN, int nq, in
     }
     ctx_bind_shared(ctx, sh);
     if (sfg_encoder_init(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
+    if (sfg_rvec_init(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
     // dynamic-LDS limits are per (function, device): set here for this context's device, not behind process-wide flags
     if (mac_bc_set_attrs(ctx) || ntt_set_attrs(ctx) || encode_set_attrs(ctx) || mac_i8_set_attrs(ctx) || encrypt_set_attrs(ctx) || decrypt_set_attrs(ctx) || keygen_set_attrs(ctx)) { std::string e = ctx->err; return fail(e.c_str()); }
     *out = ctx;
@@ -214,6 +215,7 @@ extern "C" void sfg_ctx_destroy(sfg_ctx *ctx) {
         sfg_encoder_destroy(sh);
         sfg_encrypt_destroy(sh);
         sfg_keygen_destroy(sh);
+        sfg_rvec_destroy(sh);
         (void)hipFree(sh->tw_fwd); (void)hipFree(sh->tw_inv); (void)hipFree(sh->pack_fwd); (void)hipFree(sh->pack_inv); (void)hipFree(sh->modc); (void)hipFree(sh->zeros_dev); (void)hipFree(sh->sk_dev);
         delete sh;
     }

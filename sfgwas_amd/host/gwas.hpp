@@ -1413,6 +1413,62 @@ inline std::vector<std::vector<double>> CollectiveDecryptFinish(crypto::CryptoPa
     for (size_t i = 0; i < cm.rows; i++) out[i].assign(all.begin() + i * cm.cols * slots, all.begin() + (i + 1) * cm.cols * slots);
     return out;
 }
+
+// ---- secret shares <-> CKKS, local halves (mpc/ss.go:60-144 SSToCMat, :146-281 CMatToSS; rvec.hip).  The network steps between them stay in Go: RevealSymMat
+//      (ss.go:103) and the aggregation of the decryption shares (ss.go:238).  PARITY UNPINNED against the lattigo fork's EncodeRVecNew / DecodeRVec (see
+//      include/sfgwas_hip.h).  Randomness stays with the caller as the reference draws it: rand = ring.RandInt(bound) per element, the big-integer masks and the
+//      Gaussian error of CMatToSS - all device resident; the encryption draws from the context's seeded stream (sfg_ctx_seed_encryptor).
+//      A share matrix is nct plaintexts of nElem (<= slots) field elements each, [nct][nElem][limbs] words.
+using DevWords = std::shared_ptr<crypto::detail::DevBuf>;
+struct SSMasked { DevWords masked, mask; size_t n = 0; };             // rm - mask (what RevealSym opens) and the recentred mask, n elements each
+// ss.go:84-102: mask = recentred rand (rand < bound = Modulus / (4 (nParty - 1))), rmMask = rm - mask
+inline SSMasked SSToCMatMask(MPC *m, const uint64_t *rm_dev, const uint64_t *rand_dev, const std::vector<uint64_t> &bound, size_t n) {
+    const int limbs = (int)m->modulus.size();
+    SSMasked s; s.n = n;
+    s.masked = std::make_shared<crypto::detail::DevBuf>(m->cps, n * limbs * 8);
+    s.mask = std::make_shared<crypto::detail::DevBuf>(m->cps, n * limbs * 8);
+    m->cps->check(sfg_ss_mask_dev(m->cps->ctx, limbs, m->modulus.data(), bound.data(), rm_dev, rand_dev, s.masked->u(), s.mask->u(), n), "SSToCMat mask");
+    return s;
+}
+// ss.go:104-134 after the reveal: the hub's share is revealed + mask, every other party's its mask; EncodeRVecNew of the share at `level`, then the encryption under
+// the collective public key (a fresh encryption of zero with the plaintext added to polynomial 0).  revealed_dev: the hub only.  s.n = nct * nElem
+inline crypto::DevCipherVector SSToCMatFinish(MPC *m, const SSMasked &s, const uint64_t *revealed_dev, bool isHub, int nElem, int level, int fracBits) {
+    crypto::CryptoParams *cps = m->cps;
+    const int limbs = (int)m->modulus.size();
+    if (nElem < 1 || s.n % (size_t)nElem) throw std::runtime_error("SSToCMat: the share count is not a whole number of plaintexts");
+    const int nct = (int)(s.n / (size_t)nElem);
+    DevWords share = s.mask;
+    if (isHub) {
+        share = std::make_shared<crypto::detail::DevBuf>(cps, s.n * limbs * 8);
+        cps->check(sfg_ss_hub_share_dev(cps->ctx, limbs, m->modulus.data(), revealed_dev, s.mask->u(), share->u(), s.n), "SSToCMat hub share");
+    }
+    crypto::detail::DevBuf pt(cps, (size_t)nct * (level + 1) * cps->N() * 8);
+    cps->check(sfg_rvec_encode_dev(cps->ctx, limbs, m->modulus.data(), share->u(), nElem, nct, level, cps->scale, fracBits, pt.u()), "EncodeRVecNew");
+    crypto::DevCipherVector ct = crypto::CZerosDev(cps, (size_t)nct, level);
+    cps->check(sfg_ct_add_plain_dev(cps->ctx, ct.ptr(), pt.u(), (size_t)(level + 1) * cps->N(), ct.ptr(), nct, level), "SSToCMat encrypt");
+    return ct;
+}
+// ss.go:200-237: this party's masked decryption share of every ciphertext and NTT(mask).  masks [nct][N][maskLimbs] two's-complement words below
+// Q_level / (2 (nParty - 1)) in magnitude, e0 [nct][N]
+struct CKKSToSSShares { DevWords h0, maskNTT; size_t nct = 0; int level = 0; };
+inline CKKSToSSShares CMatToSSShares(crypto::CryptoParams *cps, const crypto::DevCipherVector &cv, const uint64_t *mask_dev, int maskLimbs, const int32_t *e0_dev) {
+    CKKSToSSShares sh; sh.nct = cv.n; sh.level = cv.level;
+    const size_t bytes = cv.n * (cv.level + 1) * (size_t)cps->N() * 8;
+    sh.h0 = std::make_shared<crypto::detail::DevBuf>(cps, bytes);
+    sh.maskNTT = std::make_shared<crypto::detail::DevBuf>(cps, bytes);
+    cps->check(sfg_ckks_to_ss_share_dev(cps->ctx, cv.ptr(), (int)cv.n, cv.level, mask_dev, maskLimbs, e0_dev, sh.h0->u(), sh.maskNTT->u()), "CMatToSS shares");
+    return sh;
+}
+// ss.go:239-279 with the aggregated shares: the hub decodes c0 + h0agg and subtracts its decoded mask, every other party negates its decoded mask.
+// -> [nct][nElem][limbs] words on the device; h0agg_dev: the hub only
+inline DevWords CMatToSSFinish(MPC *m, const crypto::DevCipherVector &cv, const CKKSToSSShares &sh, const uint64_t *h0agg_dev, bool isHub, int nElem, int fracBits) {
+    crypto::CryptoParams *cps = m->cps;
+    const int limbs = (int)m->modulus.size();
+    DevWords out = std::make_shared<crypto::detail::DevBuf>(cps, sh.nct * (size_t)nElem * limbs * 8);
+    cps->check(sfg_ckks_to_ss_finish_dev(cps->ctx, limbs, m->modulus.data(), isHub ? cv.ptr() : nullptr, (int)sh.nct, sh.level, cv.scale, fracBits,
+                                         isHub ? h0agg_dev : nullptr, sh.maskNTT->u(), isHub ? 1 : 0, nElem, out->u()), "CMatToSS finish");
+    return out;
+}
 }  // namespace mpc
 
 // ---- collective key generation, local halves (mpc/mhe.go:24-105, 381-502 CollectiveInit; keygen.hip).  PARITY UNPINNED (see include/sfgwas_hip.h).  The network
