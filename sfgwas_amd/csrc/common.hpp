@@ -8,6 +8,7 @@
 #include <vector>
 #include <map>
 #include <set>
+#include <unistd.h>
 #include "../../include/sfgwas_hip.h"
 #include "consts.hpp"          // SFG_N, SFG_SLOTS, SFG_D, SFG_MAXMOD, SFG_I8_KEEP_RESERVE, the PT_* panel flags
 
@@ -211,6 +212,26 @@ struct AuxScope {
     sfg_ctx *c; hipStream_t saved;
     explicit AuxScope(sfg_ctx *c_, bool on = true) : c(c_), saved(c_->stream) { if (on) c->stream = c->aux_stream; }
     ~AuxScope() { c->stream = saved; }
+};
+// Move-only owners of what a call acquires for itself: given back at scope exit, in reverse order of declaration, on every path (release() hands the handle on)
+template <class T, hipError_t (*Free)(T)> struct HipOwner {
+    T h = T();
+    HipOwner() {}
+    HipOwner(HipOwner &&o) : h(o.release()) {}
+    HipOwner(const HipOwner &) = delete; HipOwner &operator=(const HipOwner &) = delete;
+    ~HipOwner() { if (h) (void)Free(h); }
+    T release() { T t = h; h = T(); return t; }
+};
+typedef HipOwner<void *, hipFree> DevMem;                 // a device allocation: hipMalloc(&m.h, bytes)
+typedef HipOwner<hipEvent_t, hipEventDestroy> EventOwner;
+typedef HipOwner<hipStream_t, hipStreamDestroy> StreamOwner;
+struct FdOwner {                                          // a file descriptor
+    int fd;
+    explicit FdOwner(int fd_ = -1) : fd(fd_) {}
+    FdOwner(FdOwner &&o) : fd(o.fd) { o.fd = -1; }
+    FdOwner(const FdOwner &) = delete; FdOwner &operator=(const FdOwner &) = delete;
+    ~FdOwner() { reset(); }
+    void reset(int fd_ = -1) { if (fd >= 0) close(fd); fd = fd_; }
 };
 // order `waiter` after everything enqueued so far on `signaller` (no host wait)
 int sfg_stream_after(sfg_ctx *ctx, hipStream_t waiter, hipStream_t signaller);

@@ -141,14 +141,14 @@ extern "C" int sfg_geno_unpack(sfg_ctx *ctx, const sfg_geno *g, sfg_geno **out) 
     sfg_geno *u = new sfg_geno(); u->dev = d; u->nrow = g->nrow; u->ncol = g->ncol; u->ld = g->ncol; u->owned = true;
     *out = u; return 0;
 }
-static int make_map(sfg_ctx *ctx, const uint8_t *filt, size_t n, int32_t **dev, size_t *kept) {
-    *dev = nullptr; *kept = n;
+// a byte filter as the device map k_bed_decode reads (filter_map, assoc_plan.hpp); NULL filter: no map, everything kept
+int upload_filter_map(sfg_ctx *ctx, const uint8_t *filt, size_t n, DevMem &map, size_t *kept) {
+    *kept = n;
     if (!filt) return 0;
-    std::vector<int32_t> m(n); size_t k = 0;
-    for (size_t i = 0; i < n; i++) m[i] = filt[i] ? (int32_t)k++ : -1;
-    *kept = k;
-    SFG_HIP(ctx, hipMalloc(dev, n * sizeof(int32_t)));
-    SFG_HIP(ctx, hipMemcpy(*dev, m.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+    std::vector<int32_t> m(n);
+    *kept = filter_map(filt, n, m.data());
+    SFG_HIP(ctx, hipMalloc(&map.h, n * sizeof(int32_t)));
+    SFG_HIP(ctx, hipMemcpy(map.h, m.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -160,20 +160,18 @@ extern "C" int sfg_geno_from_bed(sfg_ctx *ctx, const uint8_t *bed_host, size_t b
     if (bed_bytes != 3 + num_snp * bps) SFG_FAIL(ctx, "sfg_geno_from_bed: file holds %zu bytes, expected 3 + %zu x %zu", bed_bytes, num_snp, bps);  // the script's assert
     if (bed_host[0] != 0x6C || bed_host[1] != 0x1B || bed_host[2] != 0x01) SFG_FAIL(ctx, "sfg_geno_from_bed: not a SNP-major PLINK .bed (magic %02x %02x %02x)", bed_host[0], bed_host[1], bed_host[2]);
     if (num_sample >= (1ULL << 31) || num_snp >= (1ULL << 31)) SFG_FAIL(ctx, "sfg_geno_from_bed: dimension too large");
-    int32_t *rmap = nullptr, *cmap = nullptr; size_t nr, nc;
-    SFG_TRY(make_map(ctx, row_filter, num_sample, &rmap, &nr));
-    SFG_TRY(make_map(ctx, col_filter, num_snp, &cmap, &nc));
-    if (!nr || !nc) { (void)hipFree(rmap); (void)hipFree(cmap); SFG_FAIL(ctx, "sfg_geno_from_bed: filters keep nothing"); }
-    uint8_t *dbed = nullptr; int8_t *d = nullptr;
-    SFG_HIP(ctx, hipMalloc(&dbed, num_snp * bps));
-    SFG_HIP(ctx, hipMalloc(&d, nr * nc));
-    SFG_HIP(ctx, hipMemcpyAsync(dbed, bed_host + 3, num_snp * bps, hipMemcpyHostToDevice, ctx->stream));
+    DevMem rmap, cmap, dbed, d; size_t nr, nc;
+    SFG_TRY(upload_filter_map(ctx, row_filter, num_sample, rmap, &nr));
+    SFG_TRY(upload_filter_map(ctx, col_filter, num_snp, cmap, &nc));
+    if (!nr || !nc) SFG_FAIL(ctx, "sfg_geno_from_bed: filters keep nothing");
+    SFG_HIP(ctx, hipMalloc(&dbed.h, num_snp * bps));
+    SFG_HIP(ctx, hipMalloc(&d.h, nr * nc));
+    SFG_HIP(ctx, hipMemcpyAsync(dbed.h, bed_host + 3, num_snp * bps, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_bed_decode, dim3((unsigned)((bps + 63) / 64), (unsigned)((num_snp + 63) / 64)), dim3(256), 0, ctx->stream,
-                       dbed, bps, num_sample, num_snp, rmap, cmap, d, nc, BED_LUT);
+                       (const uint8_t *)dbed.h, bps, num_sample, num_snp, (const int32_t *)rmap.h, (const int32_t *)cmap.h, (int8_t *)d.h, nc, BED_LUT);
     SFG_HIP(ctx, hipGetLastError());
     SFG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(dbed); (void)hipFree(rmap); (void)hipFree(cmap);
-    sfg_geno *g = new sfg_geno(); g->dev = d; g->nrow = nr; g->ncol = nc; g->ld = nc; g->owned = true;
+    sfg_geno *g = new sfg_geno(); g->dev = (const int8_t *)d.release(); g->nrow = nr; g->ncol = nc; g->ld = nc; g->owned = true;
     *out = g; return 0;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "mm_plan.hpp"            // the product's launch plan; the byte models mac_i8_stream_bytes / mac_i8_tile_bytes / mac_i8_rot_tile_bytes
+#include "assoc_plan.hpp"         // the association scan's batch plan, filter maps, diag_bool, the active-baby tables
 
 // row r of a batch uses modulus m[r % period] (ciphertext rows, plaintext rows, key-switch rows are all periodic)
 // m < 0 marks a row the kernel must leave untouched
@@ -82,7 +83,6 @@ int launch_mac_bc(sfg_ctx *ctx, const double *rotf, size_t rows_per_k, const u64
                   const double *rotsum);
 // matmul.hip: the baby-step rotation cache of block rows [b0, b1) in the MAC layout; tabs = per-row active-baby flags (null: all 91)
 int rotcache_build_rows_tab(sfg_ctx *ctx, const u64 *A, int s, int in_level, int max_level, int nbr, int b0, int b1, const std::vector<std::vector<uint8_t>> *tabs, double *cache);
-int sfg_diag_bool(int r, int c, int dim, int index);
 // stream.hip: the call-wide rotation cache of an association scan (nullptr in *out = not applicable; caller hipFree()s)
 int assoc_build_rotcache(sfg_ctx *ctx, const u64 *A_dev, int s, int in_level, int max_level, size_t nr, const std::vector<size_t> &widths, double **out);
 // A caller's baby-step rotation cache held ONLY as the int8 MAC's transposed rot tiles (round 4): one pair of buffers (35-bit moduli / 46-bit modulus) per MAC group of
@@ -99,7 +99,17 @@ int launch_i8_pack_rot_to(sfg_ctx *ctx, const double *rotf, size_t rotf_k_stride
 struct AssocRot { double *f64 = nullptr; I8RotPre pre; };
 int assoc_build_rot(sfg_ctx *ctx, const u64 *A_dev, int s, int in_level, int max_level, size_t nr, const std::vector<size_t> &widths, AssocRot &out);
 void assoc_free_rot(AssocRot &r);
+struct AssocRotScope { AssocRot r; ~AssocRotScope() { assoc_free_rot(r); } };
 int assoc_product(sfg_ctx *ctx, const AssocRot &r, const uint64_t *A_dev, int s, int in_level, int max_level, const sfg_geno *g, unsigned flags, int nct, uint64_t *out);
+int assoc_batch_tail(sfg_ctx *ctx, const u64 *tmp, const sfg_geno *g, int s, size_t nct, size_t ctw, uint64_t *out_dev, size_t out_ct_capacity, size_t out_shift,
+                     double *sum_host, double *sqsum_host);      // stream.hip: rows of tmp copied into place, padded sums zeroed, column sums
+
+// genoio.hip: decode + filter + transpose of a packed SNP range in HBM on queue st; a byte filter as a device map (NULL filter: no map, *kept = n)
+int launch_bed_decode(sfg_ctx *ctx, hipStream_t st, const uint8_t *dbed, size_t bps, size_t num_sample, size_t num_snp, const int32_t *rmap, const int32_t *cmap,
+                      int8_t *out, size_t ld);
+int launch_bed_decode_lut(sfg_ctx *ctx, hipStream_t st, const uint8_t *dbed, size_t bps, size_t num_sample, size_t num_snp, const int32_t *rmap, const int32_t *cmap,
+                          int8_t *out, size_t ld, unsigned lut);
+int upload_filter_map(sfg_ctx *ctx, const uint8_t *filt, size_t n, DevMem &map, size_t *kept);
 
 // stream.hip: the streamed association scan restricted to the batches k % nparts == part (fmt 0 = .bed, 1 = .pgen); see its definition
 int assoc_stream_part(sfg_ctx *ctx, int fmt, const char *path, size_t num_sample, size_t num_snp, const uint8_t *row_filter, const uint8_t *col_filter,

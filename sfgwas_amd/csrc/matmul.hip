@@ -17,10 +17,6 @@
 #include <string>
 
 static inline int ceil_div(size_t a, size_t b) { return (int)((a + b - 1) / b); }
-static inline int diag_bool(int r, int c, int dim, int index) {          // GetDiagBool, matmult.go:627-631
-    index %= dim; if (index < 0) index += dim;
-    return (dim + 1 - r) <= index || index <= c - 1;
-}
 
 struct Shape {
     size_t nrow, ncol;      // logical operand dims (after optional transpose)
@@ -957,7 +953,6 @@ int matmul_accumulate_i8pre(sfg_ctx *ctx, const I8RotPre &pre, int s, int max_le
     return matmul_accumulate(ctx, nullptr, s, max_level, max_level, sh, flags, 0, pre.nbr, j0, j1, accumulate, (u64 *)acc, nullptr, nullptr, &pre, acc_col_words);
 }
 // GetDiagBool (matmult.go:627-631) for other translation units
-int sfg_diag_bool(int r, int c, int dim, int index) { return diag_bool(r, c, dim, index); }
 // the products on a prebuilt cache that covers exactly the operand block rows the call contracts over ([0, nbr) for X, [blk0, blk1) / [b0, b1) for X^T)
 extern "C" int sfg_matmul_resident_range_rc_dev(sfg_ctx *ctx, const double *cache, int s, int max_level, const sfg_geno *g, unsigned flags,
                                                 int blk0, int blk1, uint64_t *out) {

@@ -896,8 +896,7 @@ static int mgpu_assoc(sfg_mgpu *mg, int fmt, const char *path, size_t num_sample
 extern "C" int sfg_mgpu_assoc_stream_bed(sfg_mgpu *mg, const char *bed_path, size_t num_sample, size_t num_snp, const uint8_t *row_filter, const uint8_t *col_filter,
                                          size_t batch_snps, const uint64_t *A_host, int s, int in_level, int max_level, unsigned flags,
                                          uint64_t *out_host, size_t out_ct_capacity, size_t *out_ct, double *sum_host, double *sqsum_host) {
-    size_t nr = 0; for (size_t i = 0; i < num_sample; i++) nr += (!row_filter || row_filter[i]) ? 1 : 0;
-    return mgpu_assoc(mg, 0, bed_path, num_sample, num_snp, row_filter, col_filter, batch_snps, A_host, (nr + SFG_SLOTS - 1) / SFG_SLOTS, s, in_level, max_level, flags,
+    return mgpu_assoc(mg, 0, bed_path, num_sample, num_snp, row_filter, col_filter, batch_snps, A_host, assoc_cts(filter_map(row_filter, num_sample, nullptr)), s, in_level, max_level, flags,
                       out_host, out_ct_capacity, out_ct, sum_host, sqsum_host);
 }
 // kept_samples: the number of samples the row filter keeps (the file's sample count when row_filter is NULL) - it sizes `A_host` ([s][ceil(kept_samples / 8192)])
@@ -905,6 +904,6 @@ extern "C" int sfg_mgpu_assoc_stream_pgen(sfg_mgpu *mg, const char *pgen_path, c
                                           size_t batch_snps, const uint64_t *A_host, int s, int in_level, int max_level, unsigned flags,
                                           uint64_t *out_host, size_t out_ct_capacity, size_t *out_ct, double *sum_host, double *sqsum_host) {
     if (!kept_samples) MG_FAIL(mg, "sfg_mgpu_assoc_stream_pgen: kept_samples must be given (it sizes the input ciphertext grid)");
-    return mgpu_assoc(mg, 1, pgen_path, 0, 0, row_filter, col_filter, batch_snps, A_host, (kept_samples + SFG_SLOTS - 1) / SFG_SLOTS, s, in_level, max_level, flags,
+    return mgpu_assoc(mg, 1, pgen_path, 0, 0, row_filter, col_filter, batch_snps, A_host, assoc_cts(kept_samples), s, in_level, max_level, flags,
                       out_host, out_ct_capacity, out_ct, sum_host, sqsum_host);
 }

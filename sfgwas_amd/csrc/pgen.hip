@@ -207,9 +207,6 @@ __global__ void __launch_bounds__(256) k_pgen_counts(const uint8_t *rows, size_t
     }
 }
 
-int launch_bed_decode_lut(sfg_ctx *ctx, hipStream_t st, const uint8_t *dbed, size_t bps, size_t num_sample, size_t num_snp, const int32_t *rmap, const int32_t *cmap,
-                          int8_t *out, size_t ld, unsigned lut);
-
 // the variants a window [v0, v1) needs on the device: [start, v1) with start <= v0 the LD base of the first ones; record offsets relative to the window's
 // first byte f0, LD-base row per record
 int pgen_window(sfg_ctx *ctx, const PgenIndex &ix, size_t file_bytes, size_t v0, size_t v1, PgenWindow &w) {
@@ -230,28 +227,25 @@ int pgen_window(sfg_ctx *ctx, const PgenIndex &ix, size_t file_bytes, size_t v0,
     return 0;
 }
 size_t pgen_pitch(const PgenIndex &ix) { return ((((size_t)ix.ns + 3) / 4) + 3) & ~(size_t)3; }
-// descriptor block of a window on the device: off | len | vrt | ldbase | err, `bytes` = pgen_desc_bytes(nr)
-size_t pgen_desc_bytes(size_t nr) { auto al = [](size_t x) { return (x + 255) & ~(size_t)255; }; return al(nr * 8) + al(nr * 4) + al(nr) + al(nr * 4) + 256; }
+// descriptor block of a window on the device (PgenDesc, assoc_plan.hpp: off | len | vrt | ldbase | err), PgenDesc(w.nr).bytes of it
 int pgen_upload_desc(sfg_ctx *ctx, hipStream_t st, const PgenIndex &ix, const PgenWindow &w, uint8_t *desc) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t nr = w.nr, o_len = al(nr * 8), o_vrt = o_len + al(nr * 4), o_ldb = o_vrt + al(nr), o_err = o_ldb + al(nr * 4);
+    const size_t nr = w.nr; const PgenDesc o(nr);
     SFG_HIP(ctx, hipMemcpyAsync(desc, w.off.data(), nr * 8, hipMemcpyHostToDevice, st));
-    SFG_HIP(ctx, hipMemcpyAsync(desc + o_len, ix.len.data() + w.start, nr * 4, hipMemcpyHostToDevice, st));
-    SFG_HIP(ctx, hipMemcpyAsync(desc + o_vrt, ix.vrt.data() + w.start, nr, hipMemcpyHostToDevice, st));
-    SFG_HIP(ctx, hipMemcpyAsync(desc + o_ldb, w.ldb.data(), nr * 4, hipMemcpyHostToDevice, st));
-    SFG_HIP(ctx, hipMemsetAsync(desc + o_err, 0, 4, st));
+    SFG_HIP(ctx, hipMemcpyAsync(desc + o.len, ix.len.data() + w.start, nr * 4, hipMemcpyHostToDevice, st));
+    SFG_HIP(ctx, hipMemcpyAsync(desc + o.vrt, ix.vrt.data() + w.start, nr, hipMemcpyHostToDevice, st));
+    SFG_HIP(ctx, hipMemcpyAsync(desc + o.ldb, w.ldb.data(), nr * 4, hipMemcpyHostToDevice, st));
+    SFG_HIP(ctx, hipMemsetAsync(desc + o.err, 0, 4, st));
     return 0;
 }
 // the two decode passes of a window whose bytes and descriptors are on the device; rows: [nr][pitch].  *err_dev (returned) holds the error flags afterwards
 int launch_pgen_decode(sfg_ctx *ctx, hipStream_t st, const uint8_t *file_dev, const uint8_t *desc, size_t nr, uint32_t ns, size_t pitch, uint8_t *rows, const int **err_dev) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_len = al(nr * 8), o_vrt = o_len + al(nr * 4), o_ldb = o_vrt + al(nr), o_err = o_ldb + al(nr * 4);
+    const PgenDesc o(nr);
     for (int pass = 0; pass < 2; pass++) {
-        hipLaunchKernelGGL(k_pgen_decode, dim3((unsigned)nr), dim3(256), 0, st, file_dev, (const uint64_t *)desc, (const uint32_t *)(desc + o_len), desc + o_vrt,
-                           (const uint32_t *)(desc + o_ldb), ns, pitch, rows, pass, (int *)(desc + o_err));
+        hipLaunchKernelGGL(k_pgen_decode, dim3((unsigned)nr), dim3(256), 0, st, file_dev, (const uint64_t *)desc, (const uint32_t *)(desc + o.len), desc + o.vrt,
+                           (const uint32_t *)(desc + o.ldb), ns, pitch, rows, pass, (int *)(desc + o.err));
         SFG_HIP(ctx, hipGetLastError());
     }
-    if (err_dev) *err_dev = (const int *)(desc + o_err);
+    if (err_dev) *err_dev = (const int *)(desc + o.err);
     return 0;
 }
 int pgen_decode_error(sfg_ctx *ctx, int herr) {
@@ -262,22 +256,20 @@ int pgen_decode_error(sfg_ctx *ctx, int herr) {
 }
 
 // decodes variants [v0, v1) of a file image in host memory into device rows; returns the rows of [v0, v1)
-struct PgenRows { uint8_t *buf = nullptr; uint8_t *rows = nullptr; size_t pitch = 0; };
+struct PgenRows { DevMem buf; uint8_t *rows = nullptr; size_t pitch = 0; };
 static int pgen_decode_window(sfg_ctx *ctx, const uint8_t *f, size_t bytes, const PgenIndex &ix, size_t v0, size_t v1, PgenRows &out) {
     PgenWindow w; SFG_TRY(pgen_window(ctx, ix, bytes, v0, v1, w));
     const size_t pitch = pgen_pitch(ix), fb = (size_t)(w.f1 - w.f0);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_file = al(w.nr * pitch), o_desc = o_file + al(fb + 8);            // one allocation: rows | file bytes | descriptors
-    uint8_t *d = nullptr;
-    SFG_HIP(ctx, hipMalloc(&d, o_desc + pgen_desc_bytes(w.nr)));
-    int rc = 0, herr = 0; const int *err_dev = nullptr;
-    if (hipMemcpyAsync(d + o_file, f + w.f0, fb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = 1;
-    if (!rc) rc = pgen_upload_desc(ctx, ctx->stream, ix, w, d + o_desc);
-    if (!rc) rc = launch_pgen_decode(ctx, ctx->stream, d + o_file, d + o_desc, w.nr, ix.ns, pitch, d, &err_dev);
-    if (!rc && (hipMemcpyAsync(&herr, err_dev, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)) rc = 1;   // the host vectors are done with, too
-    if (rc) { (void)hipFree(d); if (ctx->err.empty()) ctx->err = "pgen: device decode failed to launch"; return 1; }
-    if (pgen_decode_error(ctx, herr)) { (void)hipFree(d); return 1; }
-    out.buf = d; out.rows = d + w.lead * pitch; out.pitch = pitch;
+    const size_t o_file = align256(w.nr * pitch), o_desc = o_file + align256(fb + 8);            // one allocation: rows | file bytes | descriptors
+    SFG_HIP(ctx, hipMalloc(&out.buf.h, o_desc + PgenDesc(w.nr).bytes));
+    uint8_t *d = (uint8_t *)out.buf.h; int herr = 0; const int *err_dev = nullptr;
+    SFG_HIP(ctx, hipMemcpyAsync(d + o_file, f + w.f0, fb, hipMemcpyHostToDevice, ctx->stream));
+    SFG_TRY(pgen_upload_desc(ctx, ctx->stream, ix, w, d + o_desc));
+    SFG_TRY(launch_pgen_decode(ctx, ctx->stream, d + o_file, d + o_desc, w.nr, ix.ns, pitch, d, &err_dev));
+    SFG_HIP(ctx, hipMemcpyAsync(&herr, err_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SFG_HIP(ctx, hipStreamSynchronize(ctx->stream));                                               // the host vectors are done with, too
+    SFG_TRY(pgen_decode_error(ctx, herr));
+    out.rows = d + w.lead * pitch; out.pitch = pitch;
     return 0;
 }
 
@@ -288,33 +280,20 @@ extern "C" int sfg_pgen_dims(sfg_ctx *ctx, const uint8_t *pgen_host, size_t pgen
     return 0;
 }
 
-static int make_map32(sfg_ctx *ctx, const uint8_t *filt, size_t n, int32_t **dev, size_t *kept) {
-    *dev = nullptr; *kept = n;
-    if (!filt) return 0;
-    std::vector<int32_t> m(n); size_t k = 0;
-    for (size_t i = 0; i < n; i++) m[i] = filt[i] ? (int32_t)k++ : -1;
-    *kept = k;
-    SFG_HIP(ctx, hipMalloc(dev, n * sizeof(int32_t)));
-    SFG_HIP(ctx, hipMemcpy(*dev, m.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-    return 0;
-}
-
 extern "C" int sfg_geno_from_pgen(sfg_ctx *ctx, const uint8_t *pgen_host, size_t pgen_bytes, size_t v0, size_t v1,
                                   const uint8_t *row_filter, const uint8_t *col_filter, sfg_geno **out) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
     PgenIndex ix; SFG_TRY(pgen_index(ctx, pgen_host, pgen_bytes, pgen_bytes, ix));
     if (v1 == 0) v1 = ix.nv;                                       // [0, 0) = the whole file
     PgenRows rows; SFG_TRY(pgen_decode_window(ctx, pgen_host, pgen_bytes, ix, v0, v1, rows));
-    int32_t *rmap = nullptr, *cmap = nullptr; size_t nr = 0, nc = 0; int8_t *d = nullptr;
-    int rc = make_map32(ctx, row_filter, ix.ns, &rmap, &nr);
-    if (!rc) rc = make_map32(ctx, col_filter, v1 - v0, &cmap, &nc);
-    if (!rc && (!nr || !nc)) { ctx->err = "sfg_geno_from_pgen: filters keep nothing"; rc = 1; }
-    if (!rc && hipMalloc(&d, nr * nc) != hipSuccess) { ctx->err = "sfg_geno_from_pgen: out of device memory"; rc = 1; }
-    if (!rc) rc = launch_bed_decode_lut(ctx, ctx->stream, rows.rows, rows.pitch, ix.ns, v1 - v0, rmap, cmap, d, nc, 0xFF020100u);     // code -> int8 {0, 1, 2, -1}
-    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "sfg_geno_from_pgen: decode failed"; rc = 1; }
-    (void)hipFree(rows.buf); (void)hipFree(rmap); (void)hipFree(cmap);
-    if (rc) { (void)hipFree(d); return rc; }
-    sfg_geno *g = new sfg_geno(); g->dev = d; g->nrow = nr; g->ncol = nc; g->ld = nc; g->owned = true;
+    DevMem rmap, cmap, d; size_t nr = 0, nc = 0;
+    SFG_TRY(upload_filter_map(ctx, row_filter, ix.ns, rmap, &nr));
+    SFG_TRY(upload_filter_map(ctx, col_filter, v1 - v0, cmap, &nc));
+    if (!nr || !nc) SFG_FAIL(ctx, "sfg_geno_from_pgen: filters keep nothing");
+    if (hipMalloc(&d.h, nr * nc) != hipSuccess) SFG_FAIL(ctx, "sfg_geno_from_pgen: out of device memory");
+    SFG_TRY(launch_bed_decode_lut(ctx, ctx->stream, rows.rows, rows.pitch, ix.ns, v1 - v0, (const int32_t *)rmap.h, (const int32_t *)cmap.h, (int8_t *)d.h, nc, 0xFF020100u));     // code -> int8 {0, 1, 2, -1}
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) SFG_FAIL(ctx, "sfg_geno_from_pgen: decode failed");
+    sfg_geno *g = new sfg_geno(); g->dev = (const int8_t *)d.release(); g->nrow = nr; g->ncol = nc; g->ld = nc; g->owned = true;
     *out = g; return 0;
 }
 
@@ -324,14 +303,14 @@ extern "C" int sfg_pgen_geno_counts(sfg_ctx *ctx, const uint8_t *pgen_host, size
     PgenRows rows; SFG_TRY(pgen_decode_window(ctx, pgen_host, pgen_bytes, ix, 0, ix.nv, rows));
     std::vector<unsigned> keep(rows.pitch / 4, 0u);
     for (uint32_t i = 0; i < ix.ns; i++) if (!row_filter || row_filter[i]) keep[i >> 4] |= 1u << (2 * (i & 15));
-    unsigned *dk = nullptr; uint32_t *dc = nullptr; int rc = 0;
-    if (hipMalloc(&dk, keep.size() * 4) != hipSuccess || hipMalloc(&dc, (size_t)6 * ix.nv * 4) != hipSuccess) { ctx->err = "sfg_pgen_geno_counts: out of device memory"; rc = 1; }
-    if (!rc && hipMemcpyAsync(dk, keep.data(), keep.size() * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = 1;
-    if (!rc) { hipLaunchKernelGGL(k_pgen_counts, dim3(ix.nv), dim3(256), 0, ctx->stream, rows.rows, rows.pitch, dk, ix.nv, dc); if (hipGetLastError() != hipSuccess) rc = 1; }
-    if (!rc && (hipMemcpyAsync(counts_host, dc, (size_t)6 * ix.nv * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)) rc = 1;
-    if (rc && ctx->err.empty()) ctx->err = "sfg_pgen_geno_counts: device work failed";
-    (void)hipFree(rows.buf); (void)hipFree(dk); (void)hipFree(dc);
-    return rc;
+    DevMem dk, dc;
+    if (hipMalloc(&dk.h, keep.size() * 4) != hipSuccess || hipMalloc(&dc.h, (size_t)6 * ix.nv * 4) != hipSuccess) SFG_FAIL(ctx, "sfg_pgen_geno_counts: out of device memory");
+    SFG_HIP(ctx, hipMemcpyAsync(dk.h, keep.data(), keep.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_pgen_counts, dim3(ix.nv), dim3(256), 0, ctx->stream, rows.rows, rows.pitch, (const unsigned *)dk.h, ix.nv, (uint32_t *)dc.h);
+    SFG_HIP(ctx, hipGetLastError());
+    SFG_HIP(ctx, hipMemcpyAsync(counts_host, dc.h, (size_t)6 * ix.nv * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SFG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 // GenoBlockMult over one chromosome's .pgen (gwas/assoc.go:340-420) - what config 1 runs: per batch of `batch_snps` KEPT variants FilterMatrixFilePgen +
@@ -346,45 +325,26 @@ extern "C" int sfg_assoc_pgen(sfg_ctx *ctx, const uint8_t *pgen_host, size_t pge
     if (!batch_snps) SFG_FAIL(ctx, "assoc_pgen: bad batch size");
     if (flags & SFG_TRANSPOSE) SFG_FAIL(ctx, "assoc_pgen: batches are multiplied as X (samples x SNPs)");
     PgenIndex ix; SFG_TRY(pgen_index(ctx, pgen_host, pgen_bytes, pgen_bytes, ix));
-    const size_t slots = SFG_SLOTS, N = SFG_N, ctw = (size_t)2 * max_level * N;
-    struct B { size_t v0, v1, kept; };
-    std::vector<B> bt; size_t start = 0, counter = 0;                     // assoc.go:371-416: a batch closes at batch_snps kept variants or at the end of the file
-    for (size_t idx = 0; idx < ix.nv; idx++) {
-        if (!col_filter || col_filter[idx]) counter++;
-        if (counter == batch_snps || (idx == (size_t)ix.nv - 1 && counter > 0)) { bt.push_back({start, idx + 1, counter}); start = idx + 1; counter = 0; }
-    }
-    size_t total_ct = 0, max_kept = 0, nr = 0;
-    for (const B &b : bt) { total_ct += (b.kept + slots - 1) / slots; max_kept = std::max(max_kept, b.kept); }
-    for (uint32_t i = 0; i < ix.ns; i++) nr += !row_filter || row_filter[i];
-    if (out_ct) *out_ct = total_ct;
-    if (bt.empty()) return 0;
+    const size_t ctw = (size_t)2 * max_level * SFG_N;
+    const AssocPlan plan = assoc_plan(col_filter, ix.nv, batch_snps);
+    const size_t nr = filter_map(row_filter, ix.ns, nullptr);
+    if (out_ct) *out_ct = plan.total_ct;
+    if (plan.bt.empty()) return 0;
     if (!nr) SFG_FAIL(ctx, "assoc_pgen: the row filter keeps nothing");
-    if (total_ct > out_ct_capacity) SFG_FAIL(ctx, "assoc_pgen: output needs %zu ciphertexts per row, capacity %zu", total_ct, out_ct_capacity);
-    std::vector<size_t> widths;
-    for (const B &b : bt) for (size_t c0 = 0; c0 < b.kept; c0 += slots) { const size_t w = std::min(slots, b.kept - c0); if (std::find(widths.begin(), widths.end(), w) == widths.end()) widths.push_back(w); }
-    AssocRot rot; u64 *tmp = nullptr;
-    SFG_TRY(assoc_build_rot(ctx, (const u64 *)A_dev, s, in_level, max_level, nr, widths, rot));
+    if (plan.total_ct > out_ct_capacity) SFG_FAIL(ctx, "assoc_pgen: output needs %zu ciphertexts per row, capacity %zu", plan.total_ct, out_ct_capacity);
+    AssocRotScope rot; DevMem tmp;                                    // (tmp is freed first, then assoc_free_rot)
+    SFG_TRY(assoc_build_rot(ctx, (const u64 *)A_dev, s, in_level, max_level, nr, plan.widths, rot.r));
+    if (hipMalloc(&tmp.h, (size_t)s * assoc_cts(plan.max_kept) * ctw * 8) != hipSuccess) SFG_FAIL(ctx, "assoc_pgen: out of device memory");
     int rc = 0;
-    if (hipMalloc(&tmp, (size_t)s * ((max_kept + slots - 1) / slots) * ctw * 8) != hipSuccess) { ctx->err = "assoc_pgen: out of device memory"; rc = 1; }
-    size_t out_shift = 0;
-    for (size_t k = 0; k < bt.size() && !rc; k++) {
-        const B &b = bt[k];
+    for (size_t k = 0; k < plan.bt.size() && !rc; k++) {
+        const AssocBatch &b = plan.bt[k];
         sfg_geno *g = nullptr;
-        rc = sfg_geno_from_pgen(ctx, pgen_host, pgen_bytes, b.v0, b.v1, row_filter, col_filter ? col_filter + b.v0 : nullptr, &g);
-        if (rc) break;
-        const size_t nct = (b.kept + slots - 1) / slots;
-        rc = assoc_product(ctx, rot, A_dev, s, in_level, max_level, g, flags, (int)nct, (uint64_t *)tmp);
-        for (int i = 0; i < s && !rc; i++)
-            if (hipMemcpyAsync(out_dev + ((size_t)i * out_ct_capacity + out_shift) * ctw, tmp + (size_t)i * nct * ctw, nct * ctw * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) { ctx->err = "assoc_pgen: copy failed"; rc = 1; }
-        if (!rc && (sum_host || sqsum_host)) {
-            if (sum_host) std::fill(sum_host + out_shift * slots, sum_host + (out_shift + nct) * slots, 0.0);
-            if (sqsum_host) std::fill(sqsum_host + out_shift * slots, sqsum_host + (out_shift + nct) * slots, 0.0);
-            rc = sfg_geno_colsums(ctx, g, sum_host ? sum_host + out_shift * slots : nullptr, sqsum_host ? sqsum_host + out_shift * slots : nullptr);
-        }
+        SFG_TRY(sfg_geno_from_pgen(ctx, pgen_host, pgen_bytes, b.snp0, b.snp0 + b.nsnp, row_filter, col_filter ? col_filter + b.snp0 : nullptr, &g));
+        const size_t nct = assoc_cts(b.kept);
+        rc = assoc_product(ctx, rot.r, A_dev, s, in_level, max_level, g, flags, (int)nct, (uint64_t *)tmp.h);
+        if (!rc) rc = assoc_batch_tail(ctx, (const u64 *)tmp.h, g, s, nct, ctw, out_dev, out_ct_capacity, plan.shift_of[k], sum_host, sqsum_host);
         sfg_geno_free(ctx, g);                                            // synchronises the queue: tmp and the batch matrix are done with
-        out_shift += nct;
     }
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(tmp); assoc_free_rot(rot);
     return rc;
 }

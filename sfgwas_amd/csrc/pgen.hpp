@@ -7,7 +7,6 @@ size_t pgen_header_bytes(const uint8_t *first12);
 int pgen_index(sfg_ctx *ctx, const uint8_t *f, size_t bytes, size_t file_bytes, PgenIndex &ix);
 int pgen_window(sfg_ctx *ctx, const PgenIndex &ix, size_t file_bytes, size_t v0, size_t v1, PgenWindow &w);
 size_t pgen_pitch(const PgenIndex &ix);
-size_t pgen_desc_bytes(size_t nr);
 int pgen_upload_desc(sfg_ctx *ctx, hipStream_t st, const PgenIndex &ix, const PgenWindow &w, uint8_t *desc_dev);
 int launch_pgen_decode(sfg_ctx *ctx, hipStream_t st, const uint8_t *file_dev, const uint8_t *desc_dev, size_t nr, uint32_t ns, size_t pitch, uint8_t *rows_dev, const int **err_dev);
 int pgen_decode_error(sfg_ctx *ctx, int herr);

@@ -28,31 +28,16 @@
 #include <thread>
 #include <unistd.h>
 
-// genoio.hip
-int launch_bed_decode(sfg_ctx *ctx, hipStream_t st, const uint8_t *dbed, size_t bps, size_t num_sample, size_t num_snp, const int32_t *rmap, const int32_t *cmap,
-                      int8_t *out, size_t ld);
-int launch_bed_decode_lut(sfg_ctx *ctx, hipStream_t st, const uint8_t *dbed, size_t bps, size_t num_sample, size_t num_snp, const int32_t *rmap, const int32_t *cmap,
-                          int8_t *out, size_t ld, unsigned lut);
-
 namespace {
-struct Batch { size_t snp0, nsnp, kept; off_t off = 0; size_t bytes = 0; };            // file SNPs [snp0, snp0 + nsnp), `kept` of them pass the filter; their bytes in the file
-// assoc.go:371-416: a batch closes when `batch_snps` kept SNPs have been seen or the file ends with a non-empty batch
-std::vector<Batch> make_batches(const uint8_t *col_filter, size_t num_snp, size_t batch_snps) {
-    std::vector<Batch> b; size_t start = 0, counter = 0;
-    for (size_t idx = 0; idx < num_snp; idx++) {
-        if (!col_filter || col_filter[idx]) counter++;
-        if (counter == batch_snps || (idx == num_snp - 1 && counter > 0)) { b.push_back({start, idx + 1 - start, counter}); start = idx + 1; counter = 0; }
-    }
-    return b;
-}
+struct Span { off_t off; size_t bytes; };              // the bytes of a batch in the file
 struct Reader {                                        // fills pinned slot k & 1 with the bytes of batch k, one batch ahead of the consumer
-    int fd; const std::vector<Batch> *bt; uint8_t *slot[2];
+    int fd; const std::vector<Span> *bt; uint8_t *slot[2];
     bool direct = false; size_t lead[2] = {0, 0};       // O_DIRECT: 4096-byte aligned file ranges; the batch starts `lead` bytes into its slot
     std::mutex mu; std::condition_variable cv; long filled = -1, released = -1; bool failed = false; std::string err;
     void run() {
         for (size_t k = 0; k < bt->size(); k++) {
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return (long)k - 2 <= released; }); }      // slot k & 1 was last used by batch k - 2
-            const Batch &b = (*bt)[k]; const off_t off = b.off, a0 = direct ? off & ~(off_t)4095 : off;
+            const Span &b = (*bt)[k]; const off_t off = b.off, a0 = direct ? off & ~(off_t)4095 : off;
             const size_t ld = (size_t)(off - a0), want = ld + b.bytes, want_al = direct ? (want + 4095) & ~(size_t)4095 : want; size_t got = 0;
             while (got < want) {
                 ssize_t r = pread(fd, slot[k & 1] + got, want_al - got, a0 + (off_t)got);
@@ -67,20 +52,13 @@ struct Reader {                                        // fills pinned slot k & 
     bool wait_filled(size_t k) { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return failed || filled >= (long)k; }); return !failed; }
     void release(size_t k) { { std::lock_guard<std::mutex> lk(mu); released = (long)k; } cv.notify_all(); }
 };
+// Ends the reader on every way out of the scan: released past the last batch it runs out without waiting for a slot, then it is joined (the pinned slots it
+// fills are context scratch that outlives the call)
+struct ReaderEnd { Reader &rd; std::thread &th; ~ReaderEnd() { rd.release(rd.bt->size() + 2); th.join(); } };
+// both queues of the scan idle before anything they use is given back
+struct QueuesIdle { sfg_ctx *ctx; const StreamOwner &copy; ~QueuesIdle() { (void)hipStreamSynchronize(ctx->stream); if (copy.h) (void)hipStreamSynchronize(copy.h); } };
 }  // namespace
 
-static void assoc_baby_tabs(size_t nr, const std::vector<size_t> &widths, std::vector<std::vector<uint8_t>> &tabs) {
-    const size_t slots = SFG_SLOTS;
-    const int nbr = (int)((nr + slots - 1) / slots);
-    tabs.assign(nbr, std::vector<uint8_t>(SFG_D, 0));
-    for (int bi = 0; bi < nbr; bi++) {
-        const int rows = (int)(std::min((size_t)(bi + 1) * slots, nr) - (size_t)bi * slots);
-        for (int shift = 0; shift < SFG_SLOTS; shift++) {
-            if (tabs[bi][shift % SFG_D]) continue;
-            for (size_t w : widths) if (sfg_diag_bool(rows, (int)w, SFG_SLOTS, -shift)) { tabs[bi][shift % SFG_D] = 1; break; }
-        }
-    }
-}
 // The baby-step rotation cache of the ciphertext matrix every batch of an association scan multiplies (see the header comment): *out = nullptr when the
 // cache is switched off, does not fit the budget or the device (the caller then lets every product build its own rotations).  widths: the distinct
 // block-column widths of the batches, for the active-baby tables (matmult.go:1326-1336).  *out is the context's scratch entry "assoc.rotf" (kept for the next call).
@@ -116,13 +94,25 @@ int assoc_product(sfg_ctx *ctx, const AssocRot &r, const uint64_t *A_dev, int s,
     return sfg_matmul_resident_dev(ctx, A_dev, s, in_level, max_level, g, flags, out);
 }
 
+// The tail of a batch, shared by the streamed scan and sfg_assoc_pgen: the s rows of the product (tmp: [s][nct] ciphertexts of ctw words) copied to their place
+// in out_dev at out_shift, the padded sums of the batch zeroed, its column sums added (dosageSum[outShift + c], assoc.go:404-405)
+int assoc_batch_tail(sfg_ctx *ctx, const u64 *tmp, const sfg_geno *g, int s, size_t nct, size_t ctw, uint64_t *out_dev, size_t out_ct_capacity, size_t out_shift,
+                     double *sum_host, double *sqsum_host) {
+    const size_t slots = SFG_SLOTS;
+    for (int i = 0; i < s; i++)
+        SFG_HIP(ctx, hipMemcpyAsync(out_dev + ((size_t)i * out_ct_capacity + out_shift) * ctw, tmp + (size_t)i * nct * ctw, nct * ctw * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    if (!sum_host && !sqsum_host) return 0;
+    if (sum_host) std::fill(sum_host + out_shift * slots, sum_host + (out_shift + nct) * slots, 0.0);
+    if (sqsum_host) std::fill(sqsum_host + out_shift * slots, sqsum_host + (out_shift + nct) * slots, 0.0);
+    return sfg_geno_colsums(ctx, g, sum_host ? sum_host + out_shift * slots : nullptr, sqsum_host ? sqsum_host + out_shift * slots : nullptr);
+}
+
 // out_dev: [s][out_ct_capacity][2][max_level][N]; *out_ct = sum over batches of ceil(kept / slots) (the width ConcatCipherMatrix would give).
 // sum_host / sqsum_host: optional [*out_ct * slots] column sums in the reference's padded layout (dosageSum[outShift + c], assoc.go:404-405).
 // One engine for both on-disk formats: a batch is a contiguous byte range of the file (.bed: nsnp * bps bytes; .pgen: the variant records of the batch, preceded by
 // the LD base its first records may need), read ahead by the reader thread, copied as it is, decoded on the copy queue into the batch's int8 matrix.
-// part / nparts (multi-GPU scans, mgpu.hip): this call multiplies the batches k with k % nparts == part - the reference's dispatcher hands batches to
-// assoc_num_blocks_parallel workers the same way (assoc.go:360-408) - and leaves the output ciphertexts and sums of the other batches untouched; `ranges`
-// (optional) receives (first output ciphertext, count) of every batch it multiplied.
+// part / nparts (multi-GPU scans, mgpu.hip): this call multiplies the batches k with k % nparts == part (AssocPlan, assoc_plan.hpp) and leaves the output
+// ciphertexts and sums of the other batches untouched; `ranges` (optional) receives (first output ciphertext, count) of every batch it multiplied.
 enum { FMT_BED = 0, FMT_PGEN = 1 };
 int assoc_stream_part(sfg_ctx *ctx, int fmt, const char *path, size_t num_sample, size_t num_snp, const uint8_t *row_filter, const uint8_t *col_filter,
                       size_t batch_snps, const uint64_t *A_dev, int s, int in_level, int max_level, unsigned flags,
@@ -132,156 +122,131 @@ int assoc_stream_part(sfg_ctx *ctx, int fmt, const char *path, size_t num_sample
     const char *who = fmt == FMT_BED ? "assoc_stream_bed" : "assoc_stream_pgen";
     if (!batch_snps) SFG_FAIL(ctx, "%s: bad dimensions", who);
     if (flags & SFG_TRANSPOSE) SFG_FAIL(ctx, "%s: batches are multiplied as X (samples x SNPs)", who);
-    const size_t N = SFG_N, slots = SFG_SLOTS, L = (size_t)max_level;
+    const size_t N = SFG_N, L = (size_t)max_level;
     const bool direct = (flags & SFG_STREAM_DIRECT) != 0;                                        // bypass the page cache: what a 5 TB scan from NVMe sees
-    int fd = open(path, O_RDONLY);
-    if (fd < 0) SFG_FAIL(ctx, "%s: cannot open %s", who, path);                                  // os.Open panics in the reference (filestream.go:59-61)
+    FdOwner file(open(path, O_RDONLY));                                                          // closed last, after everything that reads from it is gone
+    if (file.fd < 0) SFG_FAIL(ctx, "%s: cannot open %s", who, path);                             // os.Open panics in the reference (filestream.go:59-61)
     flags &= ~SFG_STREAM_DIRECT;
     struct stat stt; uint8_t head[12] = {0};
-    if (fstat(fd, &stt) || pread(fd, head, 12, 0) < 3) { close(fd); SFG_FAIL(ctx, "%s: cannot read %s", who, path); }
+    if (fstat(file.fd, &stt) || pread(file.fd, head, 12, 0) < 3) SFG_FAIL(ctx, "%s: cannot read %s", who, path);
     PgenIndex ix; std::vector<PgenWindow> win;
     size_t bps = 0, pitch = 0;
     if (fmt == FMT_BED) {
-        if (!num_sample || !num_snp) { close(fd); SFG_FAIL(ctx, "%s: bad dimensions", who); }
+        if (!num_sample || !num_snp) SFG_FAIL(ctx, "%s: bad dimensions", who);
         bps = (num_sample + 3) / 4; pitch = bps;
-        if ((size_t)stt.st_size != 3 + num_snp * bps) { close(fd); SFG_FAIL(ctx, "%s: file holds %zu bytes, expected 3 + %zu x %zu", who, (size_t)stt.st_size, num_snp, bps); }
-        if (head[0] != 0x6C || head[1] != 0x1B || head[2] != 0x01) { close(fd); SFG_FAIL(ctx, "%s: not a SNP-major PLINK .bed", who); }
+        if ((size_t)stt.st_size != 3 + num_snp * bps) SFG_FAIL(ctx, "%s: file holds %zu bytes, expected 3 + %zu x %zu", who, (size_t)stt.st_size, num_snp, bps);
+        if (head[0] != 0x6C || head[1] != 0x1B || head[2] != 0x01) SFG_FAIL(ctx, "%s: not a SNP-major PLINK .bed", who);
     } else {
         const size_t hb = (size_t)stt.st_size >= 12 ? pgen_header_bytes(head) : 0;
-        if (!hb || hb > (size_t)stt.st_size) { close(fd); SFG_FAIL(ctx, "%s: %s is not a PLINK 2 .pgen in a supported storage mode", who, path); }
+        if (!hb || hb > (size_t)stt.st_size) SFG_FAIL(ctx, "%s: %s is not a PLINK 2 .pgen in a supported storage mode", who, path);
         std::vector<uint8_t> hdr(hb);
-        if (pread(fd, hdr.data(), hb, 0) != (ssize_t)hb) { close(fd); SFG_FAIL(ctx, "%s: cannot read the header of %s", who, path); }
-        if (pgen_index(ctx, hdr.data(), hb, (size_t)stt.st_size, ix)) { close(fd); return 1; }
+        if (pread(file.fd, hdr.data(), hb, 0) != (ssize_t)hb) SFG_FAIL(ctx, "%s: cannot read the header of %s", who, path);
+        SFG_TRY(pgen_index(ctx, hdr.data(), hb, (size_t)stt.st_size, ix));
         num_sample = ix.ns; num_snp = ix.nv; pitch = pgen_pitch(ix);
     }
     if (direct) {                                      // the header was read through the page cache; the batches go around it
-        close(fd);
-        fd = open(path, O_RDONLY | O_DIRECT);
-        if (fd < 0) SFG_FAIL(ctx, "%s: the file system of %s does not support O_DIRECT", who, path);
+        file.reset(open(path, O_RDONLY | O_DIRECT));
+        if (file.fd < 0) SFG_FAIL(ctx, "%s: the file system of %s does not support O_DIRECT", who, path);
     }
-    std::vector<Batch> bt_all = make_batches(col_filter, num_snp, batch_snps), bt;
-    std::vector<size_t> shift_of;                       // first output ciphertext of each of THIS part's batches (positions count every batch of the file)
-    if (nparts < 1 || part < 0 || part >= nparts) { close(fd); SFG_FAIL(ctx, "%s: bad part", who); }
-    {
-        size_t sh = 0;
-        for (size_t k = 0; k < bt_all.size(); k++) {
-            if ((int)(k % (size_t)nparts) == part) { bt.push_back(bt_all[k]); shift_of.push_back(sh); }
-            sh += (bt_all[k].kept + SFG_SLOTS - 1) / SFG_SLOTS;
-        }
-        if (out_ct) *out_ct = sh;
-        if (sh > out_ct_capacity) { close(fd); SFG_FAIL(ctx, "%s: output needs %zu ciphertexts per row, capacity %zu", who, sh, out_ct_capacity); }
-    }
+    if (nparts < 1 || part < 0 || part >= nparts) SFG_FAIL(ctx, "%s: bad part", who);
+    const AssocPlan plan = assoc_plan(col_filter, num_snp, batch_snps, part, nparts);
+    const std::vector<AssocBatch> &bt = plan.bt;
+    if (out_ct) *out_ct = plan.total_ct;
+    if (plan.total_ct > out_ct_capacity) SFG_FAIL(ctx, "%s: output needs %zu ciphertexts per row, capacity %zu", who, plan.total_ct, out_ct_capacity);
     if (ranges) ranges->clear();
-    size_t max_bytes = 0, max_rows = 0, max_nsnp = 0, max_kept = 0;
+    std::vector<Span> span(bt.size()); size_t max_bytes = 0, max_rows = 0;
     if (fmt == FMT_PGEN) win.resize(bt.size());
     for (size_t k = 0; k < bt.size(); k++) {
-        Batch &b = bt[k];
-        if (fmt == FMT_BED) { b.off = 3 + (off_t)(b.snp0 * bps); b.bytes = b.nsnp * bps; max_rows = std::max(max_rows, b.nsnp); }
+        const AssocBatch &b = bt[k];
+        if (fmt == FMT_BED) { span[k] = {3 + (off_t)(b.snp0 * bps), b.nsnp * bps}; max_rows = std::max(max_rows, b.nsnp); }
         else {
-            if (pgen_window(ctx, ix, (size_t)stt.st_size, b.snp0, b.snp0 + b.nsnp, win[k])) { close(fd); return 1; }
-            b.off = (off_t)win[k].f0; b.bytes = (size_t)(win[k].f1 - win[k].f0); max_rows = std::max(max_rows, win[k].nr);
+            SFG_TRY(pgen_window(ctx, ix, (size_t)stt.st_size, b.snp0, b.snp0 + b.nsnp, win[k]));
+            span[k] = {(off_t)win[k].f0, (size_t)(win[k].f1 - win[k].f0)}; max_rows = std::max(max_rows, win[k].nr);
         }
-        max_bytes = std::max(max_bytes, b.bytes); max_nsnp = std::max(max_nsnp, b.nsnp); max_kept = std::max(max_kept, b.kept);
+        max_bytes = std::max(max_bytes, span[k].bytes);
     }
-    if (bt.empty()) { close(fd); return 0; }
+    if (bt.empty()) return 0;
     // row map once; column maps per batch
-    std::vector<int32_t> rmap_h(num_sample); size_t nr = 0;
-    for (size_t i = 0; i < num_sample; i++) rmap_h[i] = (!row_filter || row_filter[i]) ? (int32_t)nr++ : -1;
-    if (!nr) { close(fd); SFG_FAIL(ctx, "%s: the row filter keeps nothing", who); }
-    int rc = 0;
-    int32_t *rmap = nullptr, *cmap[2] = {nullptr, nullptr}; uint8_t *hb[2] = {nullptr, nullptr}, *db[2] = {nullptr, nullptr}, *rows[2] = {nullptr, nullptr}, *desc[2] = {nullptr, nullptr};
-    int8_t *gb[2] = {nullptr, nullptr}; int *herr = nullptr;
-    AssocRot rot;
-    u64 *tmp = nullptr; hipStream_t copy = nullptr; hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_ready[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
-    const size_t ctw = 2 * L * N, max_ct = (max_kept + slots - 1) / slots;
-    // every buffer of the call is scratch of the context (device pool / pinned host pool): the next call of the scan - gWY makes four per block - finds them in place
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(ctx->stream); if (copy) (void)hipStreamSynchronize(copy);
-        for (int i = 0; i < 2; i++) { if (ev_h2d[i]) (void)hipEventDestroy(ev_h2d[i]); if (ev_ready[i]) (void)hipEventDestroy(ev_ready[i]); if (ev_free[i]) (void)hipEventDestroy(ev_free[i]); }
-        assoc_free_rot(rot); if (copy) (void)hipStreamDestroy(copy); close(fd);
-    };
-#define ST_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) { char _b[256]; snprintf(_b, sizeof _b, "%s: %s failed: %s", who, #call, hipGetErrorString(_e)); ctx->err = _b; rc = 1; } } while (0)
-    const auto t_call = std::chrono::steady_clock::now();
-    rc = sfg_scratch(ctx, "assoc.rmap", num_sample * sizeof(int32_t), (void **)&rmap);
-    if (!rc) ST_HIP(hipMemcpy(rmap, rmap_h.data(), num_sample * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (!rc) rc = sfg_scratch(ctx, "assoc.tmp", (size_t)s * max_ct * ctw * 8, (void **)&tmp);
-    if (!rc) ST_HIP(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
-    if (!rc && fmt == FMT_PGEN) rc = sfg_host_scratch(ctx, "assoc.herr", 2 * sizeof(int), (void **)&herr);
-    for (int i = 0; i < 2 && !rc; i++) {
-        const std::string sx = std::to_string(i);
-        rc = sfg_host_scratch(ctx, ("assoc.hb" + sx).c_str(), max_bytes + 8192, (void **)&hb[i]);       // + the alignment slack of O_DIRECT ranges
-        if (!rc) rc = sfg_scratch(ctx, ("assoc.db" + sx).c_str(), max_bytes + 16, (void **)&db[i]);
-        if (!rc) rc = sfg_scratch(ctx, ("assoc.gb" + sx).c_str(), nr * max_kept, (void **)&gb[i]);
-        if (!rc) rc = sfg_scratch(ctx, ("assoc.cmap" + sx).c_str(), max_nsnp * sizeof(int32_t), (void **)&cmap[i]);
-        if (!rc && fmt == FMT_PGEN) { rc = sfg_scratch(ctx, ("assoc.rows" + sx).c_str(), max_rows * pitch, (void **)&rows[i]); if (!rc) rc = sfg_scratch(ctx, ("assoc.desc" + sx).c_str(), pgen_desc_bytes(max_rows), (void **)&desc[i]); }
-        if (!rc) ST_HIP(hipEventCreateWithFlags(&ev_h2d[i], hipEventDisableTiming));
-        if (!rc) ST_HIP(hipEventCreateWithFlags(&ev_ready[i], hipEventDisableTiming));
-        if (!rc) ST_HIP(hipEventCreateWithFlags(&ev_free[i], hipEventDisableTiming));
-    }
-    if (rc) { cleanup(); return rc; }
+    std::vector<int32_t> rmap_h(num_sample), cmap_h(plan.max_nsnp);
+    const size_t nr = filter_map(row_filter, num_sample, rmap_h.data());
+    if (!nr) SFG_FAIL(ctx, "%s: the row filter keeps nothing", who);
+    const size_t ctw = 2 * L * N, max_ct = assoc_cts(plan.max_kept);
     const bool trace = ctx->cfg.assoc_trace;       // (A/B build, SFG_ASSOC_TRACE: wall times of the cache build and of every batch's product, each synchronised)
-    if (trace) fprintf(stderr, "[assoc] buffers: %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
-    // the reader fills the first two slots while the rotation cache is built
-    Reader rd; rd.fd = fd; rd.bt = &bt; rd.slot[0] = hb[0]; rd.slot[1] = hb[1]; rd.direct = direct;
-    std::thread reader([&rd] { rd.run(); });
-    // ---- the baby-step rotation cache of `mat`, once for all batches of the call
-    {
-        std::vector<size_t> widths;
-        for (const Batch &b : bt) for (size_t c0 = 0; c0 < b.kept; c0 += slots) { const size_t w = std::min(slots, b.kept - c0); if (std::find(widths.begin(), widths.end(), w) == widths.end()) widths.push_back(w); }
-        const auto t0 = std::chrono::steady_clock::now();
-        rc = assoc_build_rot(ctx, (const u64 *)A_dev, s, in_level, max_level, nr, widths, rot);
-        if (rc) { rd.release(bt.size() + 2); reader.join(); cleanup(); return rc; }
-        if (trace) { (void)hipStreamSynchronize(ctx->stream); fprintf(stderr, "[assoc] rotation cache (%s): %.1f ms\n", rot.pre.G ? "int8 tiles" : rot.f64 ? "fp64 rows" : "none",
-                                                                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); }
-    }
-    std::vector<int32_t> cmap_h(max_nsnp);
-    for (size_t k = 0; k < bt.size() && !rc; k++) {
-        const Batch &b = bt[k]; const int sl = (int)(k & 1);
-        const size_t out_shift = shift_of[k];
-        if (!rd.wait_filled(k)) { ctx->err = std::string(who) + ": " + rd.err; rc = 1; break; }
-        size_t kc = 0;
-        for (size_t j = 0; j < b.nsnp; j++) cmap_h[j] = (!col_filter || col_filter[b.snp0 + j]) ? (int32_t)kc++ : -1;
-        // copy queue: file bytes and column map of batch k into slot sl (free once the product of batch k - 2 has run), decode into gb[sl]
-        if (k >= 2) ST_HIP(hipStreamWaitEvent(copy, ev_free[sl], 0));
-        if (!rc) ST_HIP(hipMemcpyAsync(db[sl], hb[sl] + rd.lead[sl], b.bytes, hipMemcpyHostToDevice, copy));
-        if (!rc) ST_HIP(hipMemcpyAsync(cmap[sl], cmap_h.data(), b.nsnp * sizeof(int32_t), hipMemcpyHostToDevice, copy));
-        if (!rc && fmt == FMT_PGEN) rc = pgen_upload_desc(ctx, copy, ix, win[k], desc[sl]);
-        if (!rc) ST_HIP(hipEventRecord(ev_h2d[sl], copy));
-        if (!rc && fmt == FMT_BED) rc = launch_bed_decode(ctx, copy, db[sl], bps, num_sample, b.nsnp, rmap, cmap[sl], gb[sl], b.kept);
-        if (!rc && fmt == FMT_PGEN) {
-            const int *err_dev = nullptr;
-            rc = launch_pgen_decode(ctx, copy, db[sl], desc[sl], win[k].nr, ix.ns, pitch, rows[sl], &err_dev);
-            if (!rc) rc = launch_bed_decode_lut(ctx, copy, rows[sl] + win[k].lead * pitch, pitch, num_sample, b.nsnp, rmap, cmap[sl], gb[sl], b.kept, 0xFF020100u);
-            if (!rc) ST_HIP(hipMemcpyAsync(&herr[sl], err_dev, sizeof(int), hipMemcpyDeviceToHost, copy));
+    const auto t_call = std::chrono::steady_clock::now(); auto t_end = t_call;
+    // The owners of the body are declared so that leaving it, on every path, gives this order: reader released and joined, compute queue synchronised, copy queue
+    // synchronised, events destroyed, assoc_free_rot, copy queue destroyed - and, after the body, `file` closed.
+    const int rc = [&]() -> int {
+        StreamOwner copy; AssocRotScope rot; EventOwner ev_h2d[2], ev_ready[2], ev_free[2];
+        QueuesIdle idle{ctx, copy};
+        // every buffer of the call is scratch of the context (device pool / pinned host pool): the next call of the scan - gWY makes four per block - finds them in place
+        int32_t *rmap = nullptr, *cmap[2]; uint8_t *hb[2], *db[2], *rows[2] = {nullptr, nullptr}, *desc[2] = {nullptr, nullptr}; int8_t *gb[2]; int *herr = nullptr; u64 *tmp = nullptr;
+        SFG_TRY(sfg_scratch(ctx, "assoc.rmap", num_sample * sizeof(int32_t), (void **)&rmap));
+        SFG_HIP(ctx, hipMemcpy(rmap, rmap_h.data(), num_sample * sizeof(int32_t), hipMemcpyHostToDevice));
+        SFG_TRY(sfg_scratch(ctx, "assoc.tmp", (size_t)s * max_ct * ctw * 8, (void **)&tmp));
+        SFG_HIP(ctx, hipStreamCreateWithFlags(&copy.h, hipStreamNonBlocking));
+        if (fmt == FMT_PGEN) SFG_TRY(sfg_host_scratch(ctx, "assoc.herr", 2 * sizeof(int), (void **)&herr));
+        for (int i = 0; i < 2; i++) {
+            const std::string sx = std::to_string(i);
+            SFG_TRY(sfg_host_scratch(ctx, ("assoc.hb" + sx).c_str(), max_bytes + 8192, (void **)&hb[i]));       // + the alignment slack of O_DIRECT ranges
+            SFG_TRY(sfg_scratch(ctx, ("assoc.db" + sx).c_str(), max_bytes + 16, (void **)&db[i]));
+            SFG_TRY(sfg_scratch(ctx, ("assoc.gb" + sx).c_str(), nr * plan.max_kept, (void **)&gb[i]));
+            SFG_TRY(sfg_scratch(ctx, ("assoc.cmap" + sx).c_str(), plan.max_nsnp * sizeof(int32_t), (void **)&cmap[i]));
+            if (fmt == FMT_PGEN) {
+                SFG_TRY(sfg_scratch(ctx, ("assoc.rows" + sx).c_str(), max_rows * pitch, (void **)&rows[i]));
+                SFG_TRY(sfg_scratch(ctx, ("assoc.desc" + sx).c_str(), PgenDesc(max_rows).bytes, (void **)&desc[i]));
+            }
+            SFG_HIP(ctx, hipEventCreateWithFlags(&ev_h2d[i].h, hipEventDisableTiming));
+            SFG_HIP(ctx, hipEventCreateWithFlags(&ev_ready[i].h, hipEventDisableTiming));
+            SFG_HIP(ctx, hipEventCreateWithFlags(&ev_free[i].h, hipEventDisableTiming));
         }
-        if (!rc) ST_HIP(hipEventRecord(ev_ready[sl], copy));
-        if (!rc) ST_HIP(hipEventSynchronize(fmt == FMT_PGEN ? ev_ready[sl] : ev_h2d[sl]));   // the pinned slot (and cmap_h, the descriptors) may be refilled; the previous product is still running
-        rd.release(k);
-        if (!rc && fmt == FMT_PGEN) rc = pgen_decode_error(ctx, herr[sl]);
-        if (rc) break;
-        // compute queue: the product of batch k (MatMult4Stream(cps, mat, X, maxLevel, false, square, nproc), assoc.go:395), rows copied into place
-        ST_HIP(hipStreamWaitEvent(ctx->stream, ev_ready[sl], 0));
-        sfg_geno g; g.dev = gb[sl]; g.nrow = nr; g.ncol = b.kept; g.ld = b.kept; g.owned = false;
-        const size_t nct = (b.kept + slots - 1) / slots;
-        const auto tb = std::chrono::steady_clock::now();
-        if (!rc) rc = assoc_product(ctx, rot, A_dev, s, in_level, max_level, &g, flags, (int)nct, (uint64_t *)tmp);
-        if (trace) { const double t_enq = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count(); (void)hipStreamSynchronize(ctx->stream);
-                     fprintf(stderr, "[assoc] batch %zu: enqueued in %.1f ms, done after %.1f ms\n", k, t_enq, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count()); }
-        for (int i = 0; i < s && !rc; i++)
-            ST_HIP(hipMemcpyAsync(out_dev + ((size_t)i * out_ct_capacity + out_shift) * ctw, tmp + (size_t)i * nct * ctw, nct * ctw * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        if (!rc && (sum_host || sqsum_host)) {
-            if (sum_host) std::fill(sum_host + out_shift * slots, sum_host + (out_shift + nct) * slots, 0.0);
-            if (sqsum_host) std::fill(sqsum_host + out_shift * slots, sqsum_host + (out_shift + nct) * slots, 0.0);
-            rc = sfg_geno_colsums(ctx, &g, sum_host ? sum_host + out_shift * slots : nullptr, sqsum_host ? sqsum_host + out_shift * slots : nullptr);
+        if (trace) fprintf(stderr, "[assoc] buffers: %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
+        // the reader fills the first two slots while the rotation cache is built
+        Reader rd; rd.fd = file.fd; rd.bt = &span; rd.slot[0] = hb[0]; rd.slot[1] = hb[1]; rd.direct = direct;
+        std::thread reader([&rd] { rd.run(); });
+        ReaderEnd reader_end{rd, reader};
+        // ---- the baby-step rotation cache of `mat`, once for all batches of the call
+        {
+            const auto t0 = std::chrono::steady_clock::now();
+            SFG_TRY(assoc_build_rot(ctx, (const u64 *)A_dev, s, in_level, max_level, nr, plan.widths, rot.r));
+            if (trace) { (void)hipStreamSynchronize(ctx->stream); fprintf(stderr, "[assoc] rotation cache (%s): %.1f ms\n", rot.r.pre.G ? "int8 tiles" : rot.r.f64 ? "fp64 rows" : "none",
+                                                                           std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); }
         }
-        if (!rc) ST_HIP(hipEventRecord(ev_free[sl], ctx->stream));
-        if (ranges) ranges->push_back({out_shift, nct});
-    }
-#undef ST_HIP
-    if (rc) rd.release(bt.size() + 2);                             // let the reader run out
-    reader.join();
-    const auto t_end = std::chrono::steady_clock::now();
-    cleanup();
+        for (size_t k = 0; k < bt.size(); k++) {
+            const AssocBatch &b = bt[k]; const int sl = (int)(k & 1);
+            const size_t out_shift = plan.shift_of[k], nct = assoc_cts(b.kept);
+            if (!rd.wait_filled(k)) { ctx->err = std::string(who) + ": " + rd.err; return 1; }
+            filter_map(col_filter ? col_filter + b.snp0 : nullptr, b.nsnp, cmap_h.data());
+            // copy queue: file bytes and column map of batch k into slot sl (free once the product of batch k - 2 has run), decode into gb[sl]
+            if (k >= 2) SFG_HIP(ctx, hipStreamWaitEvent(copy.h, ev_free[sl].h, 0));
+            SFG_HIP(ctx, hipMemcpyAsync(db[sl], hb[sl] + rd.lead[sl], span[k].bytes, hipMemcpyHostToDevice, copy.h));
+            SFG_HIP(ctx, hipMemcpyAsync(cmap[sl], cmap_h.data(), b.nsnp * sizeof(int32_t), hipMemcpyHostToDevice, copy.h));
+            if (fmt == FMT_PGEN) SFG_TRY(pgen_upload_desc(ctx, copy.h, ix, win[k], desc[sl]));
+            SFG_HIP(ctx, hipEventRecord(ev_h2d[sl].h, copy.h));
+            if (fmt == FMT_BED) SFG_TRY(launch_bed_decode(ctx, copy.h, db[sl], bps, num_sample, b.nsnp, rmap, cmap[sl], gb[sl], b.kept));
+            else {
+                const int *err_dev = nullptr;
+                SFG_TRY(launch_pgen_decode(ctx, copy.h, db[sl], desc[sl], win[k].nr, ix.ns, pitch, rows[sl], &err_dev));
+                SFG_TRY(launch_bed_decode_lut(ctx, copy.h, rows[sl] + win[k].lead * pitch, pitch, num_sample, b.nsnp, rmap, cmap[sl], gb[sl], b.kept, 0xFF020100u));
+                SFG_HIP(ctx, hipMemcpyAsync(&herr[sl], err_dev, sizeof(int), hipMemcpyDeviceToHost, copy.h));
+            }
+            SFG_HIP(ctx, hipEventRecord(ev_ready[sl].h, copy.h));
+            SFG_HIP(ctx, hipEventSynchronize(fmt == FMT_PGEN ? ev_ready[sl].h : ev_h2d[sl].h));   // the pinned slot (and cmap_h, the descriptors) may be refilled; the previous product is still running
+            rd.release(k);
+            if (fmt == FMT_PGEN) SFG_TRY(pgen_decode_error(ctx, herr[sl]));
+            // compute queue: the product of batch k (MatMult4Stream(cps, mat, X, maxLevel, false, square, nproc), assoc.go:395), rows copied into place
+            SFG_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev_ready[sl].h, 0));
+            sfg_geno g; g.dev = gb[sl]; g.nrow = nr; g.ncol = b.kept; g.ld = b.kept; g.owned = false;
+            const auto tb = std::chrono::steady_clock::now();
+            SFG_TRY(assoc_product(ctx, rot.r, A_dev, s, in_level, max_level, &g, flags, (int)nct, (uint64_t *)tmp));
+            if (trace) { const double t_enq = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count(); (void)hipStreamSynchronize(ctx->stream);
+                         fprintf(stderr, "[assoc] batch %zu: enqueued in %.1f ms, done after %.1f ms\n", k, t_enq, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count()); }
+            SFG_TRY(assoc_batch_tail(ctx, tmp, &g, s, nct, ctw, out_dev, out_ct_capacity, out_shift, sum_host, sqsum_host));
+            SFG_HIP(ctx, hipEventRecord(ev_free[sl].h, ctx->stream));
+            if (ranges) ranges->push_back({out_shift, nct});
+        }
+        t_end = std::chrono::steady_clock::now();
+        return 0;
+    }();
     if (trace) fprintf(stderr, "[assoc] call: %.1f ms until the last batch is enqueued, %.1f ms with the queues drained\n", std::chrono::duration<double, std::milli>(t_end - t_call).count(),
                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
     return rc;

@@ -86,6 +86,53 @@ def test_stream_bed_batches_match_oracle(tmp_path, square):
     dA.free(); dout.free(); ctx.close()
 
 
+def test_stream_bed_refused_calls_leave_no_descriptor_and_no_change(tmp_path):
+    """Four calls the scan refuses before any launch (a missing file, a wrong sample count, an output one ciphertext short, a row filter that keeps nothing), on
+    the context and file of test_stream_bed_batches_match_oracle: every one closes the file it opened, and the good call repeated afterwards gives the words
+    and sums it gave before."""
+    import os
+    from sfgwas_amd import capi
+    ns, nv, batch, s, level, maxl = 130, 260, 100, 2, 5, 5
+    rnd = np.random.default_rng(17)
+    geno = rnd.choice(np.array([2, -1, 1, 0], dtype=np.int8), size=(ns, nv), p=[0.2, 0.05, 0.35, 0.4])
+    rowf = (rnd.random(ns) < 0.9).astype(np.uint8); colf = (rnd.random(nv) < 0.85).astype(np.uint8)
+    path = str(tmp_path / "chr1.bed")
+    write_bed(path, geno)
+    ctx = capi.Context(ol.Q_PN14, ol.P_PN14)
+    ring = ol.Ring(14, ol.Q_PN14, ol.P_PN14)
+    slots, d = ring.slots, 91
+    shifts = set(range(int(rowf.sum()))) | set(range(slots - batch + 1, slots))
+    for k in sorted({sh % d for sh in shifts if sh % d} | {(sh // d) * d for sh in shifts if sh // d}):
+        ctx.load_rotkey(ring.galois(k), capi.random_rotkey(ring.moduli, ring.beta, ring.N, 900 + k))
+    A = np.stack([np.stack([ring.fill_uniform(level, 40 + i)]) for i in range(s)])
+    nct_total = sum((int(colf[a:b].sum()) - 1) // slots + 1 for a, b in batches(colf, batch))
+    cap = nct_total + 1
+    dA = capi.DevArray.from_host(ctx, A)
+    dout = capi.DevArray(ctx, (s, cap, 2, maxl, ring.N))
+    got_ct = C.c_size_t()
+
+    def scan(path_=path, ns_=ns, rowf_=rowf, cap_=cap):
+        sums = np.full(cap * slots, -7.0); sq = np.full(cap * slots, -7.0)
+        ctx.check(capi.lib().sfg_assoc_stream_bed(ctx.h, path_.encode(), ns_, nv, rowf_.ctypes.data_as(C.c_void_p), colf.ctypes.data_as(C.c_void_p), batch,
+                                                  dA.p, s, level, maxl, 0, dout.p, cap_, C.byref(got_ct), sums.ctypes.data_as(C.c_void_p),
+                                                  sq.ctypes.data_as(C.c_void_p)), "assoc_stream_bed")
+        return dout.host(), sums, sq
+
+    before = scan()
+    assert got_ct.value == nct_total
+    nfd = len(os.listdir("/proc/self/fd"))
+    for match, kw in [("cannot open", dict(path_=str(tmp_path / "missing.bed"))), ("expected 3 \\+", dict(ns_=ns + 4, rowf_=np.ones(ns + 4, np.uint8))),
+                      ("output needs", dict(cap_=nct_total - 1)), ("keeps nothing", dict(rowf_=np.zeros(ns, np.uint8)))]:
+        with pytest.raises(capi.SfgError, match=match):
+            scan(**kw)
+    after = scan()
+    assert got_ct.value == nct_total
+    for x, y in zip(before, after):
+        assert np.array_equal(x, y)
+    assert len(os.listdir("/proc/self/fd")) == nfd
+    dA.free(); dout.free(); ctx.close()
+
+
 @pytest.mark.parametrize("s,level,maxl,form", [(16, 5, 5, "assoc.rotf"), (3, 5, 3, "assoc.rot8"), (15, 4, 4, "assoc.rot8")])
 def test_stream_bed_cache_forms_at_their_limits(tmp_path, s, level, maxl, form):
     """The call-wide rotation cache is kept as int8 rot tiles while the 2 s ciphertext rows of a k-slice fit the MAC's two row tiles in one launch (s <= 15) and as fp64 operand
