@@ -20,6 +20,7 @@
 // tested on a one-GPU box; host-side rendezvous, no overlap).  Integer sums: both give identical words.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mg_plan.hpp"         // the engine's host arithmetic: shards, the plan of a rank's Q'X^T, host-form offsets, re-shard segments
 #include "rendezvous.hpp"      // the host-side meeting point of the rank threads (agreement point, direct transport)
 #include "reshard.hpp"         // a rank's share of the re-sharding filter
 #include <rccl/rccl.h>          // types and prototypes only; the functions are resolved at run time (Rccl below)
@@ -137,9 +138,9 @@ struct MgApiScope {
 
 extern "C" int sfg_mgpu_shard(int world, size_t ncol, int rank, size_t *blk0, size_t *blk1, size_t *col0, size_t *col1) {
     if (world < 1 || rank < 0 || rank >= world || !ncol) return 1;
-    const size_t nblk = (ncol + SFG_SLOTS - 1) / SFG_SLOTS, b0 = nblk * (size_t)rank / (size_t)world, b1 = nblk * ((size_t)rank + 1) / (size_t)world;
-    if (blk0) *blk0 = b0; if (blk1) *blk1 = b1;
-    if (col0) *col0 = b0 * SFG_SLOTS; if (col1) *col1 = std::min(b1 * (size_t)SFG_SLOTS, ncol);
+    const MgShard sh = mg_shard(world, ncol, rank);
+    if (blk0) *blk0 = sh.blk0; if (blk1) *blk1 = sh.blk1;
+    if (col0) *col0 = sh.col0; if (col1) *col1 = sh.col1;
     return 0;
 }
 
@@ -251,26 +252,24 @@ static int mgpu_create_common(sfg_mgpu **out, const int *devices, int n, int ran
     *out = mg;
     return 0;
 }
-extern "C" int sfg_mgpu_create(sfg_mgpu **out, const int *devices, int n, int logN, int nq, int np, const uint64_t *moduli, const uint64_t *psi, double scale) {
-    if (!devices) { g_mgpu_create_error = "sfg_mgpu_create: null device list"; *out = nullptr; return 1; }
-    return mgpu_create_common(out, devices, n, 0, n, nullptr, logN, nq, np, moduli, psi, scale, nullptr);
-}
 extern "C" int sfg_mgpu_create_ex(sfg_mgpu **out, const int *devices, int n, int logN, int nq, int np, const uint64_t *moduli, const uint64_t *psi, double scale,
                                   const sfg_config *config) {
     if (!out) { g_mgpu_create_error = "sfg_mgpu_create: null result pointer"; return 1; }
     if (!devices) { g_mgpu_create_error = "sfg_mgpu_create: null device list"; *out = nullptr; return 1; }
     return mgpu_create_common(out, devices, n, 0, n, nullptr, logN, nq, np, moduli, psi, scale, config);
 }
-extern "C" int sfg_mgpu_create_rank(sfg_mgpu **out, int device, int rank, int world, const uint8_t *id128, int logN, int nq, int np, const uint64_t *moduli,
-                                    const uint64_t *psi, double scale) {
-    if (!id128 || rank < 0 || rank >= world) { g_mgpu_create_error = "sfg_mgpu_create_rank: bad rank / missing id"; *out = nullptr; return 1; }
-    return mgpu_create_common(out, &device, 1, rank, world, id128, logN, nq, np, moduli, psi, scale, nullptr);
+extern "C" int sfg_mgpu_create(sfg_mgpu **out, const int *devices, int n, int logN, int nq, int np, const uint64_t *moduli, const uint64_t *psi, double scale) {
+    return sfg_mgpu_create_ex(out, devices, n, logN, nq, np, moduli, psi, scale, nullptr);
 }
 extern "C" int sfg_mgpu_create_rank_ex(sfg_mgpu **out, int device, int rank, int world, const uint8_t *id128, int logN, int nq, int np, const uint64_t *moduli,
                                        const uint64_t *psi, double scale, const sfg_config *config) {
     if (!out) { g_mgpu_create_error = "sfg_mgpu_create_rank: null result pointer"; return 1; }
     if (!id128 || rank < 0 || rank >= world) { g_mgpu_create_error = "sfg_mgpu_create_rank: bad rank / missing id"; *out = nullptr; return 1; }
     return mgpu_create_common(out, &device, 1, rank, world, id128, logN, nq, np, moduli, psi, scale, config);
+}
+extern "C" int sfg_mgpu_create_rank(sfg_mgpu **out, int device, int rank, int world, const uint8_t *id128, int logN, int nq, int np, const uint64_t *moduli,
+                                    const uint64_t *psi, double scale) {
+    return sfg_mgpu_create_rank_ex(out, device, rank, world, id128, logN, nq, np, moduli, psi, scale, nullptr);
 }
 extern "C" const char *sfg_mgpu_last_error(const sfg_mgpu *mg) { return mg ? mg->err.c_str() : g_mgpu_create_error.c_str(); }
 extern "C" int sfg_mgpu_world(const sfg_mgpu *mg) { return mg ? mg->world : 0; }
@@ -343,19 +342,40 @@ extern "C" void sfg_mgpu_geno_free(sfg_mgpu *mg, sfg_mgeno *g) {
     }
     delete g;
 }
+// a new sharded matrix: one pass in which every local rank takes its window and, where it is not empty, fills it with fn(g, R, i, col0, col1); nothing is left behind on failure
+template <class F> static int mgeno_build(sfg_mgpu *mg, size_t nrow, size_t ncol, sfg_mgeno **out, F &&fn) {
+    sfg_mgeno *g = mgeno_new(mg, nrow, ncol);
+    const int rc = run_ranks(mg, [&](MgRank &R, int i) {
+        const MgShard sh = mg_shard(mg->world, ncol, R.rank);
+        g->blk0[(size_t)i] = sh.blk0; g->blk1[(size_t)i] = sh.blk1;
+        return sh.col1 > sh.col0 ? fn(g, R, i, sh.col0, sh.col1) : 0;
+    });
+    if (rc) { sfg_mgpu_geno_free(mg, g); return 1; }
+    *out = g; return 0;
+}
+// every local rank that holds a shard runs fn(R, i, shard, c0) on it; c0: the global column of the shard's first stored column
+template <class F> static int run_shards(sfg_mgpu *mg, const sfg_mgeno *g, F &&fn) {
+    return run_ranks(mg, [&](MgRank &R, int i) { const sfg_geno *sh = g->shard[(size_t)i]; return sh ? fn(R, i, sh, g->blk0[(size_t)i] * SFG_SLOTS) : 0; });
+}
+// part[i]: `planes` planes of the width of local rank i's window, laid out at the window's columns of dst [planes][ncol]; columns no rank holds are zero
+template <class T> static void gather_planes(const sfg_mgeno *g, const std::vector<std::vector<T>> &part, size_t planes, T *dst) {
+    if (!dst) return;
+    std::fill(dst, dst + planes * g->ncol, T(0));
+    for (size_t i = 0; i < g->shard.size(); i++) {
+        if (!g->shard[i]) continue;
+        const size_t c0 = g->blk0[i] * SFG_SLOTS, w = g->shard[i]->ncol;
+        for (size_t k = 0; k < planes; k++) std::copy(part[i].begin() + (ptrdiff_t)(k * w), part[i].begin() + (ptrdiff_t)((k + 1) * w), dst + k * g->ncol + c0);
+    }
+}
 // geno_host: the party's WHOLE matrix, row-major int8 with row stride ld (what GenoFileStream delivers); every local rank uploads its own column window
 extern "C" int sfg_mgpu_geno_upload(sfg_mgpu *mg, const int8_t *geno_host, size_t nrow, size_t ncol, size_t ld, sfg_mgeno **out) {
     MG_NEED(mg, mg != nullptr && out != nullptr, "null engine / result pointer");
     *out = nullptr;
     if (!geno_host || !nrow || !ncol || ld < ncol) MG_FAIL(mg, "sfg_mgpu_geno_upload: bad dimensions");
-    sfg_mgeno *g = mgeno_new(mg, nrow, ncol);
-    const int rc = run_ranks(mg, [&](MgRank &R, int i) {
-        size_t c0, c1; (void)sfg_mgpu_shard(mg->world, ncol, R.rank, &g->blk0[(size_t)i], &g->blk1[(size_t)i], &c0, &c1);
-        if (c1 > c0) R_CTX(R, sfg_geno_upload(R.ctx, geno_host + c0, nrow, c1 - c0, ld, &g->shard[(size_t)i]));
+    return mgeno_build(mg, nrow, ncol, out, [&](sfg_mgeno *g, MgRank &R, int i, size_t c0, size_t c1) {
+        R_CTX(R, sfg_geno_upload(R.ctx, geno_host + c0, nrow, c1 - c0, ld, &g->shard[(size_t)i]));
         return 0;
     });
-    if (rc) { sfg_mgpu_geno_free(mg, g); return 1; }
-    *out = g; return 0;
 }
 // Row-streamed form (MatMult4StreamPreprocess reads one row at a time: matmult.go:914-1041, filestream.go:414-426): _create makes every rank's window, _write_rows
 // scatters a chunk of whole-matrix rows to the ranks' column windows, _compare_rows compares a chunk of the rows of the matrix (or, with SFG_TRANSPOSE, of its
@@ -364,14 +384,10 @@ extern "C" int sfg_mgpu_geno_create(sfg_mgpu *mg, size_t nrow, size_t ncol, sfg_
     MG_NEED(mg, mg != nullptr && out != nullptr, "null engine / result pointer");
     *out = nullptr;
     if (!nrow || !ncol) MG_FAIL(mg, "sfg_mgpu_geno_create: bad dimensions");
-    sfg_mgeno *g = mgeno_new(mg, nrow, ncol);
-    const int rc = run_ranks(mg, [&](MgRank &R, int i) {
-        size_t c0, c1; (void)sfg_mgpu_shard(mg->world, ncol, R.rank, &g->blk0[(size_t)i], &g->blk1[(size_t)i], &c0, &c1);
-        if (c1 > c0) R_CTX(R, sfg_geno_create(R.ctx, nrow, c1 - c0, &g->shard[(size_t)i]));
+    return mgeno_build(mg, nrow, ncol, out, [&](sfg_mgeno *g, MgRank &R, int i, size_t c0, size_t c1) {
+        R_CTX(R, sfg_geno_create(R.ctx, nrow, c1 - c0, &g->shard[(size_t)i]));
         return 0;
     });
-    if (rc) { sfg_mgpu_geno_free(mg, g); return 1; }
-    *out = g; return 0;
 }
 extern "C" int sfg_mgpu_geno_write_rows(sfg_mgpu *mg, sfg_mgeno *g, size_t row0, size_t nrows, const int8_t *rows_host, size_t ld) {
     MG_NEED(mg, mg != nullptr, "null engine");
@@ -391,10 +407,8 @@ extern "C" int sfg_mgpu_geno_compare_rows(sfg_mgpu *mg, const sfg_mgeno *g, unsi
     if (!nrows) return 0;
     if (!rows_host || ld < ncol_l || row0 > nrow_l || nrows > nrow_l - row0) MG_FAIL(mg, "sfg_mgpu_geno_compare_rows: rows [%zu, %zu) of a %zu x %zu matrix, row stride %zu", row0, row0 + nrows, nrow_l, ncol_l, ld);
     std::vector<uint64_t> bad(mg->r.size(), 0);
-    const int rc = run_ranks(mg, [&](MgRank &R, int i) {
-        const sfg_geno *sh = g->shard[(size_t)i];
-        if (!sh) return 0;
-        const size_t c0 = g->blk0[(size_t)i] * SFG_SLOTS, c1 = c0 + sh->ncol;          // the rank's window of stored columns
+    const int rc = run_shards(mg, g, [&](MgRank &R, int i, const sfg_geno *sh, size_t c0) {
+        const size_t c1 = c0 + sh->ncol;                                               // the rank's window of stored columns
         if (!tr) { R_CTX(R, sfg_geno_compare_rows(R.ctx, sh, 0, row0, nrows, rows_host + c0, ld, &bad[(size_t)i])); return 0; }
         // rows of the transpose are stored COLUMNS: this rank answers for the rows that fall into its window
         const size_t lo = std::max(row0, c0), hi = std::min(row0 + nrows, c1);
@@ -413,7 +427,8 @@ extern "C" int sfg_mgpu_geno_adopt(sfg_mgpu *mg, size_t nrow, size_t ncol, sfg_g
     MG_NEED(mg, shards != nullptr && nrow && ncol, "null shard list / empty matrix");
     sfg_mgeno *g = mgeno_new(mg, nrow, ncol);
     for (size_t i = 0; i < mg->r.size(); i++) {
-        size_t c0, c1; (void)sfg_mgpu_shard(mg->world, ncol, mg->r[i].rank, &g->blk0[i], &g->blk1[i], &c0, &c1);
+        const MgShard sh = mg_shard(mg->world, ncol, mg->r[i].rank);
+        const size_t c0 = sh.col0, c1 = sh.col1; g->blk0[i] = sh.blk0; g->blk1[i] = sh.blk1;
         if ((c1 > c0) != (shards[i] != nullptr) || (shards[i] && (shards[i]->nrow != nrow || shards[i]->ncol != c1 - c0))) {
             delete g; MG_FAIL(mg, "sfg_mgpu_geno_adopt: shard %zu is not the %zu x %zu window [%zu, %zu) of rank %d", i, nrow, c1 - c0, c0, c1, mg->r[i].rank); }
     }
@@ -426,10 +441,7 @@ extern "C" int sfg_mgpu_geno_synthetic(sfg_mgpu *mg, size_t nrow, size_t ncol, u
     MG_NEED(mg, mg != nullptr && out != nullptr, "null engine / result pointer");
     *out = nullptr;
     if (!nrow || !ncol) MG_FAIL(mg, "sfg_mgpu_geno_synthetic: bad dimensions");
-    sfg_mgeno *g = mgeno_new(mg, nrow, ncol);
-    const int rc = run_ranks(mg, [&](MgRank &R, int i) {
-        size_t c0, c1; (void)sfg_mgpu_shard(mg->world, ncol, R.rank, &g->blk0[(size_t)i], &g->blk1[(size_t)i], &c0, &c1);
-        if (c1 <= c0) return 0;
+    return mgeno_build(mg, nrow, ncol, out, [&](sfg_mgeno *g, MgRank &R, int i, size_t c0, size_t c1) {
         const size_t w = c1 - c0; void *buf = nullptr;
         R_CTX(R, sfg_malloc(R.ctx, &buf, nrow * w));
         g->owned[(size_t)i] = buf;
@@ -443,8 +455,6 @@ extern "C" int sfg_mgpu_geno_synthetic(sfg_mgpu *mg, size_t nrow, size_t ncol, u
         }
         return 0;
     });
-    if (rc) { sfg_mgpu_geno_free(mg, g); return 1; }
-    *out = g; return 0;
 }
 extern "C" const sfg_geno *sfg_mgpu_geno_shard(const sfg_mgeno *g, int local) { return g && local >= 0 && (size_t)local < g->shard.size() ? g->shard[(size_t)local] : nullptr; }
 extern "C" int sfg_mgpu_geno_dims(const sfg_mgeno *g, size_t *nrow, size_t *ncol) { if (!g) return 1; if (nrow) *nrow = g->nrow; if (ncol) *ncol = g->ncol; return 0; }
@@ -465,13 +475,10 @@ extern "C" int sfg_mgpu_geno_qc_scan(sfg_mgpu *mg, const sfg_mgeno *g, const uin
     MG_NEED(mg, mg != nullptr, "null engine");
     MG_NEED(mg, g && g->shard.size() == mg->r.size(), "the matrix belongs to another engine");
     if (!col_counts_host && !row_miss_host && !row_het_host) MG_FAIL(mg, "sfg_mgpu_geno_qc_scan: no output requested");
-    const size_t n = mg->r.size(), nrow = g->nrow, ncol = g->ncol;
+    const size_t n = mg->r.size(), nrow = g->nrow;
     const bool want_rows = row_miss_host || row_het_host;
     std::vector<std::vector<uint32_t>> cc(n), rm(n), rh(n);
-    const int rc = run_ranks(mg, [&](MgRank &R, int i) {
-        const sfg_geno *sh = g->shard[(size_t)i];
-        if (!sh) return 0;
-        const size_t c0 = g->blk0[(size_t)i] * SFG_SLOTS;
+    const int rc = run_shards(mg, g, [&](MgRank &R, int i, const sfg_geno *sh, size_t c0) {
         if (col_counts_host) cc[(size_t)i].resize(8 * sh->ncol);
         if (want_rows) { rm[(size_t)i].resize(nrow); rh[(size_t)i].resize(nrow); }
         R_CTX(R, sfg_geno_qc_scan(R.ctx, sh, row_filter, col_filter ? col_filter + c0 : nullptr, row_ctrl, col_counts_host ? cc[(size_t)i].data() : nullptr,
@@ -479,14 +486,11 @@ extern "C" int sfg_mgpu_geno_qc_scan(sfg_mgpu *mg, const sfg_mgeno *g, const uin
         return 0;
     });
     if (rc) return rc;
-    if (col_counts_host) std::fill(col_counts_host, col_counts_host + 8 * ncol, 0u);
+    gather_planes(g, cc, 8, col_counts_host);
     if (row_miss_host) std::fill(row_miss_host, row_miss_host + nrow, 0u);
     if (row_het_host) std::fill(row_het_host, row_het_host + nrow, 0u);
     for (size_t i = 0; i < n; i++) {
-        const sfg_geno *sh = g->shard[i];
-        if (!sh) continue;
-        const size_t c0 = g->blk0[i] * SFG_SLOTS, w = sh->ncol;
-        if (col_counts_host) for (int k = 0; k < 8; k++) std::copy(cc[i].begin() + (size_t)k * w, cc[i].begin() + (size_t)(k + 1) * w, col_counts_host + (size_t)k * ncol + c0);
+        if (!g->shard[i]) continue;
         if (row_miss_host) for (size_t r = 0; r < nrow; r++) row_miss_host[r] += rm[i][r];
         if (row_het_host) for (size_t r = 0; r < nrow; r++) row_het_host[r] += rh[i][r];
     }
@@ -517,32 +521,25 @@ extern "C" int sfg_mgpu_geno_filter(sfg_mgpu *mg, const sfg_mgeno *g, const uint
         if (sh->packed != packed) MG_FAIL(mg, "sfg_mgpu_geno_filter: int8 and packed shards in one matrix");
     }
     // per local rank: its new window [c0, c1) of the kept columns and the old shards that serve it
-    std::vector<size_t> c0(n, 0), c1(n, 0), b0(n, 0), b1(n, 0);
+    std::vector<MgShard> win(n);
+    std::vector<std::pair<size_t, size_t>> old(n, {0, 0});       // the old window of every local rank (empty: it holds no shard)
+    for (size_t j = 0; j < n; j++) if (const sfg_geno *sh = g->shard[j]) old[j] = {g->blk0[j] * SFG_SLOTS, g->blk0[j] * SFG_SLOTS + sh->ncol};
     std::vector<ReshardSegs> segs(n);
+    std::vector<MgSeg> run;
     for (size_t i = 0; i < n; i++) {
-        (void)sfg_mgpu_shard(mg->world, nc, mg->r[i].rank, &b0[i], &b1[i], &c0[i], &c1[i]);
+        win[i] = mg_shard(mg->world, nc, mg->r[i].rank);
+        if (!mg_reshard_segments(cols.data(), win[i].col0, win[i].col1, old, run))
+            MG_FAIL(mg, "sfg_mgpu_geno_filter: the shards of this matrix do not cover the columns of rank %d's new window", mg->r[i].rank);
         ReshardSegs &t = segs[i]; t.n = 0;
-        size_t served = 0;
-        for (size_t j = 0; j < n && c1[i] > c0[i]; j++) {
-            const sfg_geno *sh = g->shard[j];
-            if (!sh) continue;
-            const size_t o0 = g->blk0[j] * SFG_SLOTS, o1 = o0 + sh->ncol;                  // the old window of local rank j
-            const auto wb = cols.begin() + (ptrdiff_t)c0[i], we = cols.begin() + (ptrdiff_t)c1[i];
-            const size_t lo = (size_t)(std::lower_bound(wb, we, o0) - wb), hi = (size_t)(std::lower_bound(wb, we, o1) - wb);
-            if (hi == lo) continue;
-            if (lo != served) break;                                                       // (the old windows leave a hole: caught below)
-            t.s[t.n].base = (const uint8_t *)sh->dev; t.s[t.n].ld = sh->ld; t.s[t.n].gcol0 = (unsigned)o0; t.s[t.n].out0 = (unsigned)lo; t.n++;
-            served = hi;
-        }
-        if (served != c1[i] - c0[i]) MG_FAIL(mg, "sfg_mgpu_geno_filter: the shards of this matrix do not cover the columns of rank %d's new window", mg->r[i].rank);
+        for (const MgSeg &m : run) { const sfg_geno *sh = g->shard[(size_t)m.old]; t.s[t.n++] = {(const uint8_t *)sh->dev, sh->ld, (unsigned)m.gcol0, (unsigned)m.out0}; }
     }
     { const std::string e = mgpu_enable_peer_access(mg, "sfg_mgpu_geno_filter"); if (!e.empty()) MG_FAIL(mg, "%s", e.c_str()); }
     sfg_mgeno *f = mgeno_new(mg, nr, nc);                        // (nothing below returns without handing it on or freeing it)
-    f->blk0 = b0; f->blk1 = b1;
+    for (size_t i = 0; i < n; i++) { f->blk0[i] = win[i].blk0; f->blk1[i] = win[i].blk1; }
     int rc = run_ranks(mg, [&](MgRank &R, int) { R_HIP(R, hipSetDevice(R.device)); R_CTX(R, sfg_ctx_synchronize(R.ctx)); return 0; });
     if (!rc) rc = run_ranks(mg, [&](MgRank &R, int i) {
-        const size_t k = (size_t)i;
-        if (c1[k] > c0[k]) R_CTX(R, sfg_reshard_window(R.ctx, segs[k], cols.data() + c0[k], c1[k] - c0[k], rows.data(), nr, packed, &f->shard[k]));
+        const size_t k = (size_t)i; const MgShard &w = win[k];
+        if (w.col1 > w.col0) R_CTX(R, sfg_reshard_window(R.ctx, segs[k], cols.data() + w.col0, w.col1 - w.col0, rows.data(), nr, packed, &f->shard[k]));
         return 0;
     });
     if (rc) { sfg_mgpu_geno_free(mg, f); return 1; }
@@ -557,12 +554,10 @@ extern "C" int sfg_mgpu_sketch(sfg_mgpu *mg, const sfg_mgeno *g, const int32_t *
     MG_NEED(mg, bucket_host && sgn_host, "null bucket / sign table");
     for (const sfg_geno *sh : g->shard) if (sh && sh->packed) MG_FAIL(mg, "sfg_sketch: 2-bit packed matrix (sketch before sfg_geno_pack, or sfg_geno_unpack first)");
     if (kp < 1 || kp > 16) MG_FAIL(mg, "sfg_sketch: kp must be in 1..16 (one MFMA tile of buckets)");
-    const size_t n = mg->r.size(), ncol = g->ncol;
+    const size_t n = mg->r.size();
     std::vector<std::vector<double>> sk(n);
     std::vector<std::vector<uint64_t>> xs(n), x2(n);
-    const int rc = run_ranks(mg, [&](MgRank &R, int i) {
-        const sfg_geno *sh = g->shard[(size_t)i];
-        if (!sh) return 0;
+    const int rc = run_shards(mg, g, [&](MgRank &R, int i, const sfg_geno *sh, size_t) {
         if (sketch_host) sk[(size_t)i].resize((size_t)kp * sh->ncol);
         if (xsum_host) xs[(size_t)i].resize(sh->ncol);
         if (x2sum_host) x2[(size_t)i].resize(sh->ncol);
@@ -571,17 +566,9 @@ extern "C" int sfg_mgpu_sketch(sfg_mgpu *mg, const sfg_mgeno *g, const int32_t *
         return 0;
     });
     if (rc) return rc;
-    if (sketch_host) std::fill(sketch_host, sketch_host + (size_t)kp * ncol, 0.0);
-    if (xsum_host) std::fill(xsum_host, xsum_host + ncol, (uint64_t)0);
-    if (x2sum_host) std::fill(x2sum_host, x2sum_host + ncol, (uint64_t)0);
-    for (size_t i = 0; i < n; i++) {
-        const sfg_geno *sh = g->shard[i];
-        if (!sh) continue;
-        const size_t c0 = g->blk0[i] * SFG_SLOTS, w = sh->ncol;
-        if (sketch_host) for (int k = 0; k < kp; k++) std::copy(sk[i].begin() + (ptrdiff_t)((size_t)k * w), sk[i].begin() + (ptrdiff_t)((size_t)(k + 1) * w), sketch_host + (size_t)k * ncol + c0);
-        if (xsum_host) std::copy(xs[i].begin(), xs[i].end(), xsum_host + c0);
-        if (x2sum_host) std::copy(x2[i].begin(), x2[i].end(), x2sum_host + c0);
-    }
+    gather_planes(g, sk, (size_t)kp, sketch_host);
+    gather_planes(g, xs, 1, xsum_host);
+    gather_planes(g, x2, 1, x2sum_host);
     return 0;
 }
 extern "C" int sfg_mgpu_geno_colsums(sfg_mgpu *mg, const sfg_mgeno *g, double *sum_host, double *sqsum_host) {
@@ -590,10 +577,7 @@ extern "C" int sfg_mgpu_geno_colsums(sfg_mgpu *mg, const sfg_mgeno *g, double *s
     // a rank's window is a slice of the global layout: it writes there itself (the windows are disjoint)
     if (sum_host) std::fill(sum_host, sum_host + g->ncol, 0.0);
     if (sqsum_host) std::fill(sqsum_host, sqsum_host + g->ncol, 0.0);
-    return run_ranks(mg, [&](MgRank &R, int i) {
-        const sfg_geno *sh = g->shard[(size_t)i];
-        if (!sh) return 0;
-        const size_t c0 = g->blk0[(size_t)i] * SFG_SLOTS;
+    return run_shards(mg, g, [&](MgRank &R, int, const sfg_geno *sh, size_t c0) {
         R_CTX(R, sfg_geno_colsums(R.ctx, sh, sum_host ? sum_host + c0 : nullptr, sqsum_host ? sqsum_host + c0 : nullptr));
         return 0;
     });
@@ -701,91 +685,74 @@ static int rank_contract(sfg_mgpu *mg, MgRank &R, int li, const uint64_t *A, int
     sfg_ctx *ctx = R.ctx;
     if (!pre_rc && hipSetDevice(R.device) != hipSuccess) { R.err = "hipSetDevice failed (mgpu.hip:" + std::to_string(__LINE__) + ")"; pre_rc = 1; }
     ApiScope api_scope(ctx);                             // one top-level call for the scratch pools' bookkeeping
-    const int world = mg->world, d = SFG_D, N = SFG_N;
     const sfg_geno *shard = g->shard[(size_t)li];
-    const int nloc = (int)(g->blk1[(size_t)li] - g->blk0[(size_t)li]), nbr_x = (int)((g->nrow + SFG_SLOTS - 1) / SFG_SLOTS);
+    const int nloc = (int)(g->blk1[(size_t)li] - g->blk0[(size_t)li]), nbr_x = (int)assoc_cts(g->nrow);
     const unsigned fl = (flags & SFG_SQUARE) | SFG_TRANSPOSE;
-    const size_t outw = (size_t)2 * L * N, accw = (size_t)s * outw;
-    const int gpr = (d + world - 1) / world, g_lo = R.rank * gpr;
-    const size_t col = (size_t)d * accw, colp = (size_t)world * gpr * accw, mine = (size_t)gpr * accw;
-    if (world == 1 && !mg->force_coll) { if (pre_rc) return pre_rc; R_CTX(R, sfg_matmul_resident_dev(ctx, A, s, in_level, L, shard, fl, out)); return 0; }
-    I8RotPre pre8;
-    bool pipe = false;
-    int PW = 1;                                          // block columns per multiply call of the pipeline: with int8 rot tiles TWO, so that the second column's encode carries the
-                                                         // first one's plaintext transposition (kernels.hpp PtRide; a one-column call of one MAC group has nothing to ride in)
+    if (mg->world == 1 && !mg->force_coll) { if (pre_rc) return pre_rc; R_CTX(R, sfg_matmul_resident_dev(ctx, A, s, in_level, L, shard, fl, out)); return 0; }
+    I8RotPreScope rot8;                                  // (the tile buffers stay in the context's pool for the next product)
+    const I8RotPre &pre8 = rot8.pre;
+    MgContractPlan P;                                    // every size, offset and step below (mg_plan.hpp); made in prepare(), once the form of the rank's rotations is known
     uint64_t *acc_mine = nullptr, *acc2 = nullptr; double *cache = nullptr;
     hipStream_t cs = ctx->stream;
-    size_t acc_w = 0;
+    // columns [st.j, st.je) of the rank's partial product into their place of mg.acc2.  With int8 rot tiles a pipelined step is TWO columns, so that the second column's
+    // encode carries the first one's plaintext transposition (kernels.hpp PtRide; a one-column call of one MAC group has nothing to ride in)
+    auto multiply = [&](const MgStep &st) -> int {
+        uint64_t *buf = acc2 + P.buf_words(st);
+        if (!nloc) return 0;
+        if (!P.pipe) R_CTX(R, sfg_matmul_accumulate_dev(ctx, A, s, in_level, L, shard, fl, 0, nloc, st.j, st.je, 0, buf));
+        else if (pre8.G) R_CTX(R, matmul_accumulate_i8pre(ctx, pre8, s, L, shard, fl, st.j, st.je, 0, buf, P.colp));
+        else R_CTX(R, sfg_matmul_accumulate_rc_dev(ctx, cache, s, L, shard, fl, 0, nloc, st.j, st.je, 0, buf));
+        return 0;
+    };
     // ---- everything that allocates or can fail on this rank's own account, BEFORE the first exchange
     auto prepare = [&]() -> int {
         if (mg->broken) R_FAIL(R, "sfg_mgpu_matmul: the engine's communicator was aborted by an earlier failure");
         if (in_level < L) R_FAIL(R, "sfg_mgpu_matmul: input level %d below max_level %d", in_level, L);
         size_t jobw = 0, tailw = 0;
         R_CTX(R, sfg_rotcache_layout(ctx, s, L, &jobw, &tailw));
-        const size_t cache_w = (size_t)nloc * s * jobw + tailw;
         // The rank's own baby-step rotations, once per product, for the per-column pipeline: as the int8 MAC's rot TILES where the context multiplies on the matrix core
         // (1.3 GB per block row at s = 15; every column then multiplies there whatever the number of MAC groups - with fp64 rows a rank of more than two groups, i.e. a world
-        // of 4 or fewer at 100k x 1M, fell back to the fp64 kernel: 1.04 s of a 3.28 s rank step), else as fp64 operand rows (2.15 GB per block row) while they fit
-        if (nloc) R_CTX(R, i8_rotpre_build(ctx, (const u64 *)A, s, in_level, L, nloc, nullptr, mg->cache_budget, "mg.rot8", pre8));
-        pipe = !nloc || pre8.G || cache_w * 8 <= mg->cache_budget;
-        R_CTX(R, sfg_scratch(ctx, "mg.mine", (size_t)nbr_x * mine * 8, (void **)&acc_mine));
-        if (mg->direct) { uint64_t *tmp = nullptr; R_CTX(R, sfg_scratch(ctx, "mg.ar", (size_t)s * nbr_x * outw * 8, (void **)&tmp)); }      // (the direct all-reduce's private copy: not after the agreement)
+        // of 4 or fewer at 100k x 1M, fell back to the fp64 kernel: 1.04 s of a 3.28 s rank step), else as fp64 operand rows (2.15 GB per block row) while they fit; where
+        // they would not, the library's grouped rotation cache and the reduce-scatters after the whole product (P.pipe == false)
+        if (nloc) R_CTX(R, i8_rotpre_build(ctx, (const u64 *)A, s, in_level, L, nloc, nullptr, mg->cache_budget, "mg.rot8", rot8.pre));
+        P = mg_contract_plan({mg->world, R.rank, s, L, nbr_x, nloc, mg->direct, pre8.G != 0, (size_t)nloc * s * jobw + tailw, mg->cache_budget});
+        R_CTX(R, sfg_scratch(ctx, "mg.mine", P.mine_bytes, (void **)&acc_mine));
+        if (P.ar_bytes) { uint64_t *tmp = nullptr; R_CTX(R, sfg_scratch(ctx, "mg.ar", P.ar_bytes, (void **)&tmp)); }      // (the direct all-reduce's private copy: not after the agreement)
         // (the collectives' queue must not start before earlier work of the compute queue that still reads these buffers: previous call's finalize)
         R_HIP(R, hipEventRecord(R.ev_c, cs)); R_HIP(R, hipStreamWaitEvent(R.coll, R.ev_c, 0));
-        if (pipe) {
-            PW = pre8.G ? 2 : 1;
-            const size_t acc2_bytes = (size_t)2 * PW * colp * 8;
-            const bool fresh = ctx->pool.find("mg.acc2") == ctx->pool.end() || ctx->pool["mg.acc2"].second < acc2_bytes;
-            R_CTX(R, sfg_scratch(ctx, "mg.acc2", acc2_bytes, (void **)&acc2));
-            if (fresh || !nloc) R_HIP(R, hipMemsetAsync(acc2, 0, acc2_bytes, cs));       // the padded giant slots (>= 91) are never written by a product: zero once
-            if (nloc && !pre8.G) {
-                R_CTX(R, sfg_scratch(ctx, "mg.cache", cache_w * 8, (void **)&cache));
-                R_CTX(R, sfg_rotcache_build_rows_dev(ctx, A, s, in_level, L, nloc, 0, nloc, cache));
-            }
-            // the first column(s) are multiplied before the agreement too: that grows the product's own scratch pools (panel, tiles, accumulators) to their final shape
-            if (nloc && pre8.G) R_CTX(R, matmul_accumulate_i8pre(ctx, pre8, s, L, shard, fl, 0, std::min(PW, nbr_x), 0, acc2, colp));
-            else if (nloc) R_CTX(R, sfg_matmul_accumulate_rc_dev(ctx, cache, s, L, shard, fl, 0, nloc, 0, 1, 0, acc2));
-        } else {                                           // the rank's own cache would not fit: the library's grouped rotation cache, reduce-scatters after the product
-            acc_w = ((size_t)nbr_x * d + ((size_t)world * gpr - d)) * accw;
-            R_CTX(R, sfg_scratch(ctx, "mg.acc2", acc_w * 8, (void **)&acc2));
-            R_HIP(R, hipMemsetAsync(acc2, 0, acc_w * 8, cs));
-            if (nloc) R_CTX(R, sfg_matmul_accumulate_dev(ctx, A, s, in_level, L, shard, fl, 0, nloc, 0, nbr_x, 0, acc2));
+        const bool fresh = ctx->pool.find("mg.acc2") == ctx->pool.end() || ctx->pool["mg.acc2"].second < P.acc2_bytes;
+        R_CTX(R, sfg_scratch(ctx, "mg.acc2", P.acc2_bytes, (void **)&acc2));
+        // pipelined: the padded giant slots (>= 91) are never written by a product: zero once.  Unpipelined: the product adds to the dense columns: zero every time
+        if (!P.pipe || fresh || !nloc) R_HIP(R, hipMemsetAsync(acc2, 0, P.acc2_bytes, cs));
+        if (P.cache_bytes) {
+            R_CTX(R, sfg_scratch(ctx, "mg.cache", P.cache_bytes, (void **)&cache));
+            R_CTX(R, sfg_rotcache_build_rows_dev(ctx, A, s, in_level, L, nloc, 0, nloc, cache));
         }
+        // the first step is multiplied before the agreement too: that grows the product's own scratch pools (panel, tiles, accumulators) to their final shape
+        if (multiply(P.steps.front())) return 1;
         return rank_injected(R, 1);
     };
-    if (coll_agree(mg, R, pre_rc ? pre_rc : prepare())) { i8_rotpre_free(pre8); return 1; }
+    if (coll_agree(mg, R, pre_rc ? pre_rc : prepare())) return 1;
     // ---- from here on a failure aborts the communicator: the peers are inside (or about to enter) their collectives
     auto exchange = [&]() -> int {
-        if (pipe) {
-            for (int j = 0, p = 0; j < nbr_x; j += PW, p++) {      // columns [j, j + PW) are multiplied while the previous PW columns are reduce-scattered
-                const int je = std::min(nbr_x, j + PW);
-                uint64_t *buf = acc2 + (size_t)(p & 1) * PW * colp;
-                if (p >= 2) R_HIP(R, hipStreamWaitEvent(cs, R.ev_rs[p & 1], 0));            // the reduce-scatters of the call before last have read this buffer
-                if (j > 0) {
-                    if (nloc && pre8.G) R_CTX(R, matmul_accumulate_i8pre(ctx, pre8, s, L, shard, fl, j, je, 0, buf, colp));
-                    else if (nloc) R_CTX(R, sfg_matmul_accumulate_rc_dev(ctx, cache, s, L, shard, fl, 0, nloc, j, je, 0, buf));
-                }
-                R_HIP(R, hipEventRecord(R.ev_acc[p & 1], cs)); R_HIP(R, hipStreamWaitEvent(R.coll, R.ev_acc[p & 1], 0));
-                for (int c = j; c < je; c++)
-                    if (coll_reduce_scatter(mg, R, buf + (size_t)(c - j) * colp, acc_mine + (size_t)c * mine, mine, R.coll)) return 1;
-                R_HIP(R, hipEventRecord(R.ev_rs[p & 1], R.coll));
-            }
-        } else {
-            R_HIP(R, hipEventRecord(R.ev_acc[0], cs)); R_HIP(R, hipStreamWaitEvent(R.coll, R.ev_acc[0], 0));
-            for (int j = 0; j < nbr_x; j++)                 // the window of the last giants runs into the next block column: those slots are ignored by the finalize
-                if (coll_reduce_scatter(mg, R, acc2 + (size_t)j * col, acc_mine + (size_t)j * mine, mine, R.coll)) return 1;
+        for (const MgStep &st : P.steps) {                // pipelined: columns [j, je) are multiplied while the previous step's are reduce-scattered; else one step, the whole product
+            if (st.wait_rs) R_HIP(R, hipStreamWaitEvent(cs, R.ev_rs[st.half], 0));           // the reduce-scatters of the step before last have read this half
+            if (st.multiply && multiply(st)) return 1;
+            R_HIP(R, hipEventRecord(R.ev_acc[st.half], cs)); R_HIP(R, hipStreamWaitEvent(R.coll, R.ev_acc[st.half], 0));
+            for (int c = st.j; c < st.je; c++)             // (unpipelined: the window of the last giants runs into the next block column: those slots are ignored by the finalize)
+                if (coll_reduce_scatter(mg, R, acc2 + P.rs[(size_t)c].src_words, acc_mine + P.rs[(size_t)c].dst_words, P.mine, R.coll)) return 1;
+            if (P.pipe) R_HIP(R, hipEventRecord(R.ev_rs[st.half], R.coll));
         }
         R_HIP(R, hipEventRecord(R.ev_c, R.coll)); R_HIP(R, hipStreamWaitEvent(cs, R.ev_c, 0));
-        R_CTX(R, sfg_reduce_rows_dev(ctx, acc_mine, (size_t)nbr_x * gpr * s * 2, L));
-        R_CTX(R, sfg_matmul_finalize_slots_dev(ctx, acc_mine, s, L, nbr_x, gpr, g_lo, 0, gpr, 0, out));
+        R_CTX(R, sfg_reduce_rows_dev(ctx, acc_mine, P.reduce_mine_rows, L));
+        R_CTX(R, sfg_matmul_finalize_slots_dev(ctx, acc_mine, s, L, nbr_x, P.gpr, P.g_lo, 0, P.gpr, 0, out));
         R_HIP(R, hipEventRecord(R.ev_c, cs)); R_HIP(R, hipStreamWaitEvent(R.coll, R.ev_c, 0));
-        if (coll_all_reduce(mg, R, out, (size_t)s * nbr_x * outw, R.coll)) return 1;     // aligned partial outputs of the ranks' giant shards
+        if (coll_all_reduce(mg, R, out, P.allreduce_words, R.coll)) return 1;     // aligned partial outputs of the ranks' giant shards
         R_HIP(R, hipEventRecord(R.ev_c, R.coll)); R_HIP(R, hipStreamWaitEvent(cs, R.ev_c, 0));
-        R_CTX(R, sfg_reduce_rows_dev(ctx, out, (size_t)s * nbr_x * 2, L));
+        R_CTX(R, sfg_reduce_rows_dev(ctx, out, P.reduce_out_rows, L));
         return 0;
     };
     const int rc = exchange();
-    i8_rotpre_free(pre8);                               // (the tile buffers stay in the context's pool for the next product)
     if (rc) coll_abort(mg, R);
     return rc;
 }
@@ -840,8 +807,10 @@ extern "C" int sfg_mgpu_matmul(sfg_mgpu *mg, const uint64_t *A_host, int s, int 
             R_CTX(R, sfg_scratch(R.ctx, "mg.Ain", std::max<size_t>(na, 1) * s * ctw * 8, (void **)&A[(size_t)i]));
             R_CTX(R, sfg_scratch(R.ctx, "mg.Oout", std::max<size_t>(no, 1) * s * outw * 8, (void **)&O[(size_t)i]));
             if (!tr) { if (na) R_CTX(R, sfg_memcpy_h2d(R.ctx, A[(size_t)i], A_host, (size_t)s * nbr_x * ctw * 8)); }
-            else for (int r = 0; r < s && nloc; r++)      // row r of the input grid: the rank's block range
-                R_CTX(R, sfg_memcpy_h2d(R.ctx, A[(size_t)i] + (size_t)r * nloc * ctw, A_host + ((size_t)r * mct + g->blk0[(size_t)i]) * ctw, nloc * ctw * 8));
+            else for (int r = 0; r < s && nloc; r++) {    // row r of the input grid: the rank's block range
+                const MgSlice sl = mg_row_slice((size_t)r, mct, g->blk0[(size_t)i], nloc, ctw);
+                R_CTX(R, sfg_memcpy_h2d(R.ctx, A[(size_t)i] + sl.dev_words, A_host + sl.host_words, sl.words * 8));
+            }
             return tr && !mg->solo && (mg->world > 1 || mg->force_coll) ? rank_injected(R, 0) : 0;
         };
         io_rc[(size_t)i] = upload(); io_err[(size_t)i] = R.err;
@@ -857,8 +826,10 @@ extern "C" int sfg_mgpu_matmul(sfg_mgpu *mg, const uint64_t *A_host, int s, int 
     return run_ranks(mg, [&](MgRank &R, int i) {
         const size_t nloc = g->blk1[(size_t)i] - g->blk0[(size_t)i];
         if (tr) { if (i == 0) R_CTX(R, sfg_memcpy_d2h(R.ctx, out_host, O[(size_t)i], (size_t)s * nbr_x * outw * 8)); else R_CTX(R, sfg_ctx_synchronize(R.ctx)); }
-        else for (int r = 0; r < s && nloc; r++)
-            R_CTX(R, sfg_memcpy_d2h(R.ctx, out_host + ((size_t)r * mct + g->blk0[(size_t)i]) * outw, O[(size_t)i] + (size_t)r * nloc * outw, nloc * outw * 8));
+        else for (int r = 0; r < s && nloc; r++) {        // row r of the output grid: the rank's block columns
+            const MgSlice sl = mg_row_slice((size_t)r, mct, g->blk0[(size_t)i], nloc, outw);
+            R_CTX(R, sfg_memcpy_d2h(R.ctx, out_host + sl.host_words, O[(size_t)i] + sl.dev_words, sl.words * 8));
+        }
         return 0;
     });
 }
@@ -885,8 +856,10 @@ static int mgpu_assoc(sfg_mgpu *mg, int fmt, const char *path, size_t num_sample
         std::vector<std::pair<size_t, size_t>> ranges;
         R_CTX(R, assoc_stream_part(R.ctx, fmt, path, num_sample, num_snp, row_filter, col_filter, batch_snps, A, s, in_level, max_level, flags, out, out_ct_capacity, &totals[(size_t)i],
                                    sum_host, sqsum_host, R.rank, mg->world, &ranges));       // (sums: every rank writes the slices of its own batches - disjoint)
-        for (const auto &rg : ranges) for (int r = 0; r < s; r++)
-            R_CTX(R, sfg_memcpy_d2h(R.ctx, out_host + ((size_t)r * out_ct_capacity + rg.first) * ctw, out + ((size_t)r * out_ct_capacity + rg.first) * ctw, rg.second * ctw * 8));
+        for (const auto &rg : ranges) for (int r = 0; r < s; r++) {
+            const MgSlice sl = mg_assoc_slice((size_t)r, out_ct_capacity, rg.first, rg.second, ctw);
+            R_CTX(R, sfg_memcpy_d2h(R.ctx, out_host + sl.host_words, out + sl.dev_words, sl.words * 8));
+        }
         return 0;
     });
     if (rc) return rc;

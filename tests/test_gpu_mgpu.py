@@ -132,6 +132,62 @@ def test_unpipelined_form_and_device_pointer_entry(ref, monkeypatch):
         mg.close()
 
 
+NROW5, NCOL5 = 4 * SLOTS + 1, SLOTS + 5               # 5 output block columns of Q'X^T, 2 SNP blocks: one per rank of a world of two
+
+
+@pytest.fixture(scope="module")
+def ref5():
+    """the single-context Q'X^T products (plain and squared) of a matrix with five block rows, s = 1"""
+    from sfgwas_amd import capi
+    ctx = capi.Context(ol.Q_PN14, ol.P_PN14)
+    ctx.check(capi.lib().sfg_fill_rotkeys_synthetic(ctx.h, (C.c_int * len(ROTS))(*ROTS), len(ROTS), 0xBEEF), "keys")
+    geno = np.random.default_rng(86).integers(-1, 3, (NROW5, NCOL5), dtype=np.int8)
+    A = ctx.fill_uniform_cts(2, LEVEL, 0xB5)
+    Ah = A.host().reshape(1, 2, 2, LEVEL + 1, ctx.N).copy()
+    g = ctx.geno_upload(geno)
+    want = {}
+    for f in (T, T | SQ):
+        o = ctx.matmul_resident(A, 1, LEVEL, L, g, f); want[f] = o.host().copy(); o.free()
+    ctx.geno_free(g); A.free(); ctx.close()
+    return geno, Ah, want
+
+
+@pytest.mark.parametrize("cache_gb", [None, "0"])
+def test_five_output_columns_reuse_a_buffer_half_behind_the_reduce_scatters(ref5, monkeypatch, cache_gb):
+    """Two ranks on one device, five output block columns.  With the rank's rotations as int8 rot tiles a step is two columns: steps 0, 1, 2 - step 2 is the first
+    that multiplies into a half of mg.acc2 the collectives' queue has read (it waits for step 0's reduce-scatters), and it is ragged (one column).
+    SFG_MGPU_CACHE_GB=0: the same product in the unpipelined form.  Which form ran is read off the ranks' scratch pools: the tile buffers exist, and mg.acc2 has the
+    size of two halves of two padded columns - of the dense product plus the padding behind its last column in the unpipelined form."""
+    from sfgwas_amd import capi
+    from sfgwas_amd.sharding import giant_slots, ceil_div
+    geno, Ah, want = ref5
+    mg = make_engine(monkeypatch, [0, 0], {} if cache_gb is None else {"SFG_MGPU_CACHE_GB": cache_gb})
+    g = mg.geno_upload(geno)
+    try:
+        assert (mg.world, mg.nlocal, mg.transport) == (2, 2, "direct")
+        assert [mg.geno_blocks(g, i) for i in range(2)] == [(0, 1), (1, 2)]
+        for f in (T, T | SQ):
+            got = mg.matmul(Ah, 1, LEVEL, L, g, f)
+            assert got.shape == want[f].shape
+            assert np.array_equal(got, want[f]), f"flags {f}: {np.count_nonzero(got != want[f])} words differ"
+        nbr_x, accw = ceil_div(NROW5, SLOTS), 1 * 2 * L * mg.N
+        assert nbr_x == 5
+        for i in range(mg.nlocal):
+            gpr = giant_slots(mg.ranks[i], mg.world)[0]
+            colp = mg.world * gpr * accw
+            rot8, acc2 = C.c_size_t(), C.c_size_t()
+            mg.ctx[i].check(capi.lib().sfg_ctx_scratch_bytes(mg.ctx[i].h, b"mg.rot8", C.byref(rot8)), "scratch_bytes")
+            mg.ctx[i].check(capi.lib().sfg_ctx_scratch_bytes(mg.ctx[i].h, b"mg.acc2", C.byref(acc2)), "scratch_bytes")
+            if cache_gb is None:
+                assert rot8.value != 0, i                                     # the tile form ran
+                assert acc2.value == 2 * 2 * colp * 8, (i, acc2.value)
+            else:
+                assert acc2.value == (nbr_x * D + (mg.world * gpr - D)) * accw * 8, (i, acc2.value)
+    finally:
+        mg.geno_free(g)
+        mg.close()
+
+
 def test_multi_process_entry_at_world_1(ref, monkeypatch):
     """sfg_mgpu_unique_id + sfg_mgpu_create_rank: how bench.py's ranks (one process per GPU) join; here one rank, the exchange forced over RCCL"""
     from sfgwas_amd import capi
