@@ -749,6 +749,60 @@ int sfg_last_phase_launches(const sfg_ctx *ctx, const char *phase);
 /* algorithmic bytes (operands read once + results written once, as laid out in HBM) credited to the phase's launches */
 double sfg_last_phase_bytes(const sfg_ctx *ctx, const char *phase);
 
+/* ---- the general ring: evaluator operations at the other CKKS presets (gwas/gwas.go:164-177: PN12QP109 .. PN16QP1761) ----
+ * sfg_ctx is built for PN14QP438 alone (N = 16384, moduli below 2^47 held exactly in fp64).  sfg_ring serves 12 <= logN <= 16 and any prime modulus
+ * q < 2^61 with q == 1 mod 2N (lattigo's own bound) in integer arithmetic; nq >= 1, np >= 1, nq + np <= 48.  It covers the ring arithmetic of
+ * crypto/basics.go on device-resident ciphertexts - every word equal to lattigo's canonical residue; encode, encrypt, decrypt and the matrix products stay
+ * with the caller at these presets.  Layouts are those of the sfg_ctx twin of each call: ciphertext [nct][2][level+1][N], key [beta][2][nq+np][N] in the NTT
+ * domain with beta = ceil(nq/np), montgomery_form != 0 for lattigo's stored representation.  PN14QP438's own parameters are accepted as well.
+ * Every call returns 0, or 1 with the cause in sfg_ring_last_error; all device work is ordered on the ring's own non-blocking stream.
+ * psi NULL: derived as lattigo's ring.NewRing derives it; otherwise psi[m] must be a primitive 2N-th root of unity modulo moduli[m]. */
+typedef struct sfg_ring sfg_ring;
+/* ckks.NewParametersFromLiteral + ckks.NewEvaluator (crypto.go:60-110) for a preset other than PN14QP438 */
+int sfg_ring_create(sfg_ring **out, int device, int logN, int nq, int np, const uint64_t *moduli, const uint64_t *psi);
+void sfg_ring_destroy(sfg_ring *ring);
+const char *sfg_ring_last_error(const sfg_ring *ring);     /* ring may be NULL: error of a failed sfg_ring_create */
+int sfg_ring_synchronize(sfg_ring *ring);
+/* device memory of the ring's device (twins: sfg_malloc, sfg_free, sfg_memcpy_h2d, sfg_memcpy_d2h) */
+int sfg_ring_malloc(sfg_ring *ring, void **dev_ptr, size_t bytes);
+int sfg_ring_free(sfg_ring *ring, void *dev_ptr);
+int sfg_ring_memcpy_h2d(sfg_ring *ring, void *dst_dev, const void *src_host, size_t bytes);
+int sfg_ring_memcpy_d2h(sfg_ring *ring, void *dst_host, const void *src_dev, size_t bytes);
+/* lattigo ring.NTT / ring.InvNTT behind crypto/basics.go (twins: sfg_ntt_rows, sfg_intt_rows): nrows device rows of N canonical words, natural order in,
+ * bit-reversed out; mod_idx_host[r] in 0..nq+np-1 */
+int sfg_ring_ntt_rows(sfg_ring *ring, uint64_t *rows_dev, int nrows, const int *mod_idx_host);
+int sfg_ring_intt_rows(sfg_ring *ring, uint64_t *rows_dev, int nrows, const int *mod_idx_host);
+/* cryptoParams.RotKs (crypto.go:50; generated at mhe.go:73, crypto.go:232-275) and cryptoParams.Rlk (crypto.go:47) (twins: sfg_ctx_load_rotkey,
+ * sfg_ctx_has_rotkey, sfg_ctx_load_relinkey, sfg_galois_for_rotation) */
+int sfg_ring_load_rotkey(sfg_ring *ring, uint64_t galois_el, const uint64_t *key_host, int montgomery_form);
+int sfg_ring_has_rotkey(const sfg_ring *ring, uint64_t galois_el);
+int sfg_ring_load_relinkey(sfg_ring *ring, const uint64_t *key_host, int montgomery_form);
+uint64_t sfg_ring_galois_for_rotation(const sfg_ring *ring, int k_left);
+/* crypto.RotateRight / RotateRightWithEvaluator (basics.go:201-224 -> eval.RotateNew): ct j rotated RIGHT by nrot_host[j] mod slots, 0 = copy; in/out may not alias */
+int sfg_ring_rotate_right_dev(sfg_ring *ring, const uint64_t *ct_in_dev, uint64_t *ct_out_dev, int nct, int level, const int *nrot_host);
+/* eval.ConjugateNew behind crypto.ComplexConjugate / CReal (basics.go:826-846) and any automorphism X -> X^galois_el whose key is loaded; in/out may not alias */
+int sfg_ring_ct_galois_dev(sfg_ring *ring, const uint64_t *ct_in_dev, uint64_t *ct_out_dev, int nct, int level, uint64_t galois_el);
+/* eval.Add (basics.go:174, matmult.go:1225,1494) and eval.Sub (crypto.CSub, basics.go:575-590) */
+int sfg_ring_ct_add_dev(sfg_ring *ring, const uint64_t *a_dev, const uint64_t *b_dev, uint64_t *out_dev, int nct, int level);
+int sfg_ring_ct_sub_dev(sfg_ring *ring, const uint64_t *a_dev, const uint64_t *b_dev, uint64_t *out_dev, int nct, int level);
+/* crypto.DropLevel -> eval.DropLevelNew (basics.go:806-824; FlattenLevels :514-531); level_out == level_in copies, level_out > level_in fails; in/out may not alias */
+int sfg_ring_ct_drop_level_dev(sfg_ring *ring, const uint64_t *in_dev, uint64_t *out_dev, int nct, int level_in, int level_out);
+/* eval.MultByConst / MultByConstAndAdd / AddConst / AddNew(ct, plaintext) behind crypto.CMultConst, CMultConstRescale, AddConst, CAddConst, AddPlain, CPAdd
+ * (basics.go:183-199, 472-497, 533-551, 592-611; pca.go:264; qrfact.go:195,280).  scalars_host[level+1]: one canonical residue per modulus (the host side owns
+ * lattigo's scaleUpExact and the scale bookkeeping, as for the twins).  out may alias ct. */
+int sfg_ring_ct_mul_scalar_dev(sfg_ring *ring, const uint64_t *ct_dev, const uint64_t *scalars_host, uint64_t *out_dev, int nct, int level);
+int sfg_ring_ct_mul_scalar_add_dev(sfg_ring *ring, const uint64_t *ct_dev, const uint64_t *scalars_host, uint64_t *acc_dev, int nct, int level);
+int sfg_ring_ct_add_scalar_dev(sfg_ring *ring, const uint64_t *ct_dev, const uint64_t *scalars_host, uint64_t *out_dev, int nct, int level);
+int sfg_ring_ct_add_plain_dev(sfg_ring *ring, const uint64_t *ct_dev, const uint64_t *pt_dev, size_t pt_stride, uint64_t *out_dev, int nct, int level);
+/* eval.MulRelinNew(plaintext, ct) behind crypto.CPMult / Mask (basics.go:110-172): ct j uses pt_dev + j*pt_stride words (0 = one plaintext for all); out may alias ct */
+int sfg_ring_ct_mul_plain_dev(sfg_ring *ring, const uint64_t *ct_dev, const uint64_t *pt_dev, size_t pt_stride, uint64_t *out_dev, int nct, int level);
+/* eval.MulRelinNew(a, b) behind crypto.CMult (basics.go:386-470): tensor product + relinearisation, no rescale; out may alias neither input */
+int sfg_ring_ct_mulrelin_dev(sfg_ring *ring, const uint64_t *a_dev, const uint64_t *b_dev, uint64_t *out_dev, int nct, int level);
+/* one step of eval.Rescale (basics.go:123,394) = ring.DivRoundByLastModulusNTT: in [nct][2][level+1][N] -> out [nct][2][level][N]; fails at level 0; in/out may not alias */
+int sfg_ring_ct_rescale_dev(sfg_ring *ring, const uint64_t *in_dev, uint64_t *out_dev, int nct, int level);
+/* crypto.InnerSumAll (basics.go:278-292): needs the keys of the left rotations by 1, 2, 4, .., slots/2; in/out may not alias */
+int sfg_ring_ct_innersum_dev(sfg_ring *ring, const uint64_t *in_dev, int nct, int level, uint64_t *out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
 // Drop-in bodies of the ciphertext-vector wrappers of crypto/basics.go that sit between the hot products (rows C1-C4 of
 // SURVEY.md §8).  The untagged originals move behind `//go:build !hip`.  Each function keeps the reference's signature and
 // scale / level bookkeeping; only the ring arithmetic runs on the device.  NOT COMPILED in the sfgwas-hip repository.
+// hip.For picks the device evaluator: the specialised context at PN14QP438, the general ring (hip.Ring) at every other preset.
 //
 // These bodies round-trip through host memory per call, which is the minimal drop-in.  The resident form (ciphertexts stay on the device between
 // CMult -> product -> InnerProd) is hip.DevVec + gwas/matmult_hip.go's QXLazyNormStream; the C++ mirror sfgwas_amd/host/gwas.hpp carries it through Sub / MaskTrunc too.
@@ -25,8 +26,8 @@ func minLevel(v CipherVector) int {
 
 // rescaleLoop is ckks.Evaluator.Rescale(ct, minScale, ct) on a flat batch: divide by the last modulus while
 // scale / q_level >= minScale / 2 (lattigo v2 ckks/evaluator.go: the threshold scale) and a level is left.
-func rescaleLoop(h *hip.Ctx, flat []uint64, n, level int, scale, minScale float64) ([]uint64, int, float64) {
-	qi := h.Params.Qi()
+func rescaleLoop(h hip.Evaluator, flat []uint64, n, level int, scale, minScale float64) ([]uint64, int, float64) {
+	qi := h.Parameters().Qi()
 	for level > 0 && scale/float64(qi[level]) >= minScale/2 {
 		flat = h.Rescale(flat, n, level)
 		scale /= float64(qi[level])
@@ -46,7 +47,7 @@ func RotateRight(cryptoParams *CryptoParams, ct *ckks.Ciphertext, nrot int) *ckk
 	if nrot == 0 {
 		return ct.CopyNew().Ciphertext()
 	}
-	h := hip.Default
+	h := hip.For(cryptoParams.Params)
 	level := ct.Level()
 	flat := make([]uint64, h.CtWords(level))
 	h.FlattenCt(ct, level, flat)
@@ -88,7 +89,7 @@ func groupPairs(n int, lx, ly func(int) int, sx, sy func(int) float64) ([]opGrou
 	return order, idx
 }
 
-func flattenPicked(h *hip.Ctx, v CipherVector, ids []int, level int) []uint64 {
+func flattenPicked(h hip.Evaluator, v CipherVector, ids []int, level int) []uint64 {
 	w := h.CtWords(level)
 	flat := make([]uint64, len(ids)*w)
 	for j, i := range ids {
@@ -99,7 +100,7 @@ func flattenPicked(h *hip.Ctx, v CipherVector, ids []int, level int) []uint64 {
 
 // CMult - crypto/basics.go:386-427: element-wise MulRelinNew + Rescale(Params.Scale()) with length-1 broadcasting, per ciphertext level and scale.
 func CMult(cryptoParams *CryptoParams, X CipherVector, Y CipherVector) CipherVector {
-	h := hip.Default
+	h := hip.For(cryptoParams.Params)
 	n := Max(len(X), len(Y))
 	res := make(CipherVector, n)
 	order, idx := groupPairs(n, func(i int) int { return pick(X, i).Level() }, func(i int) int { return pick(Y, i).Level() },
@@ -117,7 +118,7 @@ func CMult(cryptoParams *CryptoParams, X CipherVector, Y CipherVector) CipherVec
 
 // CPMult - crypto/basics.go:429-470: the same with NTT-domain plaintexts (eval.MulRelinNew(ct, plaintext) multiplies both polynomials by the plaintext).
 func CPMult(cryptoParams *CryptoParams, X CipherVector, Y PlainVector) CipherVector {
-	h := hip.Default
+	h := hip.For(cryptoParams.Params)
 	n := Max(len(X), len(Y))
 	res := make(CipherVector, n)
 	py := func(i int) *ckks.Plaintext {
@@ -131,10 +132,10 @@ func CPMult(cryptoParams *CryptoParams, X CipherVector, Y PlainVector) CipherVec
 	for _, k := range order {
 		ids := idx[k]
 		nl := k.level + 1
-		pts := make([]uint64, len(ids)*nl*h.N)
+		pts := make([]uint64, len(ids)*nl*h.Degree())
 		for j, i := range ids {
 			for l := 0; l < nl; l++ {
-				copy(pts[(j*nl+l)*h.N:], py(i).Value()[0].Coeffs[l][:h.N])
+				copy(pts[(j*nl+l)*h.Degree():], py(i).Value()[0].Coeffs[l][:h.Degree()])
 			}
 		}
 		prod := h.MulPlain(flattenPicked(h, X, ids, k.level), pts, len(ids), len(ids), k.level)
@@ -155,7 +156,7 @@ func CSub(cryptoParams *CryptoParams, X CipherVector, Y CipherVector) CipherVect
 	return addSub(cryptoParams, X, Y, "sub")
 }
 func addSub(cryptoParams *CryptoParams, X, Y CipherVector, op string) CipherVector {
-	h := hip.Default
+	h := hip.For(cryptoParams.Params)
 	n := len(X)
 	res := make(CipherVector, n)
 	order, idx := groupPairs(n, func(i int) int { return X[i].Level() }, func(i int) int { return Y[i].Level() },
@@ -190,7 +191,7 @@ func addSub(cryptoParams *CryptoParams, X, Y CipherVector, op string) CipherVect
 // one after a Rebalance, the only call sites that can) is summed by the reference's own lines on the host, so that whatever lattigo's Add does about the
 // mismatch is what happens here too; the device then takes the one summed ciphertext through the 13 rotation steps.
 func InnerSumAll(cryptoParams *CryptoParams, X CipherVector) *ckks.Ciphertext {
-	h := hip.Default
+	h := hip.For(cryptoParams.Params)
 	uniform := true
 	for i := 1; i < len(X); i++ {
 		if X[i].Level() != X[0].Level() || X[i].Scale() != X[0].Scale() {
@@ -218,7 +219,7 @@ func InnerSumAll(cryptoParams *CryptoParams, X CipherVector) *ckks.Ciphertext {
 
 // CRescale - crypto/basics.go:707-719 (in place in the reference: the returned vector replaces X's entries).
 func CRescale(cryptoParams *CryptoParams, X CipherVector) CipherVector {
-	h := hip.Default
+	h := hip.For(cryptoParams.Params)
 	for i := range X {
 		level := X[i].Level()
 		flat := make([]uint64, h.CtWords(level))
@@ -232,6 +233,11 @@ func CRescale(cryptoParams *CryptoParams, X CipherVector) CipherVector {
 // DecryptFloatVector - crypto/crypto.go:489-510: decrypt under the loaded secret key and decode on the device; the first N values.  The ciphertexts of X are
 // read at their common (lowest) level and X[0]'s scale, as the reference decrypts one vector of one computation.
 func DecryptFloatVector(cryptoParams *CryptoParams, X CipherVector, N int) []float64 {
+	if _, general := hip.For(cryptoParams.Params).(*hip.Ring); general {
+		// a preset other than PN14QP438: the general ring has no decoder - lattigo decrypts and decodes (the reference's own body, which the maintainer
+		// keeps under this name when the original moves behind `!hip`: INTEGRATION.md, "The other CKKS presets")
+		return decryptFloatVectorLattigo(cryptoParams, X, N)
+	}
 	h := hip.Default
 	level := minLevel(X)
 	return h.DecryptFloatVector(h.FlattenVec(X, len(X), level), len(X), level, X[0].Scale())[:N]

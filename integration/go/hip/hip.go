@@ -1098,3 +1098,272 @@ func (h *Ctx) BeaverMatmul(pid, limbs int, modulus, ar, am, br, bm []uint64, m, 
 	h.check(C.sfg_beaver_matmul(h.p, C.int(pid), C.int(limbs), p(modulus), p(ar), p(am), p(br), p(bm), p(out), C.int(m), C.int(k), C.int(n)), "beaver_matmul")
 	return out
 }
+
+// ----------------------------------------------------------------------------------------------------------------
+// The general ring: the evaluator operations of crypto/basics.go at the presets the specialised context does not serve (gwas/gwas.go:164-177: PN12QP109,
+// PN13QP218, PN15QP880, PN16QP1761 - any logN 12..16 with prime moduli below 2^61).  Encoding, encryption, decryption and the matrix products stay on lattigo
+// there (INTEGRATION.md, "The other CKKS presets").  A Ring keeps Ctx's host-side conventions: flat [nct][2][level+1][N] words in and out, panics on failure.
+type Ring struct {
+	p      *C.sfg_ring
+	Params *ckks.Parameters
+	N      int
+	NQ, NP int
+}
+
+// DefaultRing is set by InitRing; gwas.go calls InitRing instead of Init when config.CkksParams is not "PN14QP438".
+var DefaultRing *Ring
+
+// Evaluator is what the drop-in bodies of crypto/basics_hip.go need of a device evaluator; *Ctx and *Ring both provide it.
+type Evaluator interface {
+	Degree() int
+	Parameters() *ckks.Parameters
+	CtWords(level int) int
+	FlattenCt(ct *ckks.Ciphertext, level int, dst []uint64)
+	FlattenVec(v []*ckks.Ciphertext, n, level int) []uint64
+	CtFromFlat(src []uint64, level int, scale float64) *ckks.Ciphertext
+	VecFromFlat(src []uint64, n, level int, scale float64) []*ckks.Ciphertext
+	RotateRight(flat []uint64, nct, level int, nrot []int) []uint64
+	Binary(op string, a, b []uint64, nct, level int) []uint64
+	Rescale(in []uint64, nct, level int) []uint64
+	InnerSumAll(in []uint64, nct, level int) []uint64
+	MulPlain(cts, pts []uint64, nct, npt, level int) []uint64
+}
+
+// For returns the device evaluator of the process: the general ring when InitRing made one (a preset other than PN14QP438), else the specialised context.
+func For(params *ckks.Parameters) Evaluator {
+	if DefaultRing != nil && DefaultRing.Params == params {
+		return DefaultRing
+	}
+	return Default
+}
+
+func (h *Ctx) Degree() int                   { return h.N }
+func (h *Ctx) Parameters() *ckks.Parameters  { return h.Params }
+func (r *Ring) Degree() int                  { return r.N }
+func (r *Ring) Parameters() *ckks.Parameters { return r.Params }
+
+func (r *Ring) check(rc C.int, what string) {
+	if rc != 0 {
+		panic(fmt.Sprintf("sfgwas-hip: %s: %s", what, C.GoString(C.sfg_ring_last_error(r.p))))
+	}
+}
+
+// InitRing creates the general ring from the CKKS parameters (lattigo's own moduli and 2N-th roots) and uploads the switching keys the party holds.
+func InitRing(params *ckks.Parameters, rotKs *ckks.RotationKeySet, rlk *ckks.RelinearizationKey, device int) *Ring {
+	qi, pi := params.Qi(), params.Pi()
+	moduli := append(append([]uint64{}, qi...), pi...)
+	ringQP, err := ring.NewRing(params.N(), moduli)
+	if err != nil {
+		panic(err)
+	}
+	psi := make([]uint64, len(moduli))
+	for i := range moduli {
+		psi[i] = ring.InvMForm(ringQP.PsiMont[i], moduli[i], ringQP.MredParams[i])
+	}
+	r := &Ring{Params: params, N: params.N(), NQ: len(qi), NP: len(pi)}
+	if C.sfg_ring_create(&r.p, C.int(device), C.int(params.LogN()), C.int(len(qi)), C.int(len(pi)),
+		(*C.uint64_t)(unsafe.Pointer(&moduli[0])), (*C.uint64_t)(unsafe.Pointer(&psi[0]))) != 0 {
+		panic("sfgwas-hip: sfg_ring_create: " + C.GoString(C.sfg_ring_last_error(nil)))
+	}
+	if rotKs != nil {
+		for galEl, swk := range rotKs.Keys {
+			r.LoadRotKey(galEl, swk)
+		}
+	}
+	if rlk != nil && len(rlk.Keys) > 0 {
+		r.LoadRelinKey(rlk.Keys[0])
+	}
+	DefaultRing = r
+	return r
+}
+
+func (r *Ring) Close() {
+	if r.p != nil {
+		C.sfg_ring_destroy(r.p)
+		r.p = nil
+	}
+	if DefaultRing == r {
+		DefaultRing = nil
+	}
+}
+
+func (r *Ring) Sync() { r.check(C.sfg_ring_synchronize(r.p), "ring_synchronize") }
+
+// LoadRotKey / LoadRelinKey: lattigo's switching keys, flattened to [beta][2][nq+np][N], in their stored Montgomery form.
+func (r *Ring) LoadRotKey(galEl uint64, swk *ckks.SwitchingKey) {
+	flat := FlattenSwitchingKey(swk, r.NQ+r.NP, r.N)
+	r.check(C.sfg_ring_load_rotkey(r.p, C.uint64_t(galEl), (*C.uint64_t)(unsafe.Pointer(&flat[0])), 1), "ring_load_rotkey")
+}
+func (r *Ring) HasRotKey(galEl uint64) bool { return C.sfg_ring_has_rotkey(r.p, C.uint64_t(galEl)) != 0 }
+func (r *Ring) LoadRelinKey(swk *ckks.SwitchingKey) {
+	flat := FlattenSwitchingKey(swk, r.NQ+r.NP, r.N)
+	r.check(C.sfg_ring_load_relinkey(r.p, (*C.uint64_t)(unsafe.Pointer(&flat[0])), 1), "ring_load_relinkey")
+}
+func (r *Ring) GaloisForRotation(kLeft int) uint64 {
+	return uint64(C.sfg_ring_galois_for_rotation(r.p, C.int(kLeft)))
+}
+
+// device memory of the ring
+func (r *Ring) alloc(words int) *C.uint64_t {
+	var p unsafe.Pointer
+	r.check(C.sfg_ring_malloc(r.p, &p, C.size_t(8*words)), "ring_malloc")
+	return (*C.uint64_t)(p)
+}
+func (r *Ring) free(p *C.uint64_t) { r.check(C.sfg_ring_free(r.p, unsafe.Pointer(p)), "ring_free") }
+func (r *Ring) upload(words []uint64) *C.uint64_t {
+	p := r.alloc(len(words))
+	r.check(C.sfg_ring_memcpy_h2d(r.p, unsafe.Pointer(p), unsafe.Pointer(&words[0]), C.size_t(8*len(words))), "ring_memcpy_h2d")
+	return p
+}
+func (r *Ring) download(p *C.uint64_t, words int) []uint64 {
+	out := make([]uint64, words)
+	r.check(C.sfg_ring_memcpy_d2h(r.p, unsafe.Pointer(&out[0]), unsafe.Pointer(p), C.size_t(8*words)), "ring_memcpy_d2h")
+	return out
+}
+
+// the flat-layout helpers are Ctx's own, on the ring's parameters
+func (r *Ring) host() *Ctx           { return &Ctx{Params: r.Params, N: r.N, NQ: r.NQ, NP: r.NP} }
+func (r *Ring) CtWords(level int) int { return 2 * (level + 1) * r.N }
+func (r *Ring) FlattenCt(ct *ckks.Ciphertext, level int, dst []uint64) {
+	r.host().FlattenCt(ct, level, dst)
+}
+func (r *Ring) FlattenVec(v []*ckks.Ciphertext, n, level int) []uint64 {
+	return r.host().FlattenVec(v, n, level)
+}
+func (r *Ring) CtFromFlat(src []uint64, level int, scale float64) *ckks.Ciphertext {
+	return r.host().CtFromFlat(src, level, scale)
+}
+func (r *Ring) VecFromFlat(src []uint64, n, level int, scale float64) []*ckks.Ciphertext {
+	return r.host().VecFromFlat(src, n, level, scale)
+}
+
+// unary runs one call that maps a batch at `level` to a batch of outWords words
+func (r *Ring) unary(in []uint64, outWords int, what string, call func(dIn, dOut *C.uint64_t) C.int) []uint64 {
+	dIn := r.upload(in)
+	defer r.free(dIn)
+	dOut := r.alloc(outWords)
+	defer r.free(dOut)
+	r.check(call(dIn, dOut), what)
+	return r.download(dOut, outWords)
+}
+
+// NTTRows / INTTRows: rows of N words, row i modulo moduli[modIdx[i]] (lattigo ring.NTT / ring.InvNTT).
+func (r *Ring) NTTRows(rows []uint64, modIdx []int) []uint64 {
+	mi := make([]C.int, len(modIdx))
+	for i := range mi {
+		mi[i] = C.int(modIdx[i])
+	}
+	d := r.upload(rows)
+	defer r.free(d)
+	r.check(C.sfg_ring_ntt_rows(r.p, d, C.int(len(mi)), &mi[0]), "ring_ntt_rows")
+	return r.download(d, len(rows))
+}
+func (r *Ring) INTTRows(rows []uint64, modIdx []int) []uint64 {
+	mi := make([]C.int, len(modIdx))
+	for i := range mi {
+		mi[i] = C.int(modIdx[i])
+	}
+	d := r.upload(rows)
+	defer r.free(d)
+	r.check(C.sfg_ring_intt_rows(r.p, d, C.int(len(mi)), &mi[0]), "ring_intt_rows")
+	return r.download(d, len(rows))
+}
+
+// RotateRight - crypto/basics.go:201-224 on a batch: ct j rotated right by nrot[j].
+func (r *Ring) RotateRight(flat []uint64, nct, level int, nrot []int) []uint64 {
+	cn := make([]C.int, nct)
+	for i := range cn {
+		cn[i] = C.int(nrot[i])
+	}
+	return r.unary(flat, len(flat), "ring_rotate_right", func(dIn, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_rotate_right_dev(r.p, dIn, dOut, C.int(nct), C.int(level), &cn[0])
+	})
+}
+
+// Galois - eval.ConjugateNew (galEl = 2N-1) and any other automorphism whose key is loaded (crypto/basics.go:826-846).
+func (r *Ring) Galois(flat []uint64, nct, level int, galEl uint64) []uint64 {
+	return r.unary(flat, len(flat), "ring_ct_galois", func(dIn, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_ct_galois_dev(r.p, dIn, dOut, C.int(nct), C.int(level), C.uint64_t(galEl))
+	})
+}
+
+// Binary element-wise ops on equal-level batches: "add", "sub", "mulrelin".
+func (r *Ring) Binary(op string, a, b []uint64, nct, level int) []uint64 {
+	dB := r.upload(b)
+	defer r.free(dB)
+	return r.unary(a, nct*r.CtWords(level), "ring_"+op, func(dA, dOut *C.uint64_t) C.int {
+		switch op {
+		case "add":
+			return C.sfg_ring_ct_add_dev(r.p, dA, dB, dOut, C.int(nct), C.int(level))
+		case "sub":
+			return C.sfg_ring_ct_sub_dev(r.p, dA, dB, dOut, C.int(nct), C.int(level))
+		case "mulrelin":
+			return C.sfg_ring_ct_mulrelin_dev(r.p, dA, dB, dOut, C.int(nct), C.int(level))
+		}
+		panic("sfgwas-hip: unknown op " + op)
+	})
+}
+
+// DropLevel - crypto.DropLevel (crypto/basics.go:806-824).
+func (r *Ring) DropLevel(in []uint64, nct, levelIn, levelOut int) []uint64 {
+	return r.unary(in, nct*r.CtWords(levelOut), "ring_ct_drop_level", func(dIn, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_ct_drop_level_dev(r.p, dIn, dOut, C.int(nct), C.int(levelIn), C.int(levelOut))
+	})
+}
+
+// MulScalar / AddScalar / MulScalarAdd: one canonical residue per modulus (lattigo's scaleUpExact and the scale bookkeeping stay with the caller, as for Ctx).
+func (r *Ring) MulScalar(in, scalars []uint64, nct, level int) []uint64 {
+	return r.unary(in, len(in), "ring_ct_mul_scalar", func(dIn, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_ct_mul_scalar_dev(r.p, dIn, (*C.uint64_t)(unsafe.Pointer(&scalars[0])), dOut, C.int(nct), C.int(level))
+	})
+}
+func (r *Ring) AddScalar(in, scalars []uint64, nct, level int) []uint64 {
+	return r.unary(in, len(in), "ring_ct_add_scalar", func(dIn, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_ct_add_scalar_dev(r.p, dIn, (*C.uint64_t)(unsafe.Pointer(&scalars[0])), dOut, C.int(nct), C.int(level))
+	})
+}
+func (r *Ring) MulScalarAdd(in, scalars, acc []uint64, nct, level int) []uint64 {
+	dIn, dAcc := r.upload(in), r.upload(acc)
+	defer r.free(dIn)
+	defer r.free(dAcc)
+	r.check(C.sfg_ring_ct_mul_scalar_add_dev(r.p, dIn, (*C.uint64_t)(unsafe.Pointer(&scalars[0])), dAcc, C.int(nct), C.int(level)), "ring_ct_mul_scalar_add")
+	return r.download(dAcc, len(acc))
+}
+
+// AddPlain / MulPlain: ciphertext j and NTT-domain plaintext j; one plaintext for all when npt == 1 (crypto/basics.go:110-172, 183-190, 429-470, 592-602).
+func (r *Ring) AddPlain(cts, pts []uint64, nct, npt, level int) []uint64 {
+	dP := r.upload(pts)
+	defer r.free(dP)
+	stride := 0
+	if npt > 1 {
+		stride = (level + 1) * r.N
+	}
+	return r.unary(cts, len(cts), "ring_ct_add_plain", func(dC, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_ct_add_plain_dev(r.p, dC, dP, C.size_t(stride), dOut, C.int(nct), C.int(level))
+	})
+}
+func (r *Ring) MulPlain(cts, pts []uint64, nct, npt, level int) []uint64 {
+	dP := r.upload(pts)
+	defer r.free(dP)
+	stride := 0
+	if npt > 1 {
+		stride = (level + 1) * r.N
+	}
+	return r.unary(cts, len(cts), "ring_ct_mul_plain", func(dC, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_ct_mul_plain_dev(r.p, dC, dP, C.size_t(stride), dOut, C.int(nct), C.int(level))
+	})
+}
+
+// Rescale divides a batch at `level` by q_level; output at level-1.
+func (r *Ring) Rescale(in []uint64, nct, level int) []uint64 {
+	return r.unary(in, nct*r.CtWords(level-1), "ring_ct_rescale", func(dIn, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_ct_rescale_dev(r.p, dIn, dOut, C.int(nct), C.int(level))
+	})
+}
+
+// InnerSumAll: sum of nct ciphertexts, then the log2(slots) rotate-and-add steps (crypto/basics.go:278-292); one ciphertext out.
+func (r *Ring) InnerSumAll(in []uint64, nct, level int) []uint64 {
+	return r.unary(in, r.CtWords(level), "ring_ct_innersum", func(dIn, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_ct_innersum_dev(r.p, dIn, C.int(nct), C.int(level), dOut)
+	})
+}

@@ -55,6 +55,41 @@ class SfgError(RuntimeError):
     pass
 
 
+def _ring_sig():
+    """the general ring's entry points (include/sfgwas_hip.h: sfg_ring_*)"""
+    vp, i, u64, sz = C.c_void_p, C.c_int, C.c_uint64, C.c_size_t
+    ip = C.POINTER(C.c_int)
+    return {
+        "sfg_ring_create": (i, [C.POINTER(vp), i, i, i, i, u64p, u64p]),
+        "sfg_ring_destroy": (None, [vp]),
+        "sfg_ring_last_error": (C.c_char_p, [vp]),
+        "sfg_ring_synchronize": (i, [vp]),
+        "sfg_ring_malloc": (i, [vp, C.POINTER(vp), sz]),
+        "sfg_ring_free": (i, [vp, vp]),
+        "sfg_ring_memcpy_h2d": (i, [vp, vp, vp, sz]),
+        "sfg_ring_memcpy_d2h": (i, [vp, vp, vp, sz]),
+        "sfg_ring_ntt_rows": (i, [vp, vp, i, ip]),
+        "sfg_ring_intt_rows": (i, [vp, vp, i, ip]),
+        "sfg_ring_load_rotkey": (i, [vp, u64, u64p, i]),
+        "sfg_ring_has_rotkey": (i, [vp, u64]),
+        "sfg_ring_load_relinkey": (i, [vp, u64p, i]),
+        "sfg_ring_galois_for_rotation": (u64, [vp, i]),
+        "sfg_ring_rotate_right_dev": (i, [vp, vp, vp, i, i, ip]),
+        "sfg_ring_ct_galois_dev": (i, [vp, vp, vp, i, i, u64]),
+        "sfg_ring_ct_add_dev": (i, [vp, vp, vp, vp, i, i]),
+        "sfg_ring_ct_sub_dev": (i, [vp, vp, vp, vp, i, i]),
+        "sfg_ring_ct_drop_level_dev": (i, [vp, vp, vp, i, i, i]),
+        "sfg_ring_ct_mul_scalar_dev": (i, [vp, vp, u64p, vp, i, i]),
+        "sfg_ring_ct_mul_scalar_add_dev": (i, [vp, vp, u64p, vp, i, i]),
+        "sfg_ring_ct_add_scalar_dev": (i, [vp, vp, u64p, vp, i, i]),
+        "sfg_ring_ct_add_plain_dev": (i, [vp, vp, vp, sz, vp, i, i]),
+        "sfg_ring_ct_mul_plain_dev": (i, [vp, vp, vp, sz, vp, i, i]),
+        "sfg_ring_ct_mulrelin_dev": (i, [vp, vp, vp, vp, i, i]),
+        "sfg_ring_ct_rescale_dev": (i, [vp, vp, vp, i, i]),
+        "sfg_ring_ct_innersum_dev": (i, [vp, vp, i, i, vp]),
+    }
+
+
 def _sig(L):
     vp, i, u64, d, sz = C.c_void_p, C.c_int, C.c_uint64, C.c_double, C.c_size_t
     S = {
@@ -238,6 +273,7 @@ def _sig(L):
         "sfg_last_phase_launches": (i, [vp, C.c_char_p]),
         "sfg_last_phase_bytes": (d, [vp, C.c_char_p]),
     }
+    S.update(_ring_sig())
     for name, (res, args) in S.items():
         fn = getattr(L, name)         # AttributeError here = the library does not export a declared symbol
         fn.restype, fn.argtypes = res, args
@@ -1357,3 +1393,170 @@ Context.install_public_key = _ctx_install_public_key
 Context.install_rotkeys = _ctx_install_rotkeys
 Context.install_relinkey = _ctx_install_relinkey
 Context.crp_fill = _ctx_crp_fill
+
+
+class Ring:
+    """sfg_ring wrapper: the general ring (logN 12..16, prime moduli below 2^61).  Shaped like Context: host arrays in, host arrays out for the tests; the *_dev
+    entry points take the pointers of malloc / to_device for callers that keep ciphertexts resident."""
+
+    def __init__(self, logN, q, p, device=0, psi=None):
+        L = lib()
+        self.logN, self.q, self.p = logN, list(q), list(p)
+        self.nq, self.np_ = len(q), len(p)
+        self.moduli = self.q + self.p
+        self.N, self.slots = 1 << logN, (1 << logN) // 2
+        mods = np.array(self.moduli, dtype=np.uint64)
+        h = C.c_void_p()
+        ps = None if psi is None else p64(np.array(psi, dtype=np.uint64))
+        if L.sfg_ring_create(C.byref(h), device, logN, self.nq, self.np_, p64(mods) if len(mods) else None, ps):
+            raise SfgError("sfg_ring_create: " + L.sfg_ring_last_error(None).decode())
+        self.h = h
+        self.beta = (self.nq + self.np_ - 1) // self.np_
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().sfg_ring_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def check(self, rc, what):
+        if rc:
+            raise SfgError(f"{what}: {lib().sfg_ring_last_error(self.h).decode()}")
+
+    def malloc(self, nbytes):
+        p = C.c_void_p()
+        self.check(lib().sfg_ring_malloc(self.h, C.byref(p), max(int(nbytes), 8)), "sfg_ring_malloc")
+        return p
+
+    def free(self, p):
+        self.check(lib().sfg_ring_free(self.h, p), "sfg_ring_free")
+
+    def to_device(self, arr):
+        arr = np.ascontiguousarray(arr)
+        p = self.malloc(arr.nbytes)
+        self.check(lib().sfg_ring_memcpy_h2d(self.h, p, arr.ctypes.data_as(C.c_void_p), arr.nbytes), "sfg_ring_memcpy_h2d")
+        return p
+
+    def to_host(self, p, shape, dtype=np.uint64):
+        out = np.empty(shape, dtype=dtype)
+        self.check(lib().sfg_ring_memcpy_d2h(self.h, out.ctypes.data_as(C.c_void_p), p, out.nbytes), "sfg_ring_memcpy_d2h")
+        return out
+
+    def sync(self):
+        self.check(lib().sfg_ring_synchronize(self.h), "sfg_ring_synchronize")
+
+    def galois(self, k_left):
+        return lib().sfg_ring_galois_for_rotation(self.h, int(k_left))
+
+    def ntt_rows(self, rows, mod_idx, inverse=False):
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        n = rows.shape[0]
+        mi = (C.c_int * n)(*[int(x) for x in mod_idx])
+        d = self.to_device(rows)
+        name = "sfg_ring_intt_rows" if inverse else "sfg_ring_ntt_rows"
+        try:
+            self.check(getattr(lib(), name)(self.h, d, n, mi), name)
+            return self.to_host(d, rows.shape)
+        finally:
+            self.free(d)
+
+    def load_rotkey(self, galois, key, montgomery=False):
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        self.check(lib().sfg_ring_load_rotkey(self.h, int(galois), p64(key), int(montgomery)), "sfg_ring_load_rotkey")
+
+    def has_rotkey(self, galois):
+        return bool(lib().sfg_ring_has_rotkey(self.h, int(galois)))
+
+    def load_relinkey(self, key, montgomery=False):
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        self.check(lib().sfg_ring_load_relinkey(self.h, p64(key), int(montgomery)), "sfg_ring_load_relinkey")
+
+    def _run(self, name, ins, out_shape, call):
+        """upload the host arrays `ins`, allocate the output, run call(device inputs, device output), download"""
+        devs = [self.to_device(np.ascontiguousarray(a, dtype=np.uint64)) for a in ins]
+        out = self.malloc(int(np.prod(out_shape)) * 8)
+        try:
+            self.check(call(devs, out), name)
+            return self.to_host(out, out_shape)
+        finally:
+            for d_ in devs + [out]:
+                self.free(d_)
+
+    def rotate_right(self, cts, level, nrots):
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        arr = (C.c_int * cts.shape[0])(*[int(x) for x in nrots])
+        return self._run("sfg_ring_rotate_right_dev", [cts], cts.shape,
+                         lambda d, o: lib().sfg_ring_rotate_right_dev(self.h, d[0], o, cts.shape[0], level, arr))
+
+    def apply_galois(self, cts, level, galois):
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        return self._run("sfg_ring_ct_galois_dev", [cts], cts.shape,
+                         lambda d, o: lib().sfg_ring_ct_galois_dev(self.h, d[0], o, cts.shape[0], level, int(galois)))
+
+    def _binary(self, name, a, b, level):
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        return self._run(name, [a, b], a.shape, lambda d, o: getattr(lib(), name)(self.h, d[0], d[1], o, a.shape[0], level))
+
+    def add(self, a, b, level):
+        return self._binary("sfg_ring_ct_add_dev", a, b, level)
+
+    def sub(self, a, b, level):
+        return self._binary("sfg_ring_ct_sub_dev", a, b, level)
+
+    def mulrelin(self, a, b, level):
+        return self._binary("sfg_ring_ct_mulrelin_dev", a, b, level)
+
+    def drop_level(self, cts, level_in, level_out):
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        return self._run("sfg_ring_ct_drop_level_dev", [cts], (cts.shape[0], 2, max(level_out, 0) + 1, self.N),
+                         lambda d, o: lib().sfg_ring_ct_drop_level_dev(self.h, d[0], o, cts.shape[0], level_in, level_out))
+
+    def _scalar(self, name, cts, scalars, level):
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        sc = np.ascontiguousarray(scalars, dtype=np.uint64)
+        return self._run(name, [cts], cts.shape, lambda d, o: getattr(lib(), name)(self.h, d[0], p64(sc), o, cts.shape[0], level))
+
+    def mul_scalar(self, cts, scalars, level):
+        return self._scalar("sfg_ring_ct_mul_scalar_dev", cts, scalars, level)
+
+    def add_scalar(self, cts, scalars, level):
+        return self._scalar("sfg_ring_ct_add_scalar_dev", cts, scalars, level)
+
+    def mul_scalar_add(self, cts, scalars, acc, level):
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        sc = np.ascontiguousarray(scalars, dtype=np.uint64)
+        d_ct, d_acc = self.to_device(cts), self.to_device(np.ascontiguousarray(acc, dtype=np.uint64))
+        try:
+            self.check(lib().sfg_ring_ct_mul_scalar_add_dev(self.h, d_ct, p64(sc), d_acc, cts.shape[0], level), "sfg_ring_ct_mul_scalar_add_dev")
+            return self.to_host(d_acc, cts.shape)
+        finally:
+            self.free(d_ct)
+            self.free(d_acc)
+
+    def _plain(self, name, cts, pt, level):
+        """pt: [level+1][N] (one plaintext for all) or [nct][level+1][N]"""
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        pt = np.ascontiguousarray(pt, dtype=np.uint64)
+        stride = 0 if pt.ndim == 2 else pt.shape[1] * pt.shape[2]
+        return self._run(name, [cts, pt], cts.shape, lambda d, o: getattr(lib(), name)(self.h, d[0], d[1], stride, o, cts.shape[0], level))
+
+    def add_plain(self, cts, pt, level):
+        return self._plain("sfg_ring_ct_add_plain_dev", cts, pt, level)
+
+    def mul_plain(self, cts, pt, level):
+        return self._plain("sfg_ring_ct_mul_plain_dev", cts, pt, level)
+
+    def rescale(self, cts, level):
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        return self._run("sfg_ring_ct_rescale_dev", [cts], (cts.shape[0], 2, max(level, 1), self.N),
+                         lambda d, o: lib().sfg_ring_ct_rescale_dev(self.h, d[0], o, cts.shape[0], level))
+
+    def innersum(self, cts, level):
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        return self._run("sfg_ring_ct_innersum_dev", [cts], (2, level + 1, self.N),
+                         lambda d, o: lib().sfg_ring_ct_innersum_dev(self.h, d[0], cts.shape[0], level, o))
