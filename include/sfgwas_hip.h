@@ -752,8 +752,8 @@ double sfg_last_phase_bytes(const sfg_ctx *ctx, const char *phase);
 /* ---- the general ring: evaluator operations at the other CKKS presets (gwas/gwas.go:164-177: PN12QP109 .. PN16QP1761) ----
  * sfg_ctx is built for PN14QP438 alone (N = 16384, moduli below 2^47 held exactly in fp64).  sfg_ring serves 12 <= logN <= 16 and any prime modulus
  * q < 2^61 with q == 1 mod 2N (lattigo's own bound) in integer arithmetic; nq >= 1, np >= 1, nq + np <= 48.  It covers the ring arithmetic of
- * crypto/basics.go on device-resident ciphertexts - every word equal to lattigo's canonical residue; encode, encrypt, decrypt and the matrix products stay
- * with the caller at these presets.  Layouts are those of the sfg_ctx twin of each call: ciphertext [nct][2][level+1][N], key [beta][2][nq+np][N] in the NTT
+ * crypto/basics.go on device-resident ciphertexts - every word equal to lattigo's canonical residue - and, further down, public-key encryption and the collective decryption's
+ * local halves, the encoder and the decoder; the matrix products stay with the caller at these presets.  Layouts are those of the sfg_ctx twin of each call: ciphertext [nct][2][level+1][N], key [beta][2][nq+np][N] in the NTT
  * domain with beta = ceil(nq/np), montgomery_form != 0 for lattigo's stored representation.  PN14QP438's own parameters are accepted as well.
  * Every call returns 0, or 1 with the cause in sfg_ring_last_error; all device work is ordered on the ring's own non-blocking stream.
  * psi NULL: derived as lattigo's ring.NewRing derives it; otherwise psi[m] must be a primitive 2N-th root of unity modulo moduli[m]. */
@@ -802,6 +802,66 @@ int sfg_ring_ct_mulrelin_dev(sfg_ring *ring, const uint64_t *a_dev, const uint64
 int sfg_ring_ct_rescale_dev(sfg_ring *ring, const uint64_t *in_dev, uint64_t *out_dev, int nct, int level);
 /* crypto.InnerSumAll (basics.go:278-292): needs the keys of the left rotations by 1, 2, 4, .., slots/2; in/out may not alias */
 int sfg_ring_ct_innersum_dev(sfg_ring *ring, const uint64_t *in_dev, int nct, int level, uint64_t *out_dev);
+
+/* ---- the general ring's two ends (gring_io.hip): encode, encrypt, decrypt and decode at every ring sfg_ring_create accepts ----
+ * The twins of the sfg_ctx calls of "C6 on the device" and "the way back out" above, same layouts: the encryption in the ring's integer words, the two embeddings in
+ * double-double; PARITY UNPINNED in the same sense.  The ring carries no scale: every encoding and decoding call is given one.  Every refusal returns 1 with the cause
+ * in sfg_ring_last_error and launches nothing (the encoder's rounding and domain refusals come after its own launches and before anything is written to the caller's
+ * buffer); a count of 0 returns 0. */
+/* cryptoParams.Pk.Value (crypto.go:45, what crypto.go:355 NewEncryptorFromPk takes): [2][nq+np][N] NTT-domain words; montgomery_form != 0 for lattigo's stored form */
+int sfg_ring_load_public_key(sfg_ring *ring, const uint64_t *pk_host, int montgomery_form);
+int sfg_ring_has_public_key(const sfg_ring *ring);
+/* cryptoParams.Sk.Value (crypto.go:44): secret key or key shard, rows [nq][N] in the NTT domain.  Wiped from device memory in sfg_ring_destroy. */
+int sfg_ring_load_secret_key(sfg_ring *ring, const uint64_t *sk_host, int montgomery_form);
+/* the sampler's key (replaces the PRNG lattigo's NewEncryptorFromPk draws from crypto/rand, crypto.go:355), as sfg_ctx_seed_encryptor: 32 bytes from the caller's
+ * CSPRNG, no default, ONE atomic 64-bit encryption index per ring, a call takes nct consecutive indices, seeding resets it to 0.  Wiped from host and device memory
+ * in sfg_ring_destroy; never part of an error string.  The map from stream bytes to samples is sfg_ctx's with the coefficient's high part ranging over N/512 instead
+ * of 32: at N = 16384 the two samplers give the same polynomials for the same key and index. */
+int sfg_ring_seed_encryptor(sfg_ring *ring, const uint8_t *key32);
+int sfg_ring_encryptor_next_index(sfg_ring *ring, uint64_t *next_index);      /* fails on a NULL next_index */
+/* the deterministic core of pkEncryptor.EncryptNew (lattigo ckks/encryptor.go encrypt(), the ModDown branch; crypto.go:340-388), as sfg_encrypt_explicit_dev:
+ * u int8 [nct][N], e0, e1 int32 [nct][N], pt_dev NULL (zero) or [nct][level+1][N], out_dev [nct][2][level+1][N].  For every modulus m of Q_0..Q_level and of P:
+ * t_i = pk_i (.) NTT(u) + NTT(e_i);  c_i = ModDown_P(t_i) with the key switch's float-corrected extension (np = 1: a raw copy);  c_0 += pt. */
+int sfg_ring_encrypt_explicit_dev(sfg_ring *ring, const uint64_t *pt_dev, int nct, int level, const int8_t *u_dev, const int32_t *e0_dev, const int32_t *e1_dev,
+                                  uint64_t *out_dev);
+/* crypto.CZeroMat + eval.Add (matmult.go:1174,1225,1443,1494): ct += Enc(0) in place with fresh samples (nct indices); bit-identical to the explicit form, added.
+ * On zeroed words it gives crypto.CZeros (basics.go:367-384); on (pt, 0) it gives encryptor.EncryptNew(pt) (crypto.go:355-361): c_0 += pt is the core's last step.
+ * The workspace is reserved before the indices are taken: a call that fails spends none. */
+int sfg_ring_ct_add_fresh_zero_dev(sfg_ring *ring, uint64_t *ct_dev, int nct, int level);
+/* test hook (replaces nothing in the reference): the samples u, e0, e1 ([nct][N] int8 / int32 / int32) of encryption indices first_index .. first_index + nct - 1
+ * under the seeded key, without advancing the counter.  Refused unless the process set SFG_ENABLE_TEST_HOOKS=1 before sfg_ring_create. */
+int sfg_ring_encrypt_transcript_for_test(sfg_ring *ring, uint64_t first_index, int nct, int8_t *u_dev, int32_t *e0_dev, int32_t *e1_dev);
+/* mpc/mhe.go:107-220 CollectiveDecrypt*, the local half before the aggregation (PCKSProtocol.GenShare with the reference's zero public key), as sfg_pcks_gen_share_dev:
+ *   h0 [nct][level+1][N] = ModDown_P(NTT_QP(e0)) + sk (.) c1,     h1 [nct][level+1][N] = ModDown_P(NTT_QP(e1))
+ * through the encryption core with u = 0 and no plaintext (the same code path).  e0, e1 int32 [nct][N] from the caller; h1_dev may be NULL (then e1_dev is not read). */
+int sfg_ring_pcks_gen_share_dev(sfg_ring *ring, const uint64_t *ct_dev, int nct, int level, const int32_t *e0_dev, const int32_t *e1_dev, uint64_t *h0_dev, uint64_t *h1_dev);
+/* the local half after the aggregation (PCKSProtocol.KeySwitch, then .Plaintext()), as sfg_pcks_finish_dev: pt [nct][level+1][N] = c0 + h0agg, NTT domain */
+int sfg_ring_pcks_finish_dev(sfg_ring *ring, const uint64_t *ct_dev, int nct, int level, const uint64_t *h0agg_dev, uint64_t *pt_dev);
+/* the first half of crypto.DecodeFloatVector (crypto/crypto.go:525-536 -> encoder.Decode: InvNTT, the big-integer CRT with lattigo's Cmp(QHalf) centring, the division
+ * by the scale), as sfg_decode_coeffs: pt_dev NTT-domain plaintext rows [level+1][N] per plaintext, pt_stride words apart (>= (level+1) * N: polynomial 0 of resident
+ * ciphertexts can be read in place); scale any finite double >= 1; coeffs_host [nct][N]: the centred integer coefficient in (-Q/2, Q/2] divided by the scale, correctly
+ * rounded to double unless the exact quotient lies within 2^-96 relative of a rounding boundary (derived for up to 48 mixed-radix digits in gring_io_arith.hpp);
+ * a magnitude beyond 2^960 gives an infinity.  The call synchronises.  The embedding that turns coefficients into slot values stays with the caller. */
+int sfg_ring_decode_coeffs(sfg_ring *ring, const uint64_t *pt_dev, size_t pt_stride, int nct, int level, double scale, double *coeffs_host);
+/* ckks encoder.Encode behind crypto.EncryptFloatVector / EncodeFloatVector (crypto.go:340-362, 394-420), as sfg_encode_vectors_dev: values_host [nvec][N/2] real
+ * doubles -> pt_dev [nvec][level+1][N], NTT domain.  scale: a finite double >= 1 (the ring carries none).  p_c = round(scale Re w_c), p_(c+n) = round(scale Im w_c),
+ * w_c = (1/n) sum_t v_t zeta^(-5^t c), half away from zero, each reduced modulo every q_i in integer arithmetic.  The embedding runs in double-double; a coefficient
+ * whose value lies within B_enc = max(2^-50, 2^-93 (sum |p_c| + n)) of a rounding tie is unproven (derivation: gring_io_arith.hpp): the call
+ * then fails, says how many, and hands out no plaintext.  NaN, inf and |p| >= 2^62 fail before anything is written.  Every coefficient handed out is the exactly
+ * rounded integer.  The call synchronises. */
+int sfg_ring_encode_vectors_dev(sfg_ring *ring, const double *values_host, int nvec, int level, double scale, uint64_t *pt_dev);
+/* crypto.EncryptFloatVector (crypto.go:340-362) / one row of EncryptFloatMatrixRow (:364-388), as sfg_encrypt_vectors_dev: sfg_ring_encode_vectors_dev's rows (its
+ * refusals first, before an index is spent), encrypted with samples drawn on the device (nct indices): out_dev [nct][2][level+1][N].  Bit-identical to
+ * sfg_ring_encrypt_explicit_dev on the transcript's samples and the encoder's rows. */
+int sfg_ring_encrypt_vectors_dev(sfg_ring *ring, const double *values_host, int nct, int level, double scale, uint64_t *out_dev);
+/* crypto.DecodeFloatVector (crypto.go:525-536 -> encoder.Decode), as sfg_decode_vectors: sfg_ring_decode_coeffs' quotients kept as double-double pairs, then the
+ * forward embedding v_t = sum_c w_c zeta^(5^t c) in double-double, each part rounded to double once.  re_host [nct][N/2] in lattigo's slot order; im_host may be NULL
+ * (the real parts are the same bits either way).  |d_t - v_t| <= B max_t |v_t| with B = 2^-53 + 2^-86 (derived in gring_io_arith.hpp).  pt_stride as above. */
+int sfg_ring_decode_vectors(sfg_ring *ring, const uint64_t *pt_dev, size_t pt_stride, int nct, int level, double scale, double *re_host, double *im_host);
+/* the same with the slot values left on the device (re_dev, im_dev [nct][N/2] doubles; im_dev may be NULL); ordered on the ring's stream, does not synchronise */
+int sfg_ring_decode_vectors_dev(sfg_ring *ring, const uint64_t *pt_dev, size_t pt_stride, int nct, int level, double scale, double *re_dev, double *im_dev);
+/* crypto.DecryptFloatVector (crypto.go:489-510), as sfg_decrypt_vectors: pt = c0 + sk (.) c1 under the loaded (whole) secret key, then sfg_ring_decode_vectors */
+int sfg_ring_decrypt_vectors(sfg_ring *ring, const uint64_t *ct_dev, int nct, int level, double scale, double *re_host, double *im_host);
 
 #ifdef __cplusplus
 }

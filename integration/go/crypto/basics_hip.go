@@ -233,13 +233,11 @@ func CRescale(cryptoParams *CryptoParams, X CipherVector) CipherVector {
 // DecryptFloatVector - crypto/crypto.go:489-510: decrypt under the loaded secret key and decode on the device; the first N values.  The ciphertexts of X are
 // read at their common (lowest) level and X[0]'s scale, as the reference decrypts one vector of one computation.
 func DecryptFloatVector(cryptoParams *CryptoParams, X CipherVector, N int) []float64 {
-	if _, general := hip.For(cryptoParams.Params).(*hip.Ring); general {
-		// a preset other than PN14QP438: the general ring has no decoder - lattigo decrypts and decodes (the reference's own body, which the maintainer
-		// keeps under this name when the original moves behind `!hip`: INTEGRATION.md, "The other CKKS presets")
-		return decryptFloatVectorLattigo(cryptoParams, X, N)
+	level := minLevel(X)
+	if h, general := hip.For(cryptoParams.Params).(*hip.Ring); general {
+		return h.DecryptFloatVector(h.FlattenVec(X, len(X), level), len(X), level, X[0].Scale())[:N]
 	}
 	h := hip.Default
-	level := minLevel(X)
 	return h.DecryptFloatVector(h.FlattenVec(X, len(X), level), len(X), level, X[0].Scale())[:N]
 }
 
@@ -250,4 +248,46 @@ func DecryptFloatMatrix(cryptoParams *CryptoParams, X CipherMatrix, N int) [][]f
 		out[i] = DecryptFloatVector(cryptoParams, X[i], N)
 	}
 	return out
+}
+
+// EncryptFloatVector - crypto/crypto.go:340-362: f packed into ceil(len / slots) ciphertexts at MaxLevel and the default scale; also returns the number of encrypted
+// elements.  Encoded and encrypted on the device at every preset: the specialised context at PN14QP438, the general ring elsewhere.
+func EncryptFloatVector(cryptoParams *CryptoParams, f []float64) (CipherVector, int) {
+	level := cryptoParams.Params.MaxLevel()
+	if h, general := hip.For(cryptoParams.Params).(*hip.Ring); general {
+		return CipherVector(h.EncryptFloatVector(f, level)), len(f)
+	}
+	return CipherVector(hip.Default.EncryptFloatVector(f, level)), len(f)
+}
+
+// CZeros - crypto/basics.go:367-375: n fresh encryptions of zero at MaxLevel.
+func CZeros(cryptoParams *CryptoParams, n int) CipherVector {
+	params := cryptoParams.Params
+	level := params.MaxLevel()
+	if h, general := hip.For(params).(*hip.Ring); general {
+		return CipherVector(h.VecFromFlat(h.Zeros(n, level), n, level, params.Scale()))
+	}
+	cv := make(CipherVector, n)
+	for i := range cv {
+		tmp, _ := EncryptFloatVector(cryptoParams, []float64{0.0})
+		cv[i] = tmp[0]
+	}
+	return cv
+}
+
+// DecodeFloatVector - crypto/crypto.go:525-536: the first N real slot values of a vector of plaintexts, decoded on the device at every preset.
+func DecodeFloatVector(cryptoParams *CryptoParams, fEncoded PlainVector, N int) []float64 {
+	params := cryptoParams.Params
+	level := fEncoded[0].Level()
+	rows := (level + 1) * params.N()
+	flat := make([]uint64, len(fEncoded)*rows)
+	for i, pt := range fEncoded {
+		for m := 0; m <= level; m++ {
+			copy(flat[i*rows+m*params.N():], pt.Value()[0].Coeffs[m])
+		}
+	}
+	if h, general := hip.For(params).(*hip.Ring); general {
+		return h.DecodeFloatVector(flat, len(fEncoded), level, fEncoded[0].Scale())[:N]
+	}
+	return hip.Default.DecodeFloatVector(flat, len(fEncoded), level, fEncoded[0].Scale())[:N]
 }

@@ -1367,3 +1367,162 @@ func (r *Ring) InnerSumAll(in []uint64, nct, level int) []uint64 {
 		return C.sfg_ring_ct_innersum_dev(r.p, dIn, C.int(nct), C.int(level), dOut)
 	})
 }
+
+// ---- the ring's two ends (gring_io.hip): the encoder, public-key encryption, the collective decryption's local halves, decryption and the decoder.
+
+// LoadPublicKey gives the ring cryptoParams.Pk (crypto/crypto.go:45, Montgomery form) and keys the device sampler from crypto/rand, as Ctx.LoadPublicKey does.
+func (r *Ring) LoadPublicKey(pk *ckks.PublicKey) {
+	nmod := r.NQ + r.NP
+	flat := make([]uint64, 2*nmod*r.N)
+	for k := 0; k < 2; k++ {
+		for m := 0; m < nmod; m++ {
+			copy(flat[(k*nmod+m)*r.N:(k*nmod+m+1)*r.N], pk.Value[k].Coeffs[m])
+		}
+	}
+	r.check(C.sfg_ring_load_public_key(r.p, (*C.uint64_t)(unsafe.Pointer(&flat[0])), 1), "ring_load_public_key")
+	r.SeedEncryptor()
+}
+func (r *Ring) allocBytes(n int) unsafe.Pointer {
+	var p unsafe.Pointer
+	r.check(C.sfg_ring_malloc(r.p, &p, C.size_t(n)), "ring_malloc")
+	return p
+}
+func (r *Ring) freeBytes(p unsafe.Pointer) { r.check(C.sfg_ring_free(r.p, p), "ring_free") }
+func (r *Ring) HasPublicKey() bool { return C.sfg_ring_has_public_key(r.p) != 0 }
+
+// SeedEncryptor keys the ring's sampler from crypto/rand; the key is wiped from this process's memory after the call.
+func (r *Ring) SeedEncryptor() {
+	var key [32]byte
+	if _, err := rand.Read(key[:]); err != nil {
+		panic(err)
+	}
+	r.check(C.sfg_ring_seed_encryptor(r.p, (*C.uint8_t)(unsafe.Pointer(&key[0]))), "ring_seed_encryptor")
+	for i := range key {
+		key[i] = 0
+	}
+}
+func (r *Ring) EncryptorNextIndex() uint64 {
+	var n C.uint64_t
+	r.check(C.sfg_ring_encryptor_next_index(r.p, &n), "ring_encryptor_next_index")
+	return uint64(n)
+}
+
+// LoadSecretKey gives the ring cryptoParams.Sk (crypto/crypto.go:44, NTT + Montgomery form): this party's shard for PCKSGenShare.
+func (r *Ring) LoadSecretKey(sk *ckks.SecretKey) {
+	flat := make([]uint64, r.NQ*r.N)
+	for m := 0; m < r.NQ; m++ {
+		copy(flat[m*r.N:(m+1)*r.N], sk.Value.Coeffs[m])
+	}
+	r.check(C.sfg_ring_load_secret_key(r.p, (*C.uint64_t)(unsafe.Pointer(&flat[0])), 1), "ring_load_secret_key")
+}
+
+// EncodeVectors: encoder.Encode of nvec real slot vectors ([nvec][N/2] doubles) at `scale` -> NTT-domain plaintext rows [nvec][level+1][N] (every coefficient the
+// exactly rounded integer, or the call fails).
+func (r *Ring) EncodeVectors(values []float64, nvec, level int, scale float64) []uint64 {
+	words := nvec * (level + 1) * r.N
+	d := r.alloc(words)
+	defer r.free(d)
+	r.check(C.sfg_ring_encode_vectors_dev(r.p, (*C.double)(unsafe.Pointer(&values[0])), C.int(nvec), C.int(level), C.double(scale), d), "ring_encode_vectors")
+	return r.download(d, words)
+}
+
+// EncryptFloatVector: crypto.EncryptFloatVector (crypto.go:340-362) - f packed into ceil(len/slots) ciphertexts at `level` and the parameters' default scale, encoded
+// and encrypted on the device; only the doubles go up.
+func (r *Ring) EncryptFloatVector(f []float64, level int) []*ckks.Ciphertext {
+	slots := r.N / 2
+	nvec := (len(f) + slots - 1) / slots
+	padded := make([]float64, nvec*slots)
+	copy(padded, f)
+	words := nvec * r.CtWords(level)
+	d := r.alloc(words)
+	defer r.free(d)
+	r.check(C.sfg_ring_encrypt_vectors_dev(r.p, (*C.double)(unsafe.Pointer(&padded[0])), C.int(nvec), C.int(level), C.double(r.Params.Scale()), d), "ring_encrypt_vectors")
+	return r.VecFromFlat(r.download(d, words), nvec, level, r.Params.Scale())
+}
+
+// Zeros: crypto.CZeros (basics.go:367-384) - n fresh encryptions of zero: ct += Enc(0) on zeroed words.
+func (r *Ring) Zeros(n, level int) []uint64 {
+	return r.AddFreshZero(make([]uint64, n*r.CtWords(level)), n, level)
+}
+
+// EncryptExplicit: the deterministic core on the caller's samples (u in {-1, 0, 1}, e0, e1 small), pts nil or [nct][level+1][N].
+func (r *Ring) EncryptExplicit(pts []uint64, nct, level int, u []int8, e0, e1 []int32) []uint64 {
+	var dPt *C.uint64_t
+	if pts != nil {
+		dPt = r.upload(pts)
+		defer r.free(dPt)
+	}
+	du, d0, d1 := r.allocBytes(len(u)), r.allocBytes(4*len(e0)), r.allocBytes(4*len(e1))
+	defer r.freeBytes(du)
+	defer r.freeBytes(d0)
+	defer r.freeBytes(d1)
+	r.check(C.sfg_ring_memcpy_h2d(r.p, du, unsafe.Pointer(&u[0]), C.size_t(len(u))), "ring_memcpy_h2d")
+	r.check(C.sfg_ring_memcpy_h2d(r.p, d0, unsafe.Pointer(&e0[0]), C.size_t(4*len(e0))), "ring_memcpy_h2d")
+	r.check(C.sfg_ring_memcpy_h2d(r.p, d1, unsafe.Pointer(&e1[0]), C.size_t(4*len(e1))), "ring_memcpy_h2d")
+	dOut := r.alloc(nct * r.CtWords(level))
+	defer r.free(dOut)
+	r.check(C.sfg_ring_encrypt_explicit_dev(r.p, dPt, C.int(nct), C.int(level), (*C.int8_t)(du), (*C.int32_t)(d0), (*C.int32_t)(d1), dOut), "ring_encrypt_explicit")
+	return r.download(dOut, nct*r.CtWords(level))
+}
+
+// AddFreshZero: crypto.CZeroMat + eval.Add (matmult.go:1174,1225,1443,1494): every ciphertext += a fresh encryption of zero.
+func (r *Ring) AddFreshZero(flat []uint64, nct, level int) []uint64 {
+	d := r.upload(flat)
+	defer r.free(d)
+	r.check(C.sfg_ring_ct_add_fresh_zero_dev(r.p, d, C.int(nct), C.int(level)), "ring_ct_add_fresh_zero")
+	return r.download(d, len(flat))
+}
+
+// PCKSGenShare: the local half of CollectiveDecrypt* before the aggregation (mpc/mhe.go:107-220): h0 [nct][level+1][N] from this party's key shard and its own
+// error polynomials e0 [nct][N] (sigma 6.36, bound 38 in the reference); polynomial 1 of the share is not computed (the reference discards it).
+func (r *Ring) PCKSGenShare(flat []uint64, nct, level int, e0 []int32) []uint64 {
+	d := r.upload(flat)
+	defer r.free(d)
+	de := r.allocBytes(4 * len(e0))
+	defer r.freeBytes(de)
+	r.check(C.sfg_ring_memcpy_h2d(r.p, de, unsafe.Pointer(&e0[0]), C.size_t(4*len(e0))), "ring_memcpy_h2d")
+	dh := r.alloc(nct * (level + 1) * r.N)
+	defer r.free(dh)
+	r.check(C.sfg_ring_pcks_gen_share_dev(r.p, d, C.int(nct), C.int(level), (*C.int32_t)(de), nil, dh, nil), "ring_pcks_gen_share")
+	return r.download(dh, nct*(level+1)*r.N)
+}
+
+// PCKSFinish: the local half after the aggregation: the plaintext rows [nct][level+1][N] = c0 + h0agg, for lattigo's encoder.Decode.
+func (r *Ring) PCKSFinish(flat []uint64, nct, level int, h0agg []uint64) []uint64 {
+	d := r.upload(flat)
+	defer r.free(d)
+	dh := r.upload(h0agg)
+	defer r.free(dh)
+	dOut := r.alloc(nct * (level + 1) * r.N)
+	defer r.free(dOut)
+	r.check(C.sfg_ring_pcks_finish_dev(r.p, d, C.int(nct), C.int(level), dh, dOut), "ring_pcks_finish")
+	return r.download(dOut, nct*(level+1)*r.N)
+}
+
+// DecodeCoeffs: the first half of crypto.DecodeFloatVector (crypto.go:525-536 -> encoder.Decode) for nvec NTT-domain plaintexts ([nvec][level+1][N] words): inverse
+// NTT, the centred CRT and the division by the scale: [nvec][N] doubles.
+func (r *Ring) DecodeCoeffs(flat []uint64, nvec, level int, scale float64) []float64 {
+	d := r.upload(flat)
+	defer r.free(d)
+	out := make([]float64, nvec*r.N)
+	r.check(C.sfg_ring_decode_coeffs(r.p, d, C.size_t((level+1)*r.N), C.int(nvec), C.int(level), C.double(scale), (*C.double)(unsafe.Pointer(&out[0]))), "ring_decode_coeffs")
+	return out
+}
+
+// DecodeFloatVector: crypto.DecodeFloatVector (crypto.go:525-536) - the real parts of every slot of nvec NTT-domain plaintexts ([nvec][level+1][N] words, PCKSFinish's).
+func (r *Ring) DecodeFloatVector(flat []uint64, nvec, level int, scale float64) []float64 {
+	d := r.upload(flat)
+	defer r.free(d)
+	out := make([]float64, nvec*r.N/2)
+	r.check(C.sfg_ring_decode_vectors(r.p, d, C.size_t((level+1)*r.N), C.int(nvec), C.int(level), C.double(scale), (*C.double)(unsafe.Pointer(&out[0])), nil), "ring_decode_vectors")
+	return out
+}
+
+// DecryptFloatVector: crypto.DecryptFloatVector (crypto.go:489-510) under the loaded (whole) secret key: the real parts of every slot of nct ciphertexts.
+func (r *Ring) DecryptFloatVector(flat []uint64, nct, level int, scale float64) []float64 {
+	d := r.upload(flat)
+	defer r.free(d)
+	out := make([]float64, nct*r.N/2)
+	r.check(C.sfg_ring_decrypt_vectors(r.p, d, C.int(nct), C.int(level), C.double(scale), (*C.double)(unsafe.Pointer(&out[0])), nil), "ring_decrypt_vectors")
+	return out
+}

@@ -87,6 +87,22 @@ def _ring_sig():
         "sfg_ring_ct_mulrelin_dev": (i, [vp, vp, vp, vp, i, i]),
         "sfg_ring_ct_rescale_dev": (i, [vp, vp, vp, i, i]),
         "sfg_ring_ct_innersum_dev": (i, [vp, vp, i, i, vp]),
+        "sfg_ring_load_public_key": (i, [vp, u64p, i]),
+        "sfg_ring_has_public_key": (i, [vp]),
+        "sfg_ring_load_secret_key": (i, [vp, u64p, i]),
+        "sfg_ring_seed_encryptor": (i, [vp, C.c_char_p]),
+        "sfg_ring_encryptor_next_index": (i, [vp, u64p]),
+        "sfg_ring_encrypt_explicit_dev": (i, [vp, vp, i, i, vp, vp, vp, vp]),
+        "sfg_ring_ct_add_fresh_zero_dev": (i, [vp, vp, i, i]),
+        "sfg_ring_encrypt_transcript_for_test": (i, [vp, u64, i, vp, vp, vp]),
+        "sfg_ring_pcks_gen_share_dev": (i, [vp, vp, i, i, vp, vp, vp, vp]),
+        "sfg_ring_pcks_finish_dev": (i, [vp, vp, i, i, vp, vp]),
+        "sfg_ring_decode_coeffs": (i, [vp, vp, sz, i, i, C.c_double, C.POINTER(C.c_double)]),
+        "sfg_ring_encode_vectors_dev": (i, [vp, C.POINTER(C.c_double), i, i, C.c_double, vp]),
+        "sfg_ring_encrypt_vectors_dev": (i, [vp, C.POINTER(C.c_double), i, i, C.c_double, vp]),
+        "sfg_ring_decode_vectors": (i, [vp, vp, sz, i, i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "sfg_ring_decode_vectors_dev": (i, [vp, vp, sz, i, i, C.c_double, vp, vp]),
+        "sfg_ring_decrypt_vectors": (i, [vp, vp, i, i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
 
 
@@ -1560,3 +1576,151 @@ class Ring:
         cts = np.ascontiguousarray(cts, dtype=np.uint64)
         return self._run("sfg_ring_ct_innersum_dev", [cts], (2, level + 1, self.N),
                          lambda d, o: lib().sfg_ring_ct_innersum_dev(self.h, d[0], cts.shape[0], level, o))
+
+    # ---- the two ends (gring_io.hip): keys, sampler, encryption, the collective decryption's local halves
+    def load_public_key(self, pk, montgomery=False):
+        pk = np.ascontiguousarray(pk, dtype=np.uint64)
+        assert pk.shape == (2, len(self.moduli), self.N)
+        self.check(lib().sfg_ring_load_public_key(self.h, p64(pk), int(montgomery)), "sfg_ring_load_public_key")
+
+    def has_public_key(self):
+        return bool(lib().sfg_ring_has_public_key(self.h))
+
+    def load_secret_key(self, sk, montgomery=False):
+        sk = np.ascontiguousarray(sk, dtype=np.uint64)
+        assert sk.shape == (self.nq, self.N)
+        self.check(lib().sfg_ring_load_secret_key(self.h, p64(sk), int(montgomery)), "sfg_ring_load_secret_key")
+
+    def seed_encryptor(self, key32):
+        key32 = bytes(key32)
+        assert len(key32) == 32
+        self.check(lib().sfg_ring_seed_encryptor(self.h, key32), "sfg_ring_seed_encryptor")
+
+    def encryptor_next_index(self):
+        v = C.c_uint64()
+        self.check(lib().sfg_ring_encryptor_next_index(self.h, C.byref(v)), "sfg_ring_encryptor_next_index")
+        return v.value
+
+    def _run_mixed(self, name, ins, out_shapes, call):
+        """_run for inputs of any dtype (None stays a null pointer) and several uint64 outputs (a None shape stays a null pointer)"""
+        devs = [None if a is None else self.to_device(np.ascontiguousarray(a)) for a in ins]
+        outs = [None if s is None else self.malloc(int(np.prod(s)) * 8) for s in out_shapes]
+        try:
+            self.check(call(devs, outs), name)
+            return [None if s is None else self.to_host(o, s) for o, s in zip(outs, out_shapes)]
+        finally:
+            for d_ in devs + outs:
+                if d_ is not None:
+                    self.free(d_)
+
+    def encrypt_explicit(self, pt, level, u, e0, e1):
+        """pt None or [nct][level+1][N]; u int8, e0, e1 int32 [nct][N] -> [nct][2][level+1][N]"""
+        u, e0, e1 = np.ascontiguousarray(u, dtype=np.int8), np.ascontiguousarray(e0, dtype=np.int32), np.ascontiguousarray(e1, dtype=np.int32)
+        nct = u.shape[0]
+        pt = None if pt is None else np.ascontiguousarray(pt, dtype=np.uint64)
+        return self._run_mixed("sfg_ring_encrypt_explicit_dev", [pt, u, e0, e1], [(nct, 2, level + 1, self.N)],
+                               lambda d, o: lib().sfg_ring_encrypt_explicit_dev(self.h, d[0], nct, level, d[1], d[2], d[3], o[0]))[0]
+
+    def add_fresh_zero(self, cts, level):
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        d = self.to_device(cts)
+        try:
+            self.check(lib().sfg_ring_ct_add_fresh_zero_dev(self.h, d, cts.shape[0], level), "sfg_ring_ct_add_fresh_zero_dev")
+            return self.to_host(d, cts.shape)
+        finally:
+            self.free(d)
+
+    def encrypt_transcript(self, first_index, nct):
+        """test hook -> (u int8, e0 int32, e1 int32), each [nct][N]"""
+        n = max(nct, 1) * self.N
+        du, d0, d1 = self.malloc(n), self.malloc(4 * n), self.malloc(4 * n)
+        try:
+            self.check(lib().sfg_ring_encrypt_transcript_for_test(self.h, int(first_index), nct, du, d0, d1), "sfg_ring_encrypt_transcript_for_test")
+            return (self.to_host(du, (nct, self.N), np.int8), self.to_host(d0, (nct, self.N), np.int32), self.to_host(d1, (nct, self.N), np.int32))
+        finally:
+            for d_ in (du, d0, d1):
+                self.free(d_)
+
+    def pcks_gen_share(self, cts, level, e0, e1=None):
+        """-> (h0, h1) [nct][level+1][N]; e1 None: h1 is not computed (None)"""
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        nct = cts.shape[0]
+        e0 = np.ascontiguousarray(e0, dtype=np.int32)
+        e1 = None if e1 is None else np.ascontiguousarray(e1, dtype=np.int32)
+        row = (nct, level + 1, self.N)
+        return tuple(self._run_mixed("sfg_ring_pcks_gen_share_dev", [cts, e0, e1], [row, None if e1 is None else row],
+                                     lambda d, o: lib().sfg_ring_pcks_gen_share_dev(self.h, d[0], nct, level, d[1], d[2], o[0], o[1])))
+
+    def pcks_finish(self, cts, level, h0agg):
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        nct = cts.shape[0]
+        return self._run_mixed("sfg_ring_pcks_finish_dev", [cts, np.ascontiguousarray(h0agg, dtype=np.uint64)], [(nct, level + 1, self.N)],
+                               lambda d, o: lib().sfg_ring_pcks_finish_dev(self.h, d[0], nct, level, d[1], o[0]))[0]
+
+    def decode_coeffs(self, pt, level, scale, poly0_of_cts=False):
+        """pt [nct][level+1][N] NTT-domain rows -> float64 [nct][N]: centred coefficient / scale.  poly0_of_cts: pt is [nct][2][level+1][N], polynomial 0 read in place"""
+        pt = np.ascontiguousarray(pt, dtype=np.uint64)
+        nct, rows = pt.shape[0], (level + 1) * self.N
+        stride = 2 * rows if poly0_of_cts else rows
+        out = np.empty((nct, self.N), dtype=np.float64)
+        d = self.to_device(pt)
+        try:
+            self.check(lib().sfg_ring_decode_coeffs(self.h, d, stride, nct, level, float(scale), out.ctypes.data_as(C.POINTER(C.c_double))), "sfg_ring_decode_coeffs")
+            return out
+        finally:
+            self.free(d)
+
+    def _values_call(self, name, values, level, scale, out_shape):
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        assert values.ndim == 2 and values.shape[1] == self.slots
+        out = self.malloc(int(np.prod(out_shape)) * 8)
+        try:
+            self.check(getattr(lib(), name)(self.h, values.ctypes.data_as(C.POINTER(C.c_double)), values.shape[0], level, float(scale), out), name)
+            return self.to_host(out, out_shape)
+        finally:
+            self.free(out)
+
+    def encode_vectors(self, values, level, scale):
+        """values [nvec][slots] real -> NTT-domain plaintext rows [nvec][level+1][N]"""
+        return self._values_call("sfg_ring_encode_vectors_dev", values, level, scale, (len(values), level + 1, self.N))
+
+    def encrypt_vectors(self, values, level, scale):
+        """values [nct][slots] real -> ciphertexts [nct][2][level+1][N] (EncryptFloatVector)"""
+        return self._values_call("sfg_ring_encrypt_vectors_dev", values, level, scale, (len(values), 2, level + 1, self.N))
+
+    def decode_vectors(self, pt, level, scale, want_imag=False, poly0_of_cts=False, on_device=False):
+        """pt [nct][level+1][N] -> real parts [nct][slots] (and the imaginary parts); on_device: through sfg_ring_decode_vectors_dev and a download"""
+        pt = np.ascontiguousarray(pt, dtype=np.uint64)
+        nct, rows = pt.shape[0], (level + 1) * self.N
+        stride = 2 * rows if poly0_of_cts else rows
+        re, im = np.empty((nct, self.slots)), (np.empty((nct, self.slots)) if want_imag else None)
+        pd_ = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))      # noqa: E731
+        d = self.to_device(pt)
+        try:
+            if on_device:
+                dre, dim_ = self.malloc(re.nbytes), (self.malloc(re.nbytes) if want_imag else None)
+                try:
+                    self.check(lib().sfg_ring_decode_vectors_dev(self.h, d, stride, nct, level, float(scale), dre, dim_), "sfg_ring_decode_vectors_dev")
+                    re = self.to_host(dre, re.shape, np.float64)
+                    im = self.to_host(dim_, re.shape, np.float64) if want_imag else None
+                finally:
+                    self.free(dre)
+                    if dim_ is not None:
+                        self.free(dim_)
+            else:
+                self.check(lib().sfg_ring_decode_vectors(self.h, d, stride, nct, level, float(scale), pd_(re), pd_(im)), "sfg_ring_decode_vectors")
+        finally:
+            self.free(d)
+        return (re, im) if want_imag else re
+
+    def decrypt_vectors(self, cts, level, scale, want_imag=False):
+        cts = np.ascontiguousarray(cts, dtype=np.uint64)
+        nct = cts.shape[0]
+        re, im = np.empty((nct, self.slots)), (np.empty((nct, self.slots)) if want_imag else None)
+        d = self.to_device(cts)
+        try:
+            self.check(lib().sfg_ring_decrypt_vectors(self.h, d, nct, level, float(scale), re.ctypes.data_as(C.POINTER(C.c_double)),
+                                                      None if im is None else im.ctypes.data_as(C.POINTER(C.c_double))), "sfg_ring_decrypt_vectors")
+        finally:
+            self.free(d)
+        return (re, im) if want_imag else re

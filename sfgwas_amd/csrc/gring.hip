@@ -4,39 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
 #include <vector>
-#include "../../include/sfgwas_hip.h"
-#include "gring_arith.hpp"
-#include "gring_plan.hpp"
-
-using gr::u64;
-using gr::u128;
-
-// ---------------------------------------------------------------- device-side tables
-struct GrMod { u64 q, uhi, ulo, ninv, ninv_sh, r64inv, r64inv_sh; };        // per modulus: q, floor(2^128 / q), N^-1 and 2^-64 with their Shoup quotients
-// which modulus a row of a batch belongs to: an explicit table, or t = row % period, t < split ? t + base0 : t - split + base1
-struct GrRowMap { const int *table; int period, split, base0, base1; };
-__device__ __forceinline__ int gr_row_mod(const GrRowMap &m, size_t row) {
-    if (m.table) return m.table[row];
-    int t = (int)(row % (size_t)m.period);
-    return t < m.split ? t + m.base0 : t - m.split + m.base1;
-}
-// one basis-extension configuration (lattigo modUpExact): sources in digits of alpha moduli, a list of target moduli
-struct GrExt {
-    int nsrc, ndig, alpha, tgt_cap;
-    const int *src_mod;       // [nsrc]
-    const u64 *inv;           // [nsrc][2]   (D / q_m)^-1 mod q_m of the source's digit, and its Shoup quotient
-    const int *tgt_mod;       // [tgt_cap]
-    const int *tgt_src;       // [ndig][tgt_cap]   source row when the target is one of the digit's own moduli, else -1
-    const u64 *tgt_tab;       // [ndig][tgt_cap][1 + alpha]   D mod qt, then (D / q_m) mod qt
-};
-struct GrJob { const u64 *key; const uint32_t *idx; long long ct; };     // one key switch of a batch: its key, its automorphism index (or null), its ciphertext
-struct GrScalars { u64 s[gr::kMaxMod]; };
-
-constexpr int GR_T = 256;
+#include "gring_dev.hpp"      // the device-side tables, struct sfg_ring and the error macros, shared with gring_io.hip
 
 // ---------------------------------------------------------------- the transform: two launches, logN = a + b (gring_plan.hpp)
 // Twiddle tables tw[mod][4][N]: psi^brev forward, its Shoup quotients, psi^-brev inverse, its Shoup quotients - lattigo's and the oracle's order
@@ -210,30 +183,6 @@ __global__ __launch_bounds__(GR_T) void k_gr_from_mont(u64 *rows, const GrMod *m
 // ---------------------------------------------------------------- host side
 static thread_local std::string g_ring_create_error;
 
-struct GrKey { u64 *key = nullptr; uint32_t *idx = nullptr; };
-struct GrExtOwner { GrExt e{}; void *buf = nullptr; };
-struct GrLevel { GrExtOwner up; u64 *rescale_tab = nullptr; };
-struct sfg_ring {
-    int device = 0, logN = 0, N = 0, nq = 0, np = 0, nmod = 0, beta = 0;
-    u64 q[gr::kMaxMod] = {}, psi[gr::kMaxMod] = {};
-    GrNttPlan plan;
-    hipStream_t stream = nullptr;
-    GrMod *modc = nullptr; u64 *tw = nullptr; u64 *pinv = nullptr;
-    GrExtOwner down;                                   // ModDown: P -> Q
-    std::map<int, GrLevel> levels;
-    std::map<u64, GrKey> rotkeys; GrKey rlk;
-    void *ws = nullptr; size_t ws_bytes = 0;           // grow-only workspace of the key switch and the rescale
-    int *modidx = nullptr; size_t modidx_cap = 0;      // sfg_ring_ntt_rows' modulus table
-    unsigned char *pin = nullptr; size_t pin_bytes = 0, pin_head = 0;       // pinned staging of small uploads
-    void *small = nullptr; size_t small_bytes = 0;     // the inner sum's rotated ciphertext
-    size_t ws_budget = 768ull << 20;
-    std::string err;
-};
-#define GR_FAIL(r, ...) do { char _b[512]; snprintf(_b, sizeof _b, __VA_ARGS__); (r)->err = _b; return 1; } while (0)
-#define GR_HIP(r, call) do { hipError_t _e = (call); if (_e != hipSuccess) { char _b[512]; \
-    snprintf(_b, sizeof _b, "HIP call failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); (r)->err = _b; return 1; } } while (0)
-#define GR_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 static u64 hm_mul(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
 static u64 hm_pow(u64 a, u64 e, u64 q) { u64 r = 1 % q; a %= q; while (e) { if (e & 1) r = hm_mul(r, a, q); a = hm_mul(a, a, q); e >>= 1; } return r; }
 static u64 hm_inv(u64 a, u64 q) { return hm_pow(a, q - 2, q); }
@@ -263,7 +212,7 @@ static u64 hm_derive_psi(u64 q, int logN) {
 }
 
 // stream-ordered upload of a small host table through the pinned ring (the host array may die at return)
-static int gr_upload(sfg_ring *r, void *dst, const void *src, size_t bytes) {
+int gr_upload(sfg_ring *r, void *dst, const void *src, size_t bytes) {
     if (!bytes) return 0;
     const size_t need = (bytes + 255) & ~(size_t)255;
     if (need > r->pin_bytes) { GR_HIP(r, hipStreamSynchronize(r->stream)); GR_HIP(r, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return 0; }
@@ -273,7 +222,7 @@ static int gr_upload(sfg_ring *r, void *dst, const void *src, size_t bytes) {
     GR_HIP(r, hipMemcpyAsync(dst, slot, bytes, hipMemcpyHostToDevice, r->stream));
     return 0;
 }
-static int gr_reserve(sfg_ring *r, void **buf, size_t *have, size_t bytes) {
+int gr_reserve(sfg_ring *r, void **buf, size_t *have, size_t bytes) {
     if (bytes <= *have) return 0;
     GR_HIP(r, hipStreamSynchronize(r->stream));
     if (*buf) GR_HIP(r, hipFree(*buf));
@@ -342,7 +291,7 @@ static int gr_level(sfg_ring *r, int level, GrLevel **out) {
     return 0;
 }
 
-static int gr_transform(sfg_ring *r, u64 *rows, size_t nrows, GrRowMap map, bool inv) {
+int gr_transform(sfg_ring *r, u64 *rows, size_t nrows, GrRowMap map, bool inv) {
     const GrNttPlan &p = r->plan;
     for (size_t row0 = 0; row0 < nrows; row0 += 32768) {
         dim3 grid((unsigned)p.tiles_per_row, (unsigned)std::min<size_t>(32768, nrows - row0));
@@ -357,10 +306,10 @@ static int gr_transform(sfg_ring *r, u64 *rows, size_t nrows, GrRowMap map, bool
     GR_HIP(r, hipGetLastError());
     return 0;
 }
-static GrRowMap gr_map(int period, int split, int base0, int base1) { GrRowMap m; m.table = nullptr; m.period = period; m.split = split; m.base0 = base0; m.base1 = base1; return m; }
+GrRowMap gr_map(int period, int split, int base0, int base1) { GrRowMap m; m.table = nullptr; m.period = period; m.split = split; m.base0 = base0; m.base1 = base1; return m; }
 
 // basis extension of npoly polynomials: src [npoly][nsrc][N] (coefficient domain) -> out [npoly][ndig][ntgt][N] (coefficient domain)
-static int gr_extend(sfg_ring *r, const GrExt &e, const u64 *src, u64 *Y, uint32_t *V, u64 *out, int ntgt, size_t npoly) {
+int gr_extend(sfg_ring *r, const GrExt &e, const u64 *src, u64 *Y, uint32_t *V, u64 *out, int ntgt, size_t npoly) {
     const unsigned gx = r->N / GR_T;
     hipLaunchKernelGGL(k_gr_ext_y, dim3(gx, e.nsrc, (unsigned)npoly), dim3(GR_T), 0, r->stream, src, Y, e, r->modc, r->N);
     hipLaunchKernelGGL(k_gr_ext_v, dim3(gx, e.ndig, (unsigned)npoly), dim3(GR_T), 0, r->stream, Y, V, e, r->modc, r->N);
@@ -408,7 +357,7 @@ static int gr_keyswitch(sfg_ring *r, int level, size_t J, const GrKsWs &w, const
 }
 
 static bool gr_overlap(const void *a, size_t na, const void *b, size_t nb) { const char *x = (const char *)a, *y = (const char *)b; return x < y + nb && y < x + na; }
-static int gr_check_level(sfg_ring *r, const char *what, int nct, int level) {
+int gr_check_level(sfg_ring *r, const char *what, int nct, int level) {
     if (nct < 0) GR_FAIL(r, "%s: negative ciphertext count %d", what, nct);
     if (level < 0 || level >= r->nq) GR_FAIL(r, "%s: level %d out of range 0..%d", what, level, r->nq - 1);
     return 0;
@@ -463,6 +412,7 @@ extern "C" void sfg_ring_destroy(sfg_ring *r) {
     (void)hipFree(r->rlk.key);
     for (auto &kv : r->levels) { (void)hipFree(kv.second.up.buf); (void)hipFree(kv.second.rescale_tab); }
     (void)hipFree(r->down.buf); (void)hipFree(r->modc); (void)hipFree(r->tw); (void)hipFree(r->pinv); (void)hipFree(r->ws); (void)hipFree(r->modidx); (void)hipFree(r->small);
+    gr_io_destroy(r);
     if (r->pin) (void)hipHostFree(r->pin);
     if (r->stream) (void)hipStreamDestroy(r->stream);
     delete r;
@@ -489,6 +439,7 @@ extern "C" int sfg_ring_create(sfg_ring **out, int device, int logN, int nq, int
     if (device < 0 || device >= ndev) { g_ring_create_error = "bad device index"; return 1; }
     sfg_ring *r = new sfg_ring();
     r->device = device; r->logN = logN; r->N = N; r->nq = nq; r->np = np; r->nmod = nmod; r->beta = (nq + np - 1) / np; r->plan = plan;
+    if (const char *e = getenv("SFG_ENABLE_TEST_HOOKS")) r->test_hooks = atoi(e) == 1;
     auto fail = [&](const char *m) { std::string msg = m; sfg_ring_destroy(r); g_ring_create_error = msg; return 1; };
     if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice failed");
     if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
@@ -547,6 +498,12 @@ static int gr_rows(sfg_ring *r, const char *what, uint64_t *rows, int nrows, con
 extern "C" int sfg_ring_ntt_rows(sfg_ring *r, uint64_t *rows, int nrows, const int *mod_idx) { return gr_rows(r, "sfg_ring_ntt_rows", rows, nrows, mod_idx, false); }
 extern "C" int sfg_ring_intt_rows(sfg_ring *r, uint64_t *rows, int nrows, const int *mod_idx) { return gr_rows(r, "sfg_ring_intt_rows", rows, nrows, mod_idx, true); }
 
+int gr_rows_from_mont(sfg_ring *r, u64 *rows, size_t nrows) {
+    for (size_t r0 = 0; r0 < nrows; r0 += 32768 / r->nmod * r->nmod)       // whole groups of nmod rows per launch: blockIdx.y % nmod stays the row's modulus
+        hipLaunchKernelGGL(k_gr_from_mont, dim3(r->N / GR_T, (unsigned)std::min<size_t>(32768 / r->nmod * r->nmod, nrows - r0)), dim3(GR_T), 0, r->stream, rows + r0 * r->N, r->modc, r->nmod, r->N);
+    GR_HIP(r, hipGetLastError());
+    return 0;
+}
 static int gr_load_key(sfg_ring *r, GrKey &k, const uint64_t *key_host, int mont) {
     const size_t words = (size_t)r->beta * 2 * r->nmod * r->N;
     if (!k.key) GR_HIP(r, hipMalloc((void **)&k.key, words * 8));
