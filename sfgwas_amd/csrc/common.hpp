@@ -10,6 +10,7 @@
 #include <set>
 #include <unistd.h>
 #include "../../include/sfgwas_hip.h"
+#include "fp64mod.hpp"         // mulmod_lazy, canon, pred, ...: the fp64-held integer arithmetic
 #include "consts.hpp"          // SFG_N, SFG_SLOTS, SFG_D, SFG_MAXMOD, SFG_I8_KEEP_RESERVE, the PT_* panel flags
 
 typedef unsigned long long u64;
@@ -268,45 +269,8 @@ __device__ __host__ __forceinline__ u64 pack_limbs(u64 w) {
     return (w & 0xFFF) | (((w >> 12) & 0xFFF) << 16) | ((w >> 24) << 32);
 }
 // ---------------------------------------------------------------- device arithmetic
-// All ring arithmetic on the device is done on exact integers held in fp64 registers (|x| < 2^53):
-// measured on gfx950 v_fma_f64 and v_mad_u64_u32 issue at the same rate (profiles/r01_ubench_*.txt),
-// and the fp64 form needs no carry chains.
-
-// x*w mod q, result in (-q, q) (not canonical). Requires |x|*w < 2^105, |x| < 2^51, wq = w/q (rounded).
-__device__ __forceinline__ double mulmod_lazy(double x, double w, double wq, double q) {
-    double qh = __builtin_rint(x * wq);
-    double h = x * w;
-    double l = __builtin_fma(x, w, -h);
-    double r = __builtin_fma(-qh, q, h);
-    return r + l;
-}
-// The same product with the quotient estimated from the rounded high part: needs only 1/q, not w/q, so butterflies that take a fresh twiddle
-// spend no multiply on w * (1/q).  |x * w / q| < 2^41 keeps the estimate within 1/2 + 2^-11 of the true quotient: result in (-q, q).
-__device__ __forceinline__ double mulmod_lazy_q(double x, double w, double q, double qinv) {
-    double h = x * w;
-    double qh = __builtin_rint(h * qinv);
-    double l = __builtin_fma(x, w, -h);
-    double r = __builtin_fma(-qh, q, h);
-    return r + l;
-}
-// canonical representative in [0, q) of an integer-valued double |x| < 2^51.
-// y = fl(x * fl(1/q)) is within |x/q| * 2^-52 (1 + 2^-53) of x/q.  Write x = k q + e, 0 <= e < q: for e >= 1 both e/q and (q - e)/q exceed
-// that error (e >= 1 > |x| 2^-51), so floor(y) = k; for e = 0, y = k (1 + d) may fall just below k, floor(y) = k - 1 and the exact
-// remainder fma(-floor(y), q, x) is q.  One equality test is therefore the whole fix-up.
-__device__ __forceinline__ double canon(double x, double q, double qinv) {
-    const double r = __builtin_fma(-__builtin_floor(x * qinv), q, x);
-    return r == q ? 0.0 : r;
-}
-// partial reduction to (-q, q): cheap, for lazy sums that would otherwise grow
-// the same without the fix-up: a representative in [0, q] (q itself only for multiples of q).  Enough wherever the value is an operand of further
-// lazy arithmetic and merely has to be congruent, non-negative and <= q - e.g. the packed-limb plaintext words the MAC reads (q < 2^36 fits the limbs).
-__device__ __forceinline__ double canon_le(double x, double q, double qinv) {
-    return __builtin_fma(-__builtin_floor(x * qinv), q, x);
-}
-__device__ __forceinline__ double pred(double x, double q, double qinv) {
-    double qh = __builtin_rint(x * qinv);
-    return __builtin_fma(-qh, q, x);
-}
+// All ring arithmetic on the device is done on exact integers held in fp64 registers (|x| < 2^53): mulmod_lazy, mulmod_lazy_q, canon, canon_le, pred
+// (fp64mod.hpp, included above: __host__ __device__, so that the host tests run them too)
 __device__ __forceinline__ double u64_to_f64(u64 x) {            // exact for x < 2^52
     return __longlong_as_double((long long)(x | 0x4330000000000000ULL)) - 4503599627370496.0;
 }

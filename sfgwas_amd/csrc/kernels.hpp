@@ -28,6 +28,8 @@ int launch_ntt_plain_half(sfg_ctx *ctx, const double *pc, u64 *out_half, size_t 
 int launch_expand_half(sfg_ctx *ctx, const u64 *half, u64 *full, size_t nrows);
 int launch_ntt_fwd_map(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat, const RowMap &rm);
 int launch_ntt_inv_map(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat, const RowMap &rm);
+// dense forward NTT, out of place; staged: the rows arrive through the transform's first stage (fp64mod.hpp fwd_stage1_pair), each half-row workgroup reads only its half
+int launch_ntt_fwd_staged(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat, bool staged);
 // the MAC launches
 struct MacStrides { size_t rot_k, rot_r, pt_k, pt_n, out_n, out_r; bool pt_half = false; bool pt_packed = false; bool pt_digits = false; bool i8 = false; bool i8_big = false; bool pt_digits_big = false;
                     const int8_t *B_small = nullptr, *B_big = nullptr;
@@ -66,6 +68,8 @@ int launch_rotate_right(sfg_ctx *ctx, const u64 *in, u64 *out, int nct, int leve
 int launch_rotate_right_indexed(sfg_ctx *ctx, const u64 *in, int nin, u64 *out, int nct, int level, const int *nrot_host, const int *in_index);
 int launch_rotate_right_indexed_f64(sfg_ctx *ctx, const u64 *in, int nin, double *outf, int nct, int level, const int *nrot_host, const int *in_index, int L,
                                     const size_t *out_slot = nullptr);
+int launch_rotate_right_sum(sfg_ctx *ctx, const u64 *in, int nin, int nct, int level, const int *nrot_host, const int *in_index, const int *group, int nout,
+                            u64 *out, size_t out_stride, int accumulate);
 int launch_relinearize(sfg_ctx *ctx, const u64 *tmp, int nct, int level, const u64 *mid, u64 *out);
 int launch_ct_add(sfg_ctx *ctx, const u64 *a, const u64 *b, u64 *out, size_t nct, int level);
 // mac_dma.hip

@@ -47,19 +47,19 @@ __global__ void __launch_bounds__(256) k_drop_level(const u64 *in, u64 *out, int
     const size_t x = (blockIdx.x % (N / 256)) * 256 + threadIdx.x;
     out[row * N + x] = in[(ctp * nl_in + m) * N + x];
 }
-// out[i][j][p][l][x] (+)= sum_{k < ngiant} rot[(k*s + i)][p][l][x]   (rot holds only the aligned giants, compactly)
-__global__ void __launch_bounds__(256) k_sum_giants(const u64 *rot, int ngiant, int s, int L, u64 *out, size_t out_i_stride,
-                                                    int accumulate, const ModConst *modc) {
-    const int N = SFG_N; const size_t row = blockIdx.x / (N / 256);           // row over [i][2][L]
-    const int i = (int)(row / (2 * L)), pl = (int)(row % (2 * L)), l = pl % L;
-    const size_t x = (blockIdx.x % (N / 256)) * 256 + threadIdx.x;
-    const double q = modc[l].q, qinv = modc[l].qinv;
-    double acc = accumulate ? u64_to_f64(out[(size_t)i * out_i_stride + (size_t)pl * N + x]) : 0.0;
-    for (int g = 0; g < ngiant; g++) {
-        acc += u64_to_f64(rot[(((size_t)g * s + i) * 2 * L + pl) * N + x]);
-        if ((g & 31) == 31) acc = pred(acc, q, qinv);
-    }
-    out[(size_t)i * out_i_stride + (size_t)pl * N + x] = f64_to_u64(canon(acc, q, qinv));
+// The operand ciphertexts of jobs [job0, job0 + grid rows / (2 nl)) at the dropped level, contiguous (job = block row * s + i reads A[i][block row], A: [s][nbr][2][nl_in][N]):
+// one launch instead of one device-to-device copy per ciphertext, each of which drains the queue between two large launches.  Two words per thread.
+__global__ void __launch_bounds__(256) k_gather_operands(const u64 *A, u64 *out, int nbr, int s, int job0, int nl_in, int nl) {
+    const int N = SFG_N; const size_t row = blockIdx.x / (N / 512);           // output row over [job][2][nl]
+    const size_t k = row / (2 * (size_t)nl), p = (row / nl) & 1, m = row % nl, job = (size_t)job0 + k, bi = job / s, i = job % s;
+    const size_t x = 2 * ((blockIdx.x % (N / 512)) * 256 + threadIdx.x);
+    *reinterpret_cast<ulonglong2 *>(out + row * N + x) = *reinterpret_cast<const ulonglong2 *>(A + (((i * nbr + bi) * 2 + p) * nl_in + m) * N + x);
+}
+static int launch_gather_operands(sfg_ctx *ctx, const u64 *A, u64 *out, int nbr, int s, int job0, int njobs, int nl_in, int nl) {
+    if (njobs < 1) return 0;
+    hipLaunchKernelGGL(k_gather_operands, dim3((unsigned)((size_t)njobs * 2 * nl * (SFG_N / 512))), dim3(256), 0, ctx->stream, A, out, nbr, s, job0, nl_in, nl);
+    SFG_HIP(ctx, hipGetLastError());
+    return 0;
 }
 __global__ void __launch_bounds__(256) k_reduce_rows(u64 *rows, int L, const ModConst *modc) {
     const int N = SFG_N; const size_t row = blockIdx.x / (N / 256); const int l = (int)(row % L);
@@ -374,13 +374,8 @@ static int build_rot_row(sfg_ctx *ctx, const u64 *A, int s, int nl_in, int nl, i
 }
 static int build_rot_row_tab(sfg_ctx *ctx, const u64 *A, int s, int nl_in, int nl, int lev, int L, int nbr, int bi, const std::vector<uint8_t> &baby_t,
                              u64 *a_row, u64 *rotc, bool dma, double *rotf_dst) {
-    const int N = SFG_N, d = SFG_D; const size_t ctw = (size_t)2 * nl * N;
-    for (int i = 0; i < s; i++) {                  // A[i][bi] at the dropped level, contiguous over i
-        const u64 *src = A + ((size_t)i * nbr + bi) * 2 * nl_in * N;
-        if (nl == nl_in) SFG_HIP(ctx, hipMemcpyAsync(a_row + (size_t)i * ctw, src, ctw * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        else hipLaunchKernelGGL(k_drop_level, dim3((unsigned)(2 * nl * (N / 256))), dim3(256), 0, ctx->stream, src, a_row + (size_t)i * ctw, nl_in, nl);
-    }
-    SFG_HIP(ctx, hipGetLastError());
+    const int d = SFG_D;
+    SFG_TRY(launch_gather_operands(ctx, A, a_row, nbr, s, bi * s, s, nl_in, nl));          // A[i][bi] at the dropped level, contiguous over i
     {
         PhaseTimer t(ctx, "rotate");
         std::vector<int> nrv((size_t)d * s, 0), inv((size_t)d * s, 0);
@@ -644,28 +639,21 @@ static int matmul_finalize(sfg_ctx *ctx, const u64 *acc, int s, int max_level, i
     const int N = SFG_N, d = SFG_D, L = max_level;
     const size_t accw = (size_t)s * 2 * L * N, ctw = (size_t)2 * L * N;
     if (g0 < 0 || g1 > acc_giants || g0 > g1 || giant_base < 0) SFG_FAIL(ctx, "finalize: giant range out of bounds");
-    u64 *rot = nullptr;
-    SFG_TRY(sfg_scratch(ctx, "mm.fin_rot", (size_t)d * accw * 8, (void **)&rot));
     std::vector<int> glist;
     for (int g = g0; g < g1; g++) if (giant_base + g < d && (!giant_active || (*giant_active)[giant_base + g])) glist.push_back(g);
     const int ng = (int)glist.size();
-    // only the listed giants are aligned (a rank of a giant-sharded finalize owns ~91/world of them): job (k, i) reads
-    // accumulator ciphertext glist[k]*s + i and lands compactly at k*s + i
-    std::vector<int> nrv((size_t)ng * s), inv((size_t)ng * s);
-    for (int k = 0; k < ng; k++) for (int i = 0; i < s; i++) { nrv[(size_t)k * s + i] = -(giant_base + glist[k]) * d; inv[(size_t)k * s + i] = glist[k] * s + i; }
+    // only the listed giants are aligned (a rank of a giant-sharded finalize owns ~91/world of them): job (k, i) reads accumulator ciphertext
+    // glist[k]*s + i and adds into output i.  The aligned giants are summed where the key switch finishes them (rotate.hip k_ksw_finish_sum): no rotated
+    // ciphertext crosses HBM, and giant 0, which does not rotate, joins the sum as a plain read.
+    std::vector<int> nrv((size_t)ng * s), inv((size_t)ng * s), grp((size_t)ng * s);
+    for (int k = 0; k < ng; k++) for (int i = 0; i < s; i++) { nrv[(size_t)k * s + i] = -(giant_base + glist[k]) * d; inv[(size_t)k * s + i] = glist[k] * s + i; grp[(size_t)k * s + i] = i; }
     int rc = 0;
     for (int jb = 0; jb < ncolb && !rc; jb++) {
         const u64 *accj = acc + (size_t)jb * acc_giants * accw;
         u64 *o = out + (size_t)(jout0 + jb) * ctw;
-        if (ng) {
-            PhaseTimer t(ctx, "rotate");
-            rc = launch_rotate_right_indexed(ctx, accj, acc_giants * s, rot, ng * s, L - 1, nrv.data(), inv.data());
-            t.stop(1);
-            if (rc) break;
-        }
-        hipLaunchKernelGGL(k_sum_giants, dim3((unsigned)((size_t)s * 2 * L * (N / 256))), dim3(256), 0, ctx->stream, rot, ng, s, L,
-                           o, (size_t)m_ct_out * ctw, accumulate, ctx->modc);
-        if (hipGetLastError() != hipSuccess) { rc = 1; ctx->err = "finalize: k_sum_giants launch failed"; }
+        PhaseTimer t(ctx, "rotate");
+        rc = launch_rotate_right_sum(ctx, accj, acc_giants * s, ng * s, L - 1, nrv.data(), inv.data(), grp.data(), s, o, (size_t)m_ct_out * ctw, accumulate);
+        t.stop(1);
     }
     return rc;
 }
@@ -823,13 +811,7 @@ extern "C" int sfg_rotcache_build_jobs_dev(sfg_ctx *ctx, const uint64_t *A, int 
     PhaseTimer t(ctx, "rotate");
     for (int c0 = job0; c0 < job1; c0 += CH) {
         const int nj = std::min(CH, job1 - c0);
-        for (int k = 0; k < nj; k++) {
-            const int job = c0 + k, bi = job / s, i = job % s;
-            const u64 *src = (const u64 *)A + ((size_t)i * nbr + bi) * 2 * nl_in * N;
-            if (nl == nl_in) SFG_HIP(ctx, hipMemcpyAsync(a_in + (size_t)k * ctw, src, ctw * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            else hipLaunchKernelGGL(k_drop_level, dim3((unsigned)(2 * nl * (N / 256))), dim3(256), 0, ctx->stream, src, a_in + (size_t)k * ctw, nl_in, nl);
-        }
-        SFG_HIP(ctx, hipGetLastError());
+        SFG_TRY(launch_gather_operands(ctx, (const u64 *)A, a_in, nbr, s, c0, nj, nl_in, nl));
         std::vector<int> nrv((size_t)d * nj), inv((size_t)d * nj); std::vector<size_t> slot((size_t)d * nj);
         for (int baby = 0; baby < d; baby++) for (int k = 0; k < nj; k++) {        // key-major job order, job-major output
             nrv[(size_t)baby * nj + k] = -baby; inv[(size_t)baby * nj + k] = k; slot[(size_t)baby * nj + k] = (size_t)(c0 - job0 + k) * d + baby;

@@ -392,6 +392,9 @@ __global__ void __launch_bounds__(256, 4) k_ntt_half3_move(const double *pc_all,
 // Forward NTT of general rows as TWO such workgroups per row (the key switch, Rescale, the bootstrap shares): 256 threads and 33 KiB each, three to a
 // CU, instead of one 512-thread workgroup holding a 132 KiB image.  Each half reads both halves of the input (the second read is an L2 hit: the two
 // workgroups of a row are numbered b and b + 8, same XCD) and pays the stage-1 product itself.
+// STAGED: the row's writer has applied stage 1 (fp64mod.hpp fwd_stage1_pair: the key switch's extension kernels, which wait for memory): a half-workgroup loads its own
+// half only and starts at stage 2 - half the input bytes and 32 lazy products per thread less.
+template <bool STAGED>
 __global__ void __launch_bounds__(256, 4) k_ntt_fwd_split(const u64 *in_, u64 *out_, size_t nrows, ModPattern pat, RowMap rm, const double *tw_all, const double2 *pack_all, const ModConst *modc) {
     extern __shared__ double lds[];
     const int N = SFG_N, n = N / 2, tid = threadIdx.x;
@@ -410,7 +413,7 @@ __global__ void __launch_bounds__(256, 4) k_ntt_fwd_split(const u64 *in_, u64 *o
     const double2 *pack = pack_all + (size_t)m * (N / 2);
     const double q = modc[m].q, qinv = modc[m].qinv;
     const double W = hs ? -tw[1] : tw[1], Wq = W * qinv;
-    auto first = [&](int j) { return u64_to_f64(in[j]) + mulmod_lazy(u64_to_f64(in[n + j]), W, Wq, q); };
+    auto first = [&](int j) { return STAGED ? u64_to_f64(in[(size_t)hs * n + j]) : u64_to_f64(in[j]) + mulmod_lazy(u64_to_f64(in[n + j]), W, Wq, q); };
     ntt_half3_body(hs, first, [&](int j, double x) { out[j] = f64_to_u64(canon(x, q, qinv)); }, lds, tw, pack, q, qinv, tid);
 }
 // full rows from half rows: out[i] = out[N-1-i] = half[i]
@@ -429,7 +432,8 @@ int ntt_set_attrs(sfg_ctx *ctx) {
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_half3<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_half3<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_half3<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_fwd_split, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_fwd_split<false>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_fwd_split<true>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
 #define SFG_MV_ATTR(P, D, T) if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_half3_move<P, D, T>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES)
     SFG_MV_ATTR(false, 1, true); SFG_MV_ATTR(true, 1, true);              // the product's riding transposition: one unit in flight, streaming loads and stores
 #ifdef SFG_AB
@@ -449,9 +453,17 @@ int launch_ntt_fwd_map(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, cons
     if (!nrows) return 0;
     // in place the two half-workgroups of a row would overwrite each other's input: the split form needs distinct buffers
     if (in != out && !ctx->cfg.ntt_fwd_full)
-        hipLaunchKernelGGL(k_ntt_fwd_split, dim3((unsigned)((nrows + 7) / 8 * 16)), dim3(256), H3_LDS_BYTES, ctx->stream, in, out, nrows, pat, rm, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
+        hipLaunchKernelGGL(k_ntt_fwd_split<false>, dim3((unsigned)((nrows + 7) / 8 * 16)), dim3(256), H3_LDS_BYTES, ctx->stream, in, out, nrows, pat, rm, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
     else
         hipLaunchKernelGGL(k_ntt_fwd<0>, dim3((unsigned)nrows), dim3(512), LDS_DOUBLES * 8, ctx->stream, (const void *)in, out, pat, rm, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
+    SFG_HIP(ctx, hipGetLastError());
+    return 0;
+}
+int launch_ntt_fwd_staged(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat, bool staged) {
+    if (!staged) return launch_ntt_fwd(ctx, in, out, nrows, pat);
+    if (!nrows) return 0;
+    if (in == out) SFG_FAIL(ctx, "forward NTT: rows staged through stage 1 are transformed out of place");
+    hipLaunchKernelGGL(k_ntt_fwd_split<true>, dim3((unsigned)((nrows + 7) / 8 * 16)), dim3(256), H3_LDS_BYTES, ctx->stream, in, out, nrows, pat, dense_map(), ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
     SFG_HIP(ctx, hipGetLastError());
     return 0;
 }

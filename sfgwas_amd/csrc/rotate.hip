@@ -13,6 +13,9 @@
 //   5. out0 = perm(c0 + (acc0 - ext0) / P), out1 = perm((acc1 - ext1) / P)                        (k_ksw_finish)
 // The float correction v = uint64(sum float64(y_m)/float64(q_m)) is lattigo's (ring.Decomposer /
 // FastBasisExtender); the oracle mirrors it, so results agree bit for bit.
+// Which kernel computes what (profiles/ksw_fused_ab.txt): the extension kernels of 2 and 4 apply the forward transform's first stage to the rows they write, so the
+// split transform reads half a row per workgroup and starts at stage 2; a job written as MAC operand rows produces nothing of the moduli the MAC does not read;
+// jobs whose results are summed (the giant-step alignment) are summed in step 5 (k_ksw_finish_sum).  Every output word is the canonical word it was.
 #include "common.hpp"
 #include "kernels.hpp"
 #include "ksw.hpp"
@@ -73,32 +76,40 @@ int get_ksw(sfg_ctx *ctx, int level, KswConst **dev, KswConst *host) {
 }
 
 
-// grid (N/256, beta, B). c2: [B][nl][N] coefficient-domain c1; cx: original ct (c1 rows at +nl*N); ext: [B][beta][nt][N]
-__global__ void __launch_bounds__(256) k_ksw_extend(const u64 *c2, const u64 *ct_in, u64 *ext, const KswConst *kcp, const ModConst *modc) {
+// grid (N/512, beta, B). c2: [B][nl][N] coefficient-domain c1; ext: [B][beta][nt][N].  A thread extends positions x and x + N/2, so that it can apply
+// the forward transform's first stage to the rows it writes (PRE1, fp64mod.hpp fwd_stage1_pair): the element-wise kernels wait for memory and have fp64
+// issue slots to spare, the transforms do not.
+template <bool PRE1>
+__global__ void __launch_bounds__(256) k_ksw_extend(const u64 *c2, u64 *ext, const KswConst *kcp, const ModConst *modc, const double *tw_fwd) {
     const KswConst &kc = *kcp;
-    const int N = SFG_N, x = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y; const size_t b = blockIdx.z;
+    const int N = SFG_N, n = N / 2, x = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y; const size_t b = blockIdx.z;
     const ExtConst &e = kc.dig[i];
     const u64 *c2b = c2 + b * (size_t)kc.nl * N;
     u64 *eb = ext + (b * kc.beta + i) * (size_t)kc.nt * N;
-    double xs[KSW_MAXA], y[KSW_MAXA], v = 0.0;
+    double xs[2][KSW_MAXA], y[2][KSW_MAXA], v[2] = {0.0, 0.0};
 #pragma unroll
-    for (int m = 0; m < KSW_MAXA; m++) xs[m] = m < e.a ? u64_to_f64(c2b[(size_t)e.src[m] * N + x]) : 0.0;
-    if (e.a > 1) ext_prepare(e, modc, xs, y, v);
+    for (int h = 0; h < 2; h++)
+#pragma unroll
+        for (int m = 0; m < KSW_MAXA; m++) xs[h][m] = m < e.a ? u64_to_f64(c2b[(size_t)e.src[m] * N + h * n + x]) : 0.0;
+    if (e.a > 1) { ext_prepare(e, modc, xs[0], y[0], v[0]); ext_prepare(e, modc, xs[1], y[1], v[1]); }
     for (int t = 0; t < kc.nt; t++) {
         const int tg = kc.tmod[t];
-        u64 outv;
         if (kc.digit_of[t] == i) continue;                                            // in-digit: the original NTT row, which k_ksw_inner reads where it lies
-        else if (e.a == 1) outv = f64_to_u64(canon(xs[0], modc[tg].q, modc[tg].qinv)); // single-prime digit: raw copy mod q_t
-        else outv = f64_to_u64(ext_target(e, tg, modc[tg].q, modc[tg].qinv, y, v));
-        eb[(size_t)t * N + x] = outv;
+        const double q = modc[tg].q, qinv = modc[tg].qinv;
+        double o0, o1;
+        if (e.a == 1) { o0 = canon(xs[0][0], q, qinv); o1 = canon(xs[1][0], q, qinv); }      // single-prime digit: raw copy mod q_t
+        else { o0 = ext_target(e, tg, q, qinv, y[0], v[0]); o1 = ext_target(e, tg, q, qinv, y[1], v[1]); }
+        if (PRE1) { const double W = tw_fwd[(size_t)tg * N + 1]; fwd_stage1_pair(o0, o1, W, W * qinv, q, qinv, o0, o1); }
+        eb[(size_t)t * N + x] = f64_to_u64(o0); eb[(size_t)t * N + n + x] = f64_to_u64(o1);
     }
 }
 
-// grid (N/512, nt, B). acc: [B][2][nt][N]; inidx[b] = which decomposed input feeds output b.  Two coefficients per thread: 16-byte loads and stores.
+// grid (N/512, nq_out + np, B). acc: [B][2][nt][N]; inidx[b] = which decomposed input feeds output b.  Two coefficients per thread: 16-byte loads and stores.
+// Only the first nq_out <= nl moduli of the output are stored by the finish (F64Form): targets [nq_out, nl) are not computed, the special primes follow directly.
 // The row of digit i at a target inside digit i is the input's own NTT row (polynomial 1 of ct_in): read there, never copied (round 4: 15 of ~250 row transfers per switch less)
-__global__ void __launch_bounds__(256) k_ksw_inner(const u64 *ext, const u64 *ct_in, const u64 *const *keys, const int *inidx, u64 *acc, const KswConst *kcp, const ModConst *modc, int nmod) {
+__global__ void __launch_bounds__(256) k_ksw_inner(const u64 *ext, const u64 *ct_in, const u64 *const *keys, const int *inidx, u64 *acc, const KswConst *kcp, const ModConst *modc, int nmod, int nq_out) {
     const KswConst &kc = *kcp;
-    const int N = SFG_N, x = 2 * (blockIdx.x * 256 + threadIdx.x), t = blockIdx.y; const size_t b = blockIdx.z;
+    const int N = SFG_N, x = 2 * (blockIdx.x * 256 + threadIdx.x), t = (int)blockIdx.y < nq_out ? (int)blockIdx.y : (int)blockIdx.y + (kc.nl - nq_out); const size_t b = blockIdx.z;
     const int tg = kc.tmod[t];
     const double q = modc[tg].q, qinv = modc[tg].qinv;
     const u64 *key = keys[b];
@@ -117,19 +128,28 @@ __global__ void __launch_bounds__(256) k_ksw_inner(const u64 *ext, const u64 *ct
     *reinterpret_cast<ulonglong2 *>(acc + ((b * 2 + 1) * (size_t)kc.nt + t) * N + x) = make_ulonglong2(f64_to_u64(canon(a1x, q, qinv)), f64_to_u64(canon(a1y, q, qinv)));
 }
 
-// grid (N/256, 2, B): special-prime rows of acc (already INTT'd) -> ext2 [B][2][nl][N] coefficient domain
-__global__ void __launch_bounds__(256) k_moddown_extend(const u64 *acc, u64 *ext2, const KswConst *kcp, const ModConst *modc) {
+// grid (N/512, 2, B): special-prime rows of acc (already INTT'd) -> ext2 [B][2][nl][N] coefficient domain, rows t < nq_out (the others nobody reads).
+// Positions x and x + N/2 in one thread, PRE1 as in k_ksw_extend.
+template <bool PRE1>
+__global__ void __launch_bounds__(256) k_moddown_extend(const u64 *acc, u64 *ext2, const KswConst *kcp, const ModConst *modc, const double *tw_fwd, int nq_out) {
     const KswConst &kc = *kcp;
-    const int N = SFG_N, x = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y; const size_t b = blockIdx.z;
+    const int N = SFG_N, n = N / 2, x = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y; const size_t b = blockIdx.z;
     const ExtConst &e = kc.pq;
     const u64 *ap = acc + ((b * 2 + p) * (size_t)kc.nt + kc.nl) * N;
-    double xs[KSW_MAXA], y[KSW_MAXA], v = 0.0;
+    double xs[2][KSW_MAXA], y[2][KSW_MAXA], v[2] = {0.0, 0.0};
 #pragma unroll
-    for (int m = 0; m < KSW_MAXA; m++) xs[m] = m < e.a ? u64_to_f64(ap[(size_t)m * N + x]) : 0.0;
-    if (e.a > 1) ext_prepare(e, modc, xs, y, v);
-    for (int t = 0; t < kc.nl; t++) {
-        u64 outv = e.a == 1 ? f64_to_u64(canon(xs[0], modc[t].q, modc[t].qinv)) : f64_to_u64(ext_target(e, t, modc[t].q, modc[t].qinv, y, v));
-        ext2[((b * 2 + p) * (size_t)kc.nl + t) * N + x] = outv;
+    for (int h = 0; h < 2; h++)
+#pragma unroll
+        for (int m = 0; m < KSW_MAXA; m++) xs[h][m] = m < e.a ? u64_to_f64(ap[(size_t)m * N + h * n + x]) : 0.0;
+    if (e.a > 1) { ext_prepare(e, modc, xs[0], y[0], v[0]); ext_prepare(e, modc, xs[1], y[1], v[1]); }
+    for (int t = 0; t < nq_out; t++) {
+        const double q = modc[t].q, qinv = modc[t].qinv;
+        double o0, o1;
+        if (e.a == 1) { o0 = canon(xs[0][0], q, qinv); o1 = canon(xs[1][0], q, qinv); }
+        else { o0 = ext_target(e, t, q, qinv, y[0], v[0]); o1 = ext_target(e, t, q, qinv, y[1], v[1]); }
+        if (PRE1) { const double W = tw_fwd[(size_t)t * N + 1]; fwd_stage1_pair(o0, o1, W, W * qinv, q, qinv, o0, o1); }
+        u64 *row = ext2 + ((b * 2 + p) * (size_t)kc.nl + t) * N;
+        row[x] = f64_to_u64(o0); row[n + x] = f64_to_u64(o1);
     }
 }
 
@@ -168,6 +188,34 @@ __global__ void __launch_bounds__(256) k_ksw_finish(const u64 *ct_in, const int 
     }
 }
 
+// The finish of jobs whose results are SUMMED (the giant-step alignment, KswSum): grid (N/256, nl, segments), one thread per output word of both polynomials.
+// A segment is one output and the jobs of this chunk that add into it (jobs[start .. start + count), chunk-local numbers): each job with its own automorphism
+// table, key-switched rows and c0.  The canonical results are added as exact integers (reduced every 8 jobs: below 11 q < 2^51), an unrotated member (plain)
+// joins as a plain read, and the sum is reduced once: the canonical word the separate rotations, summed afterwards, give.
+struct KswSeg { const u64 *plain; u64 *out; int start, count, accumulate, pad; };
+__global__ void __launch_bounds__(256) k_ksw_finish_sum(const u64 *ct_in, const int *inidx, const u64 *acc, const u64 *ext2, const uint16_t *const *index,
+                                                       const KswSeg *segs, const int *jobs, const KswConst *kcp, const ModConst *modc) {
+    const KswConst &kc = *kcp;
+    const int N = SFG_N, x = blockIdx.x * 256 + threadIdx.x, t = blockIdx.y;
+    const KswSeg sg = segs[blockIdx.z];
+    const double q = modc[t].q, qinv = modc[t].qinv, pinv = kc.pinv[t], pinv_q = kc.pinv_q[t];
+    const size_t w0 = (size_t)t * N + x, w1 = ((size_t)kc.nl + t) * N + x;
+    double s0 = 0.0, s1 = 0.0;
+    if (sg.accumulate) { s0 = u64_to_f64(sg.out[w0]); s1 = u64_to_f64(sg.out[w1]); }
+    if (sg.plain) { s0 += u64_to_f64(sg.plain[w0]); s1 += u64_to_f64(sg.plain[w1]); }
+    for (int k = 0; k < sg.count; k++) {
+        const size_t b = (size_t)jobs[sg.start + k];
+        const int src = index[b][x];
+        const double a0 = u64_to_f64(acc[((b * 2 + 0) * (size_t)kc.nt + t) * N + src]), e0 = u64_to_f64(ext2[((b * 2 + 0) * (size_t)kc.nl + t) * N + src]);
+        const double a1 = u64_to_f64(acc[((b * 2 + 1) * (size_t)kc.nt + t) * N + src]), e1 = u64_to_f64(ext2[((b * 2 + 1) * (size_t)kc.nl + t) * N + src]);
+        const double c0 = u64_to_f64(ct_in[((size_t)inidx[b] * 2 * (size_t)kc.nl + t) * N + src]);
+        s0 += canon(mulmod_lazy(a0 - e0, pinv, pinv_q, q) + c0, q, qinv);
+        s1 += canon(mulmod_lazy(a1 - e1, pinv, pinv_q, q), q, qinv);
+        if ((k & 7) == 7) { s0 = pred(s0, q, qinv); s1 = pred(s1, q, qinv); }
+    }
+    sg.out[w0] = f64_to_u64(canon(s0, q, qinv)); sg.out[w1] = f64_to_u64(canon(s1, q, qinv));
+}
+
 __global__ void __launch_bounds__(256) k_ct_add(const u64 *a, const u64 *b, u64 *out, int nl, const ModConst *modc, size_t total_rows) {
     const int N = SFG_N; const size_t row = blockIdx.x / (N / 256); const int m = (int)(row % nl);
     const u64 q = modc[m].qi;
@@ -180,21 +228,29 @@ __global__ void __launch_bounds__(256) k_ct_add(const u64 *a, const u64 *b, u64 
 //   out0 = perm(in.p0 + d0), out1 = perm(d1 [+ add1[in]])            to outp[k].
 // Decomposition (steps 1-2) is done once per INPUT and shared by all its jobs ("hoisting"): the per-key work is
 // only the inner product, ModDown and the automorphism.  Same arithmetic, same bits.
+// With a KswSum the jobs' results are not stored one by one (outp is not read): job k adds into output group[k] < nout, and output i becomes
+//   [its old content, when accumulate] + [plain[i], an unrotated ciphertext, when not null] + sum of its jobs     at out + i * out_stride,
+// every word reduced once (k_ksw_finish_sum).  An input group or job chunk may hold any part of an output's jobs: the first part writes, the others add.
+struct KswSum { int nout; std::vector<int> group; std::vector<const u64 *> plain; u64 *out; size_t out_stride; int accumulate; };
 static int launch_keyswitch_jobs(sfg_ctx *ctx, const u64 *in, int nin, int level, const std::vector<int> &job_in, const std::vector<const u64 *> &keyp,
-                                 const std::vector<const uint16_t *> &idxp, const std::vector<u64 *> &outp, const u64 *add1, const F64Form *ffp = nullptr) {
+                                 const std::vector<const uint16_t *> &idxp, const std::vector<u64 *> &outp, const u64 *add1, const F64Form *ffp = nullptr,
+                                 const KswSum *sum = nullptr) {
     const int N = SFG_N, nl = level + 1;
     F64Form ff; memset(&ff, 0, sizeof ff); if (ffp) ff = *ffp;
     KswConst *kcd; KswConst kc;
     SFG_TRY(get_ksw(ctx, level, &kcd, &kc));
     const size_t ctw = (size_t)2 * nl * N;
-    const int nr = (int)job_in.size();
-    if (!nr) return 0;
+    const int nr = (int)job_in.size(), nout = sum ? sum->nout : 0;
+    if (sum && (ff.on || add1 || (int)sum->group.size() != nr || (int)sum->plain.size() != nout)) SFG_FAIL(ctx, "key switch: internal: malformed sum groups");
+    if (!nr && !nout) return 0;
+    const int nq_out = ff.on ? ff.L : nl;                       // moduli of the result that the finish stores: the rows of the others are not produced
+    const bool pre1 = !ctx->cfg.ntt_fwd_full;                   // the extension kernels apply the forward transform's first stage (the split transform starts at stage 2)
     // inputs are processed in groups whose decomposition fits the budget (4 GiB by default); jobs of a group in chunks whose acc/ext2 fit it
     const size_t in_rows = (size_t)nl + (size_t)kc.beta * kc.nt, job_rows = 2 * (size_t)kc.nt + 2 * (size_t)nl;
     const size_t budget = ctx->cfg.ksw_budget;                  // bytes of decomposition / accumulator scratch per group resp. chunk (SFG_KSW_BUDGET_MB)
     int in_grp = (int)(budget / (in_rows * N * 8)); if (in_grp < 1) in_grp = 1; if (in_grp > nin) in_grp = nin;
     int chunk = (int)(budget / (job_rows * N * 8)); if (chunk < 1) chunk = 1; if (chunk > nr) chunk = nr;
-    const size_t ptr_bytes = (size_t)nr * (3 * sizeof(void *) + sizeof(int)) + 256;     // pointer tables for every job of a group
+    const size_t ptr_bytes = (size_t)nr * (3 * sizeof(void *) + 2 * sizeof(int)) + (size_t)nout * sizeof(KswSeg) + 256;     // pointer tables for every job of a group, segments of a chunk
     // the forward NTTs run out of place (two half-row workgroups per row cannot share a buffer with their input): extT / ext2T receive the transforms
     const size_t ext_rows = (size_t)in_grp * kc.beta * kc.nt, ext2_rows = (size_t)chunk * 2 * nl;
     SFG_TRY(sfg_ws_reserve(ctx, (in_rows * in_grp + job_rows * chunk + ext_rows + ext2_rows) * N * 8 + ptr_bytes));
@@ -204,10 +260,35 @@ static int launch_keyswitch_jobs(sfg_ctx *ctx, const u64 *in, int nin, int level
     const u64 **keys_all = (const u64 **)(ext2T + ext2_rows * N);
     const uint16_t **idx_all = (const uint16_t **)(keys_all + nr);
     u64 **out_all = (u64 **)(idx_all + nr);
-    int *inidx_all = (int *)(out_all + nr);
-    ModPattern pq; pq.period = nl; for (int m = 0; m < nl; m++) pq.m[m] = (int8_t)m;
+    KswSeg *segs_d = (KswSeg *)(out_all + nr);
+    int *inidx_all = (int *)(segs_d + nout);
+    int *segjobs_d = inidx_all + nr;
+    std::vector<char> seen(nout, 0);                            // outputs of a sum that have been written by an earlier chunk
+    std::vector<KswSeg> segs; std::vector<int> segjobs;
+    auto finish_sum = [&](const std::vector<int> &jobs, size_t c0, int nb, const u64 *bin, const int *inidx_d, const uint16_t **idx_d) -> int {
+        // the chunk's jobs by output (nb == 0: the outputs no job has touched)
+        std::vector<int> cnt(nout, 0), at(nout, 0);
+        for (int k = 0; k < nb; k++) cnt[sum->group[jobs[c0 + k]]]++;
+        segs.clear(); segjobs.assign(nb, 0);
+        for (int i = 0, start = 0; i < nout; i++) {
+            if (nb ? !cnt[i] : seen[i]) continue;
+            KswSeg sg; sg.plain = seen[i] ? nullptr : sum->plain[i]; sg.out = sum->out + (size_t)i * sum->out_stride;
+            sg.start = start; sg.count = cnt[i]; sg.accumulate = (sum->accumulate || seen[i]) ? 1 : 0; sg.pad = 0;
+            at[i] = start; start += cnt[i]; seen[i] = 1; segs.push_back(sg);
+        }
+        for (int k = 0; k < nb; k++) segjobs[at[sum->group[jobs[c0 + k]]]++] = k;
+        if (segs.empty()) return 0;
+        SFG_TRY(sfg_upload_small(ctx, segs_d, segs.data(), segs.size() * sizeof(KswSeg)));
+        SFG_TRY(sfg_upload_small(ctx, segjobs_d, segjobs.data(), (size_t)nb * sizeof(int)));
+        hipLaunchKernelGGL(k_ksw_finish_sum, dim3(N / 256, nl, (unsigned)segs.size()), dim3(256), 0, ctx->stream, bin, inidx_d, acc, ext2T, idx_d, segs_d, segjobs_d, kcd, ctx->modc);
+        SFG_HIP(ctx, hipGetLastError());
+        return 0;
+    };
+    ModPattern pq; pq.period = nl; for (int m = 0; m < nl; m++) pq.m[m] = m < nq_out ? (int8_t)m : (int8_t)-2;
+    ModPattern pin; pin.period = nl; for (int m = 0; m < nl; m++) pin.m[m] = (int8_t)m;
     ModPattern pext; pext.period = kc.beta * kc.nt;
-    for (int i = 0; i < kc.beta; i++) for (int t = 0; t < kc.nt; t++) pext.m[i * kc.nt + t] = kc.digit_of[t] == i ? (int8_t)-2 : (int8_t)kc.tmod[t];      // in-digit rows: nobody reads them
+    for (int i = 0; i < kc.beta; i++) for (int t = 0; t < kc.nt; t++)           // in-digit rows and the targets the finish does not store: nobody reads them
+        pext.m[i * kc.nt + t] = (kc.digit_of[t] == i || (t >= nq_out && t < nl)) ? (int8_t)-2 : (int8_t)kc.tmod[t];
     ModPattern pp; pp.period = kc.np; for (int p = 0; p < kc.np; p++) pp.m[p] = (int8_t)(ctx->nq + p);
     for (int i0 = 0; i0 < nin; i0 += in_grp) {
         const int ni = nin - i0 < in_grp ? nin - i0 : in_grp;
@@ -217,39 +298,43 @@ static int launch_keyswitch_jobs(sfg_ctx *ctx, const u64 *in, int nin, int level
         const u64 *bin = in + (size_t)i0 * ctw;
         // 1. c2 = INTT(c1) for every input of the group
         RowMap rm1; rm1.rpg = nl; rm1.gstride_in = ctw; rm1.gstride_out = (size_t)nl * N;
-        SFG_TRY(launch_ntt_inv_map(ctx, bin + (size_t)nl * N, c2, (size_t)ni * nl, pq, rm1));
+        SFG_TRY(launch_ntt_inv_map(ctx, bin + (size_t)nl * N, c2, (size_t)ni * nl, pin, rm1));
         // 2. digit extension + NTT (in-digit rows are skipped by the pattern)
-        hipLaunchKernelGGL(k_ksw_extend, dim3(N / 256, kc.beta, ni), dim3(256), 0, ctx->stream, c2, bin, ext, kcd, ctx->modc);
+        if (pre1) hipLaunchKernelGGL(k_ksw_extend<true>, dim3(N / 512, kc.beta, ni), dim3(256), 0, ctx->stream, c2, ext, kcd, ctx->modc, ctx->tw_fwd);
+        else hipLaunchKernelGGL(k_ksw_extend<false>, dim3(N / 512, kc.beta, ni), dim3(256), 0, ctx->stream, c2, ext, kcd, ctx->modc, ctx->tw_fwd);
         SFG_HIP(ctx, hipGetLastError());
-        SFG_TRY(launch_ntt_fwd(ctx, ext, extT, (size_t)ni * kc.beta * kc.nt, pext));          // in-digit rows (pattern -1) are copied through
+        SFG_TRY(launch_ntt_fwd_staged(ctx, ext, extT, (size_t)ni * kc.beta * kc.nt, pext, pre1));
         // pointer tables of the whole group: staged in the pinned ring, stream-ordered (no host wait on the launch path)
         {
             const size_t nj = jobs.size();
             std::vector<const u64 *> kp(nj); std::vector<const uint16_t *> ip(nj); std::vector<u64 *> op(nj); std::vector<int> ii(nj);
-            for (size_t k = 0; k < nj; k++) { int jb = jobs[k]; kp[k] = keyp[jb]; ip[k] = idxp[jb]; op[k] = outp[jb]; ii[k] = job_in[jb] - i0; }
+            for (size_t k = 0; k < nj; k++) { int jb = jobs[k]; kp[k] = keyp[jb]; ip[k] = idxp[jb]; op[k] = sum ? nullptr : outp[jb]; ii[k] = job_in[jb] - i0; }
             SFG_TRY(sfg_upload_small(ctx, keys_all, kp.data(), nj * sizeof(void *)));
             SFG_TRY(sfg_upload_small(ctx, idx_all, ip.data(), nj * sizeof(void *)));
-            SFG_TRY(sfg_upload_small(ctx, out_all, op.data(), nj * sizeof(void *)));
+            if (!sum) SFG_TRY(sfg_upload_small(ctx, out_all, op.data(), nj * sizeof(void *)));
             SFG_TRY(sfg_upload_small(ctx, inidx_all, ii.data(), nj * sizeof(int)));
         }
         for (size_t c0 = 0; c0 < jobs.size(); c0 += chunk) {
             const int nb = (int)(jobs.size() - c0 < (size_t)chunk ? jobs.size() - c0 : (size_t)chunk);
             const u64 **keys_d = keys_all + c0; const uint16_t **idx_d = idx_all + c0; u64 **out_d = out_all + c0; int *inidx_d = inidx_all + c0;
             // 3. inner product with the key
-            hipLaunchKernelGGL(k_ksw_inner, dim3(N / 512, kc.nt, nb), dim3(256), 0, ctx->stream, extT, bin, keys_d, inidx_d, acc, kcd, ctx->modc, ctx->nmod);
+            hipLaunchKernelGGL(k_ksw_inner, dim3(N / 512, nq_out + kc.np, nb), dim3(256), 0, ctx->stream, extT, bin, keys_d, inidx_d, acc, kcd, ctx->modc, ctx->nmod, nq_out);
             SFG_HIP(ctx, hipGetLastError());
             // 4. ModDown: INTT special rows in place, extend to Q, NTT
             RowMap rm4; rm4.rpg = kc.np; rm4.gstride_in = (size_t)kc.nt * N; rm4.gstride_out = (size_t)kc.nt * N;
             SFG_TRY(launch_ntt_inv_map(ctx, acc + (size_t)nl * N, acc + (size_t)nl * N, (size_t)nb * 2 * kc.np, pp, rm4));
-            hipLaunchKernelGGL(k_moddown_extend, dim3(N / 256, 2, nb), dim3(256), 0, ctx->stream, acc, ext2, kcd, ctx->modc);
+            if (pre1) hipLaunchKernelGGL(k_moddown_extend<true>, dim3(N / 512, 2, nb), dim3(256), 0, ctx->stream, acc, ext2, kcd, ctx->modc, ctx->tw_fwd, nq_out);
+            else hipLaunchKernelGGL(k_moddown_extend<false>, dim3(N / 512, 2, nb), dim3(256), 0, ctx->stream, acc, ext2, kcd, ctx->modc, ctx->tw_fwd, nq_out);
             SFG_HIP(ctx, hipGetLastError());
-            SFG_TRY(launch_ntt_fwd(ctx, ext2, ext2T, (size_t)nb * 2 * nl, pq));
+            SFG_TRY(launch_ntt_fwd_staged(ctx, ext2, ext2T, (size_t)nb * 2 * nl, pq, pre1));
             // 5. finish + automorphism
-            hipLaunchKernelGGL(k_ksw_finish, dim3(N / 256, nl, nb), dim3(256), 0, ctx->stream, bin, inidx_d, acc, ext2T, idx_d, out_d, kcd, ctx->modc,
+            if (sum) { SFG_TRY(finish_sum(jobs, c0, nb, bin, inidx_d, idx_d)); continue; }
+            hipLaunchKernelGGL(k_ksw_finish, dim3(N / 256, nq_out, nb), dim3(256), 0, ctx->stream, bin, inidx_d, acc, ext2T, idx_d, out_d, kcd, ctx->modc,
                                add1 ? add1 + (size_t)i0 * nl * N : nullptr, ff);
             SFG_HIP(ctx, hipGetLastError());
         }
     }
+    if (sum) SFG_TRY(finish_sum(std::vector<int>(), 0, 0, in, inidx_all, idx_all));          // outputs without a job
     return 0;
 }
 // Rotate a batch.  `in` holds nin ciphertexts [nin][2][nl][N]; output j = RotateRight(in[in_index[j]], nrot[j])
@@ -276,6 +361,32 @@ int launch_rotate_right_indexed(sfg_ctx *ctx, const u64 *in, int nin, u64 *out, 
         job_in.push_back(src); keyp.push_back(it->second.key_dev); idxp.push_back(it->second.index_dev); outp.push_back(out + j * ctw);
     }
     return launch_keyswitch_jobs(ctx, in, nin, level, job_in, keyp, idxp, outp, nullptr);
+}
+// The same batch SUMMED where it is produced: out + i * out_stride (+)= sum over the jobs j with group[j] == i of RotateRight(in[in_index[j]], nrot[j]), i < nout.
+// A job that does not rotate joins its sum as a plain read (one per output).  No rotated ciphertext is stored.  `out` must not overlap `in`.
+int launch_rotate_right_sum(sfg_ctx *ctx, const u64 *in, int nin, int nct, int level, const int *nrot_host, const int *in_index, const int *group, int nout,
+                            u64 *out, size_t out_stride, int accumulate) {
+    const int N = SFG_N, nl = level + 1;
+    if (level < 0 || level >= ctx->nq) SFG_FAIL(ctx, "rotate: level out of range");
+    const size_t ctw = (size_t)2 * nl * N;
+    KswSum sum; sum.nout = nout; sum.plain.assign(nout, nullptr); sum.out = out; sum.out_stride = out_stride; sum.accumulate = accumulate;
+    std::vector<int> job_in; std::vector<const u64 *> keyp; std::vector<const uint16_t *> idxp;
+    for (int j = 0; j < nct; j++) {
+        int nrot = nrot_host[j] % SFG_SLOTS; if (nrot < 0) nrot += SFG_SLOTS;
+        const int src = in_index ? in_index[j] : j;
+        if (src < 0 || src >= nin) SFG_FAIL(ctx, "rotate: input index out of range");
+        if (group[j] < 0 || group[j] >= nout) SFG_FAIL(ctx, "rotate: sum group out of range");
+        if (nrot == 0) {
+            if (sum.plain[group[j]]) SFG_FAIL(ctx, "rotate: more than one unrotated member in a sum group");
+            sum.plain[group[j]] = in + (size_t)src * ctw;
+            continue;
+        }
+        u64 g = sfg_galois_for_rotation(ctx, SFG_SLOTS - nrot);
+        auto it = ctx->rotkeys().find(g);
+        if (it == ctx->rotkeys().end()) SFG_FAIL(ctx, "rotate: no rotation key loaded for right-rotation by %d (galois element %llu)", nrot, g);
+        job_in.push_back(src); keyp.push_back(it->second.key_dev); idxp.push_back(it->second.index_dev); sum.group.push_back(group[j]);
+    }
+    return launch_keyswitch_jobs(ctx, in, nin, level, job_in, keyp, idxp, std::vector<u64 *>(), nullptr, nullptr, &sum);
 }
 // The same batch written as the MAC's fp64 operand rows: job j lands at outf + j * 2 * rowf (row pair of polynomials 0, 1), rowf = nplanes * N doubles.
 // Jobs that do not rotate (nrot == 0) are converted from their input.
