@@ -1027,6 +1027,90 @@ def _ctx_matmul_finalize(self, acc, s, max_level, ncolb, g0, g1, out=None):
     return out
 
 
+# ---- the baby-step rotation cache as an object (sfg_rotcache_*, the *_rc_dev products): fp64 operand rows in caller-held DevArrays of float64
+def _ctx_rotcache_layout(self, s, max_level):
+    """(job_doubles, tail_doubles): doubles of one job's 91 rotations [91][2][rowf], of the zero tail [3][s][2][rowf]"""
+    jw, tw = C.c_size_t(), C.c_size_t()
+    self.check(lib().sfg_rotcache_layout(self.h, s, max_level, C.byref(jw), C.byref(tw)), "rotcache_layout")
+    return jw.value, tw.value
+
+
+def _f64_at(d, at):
+    return C.c_void_p(d.p.value + int(at) * 8) if d is not None else None
+
+
+def _rc_call(self, what, fn, out, made, *args):
+    rc = fn(*args)
+    if rc and made:
+        out.free()
+    self.check(rc, what)
+    return out
+
+
+def _ctx_rotcache_build_jobs(self, A_dev, s, in_level, max_level, nbr, job0, job1, staged=None, at=0):
+    """A_dev: DevArray [s][nbr][2][in_level+1][N].  Jobs [job0, job1) (job = block row * s + i) land job-major, [job - job0][91][2][rowf], from double `at`
+    of `staged` (a float64 DevArray; None: one of exactly that size is made).  Returns staged."""
+    made = staged is None
+    if made:
+        staged = DevArray(self, ((job1 - job0) * self.rotcache_layout(s, max_level)[0],), np.float64)
+    return _rc_call(self, "rotcache_build_jobs", lib().sfg_rotcache_build_jobs_dev, staged, made,
+                    self.h, A_dev.p, s, in_level, max_level, nbr, job0, job1, _f64_at(staged, at))
+
+
+def _ctx_rotcache_scatter(self, staged, s, max_level, job0, job1, row0, nrows, cache=None, at=0):
+    """staged (from double `at` on): jobs [job0, job1) job-major -> cache [nrows][91][s][2][rowf] of block rows [row0, row0 + nrows) + the zero tail.  Returns cache."""
+    made = cache is None
+    if made:
+        jw, tw = self.rotcache_layout(s, max_level)
+        cache = DevArray(self, (nrows * s * jw + tw,), np.float64)
+    return _rc_call(self, "rotcache_scatter", lib().sfg_rotcache_scatter_dev, cache, made,
+                    self.h, _f64_at(staged, at), s, max_level, job0, job1, row0, nrows, cache.p)
+
+
+def _ctx_rotcache_build_rows(self, A_dev, s, in_level, max_level, nbr, b0, b1, cache=None):
+    """cache [b1 - b0][91][s][2][rowf] of block rows [b0, b1) of A_dev + the zero tail, built in place.  Returns cache."""
+    made = cache is None
+    if made:
+        jw, tw = self.rotcache_layout(s, max_level)
+        cache = DevArray(self, ((b1 - b0) * s * jw + tw,), np.float64)
+    return _rc_call(self, "rotcache_build_rows", lib().sfg_rotcache_build_rows_dev, cache, made,
+                    self.h, A_dev.p, s, in_level, max_level, nbr, b0, b1, cache.p)
+
+
+def _ctx_rotcache_invalidate(self):
+    self.check(lib().sfg_rotcache_invalidate(self.h), "rotcache_invalidate")
+
+
+def _ctx_matmul_resident_range_rc(self, cache, s, max_level, g, flags, blk0, blk1, out=None):
+    """the product of matmul_resident(blk=(blk0, blk1)) on a prebuilt cache of the operand block rows it contracts over; cache None passes a null pointer"""
+    nr, nc = C.c_size_t(), C.c_size_t()
+    lib().sfg_geno_dims(g, C.byref(nr), C.byref(nc))
+    m_out = (nr.value - 1) // self.slots + 1 if flags & SFG_TRANSPOSE else blk1 - blk0
+    made = out is None
+    if made:
+        out = DevArray(self, (s, m_out, 2, max_level, self.N))
+    return _rc_call(self, "matmul_resident_range_rc", lib().sfg_matmul_resident_range_rc_dev, out, made,
+                    self.h, cache.p if cache is not None else None, s, max_level, g, flags, blk0, blk1, out.p)
+
+
+def _ctx_matmul_accumulate_rc(self, cache, s, max_level, g, flags, b0, b1, j0, j1, acc=None):
+    """matmul_accumulate on a prebuilt cache of block rows [b0, b1); acc given: accumulated onto"""
+    accumulate = acc is not None
+    if acc is None:
+        acc = DevArray(self, (j1 - j0, 91, s, 2, max_level, self.N))
+    return _rc_call(self, "matmul_accumulate_rc", lib().sfg_matmul_accumulate_rc_dev, acc, not accumulate,
+                    self.h, cache.p if cache is not None else None, s, max_level, g, flags, b0, b1, j0, j1, int(accumulate), acc.p)
+
+
+Context.rotcache_layout = _ctx_rotcache_layout
+Context.rotcache_build_jobs = _ctx_rotcache_build_jobs
+Context.rotcache_scatter = _ctx_rotcache_scatter
+Context.rotcache_build_rows = _ctx_rotcache_build_rows
+Context.rotcache_invalidate = _ctx_rotcache_invalidate
+Context.matmul_resident_range_rc = _ctx_matmul_resident_range_rc
+Context.matmul_accumulate_rc = _ctx_matmul_accumulate_rc
+
+
 def _filter_arg(f, n, what):
     """a row / column filter or cohort mask as the uint8 array the library reads (None stays None)"""
     if f is None:

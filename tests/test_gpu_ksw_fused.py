@@ -3,8 +3,9 @@
   * rotation words against the oracle on PN14 (levels 5 and 4) and on the chains S1 (single-prime digits), S3 and S4 of tests/ksw_ref.py, random and
     directed ciphertexts (the generators of tests/test_gpu_ksw_shapes.py): the extension kernels now take two positions per thread and hand the
     forward transform rows that are already through its first stage;
-  * hoisted job lists in the MAC-operand output form, whose unread modulus row is no longer computed: the library keeps no hook that reads rot operand
-    rows back, so a one-block-row product is compared as a whole, at input level max_level (a dead row) and max_level - 1 (none);
+  * hoisted job lists in the MAC-operand output form, whose unread modulus row is no longer computed: here a one-block-row product is compared as a whole,
+    at input level max_level (a dead row) and max_level - 1 (none); the rows themselves, word by word, are held by tests/test_gpu_rotcache.py through
+    sfg_rotcache_build_rows_dev / sfg_rotcache_build_jobs_dev;
   * the summed finalize (the giants are added where the key switch finishes them) against rotating with the public single-rotation entry point and
     summing with integers: a giant range that starts above 0, a slot base above 0, accumulate = 1, giant 0 as a plain read, one and two block columns,
     at the default key-switch budget and at the smallest one (sum groups split over input groups and job chunks); on S1 / S3 / S4 as well;
