@@ -54,3 +54,10 @@ SFG_HD void fwd_stage1_pair(double v0, double v1, double W, double Wq, double q,
     const double p = mulmod_lazy(v1, W, Wq, q);
     r0 = canon(v0 + p, q, qinv); r1 = canon(v0 - p, q, qinv);
 }
+// ---- the key switch's split inverse transform (ntt.hip k_ntt_inv_split): each half-row workgroup runs the 13 Gentleman-Sande stages that stay inside its half
+// and writes canonical words, without the 1/N factor.  The LAST stage and the scaling are done by the READER of the row: from the canonical pair (U, V) at
+// positions x and x + N/2 it forms c_x = (U + V) N^-1 and c_(x + N/2) = (U - V) w N^-1, both canonical (w = psi^-(N/2), entry 1 of the modulus' inverse table;
+// ninv = N^-1, wn = w N^-1 mod q, ninv_q and wn_q those over q, rounded): the words the one-workgroup transform stores.  |U +- V| < 2q.
+SFG_HD void inv_last_pair(double U, double V, double ninv, double ninv_q, double wn, double wn_q, double q, double qinv, double &r0, double &r1) {
+    r0 = canon(mulmod_lazy(U + V, ninv, ninv_q, q), q, qinv); r1 = canon(mulmod_lazy(U - V, wn, wn_q, q), q, qinv);
+}

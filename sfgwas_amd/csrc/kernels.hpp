@@ -30,6 +30,8 @@ int launch_ntt_fwd_map(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, cons
 int launch_ntt_inv_map(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat, const RowMap &rm);
 // dense forward NTT, out of place; staged: the rows arrive through the transform's first stage (fp64mod.hpp fwd_stage1_pair), each half-row workgroup reads only its half
 int launch_ntt_fwd_staged(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat, bool staged);
+// inverse NTT WITHOUT its last stage and without 1/N, as two half-row workgroups per row; in place or not.  The reader of the rows finishes them (fp64mod.hpp inv_last_pair)
+int launch_ntt_inv_split(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat, const RowMap &rm);
 // the MAC launches
 struct MacStrides { size_t rot_k, rot_r, pt_k, pt_n, out_n, out_r; bool pt_half = false; bool pt_packed = false; bool pt_digits = false; bool i8 = false; bool i8_big = false; bool pt_digits_big = false;
                     const int8_t *B_small = nullptr, *B_big = nullptr;

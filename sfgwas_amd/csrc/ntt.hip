@@ -416,6 +416,91 @@ __global__ void __launch_bounds__(256, 4) k_ntt_fwd_split(const u64 *in_, u64 *o
     auto first = [&](int j) { return STAGED ? u64_to_f64(in[(size_t)hs * n + j]) : u64_to_f64(in[j]) + mulmod_lazy(u64_to_f64(in[n + j]), W, Wq, q); };
     ntt_half3_body(hs, first, [&](int j, double x) { out[j] = f64_to_u64(canon(x, q, qinv)); }, lds, tw, pack, q, qinv, tid);
 }
+// The inverse counterpart for the key switch (rotate.hip): TWO 256-thread workgroups per row, each on its own half of the POSITIONS ([hs n, (hs + 1) n)), the
+// mirror image of ntt_half3_body.  A half runs the 13 Gentleman-Sande stages that stay inside it - t = 1 .. 8 on c in wave-private 16 x 16 transposes, t = 16 .. 256
+// on b, t = 512 .. 4096 on the 16 `a` values of the half, exchanged through the half image in two rounds - and stores canonical words.  The last stage (t = 8192,
+// which pairs x with x + N/2) and the factor 1/N are left to the row's reader (fp64mod.hpp inv_last_pair: k_ksw_extend and k_moddown_extend take exactly those
+// pairs).  A workgroup reads and writes only its half, and reads all of it before it writes: in place is fine.
+__global__ void __launch_bounds__(256, 4) k_ntt_inv_split(const u64 *in_, u64 *out_, size_t nrows, ModPattern pat, RowMap rm, const double *tw_all, const double2 *pack_all, const ModConst *modc) {
+    extern __shared__ double lds[];
+    const int N = SFG_N, n = N / 2, tid = threadIdx.x;
+    const size_t blk = blockIdx.x, row = (blk / 16) * 8 + blk % 8; const int hs = (int)((blk / 8) & 1);
+    if (row >= nrows) return;
+    const int m = pat.m[row % pat.period];
+    if (m < 0) return;
+    const size_t grp = row / rm.rpg, gi = row % rm.rpg;
+    const u64 *in = in_ + grp * rm.gstride_in + gi * N + (size_t)hs * n;
+    u64 *out = out_ + grp * rm.gstride_out + gi * N + (size_t)hs * n;
+    const double *tw = tw_all + (size_t)m * N;
+    const double2 *pack = pack_all + (size_t)m * (N / 2);
+    const double q = modc[m].q, qinv = modc[m].qinv;
+    const int a_b = tid >> 4, c_b = tid & 15;                  // phase B identity
+    double v[32];
+    // ---- load, phase C' (stages t = 1, 2, 4, 8 on c) and the C'->B' exchange: wave-private, one group b = (tid & 15) + 16 r at a time (ntt_half3_body backwards)
+    {
+        const int wv = tid >> 6, lane = tid & 63, al = lane >> 4, bk = lane & 15;
+        double *img = lds + wv * H3_WREG;
+        auto sw = [](int idx) { return (idx >> 8) * 272 + ((idx >> 4) & 15) * 17 + (idx & 15); };
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            double wc[16];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");           // (the previous round's reads of the image are issued)
+            // input j = a*512 + (16 r + b')*16 + c: per `a` row 256 consecutive words, 64 lanes at a time
+#pragma unroll
+            for (int ai = 0; ai < 4; ai++)
+#pragma unroll
+                for (int qd = 0; qd < 4; qd++) {
+                    const int x = qd * 64 + lane;                            // b' = x >> 4, c = x & 15
+                    img[sw(ai * 256 + (x & 15) * 16 + (x >> 4))] = u64_to_f64(in[(4 * wv + ai) * 512 + 256 * r + x]);
+                }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+            for (int c = 0; c < 16; c++) wc[c] = img[sw(al * 256 + c * 16 + bk)];
+            const int p = a_b * 32 + 16 * r + bk;                             // group (a, b)
+            double tl[16];
+            {
+                const double2 *pk = pack + (size_t)((p >> 6) + 8 * hs) * 512 + (p & 63);
+#pragma unroll
+                for (int i = 0; i < 8; i++) { const double2 e = pk[i * 64]; tl[2 * i] = e.x; tl[2 * i + 1] = e.y; }
+            }
+            gs_stage<16, 1>(wc, q, qinv, [&](int g) { return tl[7 + g]; });
+            gs_stage<16, 2>(wc, q, qinv, [&](int g) { return tl[3 + g]; });
+            gs_stage<16, 4>(wc, q, qinv, [&](int g) { return tl[1 + g]; });
+            gs_stage<16, 8>(wc, q, qinv, [&](int g) { return tl[0 + g]; });
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+            for (int c = 0; c < 16; c++) img[sw(al * 256 + c * 16 + bk)] = pred(wc[c], q, qinv);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+            for (int k = 0; k < 16; k++) v[16 * r + k] = img[sw(al * 256 + c_b * 16 + k)];
+        }
+    }
+    // ---- phase B': thread (a, c), 32 values of b; stages t = 16 .. 256
+    const int ab = 16 * hs + a_b;
+    gs_stage<32, 1>(v, q, qinv, [&](int g) { return tw[512 + ab * 16 + g]; });
+    gs_stage<32, 2>(v, q, qinv, [&](int g) { return tw[256 + ab * 8 + g]; });
+    gs_stage<32, 4>(v, q, qinv, [&](int g) { return tw[128 + ab * 4 + g]; });
+    gs_stage<32, 8>(v, q, qinv, [&](int g) { return tw[64 + ab * 2 + g]; });
+    gs_stage<32, 16>(v, q, qinv, [&](int g) { return tw[32 + ab + g]; });
+    __syncthreads();                                                      // the wave-private regions are dead: the half image takes their place
+    // ---- the two B'->A' rounds by column half h, phase A' (stages t = 512 .. 4096 on the half's 16 `a` values) and the coalesced store
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        double w[16];
+        if (h) __syncthreads();                                           // round-0 readers are done with the image
+#pragma unroll
+        for (int b = 0; b < 16; b++) lds[a_b * H3_ROWA + b * 16 + c_b] = pred(v[h * 16 + b], q, qinv);
+        __syncthreads();
+#pragma unroll
+        for (int a = 0; a < 16; a++) w[a] = lds[a * H3_ROWA + tid];
+        gs_stage<16, 1>(w, q, qinv, [&](int g) { return tw[16 + 8 * hs + g]; });
+        gs_stage<16, 2>(w, q, qinv, [&](int g) { return tw[8 + 4 * hs + g]; });
+        gs_stage<16, 4>(w, q, qinv, [&](int g) { return tw[4 + 2 * hs + g]; });
+        gs_stage<16, 8>(w, q, qinv, [&](int g) { return tw[2 + hs + g]; });
+#pragma unroll
+        for (int a = 0; a < 16; a++) out[a * 512 + tid + 256 * h] = f64_to_u64(canon(w[a], q, qinv));
+    }
+}
 // full rows from half rows: out[i] = out[N-1-i] = half[i]
 __global__ void __launch_bounds__(256) k_expand_half(const u64 *half, u64 *full) {
     const int N = SFG_N, n = N / 2; const size_t row = blockIdx.x / (n / 256);
@@ -434,6 +519,7 @@ int ntt_set_attrs(sfg_ctx *ctx) {
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_half3<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_fwd_split<false>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_fwd_split<true>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_inv_split, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES);
 #define SFG_MV_ATTR(P, D, T) if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_ntt_half3_move<P, D, T>, hipFuncAttributeMaxDynamicSharedMemorySize, H3_LDS_BYTES)
     SFG_MV_ATTR(false, 1, true); SFG_MV_ATTR(true, 1, true);              // the product's riding transposition: one unit in flight, streaming loads and stores
 #ifdef SFG_AB
@@ -518,6 +604,12 @@ int launch_expand_half(sfg_ctx *ctx, const u64 *half, u64 *full, size_t nrows) {
 int launch_ntt_inv_map(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat, const RowMap &rm) {
     if (!nrows) return 0;
     hipLaunchKernelGGL(k_ntt_inv, dim3((unsigned)nrows), dim3(512), LDS_DOUBLES * 8, ctx->stream, in, out, pat, rm, ctx->tw_inv, ctx->pack_inv, ctx->modc);
+    SFG_HIP(ctx, hipGetLastError());
+    return 0;
+}
+int launch_ntt_inv_split(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, const ModPattern &pat, const RowMap &rm) {
+    if (!nrows) return 0;
+    hipLaunchKernelGGL(k_ntt_inv_split, dim3((unsigned)((nrows + 7) / 8 * 16)), dim3(256), H3_LDS_BYTES, ctx->stream, in, out, nrows, pat, rm, ctx->tw_inv, ctx->pack_inv, ctx->modc);
     SFG_HIP(ctx, hipGetLastError());
     return 0;
 }

@@ -5,20 +5,35 @@
 //
 // Batched over ciphertexts (each may use a different key).  Per ciphertext at level l (nl = l+1 moduli,
 // alpha = np special primes per digit, beta = ceil(nl/alpha) digits, nt = nl + np targets):
-//   1. c2 = INTT(c1)                                   nl rows
-//   2. digit i -> exact (float-corrected) basis extension to every target outside the digit     (k_ksw_extend)
+//   1. c2 = INTT(c1), without the last stage and 1/N                              nl rows  (k_ntt_inv_split)
+//   2. digit i -> last inverse stage and 1/N on the pairs it loads, exact (float-corrected) basis extension to every target outside the digit (k_ksw_extend)
 //      (inside the digit the original NTT rows are reused), then NTT of the extended rows         beta*nt rows
-//   3. acc_{0,1}[t] = sum_i ext[i][t] * key[i][{0,1}][t]                                           (k_ksw_inner)
-//   4. ModDown: INTT of the np special-prime rows, basis extension P -> Q, NTT                    (k_moddown_extend)
-//   5. out0 = perm(c0 + (acc0 - ext0) / P), out1 = perm((acc1 - ext1) / P)                        (k_ksw_finish)
+//   3. special-prime targets only: acc_{0,1}[t] = sum_i ext[i][t] * key[i][{0,1}][t]              (k_ksw_inner_p)
+//   4. ModDown: INTT of those 2 np rows (split, finished by the reader), basis extension P -> Q, NTT   (k_moddown_extend)
+//   5. at the gathered position src = index[x]: acc_{0,1}[t] of the Q targets as in 3, then
+//      out0 = perm(c0 + (acc0 - ext0) / P), out1 = perm((acc1 - ext1) / P)                        (k_ksw_finish, k_ksw_finish_sum)
 // The float correction v = uint64(sum float64(y_m)/float64(q_m)) is lattigo's (ring.Decomposer /
 // FastBasisExtender); the oracle mirrors it, so results agree bit for bit.
-// Which kernel computes what (profiles/ksw_fused_ab.txt): the extension kernels of 2 and 4 apply the forward transform's first stage to the rows they write, so the
-// split transform reads half a row per workgroup and starts at stage 2; a job written as MAC operand rows produces nothing of the moduli the MAC does not read;
-// jobs whose results are summed (the giant-step alignment) are summed in step 5 (k_ksw_finish_sum).  Every output word is the canonical word it was.
+// Which kernel computes what (profiles/ksw_fused_ab.txt, profiles/ksw_inner_finish_ab.txt): the extension kernels of 2 and 4 apply the forward transform's first
+// stage to the rows they write, so the split transform reads half a row per workgroup and starts at stage 2, and the inverse transform's last stage to the rows
+// they read, so the split inverse transform stays inside half a row; a job written as MAC operand rows produces nothing of the moduli the MAC does not read; jobs
+// whose results are summed (the giant-step alignment) are summed in step 5 (k_ksw_finish_sum); no Q row of the inner product is stored - the finish forms it from
+// the rows it gathers anyway; consecutive jobs under one key and table (a tile, ksw_plan.hpp) share each load of a key word in 3 and 5.  Every output word is the
+// canonical word it was.
 #include "common.hpp"
 #include "kernels.hpp"
 #include "ksw.hpp"
+#include "ksw_plan.hpp"
+
+// Jobs per tile (ksw_plan.hpp) of k_ksw_inner_p and k_ksw_finish: a key word is loaded once for that many jobs.  Measured at 1, 3 and 5 (profiles/ksw_inner_finish_ab.txt):
+// 3 is the fastest for both.  The summed finish takes no tiles: with s = 15 outputs per block column, tiles of 3 or 5 segments leave it too few workgroups.
+#ifndef KSW_T
+#define KSW_T 3
+#endif
+// The key switch's two inverse transforms in the split form (ntt.hip k_ntt_inv_split), their last stage and 1/N done by the extension kernels that read them
+#ifndef KSW_INV_SPLIT
+#define KSW_INV_SPLIT true
+#endif
 
 
 static void fill_ext(const sfg_ctx *ctx, ExtConst &e, const std::vector<int> &src) {
@@ -76,11 +91,18 @@ int get_ksw(sfg_ctx *ctx, int level, KswConst **dev, KswConst *host) {
 }
 
 
+// the last inverse stage and 1/N on the pair (u, v) at x and x + N/2 of a row of modulus mc, w = entry 1 of its inverse table (fp64mod.hpp inv_last_pair)
+__device__ __forceinline__ void inv_last_of(const ModConst &mc, double w, double &u, double &v) {
+    const double wn = canon(mulmod_lazy(w, mc.ninv, mc.ninv_q, mc.q), mc.q, mc.qinv);
+    inv_last_pair(u, v, mc.ninv, mc.ninv_q, wn, wn * mc.qinv, mc.q, mc.qinv, u, v);
+}
 // grid (N/512, beta, B). c2: [B][nl][N] coefficient-domain c1; ext: [B][beta][nt][N].  A thread extends positions x and x + N/2, so that it can apply
 // the forward transform's first stage to the rows it writes (PRE1, fp64mod.hpp fwd_stage1_pair): the element-wise kernels wait for memory and have fp64
 // issue slots to spare, the transforms do not.
-template <bool PRE1>
-__global__ void __launch_bounds__(256) k_ksw_extend(const u64 *c2, u64 *ext, const KswConst *kcp, const ModConst *modc, const double *tw_fwd) {
+// POST1: c2 comes from the split inverse transform (ntt.hip k_ntt_inv_split) and lacks its last stage and 1/N: the pair a thread loads is exactly a pair of that
+// stage, finished here (fp64mod.hpp inv_last_pair) for the same reason.
+template <bool PRE1, bool POST1>
+__global__ void __launch_bounds__(256) k_ksw_extend(const u64 *c2, u64 *ext, const KswConst *kcp, const ModConst *modc, const double *tw_fwd, const double *tw_inv) {
     const KswConst &kc = *kcp;
     const int N = SFG_N, n = N / 2, x = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y; const size_t b = blockIdx.z;
     const ExtConst &e = kc.dig[i];
@@ -91,6 +113,10 @@ __global__ void __launch_bounds__(256) k_ksw_extend(const u64 *c2, u64 *ext, con
     for (int h = 0; h < 2; h++)
 #pragma unroll
         for (int m = 0; m < KSW_MAXA; m++) xs[h][m] = m < e.a ? u64_to_f64(c2b[(size_t)e.src[m] * N + h * n + x]) : 0.0;
+    if (POST1) {
+#pragma unroll
+        for (int m = 0; m < KSW_MAXA; m++) if (m < e.a) inv_last_of(modc[e.src[m]], tw_inv[(size_t)e.src[m] * N + 1], xs[0][m], xs[1][m]);
+    }
     if (e.a > 1) { ext_prepare(e, modc, xs[0], y[0], v[0]); ext_prepare(e, modc, xs[1], y[1], v[1]); }
     for (int t = 0; t < kc.nt; t++) {
         const int tg = kc.tmod[t];
@@ -104,43 +130,63 @@ __global__ void __launch_bounds__(256) k_ksw_extend(const u64 *c2, u64 *ext, con
     }
 }
 
-// grid (N/512, nq_out + np, B). acc: [B][2][nt][N]; inidx[b] = which decomposed input feeds output b.  Two coefficients per thread: 16-byte loads and stores.
-// Only the first nq_out <= nl moduli of the output are stored by the finish (F64Form): targets [nq_out, nl) are not computed, the special primes follow directly.
-// The row of digit i at a target inside digit i is the input's own NTT row (polynomial 1 of ct_in): read there, never copied (round 4: 15 of ~250 row transfers per switch less)
-__global__ void __launch_bounds__(256) k_ksw_inner(const u64 *ext, const u64 *ct_in, const u64 *const *keys, const int *inidx, u64 *acc, const KswConst *kcp, const ModConst *modc, int nmod, int nq_out) {
+// grid (N/512, np, tiles). acc: [B][2][np][N], the special-prime targets only (the ModDown's input): the Q targets of the inner product are formed where they
+// are consumed, in the finish.  Two coefficients per thread: 16-byte loads and stores.  A tile is up to T consecutive jobs under one key (ksw_plan.hpp): a key word
+// is loaded once and applied to the tile's T extended inputs.
+template <int T>
+__global__ void __launch_bounds__(256) k_ksw_inner_p(const u64 *ext, const u64 *const *keys, const int *inidx, const KswTile *tiles, u64 *acc, const KswConst *kcp,
+                                                    const ModConst *modc, int nmod) {
     const KswConst &kc = *kcp;
-    const int N = SFG_N, x = 2 * (blockIdx.x * 256 + threadIdx.x), t = (int)blockIdx.y < nq_out ? (int)blockIdx.y : (int)blockIdx.y + (kc.nl - nq_out); const size_t b = blockIdx.z;
+    const int N = SFG_N, x = 2 * (blockIdx.x * 256 + threadIdx.x), m = blockIdx.y, t = kc.nl + m;
+    const KswTile tl = tiles[blockIdx.z];
     const int tg = kc.tmod[t];
     const double q = modc[tg].q, qinv = modc[tg].qinv;
-    const u64 *key = keys[b];
-    const size_t bi = (size_t)inidx[b];
-    double a0x = 0.0, a0y = 0.0, a1x = 0.0, a1y = 0.0;
+    const u64 *key = keys[tl.start];
+    const u64 *eb[T];
+#pragma unroll
+    for (int j = 0; j < T; j++) eb[j] = ext + ((size_t)inidx[tl.start + (j < tl.count ? j : 0)] * kc.beta * (size_t)kc.nt + t) * N + x;
+    double a[T][4];
+#pragma unroll
+    for (int j = 0; j < T; j++) a[j][0] = a[j][1] = a[j][2] = a[j][3] = 0.0;
     for (int i = 0; i < kc.beta; i++) {
-        const ulonglong2 ev = kc.digit_of[t] == i ? *reinterpret_cast<const ulonglong2 *>(ct_in + (bi * 2 * (size_t)kc.nl + kc.nl + t) * N + x)
-                                                  : *reinterpret_cast<const ulonglong2 *>(ext + ((bi * kc.beta + i) * (size_t)kc.nt + t) * N + x);
         const ulonglong2 k0 = *reinterpret_cast<const ulonglong2 *>(key + (((size_t)i * 2 + 0) * nmod + tg) * N + x);
         const ulonglong2 k1 = *reinterpret_cast<const ulonglong2 *>(key + (((size_t)i * 2 + 1) * nmod + tg) * N + x);
-        const double ex = u64_to_f64(ev.x), ey = u64_to_f64(ev.y);
-        a0x += mulmod2(ex, u64_to_f64(k0.x), q, qinv); a0y += mulmod2(ey, u64_to_f64(k0.y), q, qinv);
-        a1x += mulmod2(ex, u64_to_f64(k1.x), q, qinv); a1y += mulmod2(ey, u64_to_f64(k1.y), q, qinv);
+        const double k0x = u64_to_f64(k0.x), k0y = u64_to_f64(k0.y), k1x = u64_to_f64(k1.x), k1y = u64_to_f64(k1.y);
+#pragma unroll
+        for (int j = 0; j < T; j++) {           // no branch on the tile's length: a short tile's spare slots repeat its first job (loads that hit), only the stores are guarded
+            const ulonglong2 ev = *reinterpret_cast<const ulonglong2 *>(eb[j] + (size_t)i * kc.nt * N);
+            const double ex = u64_to_f64(ev.x), ey = u64_to_f64(ev.y);
+            a[j][0] += mulmod2(ex, k0x, q, qinv); a[j][1] += mulmod2(ey, k0y, q, qinv);
+            a[j][2] += mulmod2(ex, k1x, q, qinv); a[j][3] += mulmod2(ey, k1y, q, qinv);
+        }
     }
-    *reinterpret_cast<ulonglong2 *>(acc + ((b * 2 + 0) * (size_t)kc.nt + t) * N + x) = make_ulonglong2(f64_to_u64(canon(a0x, q, qinv)), f64_to_u64(canon(a0y, q, qinv)));
-    *reinterpret_cast<ulonglong2 *>(acc + ((b * 2 + 1) * (size_t)kc.nt + t) * N + x) = make_ulonglong2(f64_to_u64(canon(a1x, q, qinv)), f64_to_u64(canon(a1y, q, qinv)));
+#pragma unroll
+    for (int j = 0; j < T; j++) {
+        if (j < tl.count) {
+            u64 *o = acc + ((size_t)(tl.start + j) * 2 * kc.np + m) * N + x;
+            *reinterpret_cast<ulonglong2 *>(o) = make_ulonglong2(f64_to_u64(canon(a[j][0], q, qinv)), f64_to_u64(canon(a[j][1], q, qinv)));
+            *reinterpret_cast<ulonglong2 *>(o + (size_t)kc.np * N) = make_ulonglong2(f64_to_u64(canon(a[j][2], q, qinv)), f64_to_u64(canon(a[j][3], q, qinv)));
+        }
+    }
 }
 
-// grid (N/512, 2, B): special-prime rows of acc (already INTT'd) -> ext2 [B][2][nl][N] coefficient domain, rows t < nq_out (the others nobody reads).
-// Positions x and x + N/2 in one thread, PRE1 as in k_ksw_extend.
-template <bool PRE1>
-__global__ void __launch_bounds__(256) k_moddown_extend(const u64 *acc, u64 *ext2, const KswConst *kcp, const ModConst *modc, const double *tw_fwd, int nq_out) {
+// grid (N/512, 2, B): the rows of acc [B][2][np][N] (already INTT'd) -> ext2 [B][2][nl][N] coefficient domain, rows t < nq_out (the others nobody reads).
+// Positions x and x + N/2 in one thread, PRE1 and POST1 as in k_ksw_extend.
+template <bool PRE1, bool POST1>
+__global__ void __launch_bounds__(256) k_moddown_extend(const u64 *acc, u64 *ext2, const KswConst *kcp, const ModConst *modc, const double *tw_fwd, const double *tw_inv, int nq_out) {
     const KswConst &kc = *kcp;
     const int N = SFG_N, n = N / 2, x = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y; const size_t b = blockIdx.z;
     const ExtConst &e = kc.pq;
-    const u64 *ap = acc + ((b * 2 + p) * (size_t)kc.nt + kc.nl) * N;
+    const u64 *ap = acc + (b * 2 + p) * (size_t)kc.np * N;
     double xs[2][KSW_MAXA], y[2][KSW_MAXA], v[2] = {0.0, 0.0};
 #pragma unroll
     for (int h = 0; h < 2; h++)
 #pragma unroll
         for (int m = 0; m < KSW_MAXA; m++) xs[h][m] = m < e.a ? u64_to_f64(ap[(size_t)m * N + h * n + x]) : 0.0;
+    if (POST1) {
+#pragma unroll
+        for (int m = 0; m < KSW_MAXA; m++) if (m < e.a) inv_last_of(modc[e.src[m]], tw_inv[(size_t)e.src[m] * N + 1], xs[0][m], xs[1][m]);
+    }
     if (e.a > 1) { ext_prepare(e, modc, xs[0], y[0], v[0]); ext_prepare(e, modc, xs[1], y[1], v[1]); }
     for (int t = 0; t < nq_out; t++) {
         const double q = modc[t].q, qinv = modc[t].qinv;
@@ -166,35 +212,71 @@ __device__ __forceinline__ void store_rot_f64(double *row, const F64Form &ff, in
         o[2 * x] = lo; o[2 * x + 1] = hi;
     } else o[x] = (ff.centre && v > __builtin_floor(q * 0.5)) ? v - q : v;
 }
-// grid (N/256, nl, B): out = perm(c0 + (acc0 - ext0)/P), perm((acc1 - ext1)/P); out[x] = in[index[x]]
-// add1 (nullable): [nin][nl][N] rows added to polynomial 1 (relinearisation: the degree-1 term of the tensor product)
-__global__ void __launch_bounds__(256) k_ksw_finish(const u64 *ct_in, const int *inidx, const u64 *acc, const u64 *ext2, const uint16_t *const *index,
-                                                   u64 *const *ct_out, const KswConst *kcp, const ModConst *modc, const u64 *add1, F64Form ff) {
-    const KswConst &kc = *kcp;
-    const int N = SFG_N, x = blockIdx.x * 256 + threadIdx.x, t = blockIdx.y; const size_t b = blockIdx.z;
-    if (ff.on && t >= ff.L) return;
-    const double q = modc[t].q, qinv = modc[t].qinv, pinv = kc.pinv[t], pinv_q = kc.pinv_q[t];
-    const int src = index[b][x];
+// The inner product of one Q target at one gathered position, for the (up to T) jobs that share the key word: a[j][p] += ext_j[i][t][src] * key[i][p][t][src] over the
+// digits i, the row of digit i at a target inside digit i being the input's own NTT row (polynomial 1 of ct_in): read there, never copied.  bi[j]: the job's
+// decomposed input.  Sums of beta <= 8 lazy products, |a| < 8 q < 2^51.
+template <int T>
+__device__ __forceinline__ void ksw_inner_q(const u64 *ext, const u64 *ct_in, const u64 *key, const KswConst &kc, int nmod, int t, int src, const size_t (&bi)[T],
+                                           double q, double qinv, double (&a)[T][2]) {
+    const int N = SFG_N;
 #pragma unroll
-    for (int p = 0; p < 2; p++) {
-        const double a = u64_to_f64(acc[((b * 2 + p) * (size_t)kc.nt + t) * N + src]);
-        const double e = u64_to_f64(ext2[((b * 2 + p) * (size_t)kc.nl + t) * N + src]);
-        double r = mulmod_lazy(a - e, pinv, pinv_q, q);
-        if (p == 0) r += u64_to_f64(ct_in[((size_t)inidx[b] * 2 * (size_t)kc.nl + t) * N + src]);
-        else if (add1) r += u64_to_f64(add1[((size_t)inidx[b] * (size_t)kc.nl + t) * N + src]);
-        const double v = canon(r, q, qinv);
-        if (ff.on) store_rot_f64(reinterpret_cast<double *>(ct_out[b]) + (size_t)p * ff.rowf, ff, t, x, v, q);
-        else ct_out[b][((size_t)p * kc.nl + t) * N + x] = f64_to_u64(v);
+    for (int j = 0; j < T; j++) a[j][0] = a[j][1] = 0.0;
+    for (int i = 0; i < kc.beta; i++) {
+        const double k0 = u64_to_f64(key[(((size_t)i * 2 + 0) * nmod + t) * N + src]), k1 = u64_to_f64(key[(((size_t)i * 2 + 1) * nmod + t) * N + src]);
+        const bool own = kc.digit_of[t] == i;
+#pragma unroll
+        for (int j = 0; j < T; j++) {           // no branch on the tile's length: the spare slots of a short tile repeat its first job (bi[j] = bi[0]: loads that hit)
+            const double e = u64_to_f64(own ? ct_in[(bi[j] * 2 * (size_t)kc.nl + kc.nl + t) * N + src] : ext[((bi[j] * kc.beta + i) * (size_t)kc.nt + t) * N + src]);
+            a[j][0] += mulmod2(e, k0, q, qinv); a[j][1] += mulmod2(e, k1, q, qinv);
+        }
+    }
+}
+// grid (N/256, nq_out, tiles): out = perm(c0 + (acc0 - ext0)/P), perm((acc1 - ext1)/P); out[x] = in[index[x]], with acc_p[t] = sum_i ext[i][t] * key[i][p][t] formed
+// here at the gathered position (no Q row of the inner product crosses memory).  A tile: up to T consecutive jobs with one key and one table (ksw_plan.hpp).
+// An aligned run of 256 positions maps into an aligned run of 256 sources (the low bits of x are the high bits of the evaluation point's exponent, which the
+// automorphism keeps): the gathers of a workgroup stay inside 2 KiB of each row.  Only their speed rests on that.
+// add1 (nullable): [nin][nl][N] rows added to polynomial 1 (relinearisation: the degree-1 term of the tensor product)
+template <int T>
+__global__ void __launch_bounds__(256) k_ksw_finish(const u64 *ext, const u64 *ct_in, const u64 *const *keys, const int *inidx, const u64 *ext2, const uint16_t *const *index,
+                                                   u64 *const *ct_out, const KswTile *tiles, const KswConst *kcp, const ModConst *modc, int nmod, const u64 *add1, F64Form ff) {
+    const KswConst &kc = *kcp;
+    const int N = SFG_N, x = blockIdx.x * 256 + threadIdx.x, t = blockIdx.y;
+    if (ff.on && t >= ff.L) return;
+    const KswTile tl = tiles[blockIdx.z];
+    const double q = modc[t].q, qinv = modc[t].qinv, pinv = kc.pinv[t], pinv_q = kc.pinv_q[t];
+    const int src = index[tl.start][x];
+    size_t bi[T];
+#pragma unroll
+    for (int j = 0; j < T; j++) bi[j] = (size_t)inidx[tl.start + (j < tl.count ? j : 0)];
+    double a[T][2];
+    ksw_inner_q<T>(ext, ct_in, keys[tl.start], kc, nmod, t, src, bi, q, qinv, a);
+#pragma unroll
+    for (int j = 0; j < T; j++) {
+        if (j < tl.count) {
+            const size_t b = (size_t)(tl.start + j);
+#pragma unroll
+            for (int p = 0; p < 2; p++) {
+                const double e = u64_to_f64(ext2[((b * 2 + p) * (size_t)kc.nl + t) * N + src]);
+                double r = mulmod_lazy(pred(a[j][p], q, qinv) - e, pinv, pinv_q, q);
+                if (p == 0) r += u64_to_f64(ct_in[(bi[j] * 2 * (size_t)kc.nl + t) * N + src]);
+                else if (add1) r += u64_to_f64(add1[(bi[j] * (size_t)kc.nl + t) * N + src]);
+                const double v = canon(r, q, qinv);
+                if (ff.on) store_rot_f64(reinterpret_cast<double *>(ct_out[b]) + (size_t)p * ff.rowf, ff, t, x, v, q);
+                else ct_out[b][((size_t)p * kc.nl + t) * N + x] = f64_to_u64(v);
+            }
+        }
     }
 }
 
 // The finish of jobs whose results are SUMMED (the giant-step alignment, KswSum): grid (N/256, nl, segments), one thread per output word of both polynomials.
 // A segment is one output and the jobs of this chunk that add into it (jobs[start .. start + count), chunk-local numbers): each job with its own automorphism
-// table, key-switched rows and c0.  The canonical results are added as exact integers (reduced every 8 jobs: below 11 q < 2^51), an unrotated member (plain)
-// joins as a plain read, and the sum is reduced once: the canonical word the separate rotations, summed afterwards, give.
+// table, key, extended rows and c0; the Q-row inner product of each is formed here as in k_ksw_finish.  The canonical results are added as exact integers (reduced
+// every 8 jobs: below 11 q < 2^51), an unrotated member (plain) joins as a plain read, and the sum is reduced once: the canonical word the separate rotations,
+// summed afterwards, give.  No tiles here: the jobs that share a key go to DIFFERENT outputs, and walking 3 or 5 outputs in step left the grid too few
+// workgroups (0.249 / 0.208 s per step against 0.187 s, profiles/ksw_inner_finish_ab.txt).
 struct KswSeg { const u64 *plain; u64 *out; int start, count, accumulate, pad; };
-__global__ void __launch_bounds__(256) k_ksw_finish_sum(const u64 *ct_in, const int *inidx, const u64 *acc, const u64 *ext2, const uint16_t *const *index,
-                                                       const KswSeg *segs, const int *jobs, const KswConst *kcp, const ModConst *modc) {
+__global__ void __launch_bounds__(256) k_ksw_finish_sum(const u64 *ext, const u64 *ct_in, const u64 *const *keys, const int *inidx, const u64 *ext2, const uint16_t *const *index,
+                                                       const KswSeg *segs, const int *jobs, const KswConst *kcp, const ModConst *modc, int nmod) {
     const KswConst &kc = *kcp;
     const int N = SFG_N, x = blockIdx.x * 256 + threadIdx.x, t = blockIdx.y;
     const KswSeg sg = segs[blockIdx.z];
@@ -205,12 +287,14 @@ __global__ void __launch_bounds__(256) k_ksw_finish_sum(const u64 *ct_in, const 
     if (sg.plain) { s0 += u64_to_f64(sg.plain[w0]); s1 += u64_to_f64(sg.plain[w1]); }
     for (int k = 0; k < sg.count; k++) {
         const size_t b = (size_t)jobs[sg.start + k];
+        const size_t bi[1] = {(size_t)inidx[b]};
         const int src = index[b][x];
-        const double a0 = u64_to_f64(acc[((b * 2 + 0) * (size_t)kc.nt + t) * N + src]), e0 = u64_to_f64(ext2[((b * 2 + 0) * (size_t)kc.nl + t) * N + src]);
-        const double a1 = u64_to_f64(acc[((b * 2 + 1) * (size_t)kc.nt + t) * N + src]), e1 = u64_to_f64(ext2[((b * 2 + 1) * (size_t)kc.nl + t) * N + src]);
-        const double c0 = u64_to_f64(ct_in[((size_t)inidx[b] * 2 * (size_t)kc.nl + t) * N + src]);
-        s0 += canon(mulmod_lazy(a0 - e0, pinv, pinv_q, q) + c0, q, qinv);
-        s1 += canon(mulmod_lazy(a1 - e1, pinv, pinv_q, q), q, qinv);
+        double a[1][2];
+        ksw_inner_q<1>(ext, ct_in, keys[b], kc, nmod, t, src, bi, q, qinv, a);
+        const double e0 = u64_to_f64(ext2[((b * 2 + 0) * (size_t)kc.nl + t) * N + src]), e1 = u64_to_f64(ext2[((b * 2 + 1) * (size_t)kc.nl + t) * N + src]);
+        const double c0 = u64_to_f64(ct_in[(bi[0] * 2 * (size_t)kc.nl + t) * N + src]);
+        s0 += canon(mulmod_lazy(pred(a[0][0], q, qinv) - e0, pinv, pinv_q, q) + c0, q, qinv);
+        s1 += canon(mulmod_lazy(pred(a[0][1], q, qinv) - e1, pinv, pinv_q, q), q, qinv);
         if ((k & 7) == 7) { s0 = pred(s0, q, qinv); s1 = pred(s1, q, qinv); }
     }
     sg.out[w0] = f64_to_u64(canon(s0, q, qinv)); sg.out[w1] = f64_to_u64(canon(s1, q, qinv));
@@ -250,12 +334,14 @@ static int launch_keyswitch_jobs(sfg_ctx *ctx, const u64 *in, int nin, int level
     const size_t budget = ctx->cfg.ksw_budget;                  // bytes of decomposition / accumulator scratch per group resp. chunk (SFG_KSW_BUDGET_MB)
     int in_grp = (int)(budget / (in_rows * N * 8)); if (in_grp < 1) in_grp = 1; if (in_grp > nin) in_grp = nin;
     int chunk = (int)(budget / (job_rows * N * 8)); if (chunk < 1) chunk = 1; if (chunk > nr) chunk = nr;
-    const size_t ptr_bytes = (size_t)nr * (3 * sizeof(void *) + 2 * sizeof(int)) + (size_t)nout * sizeof(KswSeg) + 256;     // pointer tables for every job of a group, segments of a chunk
-    // the forward NTTs run out of place (two half-row workgroups per row cannot share a buffer with their input): extT / ext2T receive the transforms
-    const size_t ext_rows = (size_t)in_grp * kc.beta * kc.nt, ext2_rows = (size_t)chunk * 2 * nl;
-    SFG_TRY(sfg_ws_reserve(ctx, (in_rows * in_grp + job_rows * chunk + ext_rows + ext2_rows) * N * 8 + ptr_bytes));
+    // pointer tables and tiles for every job of a group; segments of a chunk
+    const size_t ptr_bytes = (size_t)nr * (3 * sizeof(void *) + 2 * sizeof(int) + sizeof(KswTile)) + (size_t)nout * sizeof(KswSeg) + 256;
+    // the forward NTTs run out of place (two half-row workgroups per row cannot share a buffer with their input): extT / ext2T receive the transforms.
+    // acc holds the 2 np special-prime rows of a job only (the chunk size is still what the budget gave when it held all 2 nt: the job list is cut where it was)
+    const size_t ext_rows = (size_t)in_grp * kc.beta * kc.nt, ext2_rows = (size_t)chunk * 2 * nl, acc_rows = (size_t)chunk * 2 * kc.np;
+    SFG_TRY(sfg_ws_reserve(ctx, (in_rows * in_grp + acc_rows + 2 * ext2_rows + ext_rows) * N * 8 + ptr_bytes));
     u64 *c2 = (u64 *)ctx->ws, *ext = c2 + (size_t)in_grp * nl * N;
-    u64 *acc = ext + ext_rows * N, *ext2 = acc + (size_t)chunk * 2 * kc.nt * N;
+    u64 *acc = ext + ext_rows * N, *ext2 = acc + acc_rows * N;
     u64 *extT = ext2 + ext2_rows * N, *ext2T = extT + ext_rows * N;
     const u64 **keys_all = (const u64 **)(ext2T + ext2_rows * N);
     const uint16_t **idx_all = (const uint16_t **)(keys_all + nr);
@@ -263,24 +349,25 @@ static int launch_keyswitch_jobs(sfg_ctx *ctx, const u64 *in, int nin, int level
     KswSeg *segs_d = (KswSeg *)(out_all + nr);
     int *inidx_all = (int *)(segs_d + nout);
     int *segjobs_d = inidx_all + nr;
+    KswTile *tiles_all = (KswTile *)(segjobs_d + nr);
     std::vector<char> seen(nout, 0);                            // outputs of a sum that have been written by an earlier chunk
-    std::vector<KswSeg> segs; std::vector<int> segjobs;
-    auto finish_sum = [&](const std::vector<int> &jobs, size_t c0, int nb, const u64 *bin, const int *inidx_d, const uint16_t **idx_d) -> int {
-        // the chunk's jobs by output (nb == 0: the outputs no job has touched)
-        std::vector<int> cnt(nout, 0), at(nout, 0);
-        for (int k = 0; k < nb; k++) cnt[sum->group[jobs[c0 + k]]]++;
-        segs.clear(); segjobs.assign(nb, 0);
-        for (int i = 0, start = 0; i < nout; i++) {
-            if (nb ? !cnt[i] : seen[i]) continue;
-            KswSeg sg; sg.plain = seen[i] ? nullptr : sum->plain[i]; sg.out = sum->out + (size_t)i * sum->out_stride;
-            sg.start = start; sg.count = cnt[i]; sg.accumulate = (sum->accumulate || seen[i]) ? 1 : 0; sg.pad = 0;
-            at[i] = start; start += cnt[i]; seen[i] = 1; segs.push_back(sg);
+    std::vector<KswSegPlan> plan; std::vector<KswSeg> segs; std::vector<int> segjobs, grp;
+    // the summed finish of the chunk's jobs [c0, c0 + nb) of the group's list (nb == 0: the outputs no job has touched); segments: ksw_plan.hpp
+    auto finish_sum = [&](const std::vector<int> &jobs, size_t c0, int nb, const u64 *bin, const u64 **keys_d, const int *inidx_d, const uint16_t **idx_d) -> int {
+        grp.resize(nb);
+        for (int k = 0; k < nb; k++) grp[k] = sum->group[jobs[c0 + k]];
+        ksw_plan_segments(grp.data(), nb, nout, seen, plan, segjobs);
+        if (plan.empty()) return 0;
+        segs.clear();
+        for (const KswSegPlan &sp : plan) {
+            KswSeg sg; sg.plain = sp.first ? sum->plain[sp.out] : nullptr; sg.out = sum->out + (size_t)sp.out * sum->out_stride;
+            sg.start = sp.start; sg.count = sp.count; sg.accumulate = (sum->accumulate || !sp.first) ? 1 : 0; sg.pad = 0;
+            segs.push_back(sg);
         }
-        for (int k = 0; k < nb; k++) segjobs[at[sum->group[jobs[c0 + k]]]++] = k;
-        if (segs.empty()) return 0;
         SFG_TRY(sfg_upload_small(ctx, segs_d, segs.data(), segs.size() * sizeof(KswSeg)));
         SFG_TRY(sfg_upload_small(ctx, segjobs_d, segjobs.data(), (size_t)nb * sizeof(int)));
-        hipLaunchKernelGGL(k_ksw_finish_sum, dim3(N / 256, nl, (unsigned)segs.size()), dim3(256), 0, ctx->stream, bin, inidx_d, acc, ext2T, idx_d, segs_d, segjobs_d, kcd, ctx->modc);
+        hipLaunchKernelGGL(k_ksw_finish_sum, dim3(N / 256, nl, (unsigned)segs.size()), dim3(256), 0, ctx->stream, extT, bin, keys_d, inidx_d, ext2T, idx_d,
+                           segs_d, segjobs_d, kcd, ctx->modc, ctx->nmod);
         SFG_HIP(ctx, hipGetLastError());
         return 0;
     };
@@ -290,6 +377,7 @@ static int launch_keyswitch_jobs(sfg_ctx *ctx, const u64 *in, int nin, int level
     for (int i = 0; i < kc.beta; i++) for (int t = 0; t < kc.nt; t++)           // in-digit rows and the targets the finish does not store: nobody reads them
         pext.m[i * kc.nt + t] = (kc.digit_of[t] == i || (t >= nq_out && t < nl)) ? (int8_t)-2 : (int8_t)kc.tmod[t];
     ModPattern pp; pp.period = kc.np; for (int p = 0; p < kc.np; p++) pp.m[p] = (int8_t)(ctx->nq + p);
+    RowMap rm_dense; rm_dense.rpg = 1; rm_dense.gstride_in = N; rm_dense.gstride_out = N;
     for (int i0 = 0; i0 < nin; i0 += in_grp) {
         const int ni = nin - i0 < in_grp ? nin - i0 : in_grp;
         std::vector<int> jobs;
@@ -298,43 +386,54 @@ static int launch_keyswitch_jobs(sfg_ctx *ctx, const u64 *in, int nin, int level
         const u64 *bin = in + (size_t)i0 * ctw;
         // 1. c2 = INTT(c1) for every input of the group
         RowMap rm1; rm1.rpg = nl; rm1.gstride_in = ctw; rm1.gstride_out = (size_t)nl * N;
-        SFG_TRY(launch_ntt_inv_map(ctx, bin + (size_t)nl * N, c2, (size_t)ni * nl, pin, rm1));
+        if (KSW_INV_SPLIT) SFG_TRY(launch_ntt_inv_split(ctx, bin + (size_t)nl * N, c2, (size_t)ni * nl, pin, rm1));
+        else SFG_TRY(launch_ntt_inv_map(ctx, bin + (size_t)nl * N, c2, (size_t)ni * nl, pin, rm1));
         // 2. digit extension + NTT (in-digit rows are skipped by the pattern)
-        if (pre1) hipLaunchKernelGGL(k_ksw_extend<true>, dim3(N / 512, kc.beta, ni), dim3(256), 0, ctx->stream, c2, ext, kcd, ctx->modc, ctx->tw_fwd);
-        else hipLaunchKernelGGL(k_ksw_extend<false>, dim3(N / 512, kc.beta, ni), dim3(256), 0, ctx->stream, c2, ext, kcd, ctx->modc, ctx->tw_fwd);
+        if (pre1) hipLaunchKernelGGL((k_ksw_extend<true, KSW_INV_SPLIT>), dim3(N / 512, kc.beta, ni), dim3(256), 0, ctx->stream, c2, ext, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv);
+        else hipLaunchKernelGGL((k_ksw_extend<false, KSW_INV_SPLIT>), dim3(N / 512, kc.beta, ni), dim3(256), 0, ctx->stream, c2, ext, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv);
         SFG_HIP(ctx, hipGetLastError());
         SFG_TRY(launch_ntt_fwd_staged(ctx, ext, extT, (size_t)ni * kc.beta * kc.nt, pext, pre1));
-        // pointer tables of the whole group: staged in the pinned ring, stream-ordered (no host wait on the launch path)
+        // pointer tables and tiles of the whole group: staged in the pinned ring, stream-ordered (no host wait on the launch path).  Tiles: per chunk, the runs of
+        // jobs under one key and one table in pieces of KSW_T (ksw_plan.hpp; chunk-local job numbers), chunk c's at tiles_all + tile_at[c]
+        std::vector<size_t> tile_at;
         {
             const size_t nj = jobs.size();
             std::vector<const u64 *> kp(nj); std::vector<const uint16_t *> ip(nj); std::vector<u64 *> op(nj); std::vector<int> ii(nj);
             for (size_t k = 0; k < nj; k++) { int jb = jobs[k]; kp[k] = keyp[jb]; ip[k] = idxp[jb]; op[k] = sum ? nullptr : outp[jb]; ii[k] = job_in[jb] - i0; }
+            std::vector<KswTile> tiles, tl;
+            for (size_t c0 = 0; c0 < nj; c0 += chunk) {
+                ksw_job_tiles(kp.data() + c0, ip.data() + c0, (int)(nj - c0 < (size_t)chunk ? nj - c0 : (size_t)chunk), KSW_T, tl);
+                tile_at.push_back(tiles.size()); tiles.insert(tiles.end(), tl.begin(), tl.end());
+            }
+            tile_at.push_back(tiles.size());
             SFG_TRY(sfg_upload_small(ctx, keys_all, kp.data(), nj * sizeof(void *)));
             SFG_TRY(sfg_upload_small(ctx, idx_all, ip.data(), nj * sizeof(void *)));
             if (!sum) SFG_TRY(sfg_upload_small(ctx, out_all, op.data(), nj * sizeof(void *)));
             SFG_TRY(sfg_upload_small(ctx, inidx_all, ii.data(), nj * sizeof(int)));
+            SFG_TRY(sfg_upload_small(ctx, tiles_all, tiles.data(), tiles.size() * sizeof(KswTile)));
         }
-        for (size_t c0 = 0; c0 < jobs.size(); c0 += chunk) {
+        for (size_t c0 = 0, ci = 0; c0 < jobs.size(); c0 += chunk, ci++) {
             const int nb = (int)(jobs.size() - c0 < (size_t)chunk ? jobs.size() - c0 : (size_t)chunk);
             const u64 **keys_d = keys_all + c0; const uint16_t **idx_d = idx_all + c0; u64 **out_d = out_all + c0; int *inidx_d = inidx_all + c0;
-            // 3. inner product with the key
-            hipLaunchKernelGGL(k_ksw_inner, dim3(N / 512, nq_out + kc.np, nb), dim3(256), 0, ctx->stream, extT, bin, keys_d, inidx_d, acc, kcd, ctx->modc, ctx->nmod, nq_out);
+            const KswTile *tiles_d = tiles_all + tile_at[ci]; const unsigned ntiles = (unsigned)(tile_at[ci + 1] - tile_at[ci]);
+            // 3. inner product with the key, special-prime targets only
+            hipLaunchKernelGGL(k_ksw_inner_p<KSW_T>, dim3(N / 512, kc.np, ntiles), dim3(256), 0, ctx->stream, extT, keys_d, inidx_d, tiles_d, acc, kcd, ctx->modc, ctx->nmod);
             SFG_HIP(ctx, hipGetLastError());
-            // 4. ModDown: INTT special rows in place, extend to Q, NTT
-            RowMap rm4; rm4.rpg = kc.np; rm4.gstride_in = (size_t)kc.nt * N; rm4.gstride_out = (size_t)kc.nt * N;
-            SFG_TRY(launch_ntt_inv_map(ctx, acc + (size_t)nl * N, acc + (size_t)nl * N, (size_t)nb * 2 * kc.np, pp, rm4));
-            if (pre1) hipLaunchKernelGGL(k_moddown_extend<true>, dim3(N / 512, 2, nb), dim3(256), 0, ctx->stream, acc, ext2, kcd, ctx->modc, ctx->tw_fwd, nq_out);
-            else hipLaunchKernelGGL(k_moddown_extend<false>, dim3(N / 512, 2, nb), dim3(256), 0, ctx->stream, acc, ext2, kcd, ctx->modc, ctx->tw_fwd, nq_out);
+            // 4. ModDown: INTT of the special rows in place, extend to Q, NTT
+            if (KSW_INV_SPLIT) SFG_TRY(launch_ntt_inv_split(ctx, acc, acc, (size_t)nb * 2 * kc.np, pp, rm_dense));
+            else SFG_TRY(launch_ntt_inv(ctx, acc, acc, (size_t)nb * 2 * kc.np, pp));
+            if (pre1) hipLaunchKernelGGL((k_moddown_extend<true, KSW_INV_SPLIT>), dim3(N / 512, 2, nb), dim3(256), 0, ctx->stream, acc, ext2, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv, nq_out);
+            else hipLaunchKernelGGL((k_moddown_extend<false, KSW_INV_SPLIT>), dim3(N / 512, 2, nb), dim3(256), 0, ctx->stream, acc, ext2, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv, nq_out);
             SFG_HIP(ctx, hipGetLastError());
             SFG_TRY(launch_ntt_fwd_staged(ctx, ext2, ext2T, (size_t)nb * 2 * nl, pq, pre1));
-            // 5. finish + automorphism
-            if (sum) { SFG_TRY(finish_sum(jobs, c0, nb, bin, inidx_d, idx_d)); continue; }
-            hipLaunchKernelGGL(k_ksw_finish, dim3(N / 256, nq_out, nb), dim3(256), 0, ctx->stream, bin, inidx_d, acc, ext2T, idx_d, out_d, kcd, ctx->modc,
-                               add1 ? add1 + (size_t)i0 * nl * N : nullptr, ff);
+            // 5. inner product of the Q targets + finish + automorphism
+            if (sum) { SFG_TRY(finish_sum(jobs, c0, nb, bin, keys_d, inidx_d, idx_d)); continue; }
+            hipLaunchKernelGGL(k_ksw_finish<KSW_T>, dim3(N / 256, nq_out, ntiles), dim3(256), 0, ctx->stream, extT, bin, keys_d, inidx_d, ext2T, idx_d, out_d, tiles_d, kcd,
+                               ctx->modc, ctx->nmod, add1 ? add1 + (size_t)i0 * nl * N : nullptr, ff);
             SFG_HIP(ctx, hipGetLastError());
         }
     }
-    if (sum) SFG_TRY(finish_sum(std::vector<int>(), 0, 0, in, inidx_all, idx_all));          // outputs without a job
+    if (sum) SFG_TRY(finish_sum(std::vector<int>(), 0, 0, in, keys_all, inidx_all, idx_all));          // outputs without a job
     return 0;
 }
 // Rotate a batch.  `in` holds nin ciphertexts [nin][2][nl][N]; output j = RotateRight(in[in_index[j]], nrot[j])
