@@ -52,6 +52,8 @@ def lib():
         L.orc_get_diag_bool.argtypes = [C.c_int] * 4
         L.orc_get_diag.restype = C.c_int
         L.orc_get_diag.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int8), C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.orc_rot_right.restype = None
+        L.orc_rot_right.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int]
         L.orc_encode_coeffs.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int64), C.c_int]
         L.orc_encode_ntt.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_int, u64p, C.c_int]
         L.orc_rotkeys_new.restype = C.c_void_p
