@@ -143,7 +143,7 @@ struct sfg_ctx {
     hipStream_t coll_stream = nullptr;   // third queue: the multi-GPU engine's collectives (mgpu.hip)
     hipEvent_t ev_pipe[4] = {nullptr, nullptr, nullptr, nullptr};   // [0,1]: rotation cache of group parity ready; [2,3]: finalize of column pass parity done
     std::vector<hipEvent_t> ev_pool; size_t ev_next = 0;     // ordering events (no timing), reused round-robin
-    std::map<int, void *> ksw_cache;   // per-level key-switch constants (device), rotate.hip
+    std::map<int, struct KswLevel *> ksw_cache;   // per-level key-switch constants (host and device copy, ksw.hpp), built by rotate.hip get_ksw, owned here
     // scratch
     void *ws = nullptr; size_t ws_bytes = 0;
     std::map<std::string, std::pair<void *, size_t>> pool;   // named grow-only device scratch (sfg_scratch), freed with the context

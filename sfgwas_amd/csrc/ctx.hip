@@ -1,5 +1,6 @@
 // ctx.hip — context, tables, memory and key management of libsfgwas_hip.
 #include "common.hpp"
+#include "ksw.hpp"
 
 thread_local std::string g_create_error;
 
@@ -199,7 +200,7 @@ extern "C" void sfg_ctx_destroy(sfg_ctx *ctx) {
     if (ctx->user_stream) (void)hipStreamSynchronize(ctx->user_stream);
     sfg_phases_resolve(ctx);
     sfg_ptc_detach_all(ctx);           // matrices whose plaintext cache this context owns must not keep a pointer to it (their handles outlive a fork)
-    for (auto &kv : ctx->ksw_cache) (void)hipFree(kv.second);
+    for (auto &kv : ctx->ksw_cache) { (void)hipFree(kv.second->dev); delete kv.second; }
     for (auto &kv : ctx->host_pool) (void)hipHostFree(kv.second.first);
     for (auto &kv : ctx->pool) (void)hipFree(kv.second.first);
     (void)hipFree(ctx->ws); (void)hipFree(ctx->tie_count_dev);

@@ -163,7 +163,7 @@ void sfg_encrypt_destroy(SfgShared *sh) {
 // the three steps for nct ciphertexts, in chunks whose T rows fit 1 GiB of scratch.  mode 0: out = Enc(pt) (pt nullable: zero); mode 1: out += Enc(0)
 static int encrypt_run(sfg_ctx *ctx, const EncSrc &src0, const u64 *pk, const u64 *pt, int nct, int level, int mode, u64 *out) {
     const int N = SFG_N, nl = level + 1, np = ctx->np, nt = nl + np;
-    KswConst *kcd; KswConst kc;
+    const KswConst *kcd, *kc;
     SFG_TRY(get_ksw(ctx, level, &kcd, &kc));
     ApiScope scope(ctx);
     const size_t per_ct = (size_t)2 * nt * N * 8;

@@ -21,8 +21,9 @@ struct KswConst {
     ExtConst pq;                                  // special primes -> Q (ModDown)
     double pinv[SFG_MAXMOD], pinv_q[SFG_MAXMOD];  // P^-1 mod q_t by global modulus index
 };
-// per-level constants (device copy cached in the context); rotate.hip
-int get_ksw(sfg_ctx *ctx, int level, KswConst **dev, KswConst *host);
+// per-level constants, built once: the host copy and its device copy, owned by the context (sfg_ctx::ksw_cache, freed in ctx.hip); rotate.hip
+struct KswLevel { KswConst host; KswConst *dev = nullptr; };
+int get_ksw(sfg_ctx *ctx, int level, const KswConst **dev, const KswConst **host);
 
 #ifdef __HIPCC__
 // general modular product of two canonical residues held in fp64 (both variable): result in (-q, q)

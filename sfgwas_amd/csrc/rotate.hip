@@ -20,20 +20,18 @@
 // whose results are summed (the giant-step alignment) are summed in step 5 (k_ksw_finish_sum); no Q row of the inner product is stored - the finish forms it from
 // the rows it gathers anyway; consecutive jobs under one key and table (a tile, ksw_plan.hpp) share each load of a key word in 3 and 5.  Every output word is the
 // canonical word it was.
+// The host side: a front-end resolves its rotations into a list of jobs (KswJobs; resolve_rotation: one rule for index, Galois element and key) and describes the
+// batch (KswBatch); ksw_plan.hpp decides, as pure functions tested on a CPU, how many inputs share a decomposition and how many jobs a chunk, where the regions of
+// the workspace lie, and which jobs fall into which input group, chunk and tile; launch_keyswitch_jobs executes that plan: reserve, upload, launch.
 #include "common.hpp"
 #include "kernels.hpp"
 #include "ksw.hpp"
 #include "ksw_plan.hpp"
+#include <memory>
 
 // Jobs per tile (ksw_plan.hpp) of k_ksw_inner_p and k_ksw_finish: a key word is loaded once for that many jobs.  Measured at 1, 3 and 5 (profiles/ksw_inner_finish_ab.txt):
 // 3 is the fastest for both.  The summed finish takes no tiles: with s = 15 outputs per block column, tiles of 3 or 5 segments leave it too few workgroups.
-#ifndef KSW_T
-#define KSW_T 3
-#endif
-// The key switch's two inverse transforms in the split form (ntt.hip k_ntt_inv_split), their last stage and 1/N done by the extension kernels that read them
-#ifndef KSW_INV_SPLIT
-#define KSW_INV_SPLIT true
-#endif
+constexpr int KSW_T = 3;
 
 
 static void fill_ext(const sfg_ctx *ctx, ExtConst &e, const std::vector<int> &src) {
@@ -59,12 +57,17 @@ static void fill_ext(const sfg_ctx *ctx, ExtConst &e, const std::vector<int> &sr
 }
 
 
-int get_ksw(sfg_ctx *ctx, int level, KswConst **dev, KswConst *host) {
-    KswConst kc; memset(&kc, 0, sizeof kc);
-    kc.level = level; kc.nl = level + 1; kc.np = ctx->np; kc.alpha = ctx->np; kc.nt = kc.nl + kc.np;
-    kc.beta = (kc.nl + kc.alpha - 1) / kc.alpha;
-    if (kc.alpha > KSW_MAXA || kc.beta > KSW_MAXDIG) SFG_FAIL(ctx, "key-switch shape unsupported (alpha > 4 or beta > 8)");
-    if (kc.beta * kc.nt > SFG_MAXPATTERN) SFG_FAIL(ctx, "key-switch shape unsupported (beta * (level + 1 + np) = %d rows exceed the modulus pattern table)", kc.beta * kc.nt);
+// The constants are built once per level and kept, host and device copy together, in the context (freed by sfg_ctx_destroy); an unsupported shape is refused on
+// every call and caches nothing.
+int get_ksw(sfg_ctx *ctx, int level, const KswConst **dev, const KswConst **host) {
+    const int nl = level + 1, alpha = ctx->np, nt = nl + ctx->np, beta = (nl + alpha - 1) / alpha;
+    if (alpha > KSW_MAXA || beta > KSW_MAXDIG) SFG_FAIL(ctx, "key-switch shape unsupported (alpha > 4 or beta > 8)");
+    if (beta * nt > SFG_MAXPATTERN) SFG_FAIL(ctx, "key-switch shape unsupported (beta * (level + 1 + np) = %d rows exceed the modulus pattern table)", beta * nt);
+    auto it = ctx->ksw_cache.find(level);
+    if (it != ctx->ksw_cache.end()) { *dev = it->second->dev; *host = &it->second->host; return 0; }
+    std::unique_ptr<KswLevel> rec(new KswLevel);
+    KswConst &kc = rec->host; memset(&kc, 0, sizeof kc);
+    kc.level = level; kc.nl = nl; kc.np = ctx->np; kc.alpha = alpha; kc.nt = nt; kc.beta = beta;
     for (int t = 0; t < kc.nt; t++) { kc.tmod[t] = t < kc.nl ? t : ctx->nq + (t - kc.nl); kc.digit_of[t] = t < kc.nl ? t / kc.alpha : -1; }
     for (int i = 0; i < kc.beta; i++) {
         std::vector<int> src;
@@ -79,14 +82,10 @@ int get_ksw(sfg_ctx *ctx, int level, KswConst **dev, KswConst *host) {
         u64 pi = h_invmod(P, qt);
         kc.pinv[t] = (double)pi; kc.pinv_q[t] = (double)pi / (double)qt;
     }
-    *host = kc;
-    auto it = ctx->ksw_cache.find(level);
-    if (it == ctx->ksw_cache.end()) {
-        KswConst *d = nullptr;
-        SFG_HIP(ctx, hipMalloc(&d, sizeof(KswConst)));
-        SFG_HIP(ctx, hipMemcpy(d, &kc, sizeof(KswConst), hipMemcpyHostToDevice));
-        ctx->ksw_cache[level] = d; *dev = d;
-    } else *dev = (KswConst *)it->second;
+    SFG_HIP(ctx, hipMalloc(&rec->dev, sizeof(KswConst)));
+    if (hipError_t e = hipMemcpy(rec->dev, &kc, sizeof(KswConst), hipMemcpyHostToDevice)) { (void)hipFree(rec->dev); SFG_HIP(ctx, e); }
+    *dev = rec->dev; *host = &rec->host;
+    ctx->ksw_cache[level] = rec.release();
     return 0;
 }
 
@@ -96,12 +95,13 @@ __device__ __forceinline__ void inv_last_of(const ModConst &mc, double w, double
     const double wn = canon(mulmod_lazy(w, mc.ninv, mc.ninv_q, mc.q), mc.q, mc.qinv);
     inv_last_pair(u, v, mc.ninv, mc.ninv_q, wn, wn * mc.qinv, mc.q, mc.qinv, u, v);
 }
-// grid (N/512, beta, B). c2: [B][nl][N] coefficient-domain c1; ext: [B][beta][nt][N].  A thread extends positions x and x + N/2, so that it can apply
-// the forward transform's first stage to the rows it writes (PRE1, fp64mod.hpp fwd_stage1_pair): the element-wise kernels wait for memory and have fp64
-// issue slots to spare, the transforms do not.
-// POST1: c2 comes from the split inverse transform (ntt.hip k_ntt_inv_split) and lacks its last stage and 1/N: the pair a thread loads is exactly a pair of that
-// stage, finished here (fp64mod.hpp inv_last_pair) for the same reason.
-template <bool PRE1, bool POST1>
+// grid (N/512, beta, B). c2: [B][nl][N] c1 out of the split inverse transform; ext: [B][beta][nt][N].  A thread extends positions x and x + N/2, so that it can
+// apply the forward transform's first stage to the rows it writes (PRE1, fp64mod.hpp fwd_stage1_pair): the element-wise kernels wait for memory and have fp64
+// issue slots to spare, the transforms do not.  c2 lacks the inverse transform's last stage and 1/N (ntt.hip k_ntt_inv_split): the pair a thread loads is exactly
+// a pair of that stage, finished here (inv_last_of) for the same reason.
+// The body is k_moddown_extend's, line for line, and stays written out in both: moved into shared __forceinline__ helpers, the compiler schedules it differently
+// (other instruction text, other instruction counts), and these two kernels are pinned to the instruction.
+template <bool PRE1>
 __global__ void __launch_bounds__(256) k_ksw_extend(const u64 *c2, u64 *ext, const KswConst *kcp, const ModConst *modc, const double *tw_fwd, const double *tw_inv) {
     const KswConst &kc = *kcp;
     const int N = SFG_N, n = N / 2, x = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y; const size_t b = blockIdx.z;
@@ -113,14 +113,12 @@ __global__ void __launch_bounds__(256) k_ksw_extend(const u64 *c2, u64 *ext, con
     for (int h = 0; h < 2; h++)
 #pragma unroll
         for (int m = 0; m < KSW_MAXA; m++) xs[h][m] = m < e.a ? u64_to_f64(c2b[(size_t)e.src[m] * N + h * n + x]) : 0.0;
-    if (POST1) {
 #pragma unroll
-        for (int m = 0; m < KSW_MAXA; m++) if (m < e.a) inv_last_of(modc[e.src[m]], tw_inv[(size_t)e.src[m] * N + 1], xs[0][m], xs[1][m]);
-    }
+    for (int m = 0; m < KSW_MAXA; m++) if (m < e.a) inv_last_of(modc[e.src[m]], tw_inv[(size_t)e.src[m] * N + 1], xs[0][m], xs[1][m]);
     if (e.a > 1) { ext_prepare(e, modc, xs[0], y[0], v[0]); ext_prepare(e, modc, xs[1], y[1], v[1]); }
     for (int t = 0; t < kc.nt; t++) {
         const int tg = kc.tmod[t];
-        if (kc.digit_of[t] == i) continue;                                            // in-digit: the original NTT row, which k_ksw_inner reads where it lies
+        if (kc.digit_of[t] == i) continue;                                            // in-digit: the original NTT row, which the finish reads where it lies
         const double q = modc[tg].q, qinv = modc[tg].qinv;
         double o0, o1;
         if (e.a == 1) { o0 = canon(xs[0][0], q, qinv); o1 = canon(xs[1][0], q, qinv); }      // single-prime digit: raw copy mod q_t
@@ -170,9 +168,9 @@ __global__ void __launch_bounds__(256) k_ksw_inner_p(const u64 *ext, const u64 *
     }
 }
 
-// grid (N/512, 2, B): the rows of acc [B][2][np][N] (already INTT'd) -> ext2 [B][2][nl][N] coefficient domain, rows t < nq_out (the others nobody reads).
-// Positions x and x + N/2 in one thread, PRE1 and POST1 as in k_ksw_extend.
-template <bool PRE1, bool POST1>
+// grid (N/512, 2, B): the rows of acc [B][2][np][N] (out of the split inverse transform) -> ext2 [B][2][nl][N] coefficient domain, rows t < nq_out (the others
+// nobody reads).  Positions x and x + N/2 in one thread, the last inverse stage on the pairs read and PRE1 on the pairs written as in k_ksw_extend.
+template <bool PRE1>
 __global__ void __launch_bounds__(256) k_moddown_extend(const u64 *acc, u64 *ext2, const KswConst *kcp, const ModConst *modc, const double *tw_fwd, const double *tw_inv, int nq_out) {
     const KswConst &kc = *kcp;
     const int N = SFG_N, n = N / 2, x = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y; const size_t b = blockIdx.z;
@@ -183,10 +181,8 @@ __global__ void __launch_bounds__(256) k_moddown_extend(const u64 *acc, u64 *ext
     for (int h = 0; h < 2; h++)
 #pragma unroll
         for (int m = 0; m < KSW_MAXA; m++) xs[h][m] = m < e.a ? u64_to_f64(ap[(size_t)m * N + h * n + x]) : 0.0;
-    if (POST1) {
 #pragma unroll
-        for (int m = 0; m < KSW_MAXA; m++) if (m < e.a) inv_last_of(modc[e.src[m]], tw_inv[(size_t)e.src[m] * N + 1], xs[0][m], xs[1][m]);
-    }
+    for (int m = 0; m < KSW_MAXA; m++) if (m < e.a) inv_last_of(modc[e.src[m]], tw_inv[(size_t)e.src[m] * N + 1], xs[0][m], xs[1][m]);
     if (e.a > 1) { ext_prepare(e, modc, xs[0], y[0], v[0]); ext_prepare(e, modc, xs[1], y[1], v[1]); }
     for (int t = 0; t < nq_out; t++) {
         const double q = modc[t].q, qinv = modc[t].qinv;
@@ -312,50 +308,52 @@ __global__ void __launch_bounds__(256) k_ct_add(const u64 *a, const u64 *b, u64 
 //   out0 = perm(in.p0 + d0), out1 = perm(d1 [+ add1[in]])            to outp[k].
 // Decomposition (steps 1-2) is done once per INPUT and shared by all its jobs ("hoisting"): the per-key work is
 // only the inner product, ModDown and the automorphism.  Same arithmetic, same bits.
-// With a KswSum the jobs' results are not stored one by one (outp is not read): job k adds into output group[k] < nout, and output i becomes
+// With a KswSum the jobs' results are not stored one by one (outp is not read): job k adds into output group[k] < nout (KswJobs), and output i becomes
 //   [its old content, when accumulate] + [plain[i], an unrotated ciphertext, when not null] + sum of its jobs     at out + i * out_stride,
 // every word reduced once (k_ksw_finish_sum).  An input group or job chunk may hold any part of an output's jobs: the first part writes, the others add.
-struct KswSum { int nout; std::vector<int> group; std::vector<const u64 *> plain; u64 *out; size_t out_stride; int accumulate; };
-static int launch_keyswitch_jobs(sfg_ctx *ctx, const u64 *in, int nin, int level, const std::vector<int> &job_in, const std::vector<const u64 *> &keyp,
-                                 const std::vector<const uint16_t *> &idxp, const std::vector<u64 *> &outp, const u64 *add1, const F64Form *ffp = nullptr,
-                                 const KswSum *sum = nullptr) {
-    const int N = SFG_N, nl = level + 1;
-    F64Form ff; memset(&ff, 0, sizeof ff); if (ffp) ff = *ffp;
-    KswConst *kcd; KswConst kc;
-    SFG_TRY(get_ksw(ctx, level, &kcd, &kc));
+struct KswSum { int nout; std::vector<const u64 *> plain; u64 *out; size_t out_stride; int accumulate; };
+// The jobs of a batch: job k reads input job_in[k] with key keyp[k] and table idxp[k]; it writes outp[k], or adds into output group[k] of the batch's KswSum.
+struct KswJobs {
+    std::vector<int> job_in; std::vector<const u64 *> keyp; std::vector<const uint16_t *> idxp; std::vector<u64 *> outp; std::vector<int> group;
+    void add(int in, const RotKey &key, u64 *out, int grp = 0) { job_in.push_back(in); keyp.push_back(key.key_dev); idxp.push_back(key.index_dev); outp.push_back(out); group.push_back(grp); }
+    // job j = input j under one key, written to out + j * stride words
+    KswJobs(int nct, const RotKey &key, u64 *out, size_t stride) { for (int j = 0; j < nct; j++) add(j, key, out + (size_t)j * stride); }
+    KswJobs() {}
+};
+// What the jobs work on: the inputs and their level, rows added to polynomial 1 (add1, nullable), the output form (ff, nullable: u64 ciphertexts), the sum (nullable)
+struct KswBatch { const u64 *in; int nin, level; const u64 *add1 = nullptr; const F64Form *ff = nullptr; const KswSum *sum = nullptr; };
+static_assert(sizeof(KswSeg) == KSW_SEG_BYTES && sizeof(void *) == KSW_PTR_BYTES, "ksw_plan.hpp lays the tables out for these sizes");
+
+static int launch_keyswitch_jobs(sfg_ctx *ctx, const KswBatch &bt, const KswJobs &jb) {
+    const int N = SFG_N, level = bt.level, nl = level + 1, nin = bt.nin;
+    const u64 *in = bt.in, *add1 = bt.add1; const KswSum *sum = bt.sum;
+    F64Form ff; memset(&ff, 0, sizeof ff); if (bt.ff) ff = *bt.ff;
+    const KswConst *kcd, *kcp;
+    SFG_TRY(get_ksw(ctx, level, &kcd, &kcp));
+    const KswConst &kc = *kcp;
     const size_t ctw = (size_t)2 * nl * N;
-    const int nr = (int)job_in.size(), nout = sum ? sum->nout : 0;
-    if (sum && (ff.on || add1 || (int)sum->group.size() != nr || (int)sum->plain.size() != nout)) SFG_FAIL(ctx, "key switch: internal: malformed sum groups");
+    const int nr = (int)jb.job_in.size(), nout = sum ? sum->nout : 0;
+    if (sum && (ff.on || add1 || (int)sum->plain.size() != nout)) SFG_FAIL(ctx, "key switch: internal: malformed sum groups");
     if (!nr && !nout) return 0;
     const int nq_out = ff.on ? ff.L : nl;                       // moduli of the result that the finish stores: the rows of the others are not produced
     const bool pre1 = !ctx->cfg.ntt_fwd_full;                   // the extension kernels apply the forward transform's first stage (the split transform starts at stage 2)
-    // inputs are processed in groups whose decomposition fits the budget (4 GiB by default); jobs of a group in chunks whose acc/ext2 fit it
-    const size_t in_rows = (size_t)nl + (size_t)kc.beta * kc.nt, job_rows = 2 * (size_t)kc.nt + 2 * (size_t)nl;
-    const size_t budget = ctx->cfg.ksw_budget;                  // bytes of decomposition / accumulator scratch per group resp. chunk (SFG_KSW_BUDGET_MB)
-    int in_grp = (int)(budget / (in_rows * N * 8)); if (in_grp < 1) in_grp = 1; if (in_grp > nin) in_grp = nin;
-    int chunk = (int)(budget / (job_rows * N * 8)); if (chunk < 1) chunk = 1; if (chunk > nr) chunk = nr;
-    // pointer tables and tiles for every job of a group; segments of a chunk
-    const size_t ptr_bytes = (size_t)nr * (3 * sizeof(void *) + 2 * sizeof(int) + sizeof(KswTile)) + (size_t)nout * sizeof(KswSeg) + 256;
-    // the forward NTTs run out of place (two half-row workgroups per row cannot share a buffer with their input): extT / ext2T receive the transforms.
-    // acc holds the 2 np special-prime rows of a job only (the chunk size is still what the budget gave when it held all 2 nt: the job list is cut where it was)
-    const size_t ext_rows = (size_t)in_grp * kc.beta * kc.nt, ext2_rows = (size_t)chunk * 2 * nl, acc_rows = (size_t)chunk * 2 * kc.np;
-    SFG_TRY(sfg_ws_reserve(ctx, (in_rows * in_grp + acc_rows + 2 * ext2_rows + ext_rows) * N * 8 + ptr_bytes));
-    u64 *c2 = (u64 *)ctx->ws, *ext = c2 + (size_t)in_grp * nl * N;
-    u64 *acc = ext + ext_rows * N, *ext2 = acc + acc_rows * N;
-    u64 *extT = ext2 + ext2_rows * N, *ext2T = extT + ext_rows * N;
-    const u64 **keys_all = (const u64 **)(ext2T + ext2_rows * N);
-    const uint16_t **idx_all = (const uint16_t **)(keys_all + nr);
-    u64 **out_all = (u64 **)(idx_all + nr);
-    KswSeg *segs_d = (KswSeg *)(out_all + nr);
-    int *inidx_all = (int *)(segs_d + nout);
-    int *segjobs_d = inidx_all + nr;
-    KswTile *tiles_all = (KswTile *)(segjobs_d + nr);
+    // inputs are processed in groups whose decomposition fits the budget (SFG_KSW_BUDGET_MB, 4 GiB by default), jobs of a group in chunks whose acc / ext2 fit it:
+    // the sizes, the workspace layout and the groups are ksw_plan.hpp's
+    const KswSizes sz = ksw_plan_sizes(nl, kc.np, kc.nt, kc.beta, nin, nr, nout, ctx->cfg.ksw_budget, (size_t)N);
+    std::vector<KswGroup> groups;
+    ksw_plan_groups(jb.job_in.data(), jb.keyp.data(), jb.idxp.data(), nr, nin, sz.in_grp, sz.chunk, KSW_T, groups);
+    SFG_TRY(sfg_ws_reserve(ctx, sz.at.bytes));
+    u64 *const w = (u64 *)ctx->ws; char *const wb = (char *)ctx->ws;
+    u64 *c2 = w + sz.at.c2, *ext = w + sz.at.ext, *acc = w + sz.at.acc, *ext2 = w + sz.at.ext2, *extT = w + sz.at.extT, *ext2T = w + sz.at.ext2T;
+    const u64 **keys_all = (const u64 **)(wb + sz.at.keys); const uint16_t **idx_all = (const uint16_t **)(wb + sz.at.idx); u64 **out_all = (u64 **)(wb + sz.at.out);
+    KswSeg *segs_d = (KswSeg *)(wb + sz.at.segs); int *inidx_all = (int *)(wb + sz.at.inidx), *segjobs_d = (int *)(wb + sz.at.segjobs);
+    KswTile *tiles_all = (KswTile *)(wb + sz.at.tiles);
     std::vector<char> seen(nout, 0);                            // outputs of a sum that have been written by an earlier chunk
     std::vector<KswSegPlan> plan; std::vector<KswSeg> segs; std::vector<int> segjobs, grp;
     // the summed finish of the chunk's jobs [c0, c0 + nb) of the group's list (nb == 0: the outputs no job has touched); segments: ksw_plan.hpp
     auto finish_sum = [&](const std::vector<int> &jobs, size_t c0, int nb, const u64 *bin, const u64 **keys_d, const int *inidx_d, const uint16_t **idx_d) -> int {
         grp.resize(nb);
-        for (int k = 0; k < nb; k++) grp[k] = sum->group[jobs[c0 + k]];
+        for (int k = 0; k < nb; k++) grp[k] = jb.group[jobs[c0 + k]];
         ksw_plan_segments(grp.data(), nb, nout, seen, plan, segjobs);
         if (plan.empty()) return 0;
         segs.clear();
@@ -378,56 +376,45 @@ static int launch_keyswitch_jobs(sfg_ctx *ctx, const u64 *in, int nin, int level
         pext.m[i * kc.nt + t] = (kc.digit_of[t] == i || (t >= nq_out && t < nl)) ? (int8_t)-2 : (int8_t)kc.tmod[t];
     ModPattern pp; pp.period = kc.np; for (int p = 0; p < kc.np; p++) pp.m[p] = (int8_t)(ctx->nq + p);
     RowMap rm_dense; rm_dense.rpg = 1; rm_dense.gstride_in = N; rm_dense.gstride_out = N;
-    for (int i0 = 0; i0 < nin; i0 += in_grp) {
-        const int ni = nin - i0 < in_grp ? nin - i0 : in_grp;
-        std::vector<int> jobs;
-        for (int k = 0; k < nr; k++) if (job_in[k] >= i0 && job_in[k] < i0 + ni) jobs.push_back(k);
-        if (jobs.empty()) continue;
+    for (const KswGroup &g : groups) {
+        const int i0 = g.i0, ni = g.ni;
+        const std::vector<int> &jobs = g.jobs;
         const u64 *bin = in + (size_t)i0 * ctw;
-        // 1. c2 = INTT(c1) for every input of the group
+        // 1. c2 = INTT(c1) for every input of the group, without the last stage and 1/N
         RowMap rm1; rm1.rpg = nl; rm1.gstride_in = ctw; rm1.gstride_out = (size_t)nl * N;
-        if (KSW_INV_SPLIT) SFG_TRY(launch_ntt_inv_split(ctx, bin + (size_t)nl * N, c2, (size_t)ni * nl, pin, rm1));
-        else SFG_TRY(launch_ntt_inv_map(ctx, bin + (size_t)nl * N, c2, (size_t)ni * nl, pin, rm1));
+        SFG_TRY(launch_ntt_inv_split(ctx, bin + (size_t)nl * N, c2, (size_t)ni * nl, pin, rm1));
         // 2. digit extension + NTT (in-digit rows are skipped by the pattern)
-        if (pre1) hipLaunchKernelGGL((k_ksw_extend<true, KSW_INV_SPLIT>), dim3(N / 512, kc.beta, ni), dim3(256), 0, ctx->stream, c2, ext, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv);
-        else hipLaunchKernelGGL((k_ksw_extend<false, KSW_INV_SPLIT>), dim3(N / 512, kc.beta, ni), dim3(256), 0, ctx->stream, c2, ext, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv);
+        if (pre1) hipLaunchKernelGGL(k_ksw_extend<true>, dim3(N / 512, kc.beta, ni), dim3(256), 0, ctx->stream, c2, ext, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv);
+        else hipLaunchKernelGGL(k_ksw_extend<false>, dim3(N / 512, kc.beta, ni), dim3(256), 0, ctx->stream, c2, ext, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv);
         SFG_HIP(ctx, hipGetLastError());
         SFG_TRY(launch_ntt_fwd_staged(ctx, ext, extT, (size_t)ni * kc.beta * kc.nt, pext, pre1));
-        // pointer tables and tiles of the whole group: staged in the pinned ring, stream-ordered (no host wait on the launch path).  Tiles: per chunk, the runs of
-        // jobs under one key and one table in pieces of KSW_T (ksw_plan.hpp; chunk-local job numbers), chunk c's at tiles_all + tile_at[c]
-        std::vector<size_t> tile_at;
+        // pointer tables and tiles of the whole group (group-local job numbers; a chunk's tiles: chunk-local): staged in the pinned ring, stream-ordered (no host
+        // wait on the launch path)
         {
             const size_t nj = jobs.size();
             std::vector<const u64 *> kp(nj); std::vector<const uint16_t *> ip(nj); std::vector<u64 *> op(nj); std::vector<int> ii(nj);
-            for (size_t k = 0; k < nj; k++) { int jb = jobs[k]; kp[k] = keyp[jb]; ip[k] = idxp[jb]; op[k] = sum ? nullptr : outp[jb]; ii[k] = job_in[jb] - i0; }
-            std::vector<KswTile> tiles, tl;
-            for (size_t c0 = 0; c0 < nj; c0 += chunk) {
-                ksw_job_tiles(kp.data() + c0, ip.data() + c0, (int)(nj - c0 < (size_t)chunk ? nj - c0 : (size_t)chunk), KSW_T, tl);
-                tile_at.push_back(tiles.size()); tiles.insert(tiles.end(), tl.begin(), tl.end());
-            }
-            tile_at.push_back(tiles.size());
+            for (size_t k = 0; k < nj; k++) { int j = jobs[k]; kp[k] = jb.keyp[j]; ip[k] = jb.idxp[j]; op[k] = sum ? nullptr : jb.outp[j]; ii[k] = jb.job_in[j] - i0; }
             SFG_TRY(sfg_upload_small(ctx, keys_all, kp.data(), nj * sizeof(void *)));
             SFG_TRY(sfg_upload_small(ctx, idx_all, ip.data(), nj * sizeof(void *)));
             if (!sum) SFG_TRY(sfg_upload_small(ctx, out_all, op.data(), nj * sizeof(void *)));
             SFG_TRY(sfg_upload_small(ctx, inidx_all, ii.data(), nj * sizeof(int)));
-            SFG_TRY(sfg_upload_small(ctx, tiles_all, tiles.data(), tiles.size() * sizeof(KswTile)));
+            SFG_TRY(sfg_upload_small(ctx, tiles_all, g.tiles.data(), g.tiles.size() * sizeof(KswTile)));
         }
-        for (size_t c0 = 0, ci = 0; c0 < jobs.size(); c0 += chunk, ci++) {
-            const int nb = (int)(jobs.size() - c0 < (size_t)chunk ? jobs.size() - c0 : (size_t)chunk);
-            const u64 **keys_d = keys_all + c0; const uint16_t **idx_d = idx_all + c0; u64 **out_d = out_all + c0; int *inidx_d = inidx_all + c0;
-            const KswTile *tiles_d = tiles_all + tile_at[ci]; const unsigned ntiles = (unsigned)(tile_at[ci + 1] - tile_at[ci]);
+        for (const KswChunk &c : g.chunks) {
+            const int nb = c.nb;
+            const u64 **keys_d = keys_all + c.c0; const uint16_t **idx_d = idx_all + c.c0; u64 **out_d = out_all + c.c0; int *inidx_d = inidx_all + c.c0;
+            const KswTile *tiles_d = tiles_all + c.tile0; const unsigned ntiles = (unsigned)c.ntiles;
             // 3. inner product with the key, special-prime targets only
             hipLaunchKernelGGL(k_ksw_inner_p<KSW_T>, dim3(N / 512, kc.np, ntiles), dim3(256), 0, ctx->stream, extT, keys_d, inidx_d, tiles_d, acc, kcd, ctx->modc, ctx->nmod);
             SFG_HIP(ctx, hipGetLastError());
-            // 4. ModDown: INTT of the special rows in place, extend to Q, NTT
-            if (KSW_INV_SPLIT) SFG_TRY(launch_ntt_inv_split(ctx, acc, acc, (size_t)nb * 2 * kc.np, pp, rm_dense));
-            else SFG_TRY(launch_ntt_inv(ctx, acc, acc, (size_t)nb * 2 * kc.np, pp));
-            if (pre1) hipLaunchKernelGGL((k_moddown_extend<true, KSW_INV_SPLIT>), dim3(N / 512, 2, nb), dim3(256), 0, ctx->stream, acc, ext2, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv, nq_out);
-            else hipLaunchKernelGGL((k_moddown_extend<false, KSW_INV_SPLIT>), dim3(N / 512, 2, nb), dim3(256), 0, ctx->stream, acc, ext2, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv, nq_out);
+            // 4. ModDown: INTT of the special rows in place (split: finished by the extension), extend to Q, NTT
+            SFG_TRY(launch_ntt_inv_split(ctx, acc, acc, (size_t)nb * 2 * kc.np, pp, rm_dense));
+            if (pre1) hipLaunchKernelGGL(k_moddown_extend<true>, dim3(N / 512, 2, nb), dim3(256), 0, ctx->stream, acc, ext2, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv, nq_out);
+            else hipLaunchKernelGGL(k_moddown_extend<false>, dim3(N / 512, 2, nb), dim3(256), 0, ctx->stream, acc, ext2, kcd, ctx->modc, ctx->tw_fwd, ctx->tw_inv, nq_out);
             SFG_HIP(ctx, hipGetLastError());
             SFG_TRY(launch_ntt_fwd_staged(ctx, ext2, ext2T, (size_t)nb * 2 * nl, pq, pre1));
             // 5. inner product of the Q targets + finish + automorphism
-            if (sum) { SFG_TRY(finish_sum(jobs, c0, nb, bin, keys_d, inidx_d, idx_d)); continue; }
+            if (sum) { SFG_TRY(finish_sum(jobs, (size_t)c.c0, nb, bin, keys_d, inidx_d, idx_d)); continue; }
             hipLaunchKernelGGL(k_ksw_finish<KSW_T>, dim3(N / 256, nq_out, ntiles), dim3(256), 0, ctx->stream, extT, bin, keys_d, inidx_d, ext2T, idx_d, out_d, tiles_d, kcd,
                                ctx->modc, ctx->nmod, add1 ? add1 + (size_t)i0 * nl * N : nullptr, ff);
             SFG_HIP(ctx, hipGetLastError());
@@ -436,56 +423,57 @@ static int launch_keyswitch_jobs(sfg_ctx *ctx, const u64 *in, int nin, int level
     if (sum) SFG_TRY(finish_sum(std::vector<int>(), 0, 0, in, keys_all, inidx_all, idx_all));          // outputs without a job
     return 0;
 }
+// What the rotation front-ends share: job j rotates input src = in_index[j] (nullptr: j) right by nrot = nrot_host[j] mod SFG_SLOTS in [0, SFG_SLOTS); key: the
+// switching key of that rotation (basics.go:205: RotateNew(ct, slots - nrot)), nullptr for nrot == 0, which each front-end treats in its own way.
+struct RotJob { int nrot, src; const RotKey *key; };
+static int resolve_rotation(sfg_ctx *ctx, const int *nrot_host, const int *in_index, int j, int nin, RotJob &r) {
+    r.nrot = nrot_host[j] % SFG_SLOTS; if (r.nrot < 0) r.nrot += SFG_SLOTS;
+    r.src = in_index ? in_index[j] : j; r.key = nullptr;
+    if (r.src < 0 || r.src >= nin) SFG_FAIL(ctx, "rotate: input index out of range");
+    if (r.nrot == 0) return 0;
+    u64 g = sfg_galois_for_rotation(ctx, SFG_SLOTS - r.nrot);
+    auto it = ctx->rotkeys().find(g);
+    if (it == ctx->rotkeys().end()) SFG_FAIL(ctx, "rotate: no rotation key loaded for right-rotation by %d (galois element %llu)", r.nrot, g);
+    r.key = &it->second;
+    return 0;
+}
+// the run of unrotated jobs from job j (input src) on whose (source, slot) pairs are consecutive: one copy or conversion serves them all
+static int unrotated_run(const int *nrot_host, const int *in_index, int j, int nct, int src, int nin) {
+    int run = 1;
+    while (j + run < nct && (nrot_host[j + run] % SFG_SLOTS) == 0 && (in_index ? in_index[j + run] : j + run) == src + run && src + run < nin) run++;
+    return run;
+}
 // Rotate a batch.  `in` holds nin ciphertexts [nin][2][nl][N]; output j = RotateRight(in[in_index[j]], nrot[j])
 // (RotateRightWithEvaluator semantics) written to out + j*ct words.  in_index == nullptr means identity (nin == nct).
 int launch_rotate_right_indexed(sfg_ctx *ctx, const u64 *in, int nin, u64 *out, int nct, int level, const int *nrot_host, const int *in_index) {
-    const int N = SFG_N, nl = level + 1;
     if (level < 0 || level >= ctx->nq) SFG_FAIL(ctx, "rotate: level out of range");
-    const size_t ctw = (size_t)2 * nl * N;
-    std::vector<int> job_in; std::vector<const u64 *> keyp; std::vector<const uint16_t *> idxp; std::vector<u64 *> outp;
+    const size_t ctw = (size_t)2 * (level + 1) * SFG_N;
+    KswBatch bt{in, nin, level}; KswJobs jb; RotJob r;
     for (int j = 0; j < nct; j++) {
-        int nrot = nrot_host[j] % SFG_SLOTS; if (nrot < 0) nrot += SFG_SLOTS;
-        const int src = in_index ? in_index[j] : j;
-        if (src < 0 || src >= nin) SFG_FAIL(ctx, "rotate: input index out of range");
-        if (nrot == 0) {                                    // not rotated: copied; runs of consecutive (source, slot) pairs in one copy
-            int run = 1;
-            while (j + run < nct && (nrot_host[j + run] % SFG_SLOTS) == 0 && (in_index ? in_index[j + run] : j + run) == src + run && src + run < nin) run++;
-            SFG_HIP(ctx, hipMemcpyAsync(out + j * ctw, in + (size_t)src * ctw, (size_t)run * ctw * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            j += run - 1;
-            continue;
-        }
-        u64 g = sfg_galois_for_rotation(ctx, SFG_SLOTS - nrot);                 // basics.go:205: RotateNew(ct, slots - nrot)
-        auto it = ctx->rotkeys().find(g);
-        if (it == ctx->rotkeys().end()) SFG_FAIL(ctx, "rotate: no rotation key loaded for right-rotation by %d (galois element %llu)", nrot, g);
-        job_in.push_back(src); keyp.push_back(it->second.key_dev); idxp.push_back(it->second.index_dev); outp.push_back(out + j * ctw);
+        SFG_TRY(resolve_rotation(ctx, nrot_host, in_index, j, nin, r));
+        if (r.key) { jb.add(r.src, *r.key, out + j * ctw); continue; }
+        const int run = unrotated_run(nrot_host, in_index, j, nct, r.src, nin);      // not rotated: copied
+        SFG_HIP(ctx, hipMemcpyAsync(out + j * ctw, in + (size_t)r.src * ctw, (size_t)run * ctw * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        j += run - 1;
     }
-    return launch_keyswitch_jobs(ctx, in, nin, level, job_in, keyp, idxp, outp, nullptr);
+    return launch_keyswitch_jobs(ctx, bt, jb);
 }
 // The same batch SUMMED where it is produced: out + i * out_stride (+)= sum over the jobs j with group[j] == i of RotateRight(in[in_index[j]], nrot[j]), i < nout.
 // A job that does not rotate joins its sum as a plain read (one per output).  No rotated ciphertext is stored.  `out` must not overlap `in`.
 int launch_rotate_right_sum(sfg_ctx *ctx, const u64 *in, int nin, int nct, int level, const int *nrot_host, const int *in_index, const int *group, int nout,
                             u64 *out, size_t out_stride, int accumulate) {
-    const int N = SFG_N, nl = level + 1;
     if (level < 0 || level >= ctx->nq) SFG_FAIL(ctx, "rotate: level out of range");
-    const size_t ctw = (size_t)2 * nl * N;
+    const size_t ctw = (size_t)2 * (level + 1) * SFG_N;
     KswSum sum; sum.nout = nout; sum.plain.assign(nout, nullptr); sum.out = out; sum.out_stride = out_stride; sum.accumulate = accumulate;
-    std::vector<int> job_in; std::vector<const u64 *> keyp; std::vector<const uint16_t *> idxp;
+    KswBatch bt{in, nin, level}; bt.sum = &sum; KswJobs jb; RotJob r;
     for (int j = 0; j < nct; j++) {
-        int nrot = nrot_host[j] % SFG_SLOTS; if (nrot < 0) nrot += SFG_SLOTS;
-        const int src = in_index ? in_index[j] : j;
-        if (src < 0 || src >= nin) SFG_FAIL(ctx, "rotate: input index out of range");
         if (group[j] < 0 || group[j] >= nout) SFG_FAIL(ctx, "rotate: sum group out of range");
-        if (nrot == 0) {
-            if (sum.plain[group[j]]) SFG_FAIL(ctx, "rotate: more than one unrotated member in a sum group");
-            sum.plain[group[j]] = in + (size_t)src * ctw;
-            continue;
-        }
-        u64 g = sfg_galois_for_rotation(ctx, SFG_SLOTS - nrot);
-        auto it = ctx->rotkeys().find(g);
-        if (it == ctx->rotkeys().end()) SFG_FAIL(ctx, "rotate: no rotation key loaded for right-rotation by %d (galois element %llu)", nrot, g);
-        job_in.push_back(src); keyp.push_back(it->second.key_dev); idxp.push_back(it->second.index_dev); sum.group.push_back(group[j]);
+        SFG_TRY(resolve_rotation(ctx, nrot_host, in_index, j, nin, r));
+        if (r.key) { jb.add(r.src, *r.key, nullptr, group[j]); continue; }
+        if (sum.plain[group[j]]) SFG_FAIL(ctx, "rotate: more than one unrotated member in a sum group");
+        sum.plain[group[j]] = in + (size_t)r.src * ctw;                                // not rotated: the sum's plain member
     }
-    return launch_keyswitch_jobs(ctx, in, nin, level, job_in, keyp, idxp, std::vector<u64 *>(), nullptr, nullptr, &sum);
+    return launch_keyswitch_jobs(ctx, bt, jb);
 }
 // The same batch written as the MAC's fp64 operand rows: job j lands at outf + j * 2 * rowf (row pair of polynomials 0, 1), rowf = nplanes * N doubles.
 // Jobs that do not rotate (nrot == 0) are converted from their input.
@@ -501,34 +489,23 @@ int launch_rotate_right_indexed_f64(sfg_ctx *ctx, const u64 *in, int nin, double
     F64Form ff; memset(&ff, 0, sizeof ff);
     ff.on = 1; ff.L = L; ff.centre = mac_dma_packed_mask(ctx, L) != 0; ff.rowf = (size_t)nplanes * N;
     for (int l = 0; l < L; l++) { ff.plane_of[l] = plane_of[l]; ff.big[l] = is_big[l]; }
-    std::vector<int> job_in; std::vector<const u64 *> keyp; std::vector<const uint16_t *> idxp; std::vector<u64 *> outp;
+    KswBatch bt{in, nin, level}; bt.ff = &ff; KswJobs jb; RotJob r;
     for (int j = 0; j < nct; j++) {
-        int nrot = nrot_host[j] % SFG_SLOTS; if (nrot < 0) nrot += SFG_SLOTS;
-        const int src = in_index ? in_index[j] : j;
-        if (src < 0 || src >= nin) SFG_FAIL(ctx, "rotate: input index out of range");
+        SFG_TRY(resolve_rotation(ctx, nrot_host, in_index, j, nin, r));
         double *dst = outf + (out_slot ? out_slot[j] : (size_t)j) * 2 * ff.rowf;
-        if (nrot == 0) {                                    // not rotated: converted from the input; runs of consecutive (source, slot) pairs in one launch
-            int run = 1;
-            while (!out_slot && j + run < nct && (nrot_host[j + run] % SFG_SLOTS) == 0 && (in_index ? in_index[j + run] : j + run) == src + run && src + run < nin) run++;
-            SFG_TRY(launch_rot_to_f64(ctx, in + (size_t)src * ctw, (size_t)2 * run, nl, L, dst));
-            j += run - 1;
-            continue;
-        }
-        u64 g = sfg_galois_for_rotation(ctx, SFG_SLOTS - nrot);
-        auto it = ctx->rotkeys().find(g);
-        if (it == ctx->rotkeys().end()) SFG_FAIL(ctx, "rotate: no rotation key loaded for right-rotation by %d (galois element %llu)", nrot, g);
-        job_in.push_back(src); keyp.push_back(it->second.key_dev); idxp.push_back(it->second.index_dev); outp.push_back(reinterpret_cast<u64 *>(dst));
+        if (r.key) { jb.add(r.src, *r.key, reinterpret_cast<u64 *>(dst)); continue; }
+        const int run = out_slot ? 1 : unrotated_run(nrot_host, in_index, j, nct, r.src, nin);      // not rotated: converted from the input
+        SFG_TRY(launch_rot_to_f64(ctx, in + (size_t)r.src * ctw, (size_t)2 * run, nl, L, dst));
+        j += run - 1;
     }
-    return launch_keyswitch_jobs(ctx, in, nin, level, job_in, keyp, idxp, outp, nullptr, &ff);
+    return launch_keyswitch_jobs(ctx, bt, jb);
 }
 // relinearisation: out[i] = (tmp[i].p0 + d0, mid[i] + d1) with (d0, d1) = key switch of tmp[i].p1 under the key stored at Galois element 1
 int launch_relinearize(sfg_ctx *ctx, const u64 *tmp, int nct, int level, const u64 *mid, u64 *out) {
     auto it = ctx->rotkeys().find(1);
     if (it == ctx->rotkeys().end()) SFG_FAIL(ctx, "relinearize: no relinearisation key loaded");
-    const size_t ctw = (size_t)2 * (level + 1) * SFG_N;
-    std::vector<int> job_in(nct); std::vector<const u64 *> keyp(nct, it->second.key_dev); std::vector<const uint16_t *> idxp(nct, it->second.index_dev); std::vector<u64 *> outp(nct);
-    for (int j = 0; j < nct; j++) { job_in[j] = j; outp[j] = out + (size_t)j * ctw; }
-    return launch_keyswitch_jobs(ctx, tmp, nct, level, job_in, keyp, idxp, outp, mid);
+    KswBatch bt{tmp, nct, level}; bt.add1 = mid;
+    return launch_keyswitch_jobs(ctx, bt, KswJobs(nct, it->second, out, (size_t)2 * (level + 1) * SFG_N));
 }
 int launch_rotate_right(sfg_ctx *ctx, const u64 *in, u64 *out, int nct, int level, const int *nrot_host) {
     return launch_rotate_right_indexed(ctx, in, nct, out, nct, level, nrot_host, nullptr);
@@ -551,11 +528,8 @@ extern "C" int sfg_ct_galois_dev(sfg_ctx *ctx, const uint64_t *in, uint64_t *out
     if (level < 0 || level >= ctx->nq) SFG_FAIL(ctx, "galois: level out of range");
     auto it = ctx->rotkeys().find(galois_el);
     if (it == ctx->rotkeys().end() || galois_el == 1) SFG_FAIL(ctx, "galois: no switching key loaded for galois element %llu", (unsigned long long)galois_el);
-    const size_t ctw = (size_t)2 * (level + 1) * SFG_N;
-    std::vector<int> job_in(nct); std::vector<const u64 *> keyp(nct, it->second.key_dev); std::vector<const uint16_t *> idxp(nct, it->second.index_dev); std::vector<u64 *> outp(nct);
-    for (int j = 0; j < nct; j++) { job_in[j] = j; outp[j] = (u64 *)out + (size_t)j * ctw; }
     PhaseTimer t(ctx, "rotate");
-    int rc = launch_keyswitch_jobs(ctx, (const u64 *)in, nct, level, job_in, keyp, idxp, outp, nullptr);
+    int rc = launch_keyswitch_jobs(ctx, KswBatch{(const u64 *)in, nct, level}, KswJobs(nct, it->second, (u64 *)out, (size_t)2 * (level + 1) * SFG_N));
     t.stop(1);
     return rc;
 }

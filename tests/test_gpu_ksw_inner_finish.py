@@ -1,9 +1,9 @@
 """GPU parity of the key switch whose Q-row inner product lives in the finish and whose key words are read once per tile of jobs (rotate.hip k_ksw_inner_p,
 k_ksw_finish, k_ksw_finish_sum; the tiles of sfgwas_amd/csrc/ksw_plan.hpp), every word with zero tolerance.
 
-A tile is up to T consecutive jobs under one key and one automorphism table - T = 5 in the plain finish and the special-prime inner product, T = 3 segments in the
-summed finish.  The job lists below hold runs of 1, 2, 3, 4, 5, 6, 7 and 11 jobs, i.e. 1, 2, T, T + 1 and 2 T + 1 for both values (and for any T in {1, 2, 3, 5}
-a later change may pick), two keys interleaved, and a rotation by 0 inside a run:
+A tile is up to T consecutive jobs under one key and one automorphism table - T = 3 (rotate.hip KSW_T) in the plain finish and the special-prime inner product;
+the summed finish takes no tiles.  The job lists below hold runs of 1, 2, 3, 4, 5, 6, 7 and 11 jobs, i.e. 1, 2, T, T + 1 and 2 T + 1 for T = 3 and for T = 5 (and
+for any T in {1, 2, 3, 5} a later change may pick), two keys interleaved, and a rotation by 0 inside a run:
 
   * the public rotation entry on PN14 at levels 5 and 4 and on the chains S1, S3, S4 of tests/ksw_ref.py, random and directed ciphertexts: every ciphertext
     against the oracle and against the same job issued alone in a call of its own;
@@ -12,9 +12,10 @@ a later change may pick), two keys interleaved, and a rotation by 0 inside a run
     the plain member, one and two block columns, both budgets, against rotate-and-sum with integers (tests/test_gpu_ksw_fused.py _rotate_and_sum);
   * the MAC-operand form through sfg_rotcache_build_rows_dev and sfg_rotcache_build_jobs_dev for s = 1, 2, 4, 6 inputs at input levels 5 (a dead row) and 4, baby
     steps {0, 1, 2, 45, 89, 90} against tests/rotcache_ref.py, both budgets (at the smallest, 91 jobs per input pass through chunks of four);
-  * relinearisation (add1) and the Galois entry (conjugation key) at level 5 on six ciphertexts (a tile of five and one of one) against the oracle.
+  * relinearisation (add1) and the Galois entry (conjugation key) at level 5 on six ciphertexts (two tiles of three) against the oracle.
 
-The split inverse transform of the same issue was not built: k_ntt_inv is what it was, nothing here concerns it."""
+The split inverse transform of the same issue was built (ntt.hip k_ntt_inv_split, launch_ntt_inv_split): both inverse transforms of the key switch run through it,
+their last stage and 1/N done by the extension kernels, so every list here passes through it; tests/test_ksw_plan.py holds that last stage against integers."""
 import numpy as np
 import pytest
 

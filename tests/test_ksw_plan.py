@@ -1,5 +1,6 @@
-"""The key switch's job planning (sfgwas_amd/csrc/ksw_plan.hpp: tiles of jobs under one key and one automorphism table, and the segments of a summed finish)
-on the CPU, no GPU and nothing of the library linked.
+"""The key switch's job planning (sfgwas_amd/csrc/ksw_plan.hpp: how many inputs a group and how many jobs a chunk holds under a scratch budget, where the
+regions of the workspace lie, which jobs fall into which input group, chunk and tile, tiles of jobs under one key and one automorphism table, and the segments of a
+summed finish) on the CPU, no GPU and nothing of the library linked.
 
 tests/host/host_ksw_plan_test.cpp includes the header - the functions rotate.hip calls - compiled for the host with AddressSanitizer + UBSan as a plain
 executable; it checks the covering invariants itself on every call, and every line it prints is compared here with a literal restatement in Python.
@@ -174,6 +175,157 @@ def test_random_sums(exe, tmp_path):
             groups = [int(rnd.integers(0, nout)) for _ in range(nb)]
             lines.append(fmt_c(groups)); want.append(want_c(groups, nout, seen))
         lines.append(fmt_c([])); want.append(want_c([], nout, seen))
+    assert run(exe, lines, tmp_path) == want
+
+
+# ---------------------------------------------------------------------------------------------------- sizes and the workspace layout
+N14 = 16384
+MIB, GIB = 1 << 20, 1 << 30
+LEVEL5, LEVEL4 = (6, 2, 8, 3), (5, 2, 7, 3)                  # nl, np, nt, beta on PN14
+
+
+def sizes(shape, nin, nr, nout, budget, N=N14):
+    """in_grp, chunk, the row counts, the six row regions in words, the seven tables in bytes, the total"""
+    nl, np_, nt, beta = shape
+    in_grp = min(max(budget // ((nl + beta * nt) * N * 8), 1), nin)
+    chunk = min(max(budget // ((2 * nt + 2 * nl) * N * 8), 1), nr)      # cut as when a job's accumulator held all 2 nt rows
+    ext_rows, ext2_rows, acc_rows = in_grp * beta * nt, chunk * 2 * nl, chunk * 2 * np_
+    words, at = [], 0
+    for rows in [in_grp * nl, ext_rows, acc_rows, ext2_rows, ext_rows, ext2_rows]:          # c2 ext acc ext2 extT ext2T
+        words.append(at)
+        at += rows * N
+    tables, at = [], at * 8
+    for size in [nr * 8, nr * 8, nr * 8, nout * 32, nr * 4, nr * 4, nr * 8]:                # keys idx out segs inidx segjobs tiles
+        tables.append(at)
+        at += size
+    return (in_grp, chunk, ext_rows, ext2_rows, acc_rows), words, tables, at + 256
+
+
+def closed_form(shape, in_grp, chunk, nr, nout, N=N14):
+    """the bytes the launcher reserved before it had a plan"""
+    nl, np_, nt, beta = shape
+    in_rows, ext_rows, ext2_rows, acc_rows = nl + beta * nt, in_grp * beta * nt, chunk * 2 * nl, chunk * 2 * np_
+    return (in_rows * in_grp + acc_rows + 2 * ext2_rows + ext_rows) * N * 8 + nr * (3 * 8 + 2 * 4 + 8) + nout * 32 + 256
+
+
+def fmt_s(shape, nin, nr, nout, budget, N=N14):
+    return f"S {shape[0]} {shape[1]} {shape[2]} {shape[3]} {nin} {nr} {nout} {budget} {N}"
+
+
+def want_s(shape, nin, nr, nout, budget, N=N14):
+    head, words, tables, total = sizes(shape, nin, nr, nout, budget, N)
+    return " | ".join([" ".join(map(str, ("S",) + head)), " ".join(map(str, words)), " ".join(map(str, tables)), str(total)])
+
+
+# (shape, budget, nin, nr, nout) -> (in_grp, chunk)
+SIZE_CASES = [((LEVEL5, 16 * MIB, 1000, 1000, 0), (4, 4)),                # 128 rows over 30 and 28
+              ((LEVEL4, 16 * MIB, 1000, 1000, 0), (4, 5)),                # 128 rows over 26 and 24
+              ((LEVEL5, 4 * GIB, 6, 546, 0), (6, 546)),                   # clamped by the counts
+              ((LEVEL5, 4 * GIB, 2000, 2000, 15), (1092, 1170)),          # clamped by the budget
+              ((LEVEL5, 30 * N14 * 8 - 1, 7, 9, 0), (1, 1)),              # less than one input's rows
+              ((LEVEL4, 0, 1, 1, 3), (1, 1)),
+              ((LEVEL5, 4 * GIB, 3, 0, 2), (3, 0)),                       # a sum with outputs and no job
+              ((LEVEL4, 16 * MIB, 3, 0, 2), (3, 0)),
+              ((LEVEL5, 4 * GIB, 0, 0, 0), (0, 0)),
+              ((LEVEL4, 16 * MIB, 0, 0, 1), (0, 0))]
+
+
+def test_sizes_and_layout_at_the_named_budgets(exe, tmp_path):
+    rows = run(exe, [fmt_s(sh, nin, nr, nout, budget) for (sh, budget, nin, nr, nout), _ in SIZE_CASES], tmp_path)
+    for row, ((sh, budget, nin, nr, nout), (in_grp, chunk)) in zip(rows, SIZE_CASES):
+        assert row == want_s(sh, nin, nr, nout, budget)
+        assert row.split()[1:3] == [str(in_grp), str(chunk)], row
+        assert int(row.split()[-1]) == closed_form(sh, in_grp, chunk, nr, nout)
+
+
+def test_random_sizes_and_layouts(exe, tmp_path):
+    """any shape the key switch accepts (np <= 4 primes per digit, beta <= 8 digits), any row length, budgets around the sizes of one input and one job"""
+    rnd = np.random.default_rng(7)
+    cases = []
+    for _ in range(300):
+        np_ = int(rnd.integers(1, 5)); nl = int(rnd.integers(1, 8 * np_ + 1)); shape = (nl, np_, nl + np_, -(-nl // np_))
+        N = 1 << int(rnd.integers(4, 17))
+        nin, nr, nout = int(rnd.integers(0, 40)), int(rnd.integers(0, 200)), int(rnd.integers(0, 16))
+        budget = int(rnd.integers(0, 50)) * (nl + shape[3] * shape[2]) * N * 8 // int(rnd.integers(1, 5)) + int(rnd.integers(0, 3))
+        cases.append((shape, nin, nr, nout, budget, N))
+    rows = run(exe, [fmt_s(*c) for c in cases], tmp_path)
+    for row, c in zip(rows, cases):
+        assert row == want_s(*c)
+        assert int(row.split()[-1]) == closed_form(c[0], int(row.split()[1]), int(row.split()[2]), c[2], c[3], c[5])
+
+
+# ---------------------------------------------------------------------------------------------------- jobs -> input groups, chunks, tiles
+def groups_of(jobs, nin, in_grp, chunk, T):
+    """jobs: [(input, key, table)].  Per run of in_grp inputs with a job: its jobs in list order, cut into chunks, each chunk into tiles of its own numbering"""
+    out = []
+    for i0 in range(0, nin, in_grp) if in_grp > 0 and chunk > 0 else []:
+        ni = min(in_grp, nin - i0)
+        mine = [k for k, (i, _, _) in enumerate(jobs) if i0 <= i < i0 + ni]
+        if mine:
+            out.append((i0, ni, mine, [(c0, len(mine[c0:c0 + chunk]), job_tiles([jobs[k][1:] for k in mine[c0:c0 + chunk]], T)) for c0 in range(0, len(mine), chunk)]))
+    return out
+
+
+def fmt_g(jobs, nin, in_grp, chunk, T):
+    return f"G {T} {in_grp} {chunk} {nin} {len(jobs)}" + "".join(f" {i} {k} {t}" for i, k, t in jobs)
+
+
+def want_g(jobs, nin, in_grp, chunk, T):
+    gs = groups_of(jobs, nin, in_grp, chunk, T)
+    out = f"G {len(gs)}"
+    for i0, ni, mine, chunks in gs:
+        out += f" | {i0} {ni} {len(mine)}" + "".join(f" {k}" for k in mine) + f" ; {len(chunks)}"
+        for c0, nb, tl in chunks:
+            out += f" , {c0} {nb} {len(tl)}" + "".join(f" {a} {c}" for a, c in tl)
+    return out
+
+
+def runs_39():
+    """the 39-job list of tests/test_gpu_ksw_inner_finish.py: key a x 1, b x 2, a x 3, b x 4, a x 5, b x 6, a x 7, b x 11"""
+    a, b = (10, 100), (20, 200)
+    return [(b if k & 1 else a) for k, n in enumerate([1, 2, 3, 4, 5, 6, 7, 11]) for _ in range(n)]
+
+
+@pytest.mark.parametrize("T", TS)
+@pytest.mark.parametrize("in_grp,chunk", [(4, 4), (4, 5), (39, 39), (1, 1)])
+def test_the_runs_list_in_groups_and_chunks(exe, tmp_path, T, in_grp, chunk):
+    """job j over 4 and 5 inputs (j mod nin: every group's list is a sieve of the runs) and over 39 (its own input: list order is input order)"""
+    keys = runs_39()
+    lines, want = [], []
+    for nin in (4, 5, 39):
+        g = min(in_grp, nin)                                            # as the sizes clamp it
+        jobs = [(j % nin,) + keys[j] for j in range(39)]
+        lines.append(fmt_g(jobs, nin, g, chunk, T)); want.append(want_g(jobs, nin, g, chunk, T))
+    assert run(exe, lines, tmp_path) == want
+    # spelled out once: 39 inputs in groups of 4 at chunks of 4 - ten groups, the last of 3; group 0 holds jobs 0 .. 3 = a, b, b, a
+    if (in_grp, chunk, T) == (4, 4, 3):
+        assert want[2].startswith("G 10 | 0 4 4 0 1 2 3 ; 1 , 0 4 3 0 1 1 2 3 1 | 4 4 4 4 5 6 7 ; 1 , 0 4 2 0 2 2 2 |")
+        assert want[2].endswith("| 36 3 3 36 37 38 ; 1 , 0 3 1 0 3")
+    if (in_grp, chunk, T) == (1, 1, 3):
+        assert want[0].count("|") == 4 and all(f" , {c} 1 1 0 1" in want[0] for c in range(9))
+
+
+def test_descending_inputs_and_inputs_without_a_job(exe, tmp_path):
+    a, b = (10, 100), (20, 200)
+    desc = [(i,) + (a if i & 2 else b) for i in range(11, -1, -1)]      # inputs 11 .. 0: the groups come in input order, each with its jobs in list order
+    gaps = [(i,) + a for i in (9, 9, 0, 9, 1, 0)]                       # inputs 2 .. 8 and 10, 11 have no job: at groups of 2, only groups 0 and 8 exist
+    lines = [fmt_g(desc, 12, 5, 3, 3), fmt_g(gaps, 12, 2, 2, 3), fmt_g(gaps, 12, 12, 6, 2), fmt_g([], 3, 3, 0, 3), fmt_g([], 0, 0, 0, 3)]
+    want = [want_g(desc, 12, 5, 3, 3), want_g(gaps, 12, 2, 2, 3), want_g(gaps, 12, 12, 6, 2), "G 0", "G 0"]
+    assert run(exe, lines, tmp_path) == want
+    assert want[0] == "G 3 | 0 5 5 7 8 9 10 11 ; 2 , 0 3 2 0 1 1 2 , 3 2 1 0 2 | 5 5 5 2 3 4 5 6 ; 2 , 0 3 2 0 2 2 1 , 3 2 2 0 1 1 1 | 10 2 2 0 1 ; 1 , 0 2 1 0 2"
+    assert want[1] == "G 2 | 0 2 3 2 4 5 ; 2 , 0 2 1 0 2 , 2 1 1 0 1 | 8 2 3 0 1 3 ; 2 , 0 2 1 0 2 , 2 1 1 0 1"
+
+
+def test_random_groupings(exe, tmp_path):
+    rnd = np.random.default_rng(8)
+    lines, want = [], []
+    for _ in range(300):
+        nin, nr, T = int(rnd.integers(1, 13)), int(rnd.integers(0, 61)), int(rnd.choice(TS))
+        nk = int(rnd.integers(1, 4))
+        jobs = sorted([(int(rnd.integers(0, nin)), int(rnd.integers(0, nk)), int(rnd.integers(0, 2))) for _ in range(nr)], key=lambda j: j[1]) if rnd.integers(0, 2) else \
+            [(int(rnd.integers(0, nin)), int(rnd.integers(0, nk)), int(rnd.integers(0, 2))) for _ in range(nr)]
+        in_grp, chunk = int(rnd.integers(1, nin + 1)), (int(rnd.integers(1, nr + 1)) if nr else 0)
+        lines.append(fmt_g(jobs, nin, in_grp, chunk, T)); want.append(want_g(jobs, nin, in_grp, chunk, T))
     assert run(exe, lines, tmp_path) == want
 
 
