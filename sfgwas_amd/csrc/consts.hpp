@@ -9,6 +9,8 @@ constexpr int SFG_D = 91;                 // ceil(sqrt(8192)), matmult.go:1047
 constexpr int SFG_MAXMOD = 16;
 // HBM that must stay free beside the transposed copies of ALL groups of a caller's rotation cache (association scan) for the int8 MAC to take that call
 constexpr size_t SFG_I8_KEEP_RESERVE = 80ULL << 30;
+// the largest fp64 rotation cache a product of several accumulator passes builds for itself (mm_range_plan)
+constexpr size_t SFG_MM_WHOLE_CACHE_CAP = 48ULL << 30;
 
 // The flag word of a plaintext panel (PanelMap::packed_mask, the last argument of launch_encode_rows).  Bit l < 16: the rows of modulus l are written as
 // packed-limb words (mac_dma.hip).  The named bits:

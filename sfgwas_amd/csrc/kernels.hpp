@@ -78,15 +78,12 @@ int launch_ct_add(sfg_ctx *ctx, const u64 *a, const u64 *b, u64 *out, size_t nct
 int mac_dma_planes(sfg_ctx *ctx, int L, std::vector<int> &plane_of, std::vector<int> &is_big);
 double mac_big_maxterm(u64 q);
 int launch_rot_to_f64(sfg_ctx *ctx, const u64 *rot, size_t nrows, int nl_rot, int L, double *rotf);
-int launch_mac_dma(sfg_ctx *ctx, const double *rotf, size_t rows_per_k, const u64 *pt, u64 *out, int K, int R, int Ncols, int L, int accumulate, const MacStrides &st,
-                   const double *rotsum = nullptr);
-int launch_rot_sum(sfg_ctx *ctx, const double *rotf, size_t rows_per_k, int K, int L, double *rotsum);
+int launch_mac_dma(sfg_ctx *ctx, const double *rotf, size_t rows_per_k, const u64 *pt, u64 *out, int K, int R, int Ncols, int L, int accumulate, const MacStrides &st);
 int launch_pack_pt(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, size_t words_per_row, int L, unsigned packed_mask);
 unsigned mac_dma_packed_mask(sfg_ctx *ctx, int L);
 bool mac_use_dma(const sfg_ctx *ctx);
 // mac_bc.hip (same contract as launch_mac_dma; small-modulus plaintext rows packed)
-int launch_mac_bc(sfg_ctx *ctx, const double *rotf, size_t rows_per_k, const u64 *pt, u64 *out, int K, int R, int Ncols, int L, int accumulate, const MacStrides &st,
-                  const double *rotsum);
+int launch_mac_bc(sfg_ctx *ctx, const double *rotf, size_t rows_per_k, const u64 *pt, u64 *out, int K, int R, int Ncols, int L, int accumulate, const MacStrides &st);
 // matmul.hip: the baby-step rotation cache of block rows [b0, b1) in the MAC layout; tabs = per-row active-baby flags (null: all 91)
 int rotcache_build_rows_tab(sfg_ctx *ctx, const u64 *A, int s, int in_level, int max_level, int nbr, int b0, int b1, const std::vector<std::vector<uint8_t>> *tabs, double *cache);
 // stream.hip: the call-wide rotation cache of an association scan (nullptr in *out = not applicable; caller hipFree()s)
@@ -98,16 +95,35 @@ struct I8RotPre { int G = 0, nbr = 0, s = 0, L = 0; std::vector<int8_t *> As, Ab
 int i8_rotpre_build(sfg_ctx *ctx, const u64 *A_dev, int s, int in_level, int max_level, int nbr, const std::vector<std::vector<uint8_t>> *tabs, size_t budget_bytes, const char *prefix, I8RotPre &pre);   // pre.G == 0 afterwards: not taken (fp64 path)
 void i8_rotpre_free(I8RotPre &pre);
 struct I8RotPreScope { I8RotPre pre; ~I8RotPreScope() { i8_rotpre_free(pre); } };
-int matmul_resident_range_i8pre(sfg_ctx *ctx, const I8RotPre &pre, int s, int max_level, const sfg_geno *g, unsigned flags, int blk0, int blk1, uint64_t *out);
-int matmul_accumulate_i8pre(sfg_ctx *ctx, const I8RotPre &pre, int s, int max_level, const sfg_geno *g, unsigned flags, int j0, int j1, int accumulate, uint64_t *acc,
-                            size_t acc_col_words = 0);        // acc_col_words: words between consecutive block columns' accumulators (0: dense [column][91 giants]...)
+// The rotation operand of a product: where the baby-step rotations of the operand's block rows come from (mm_plan.hpp RotSrc).  A view: the holder keeps the
+// ciphertexts, the cache rows or the tiles alive.
+struct RotOperand {
+    RotSrc src = RotSrc::own;
+    const u64 *A = nullptr;               // own: the ciphertexts [s][nbr][2][in_level + 1][N], key-switched by the call group by group
+    int in_level = -1;                    // own: their level.  A cache: the level its source ciphertexts had (sizes the call's operand scratch), -1: the product's max_level
+    const double *rows = nullptr;         // f64_cache: cache[block row - b0][baby < 91][i < s][poly < 2][rowf] (+ 3 zero k-slices) of exactly the block rows the call contracts over
+    const I8RotPre *tiles = nullptr;      // i8_tiles: of ALL operand block rows of the (possibly transposed) matrix
+    static RotOperand own(const u64 *A, int in_level) { RotOperand r; r.A = A; r.in_level = in_level; return r; }
+    static RotOperand f64_cache(const double *rows, int in_level = -1) { RotOperand r; r.src = RotSrc::f64_cache; r.rows = rows; r.in_level = in_level; return r; }
+    static RotOperand i8_tiles(const I8RotPre *pre) { RotOperand r; r.src = RotSrc::i8_tiles; r.tiles = pre; return r; }
+    int level_in(int max_level) const { return in_level < 0 ? max_level : in_level; }
+    int validate(sfg_ctx *ctx, int s, int L, int nbr, int b0, int b1) const;    // matmul.hip: can it multiply block rows [b0, b1) of nbr at s rows and L moduli on this context?
+};
+// matmul.hip: a product call but for its rotation operand.  Accumulate phase: operand block rows [b0, b1) x block columns [j0, j1) into
+// acc [(j - j0)][giant < 91][i < s][2][L][N] (zero-initialised unless accumulate != 0); acc_col_words: words between consecutive block columns' accumulators
+// (0: dense, 91 giants).  Whole product: SNP blocks [blk0, blk1) of the STORED matrix - output columns for X, contraction rows for X^T - into out
+struct MmArgs { const sfg_geno *g; unsigned flags; int s, max_level, b0, b1, j0, j1, accumulate; uint64_t *acc; size_t acc_col_words; };
+struct MmRangeArgs { const sfg_geno *g; unsigned flags; int s, max_level, blk0, blk1; uint64_t *out; };
+int matmul_accumulate(sfg_ctx *ctx, const RotOperand &rot, const MmArgs &a);
+int matmul_resident_range(sfg_ctx *ctx, const RotOperand &rot, const MmRangeArgs &a);
 int launch_i8_pack_rot_to(sfg_ctx *ctx, const double *rotf, size_t rotf_k_stride, size_t rotf_r_stride, int plane0, int K, int R, int l0, int nl, bool big, int8_t *A_out);      // mac_i8.hip
-// the rotation cache of an association scan in whichever form the context multiplies with
-struct AssocRot { double *f64 = nullptr; I8RotPre pre; };
+// the rotation cache of an association scan in whichever form the context multiplies with: the operand every batch multiplies and, where that is int8 tiles, their
+// storage (op then points at pre: not to be copied once built; fp64 rows are the context's scratch entry "assoc.rotf")
+struct AssocRot { RotOperand op; I8RotPre pre; };
 int assoc_build_rot(sfg_ctx *ctx, const u64 *A_dev, int s, int in_level, int max_level, size_t nr, const std::vector<size_t> &widths, AssocRot &out);
 void assoc_free_rot(AssocRot &r);
 struct AssocRotScope { AssocRot r; ~AssocRotScope() { assoc_free_rot(r); } };
-int assoc_product(sfg_ctx *ctx, const AssocRot &r, const uint64_t *A_dev, int s, int in_level, int max_level, const sfg_geno *g, unsigned flags, int nct, uint64_t *out);
+int assoc_product(sfg_ctx *ctx, const AssocRot &r, int s, int max_level, const sfg_geno *g, unsigned flags, int nct, uint64_t *out);
 int assoc_batch_tail(sfg_ctx *ctx, const u64 *tmp, const sfg_geno *g, int s, size_t nct, size_t ctw, uint64_t *out_dev, size_t out_ct_capacity, size_t out_shift,
                      double *sum_host, double *sqsum_host);      // stream.hip: rows of tmp copied into place, padded sums zeroed, column sums
 

@@ -316,7 +316,7 @@ template <bool BIG, int ROWS> static void bc_launch(sfg_ctx *ctx, dim3 grid, con
 
 // Same contract as launch_mac_dma (mac_dma.hip).  The small-modulus plaintext rows must be in the packed-limb format.
 int launch_mac_bc(sfg_ctx *ctx, const double *rotf, size_t rows_per_k, const u64 *pt, u64 *out, int K, int R, int Ncols, int L, int accumulate,
-                  const MacStrides &st, const double *rotsum) {
+                  const MacStrides &st) {
     const int N = SFG_N;
     if (K <= 0 || R <= 0 || Ncols <= 0) return 0;
     std::vector<int> plane_of, is_big; const int nplanes = mac_dma_planes(ctx, L, plane_of, is_big);

@@ -70,8 +70,6 @@ int launch_rot_to_f64(sfg_ctx *ctx, const u64 *rot, size_t nrows, int nl_rot, in
     return 0;
 }
 
-// (kept for the call sites: the bias-free packed limbs of round 2 need no rot sums any more)
-int launch_rot_sum(sfg_ctx *, const double *, size_t, int, int, double *) { return 0; }
 int launch_pack_pt(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, size_t words_per_row, int L, unsigned packed_mask) {
     if (!nrows) return 0;
     if (nrows > 65535u * 1024u) SFG_FAIL(ctx, "pack_pt: too many rows");
@@ -89,9 +87,9 @@ int launch_pack_pt(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, size_t w
 // Contract: when K % 4 != 0 the buffer must extend over the k-slices K .. 4*ceil(K/4)-1 and hold finite doubles there
 // (they are multiplied by zero plaintexts).
 int launch_mac_dma(sfg_ctx *ctx, const double *rotf, size_t rows_per_k, const u64 *pt, u64 *out, int K, int R, int Ncols, int L, int accumulate,
-                   const MacStrides &st, const double *rotsum) {
+                   const MacStrides &st) {
     if (ctx->cfg.mac_bc && (st.pt_packed || mac_dma_packed_mask(ctx, L) == 0) && !ctx->cfg.mac_plain_pt)      // default: the DPP-broadcast kernel (mac_bc.hip)
-        return launch_mac_bc(ctx, rotf, rows_per_k, pt, out, K, R, Ncols, L, accumulate, st, rotsum);
+        return launch_mac_bc(ctx, rotf, rows_per_k, pt, out, K, R, Ncols, L, accumulate, st);
 #ifdef SFG_AB
     return ab_launch_mac_dma_tiles(ctx, rotf, rows_per_k, pt, out, K, R, Ncols, L, accumulate, st);
 #endif
@@ -125,16 +123,15 @@ extern "C" int sfg_mac_dev(sfg_ctx *ctx, const uint64_t *rot, const uint64_t *pt
         st.out_n = (size_t)R * L * SFG_N; st.out_r = (size_t)L * SFG_N;
         // default build: the small-modulus plaintext rows go through the packed-limb format the product path uses (A/B build, plain panel: as given)
         const unsigned pmask = mac_dma_packed_mask(ctx, L);
-        u64 *ptp = nullptr; double *rsum = nullptr;
+        u64 *ptp = nullptr;
         if (!rc && pmask) {
             const size_t prows = (size_t)K * Ncols * L;
-            if (hipMalloc(&ptp, prows * SFG_N * 8) != hipSuccess || hipMalloc(&rsum, (size_t)R * nplanes * SFG_N * 8) != hipSuccess) { rc = 1; ctx->err = "sfg_mac: out of device memory"; }
+            if (hipMalloc(&ptp, prows * SFG_N * 8) != hipSuccess) { rc = 1; ctx->err = "sfg_mac: out of device memory"; }
             if (!rc) rc = launch_pack_pt(ctx, (const u64 *)pt, ptp, prows, SFG_N, L, pmask);
-            if (!rc) rc = launch_rot_sum(ctx, rotf, (size_t)R, K, L, rsum);
             st.pt_packed = true;
         }
-        if (!rc) rc = launch_mac_dma(ctx, rotf, (size_t)R, pmask ? ptp : (const u64 *)pt, (u64 *)out, K, R, Ncols, L, accumulate, st, rsum);
-        (void)hipStreamSynchronize(ctx->stream); (void)hipFree(rotf); (void)hipFree(ptp); (void)hipFree(rsum);
+        if (!rc) rc = launch_mac_dma(ctx, rotf, (size_t)R, pmask ? ptp : (const u64 *)pt, (u64 *)out, K, R, Ncols, L, accumulate, st);
+        (void)hipStreamSynchronize(ctx->stream); (void)hipFree(rotf); (void)hipFree(ptp);
     }
     t.stop(1);
     return rc;

@@ -607,7 +607,7 @@ extern "C" int sfg_mac_i8_dev(sfg_ctx *ctx, const uint64_t *rot, const uint64_t 
         st.out_n = (size_t)R * L * N; st.out_r = (size_t)L * N;
         st.pt_half = true; st.pt_packed = true; st.i8 = st.i8_big = true; st.pt_digits = st.pt_digits_big = pt_form == 0;
         PhaseTimer t(ctx, "mac");
-        rc = launch_mac_bc(ctx, rotf, (size_t)R, ptp, (u64 *)out, K, R, Ncols, L, accumulate, st, nullptr);
+        rc = launch_mac_bc(ctx, rotf, (size_t)R, ptp, (u64 *)out, K, R, Ncols, L, accumulate, st);
         t.stop(1);
     }
     (void)hipStreamSynchronize(ctx->stream); (void)hipFree(rotf); (void)hipFree(ptp);

@@ -356,13 +356,9 @@ extern "C" int sfg_reduce_rows_dev(sfg_ctx *ctx, uint64_t *rows, size_t nrows_of
 // ---------------------------------------------------------------- rotation cache of one operand block row
 // rotc[baby][i] = RotateRight(A[i][bi], -baby) (matmult.go:1373-1377) for the active baby steps, then (LDS-DMA MAC) the fp64
 // operand form into rotf_dst.  a_row / rotc are scratch of s resp. d*s ciphertexts.
-static int build_rot_row_tab(sfg_ctx *ctx, const u64 *A, int s, int nl_in, int nl, int lev, int L, int nbr, int bi, const std::vector<uint8_t> &baby_t,
-                             u64 *a_row, u64 *rotc, bool dma, double *rotf_dst);
-static int build_rot_row(sfg_ctx *ctx, const u64 *A, int s, int nl_in, int nl, int lev, int L, const Shape &sh, int bi, u64 *a_row, u64 *rotc,
-                         bool dma, double *rotf_dst) {
-    const int d = SFG_D;
-    const int nr = sh.rows_of(bi);
-    // active baby steps (matmult.go:1326-1336), union over ALL block columns of the operand as in the reference
+// active baby steps of block row bi (matmult.go:1326-1336), union over ALL block columns of the operand as in the reference
+static std::vector<uint8_t> baby_table(const Shape &sh, int bi) {
+    const int d = SFG_D, nr = sh.rows_of(bi);
     std::vector<uint8_t> baby_t(d, 0);
     for (int shift = 0; shift < SFG_SLOTS; shift++) {
         if (baby_t[shift % d]) continue;
@@ -370,7 +366,7 @@ static int build_rot_row(sfg_ctx *ctx, const u64 *A, int s, int nl_in, int nl, i
         for (int bj = 0; bj < sh.m_ct && !any; bj++) any = diag_bool(nr, sh.cols_of(bj), SFG_SLOTS, -shift);
         if (any) baby_t[shift % d] = 1;
     }
-    return build_rot_row_tab(ctx, A, s, nl_in, nl, lev, L, sh.nbr, bi, baby_t, a_row, rotc, dma, rotf_dst);
+    return baby_t;
 }
 static int build_rot_row_tab(sfg_ctx *ctx, const u64 *A, int s, int nl_in, int nl, int lev, int L, int nbr, int bi, const std::vector<uint8_t> &baby_t,
                              u64 *a_row, u64 *rotc, bool dma, double *rotf_dst) {
@@ -390,44 +386,49 @@ static int build_rot_row_tab(sfg_ctx *ctx, const u64 *A, int s, int nl_in, int n
 
 // ---------------------------------------------------------------- phase 1: accumulate
 // The decisions of a call are mm_plan's (mm_plan.hpp); here are its impure inputs, its buffers and its launches.
-static MmPlanIn plan_input(sfg_ctx *ctx, int s, int L, int nblockrows, int ncolb, RotSrc rot, int pre_G) {
+
+// What the group searches may spend: free HBM plus the bytes of the pool entries the product regrows in place (mm.pt, mm.rotf, mi8.*, and a caller's tile
+// buffers under extra_prefix); what the transposed copies of all groups may spend: free HBM plus the held mi8.A* bytes
+struct PoolMemory { size_t search = 0, keep = 0; bool failed = false; };
+static PoolMemory pool_memory(sfg_ctx *ctx, const char *extra_prefix) {
+    PoolMemory m; size_t fr = 0, tot = 0;
+    m.failed = hipMemGetInfo(&fr, &tot) != hipSuccess;
+    m.search = m.keep = fr;
+    for (const auto &kv : ctx->pool) {
+        if ((extra_prefix && kv.first.rfind(extra_prefix, 0) == 0) || kv.first == "mm.pt" || kv.first == "mm.rotf" || kv.first.rfind("mi8.", 0) == 0) m.search += kv.second.second;
+        if (kv.first.rfind("mi8.A", 0) == 0) m.keep += kv.second.second;
+    }
+    return m;
+}
+static MmPlanIn plan_input(sfg_ctx *ctx, int s, int L, int nblockrows, int ncolb, const RotOperand &rot) {
     const SfgConfig &c = ctx->cfg;
     MmPlanIn in;
     in.mm_group = c.mm_group; in.mm_group_auto = c.mm_group_auto; in.mac_i8 = c.mac_i8; in.mac_i8_big = c.mac_i8_big;
     in.pt_compact = c.pt_compact; in.pt_kmajor = c.pt_kmajor; in.pt_ride = c.pt_ride; in.no_overlap = c.no_overlap;
     in.dma = mac_use_dma(ctx); in.packed_mask = in.dma ? mac_dma_packed_mask(ctx, L) : 0u; in.mods = ModSplit(ctx->q, L);
-    in.s = s; in.L = L; in.nblockrows = nblockrows; in.ncolb = ncolb; in.rot = rot; in.pre_G = pre_G;
-    if (mm_plan_reads_memory(in)) {
-        size_t fr = 0, tot = 0;
-        in.mem_failed = hipMemGetInfo(&fr, &tot) != hipSuccess;
-        in.mem_search = in.mem_keep = fr;
-        for (const auto &kv : ctx->pool) {
-            if (kv.first == "mm.pt" || kv.first == "mm.rotf" || kv.first.rfind("mi8.", 0) == 0) in.mem_search += kv.second.second;   // regrown in place
-            if (kv.first.rfind("mi8.A", 0) == 0) in.mem_keep += kv.second.second;
-        }
-    }
+    in.s = s; in.L = L; in.nblockrows = nblockrows; in.ncolb = ncolb; in.rot = rot.src; in.pre_G = rot.tiles ? rot.tiles->G : 0;
+    if (mm_plan_reads_memory(in)) { const PoolMemory m = pool_memory(ctx, nullptr); in.mem_failed = m.failed; in.mem_search = m.search; in.mem_keep = m.keep; }
     return in;
 }
 // what the launches of one call share
 struct MmCall {
-    sfg_ctx *ctx; const Shape &sh; unsigned flags; const u64 *A; const I8RotPre *pre8;
+    sfg_ctx *ctx; const Shape &sh; unsigned flags; const RotOperand &rot;
     int s, L, lev, nl, nl_in; bool dma; unsigned packed_mask; size_t ctw, accw, rowf = 0;
     MmPlan plan;
-    u64 *a_row = nullptr, *rotc = nullptr; int8_t *skew = nullptr, *unpacked = nullptr; double *rotf = nullptr, *rotsum = nullptr;
+    u64 *a_row = nullptr, *rotc = nullptr; int8_t *skew = nullptr, *unpacked = nullptr; double *rotf = nullptr;
     int8_t *rideBs = nullptr, *rideBb = nullptr;               // the riding launches' tile buffers (a launch of the same call that transposes by the pass uses them too)
 };
 // a MAC launch: the plaintext panel `ptp` of `gsn` block rows against the group's rot operand, into block column accumulator `accj`
-struct MacJob { bool on = false; u64 *ptp = nullptr; int gsn = 0, gi = 0, acc_flag = 0; u64 *accj = nullptr; const double *rotf_grp = nullptr, *rotsum_grp = nullptr; };
+struct MacJob { bool on = false; u64 *ptp = nullptr; int gsn = 0, gi = 0, acc_flag = 0; u64 *accj = nullptr; const double *rotf_grp = nullptr; };
 
 // rotation cache of the group that starts at block row bg into half `buf` of mm.rotf (on whatever stream is current)
 static int build_group(const MmCall &c, int bg, int b1, int buf) {
     sfg_ctx *ctx = c.ctx; const int d = SFG_D, s = c.s, ng = std::min(c.plan.G, b1 - bg);
     ctx->i8_gen++;                                          // (the int8 MAC keeps a transposed copy per rot operand: this one changes now)
     double *dst = c.rotf + (size_t)buf * c.plan.grp_slices * s * 2 * c.rowf;
-    for (int g = 0; g < ng; g++) SFG_TRY(build_rot_row(ctx, c.A, s, c.nl_in, c.nl, c.lev, c.L, c.sh, bg + g, c.a_row, c.rotc, c.dma, c.dma ? dst + (size_t)g * d * s * 2 * c.rowf : nullptr));
+    for (int g = 0; g < ng; g++) SFG_TRY(build_rot_row_tab(ctx, c.rot.A, s, c.nl_in, c.nl, c.lev, c.L, c.sh.nbr, bg + g, baby_table(c.sh, bg + g), c.a_row, c.rotc, c.dma, c.dma ? dst + (size_t)g * d * s * 2 * c.rowf : nullptr));
     if (c.dma && (ng * d) % 4)            // the ragged last MAC chunk reads up to 3 k-slices past the group against zero plaintexts: keep them finite
         SFG_HIP(ctx, hipMemsetAsync(dst + (size_t)ng * d * s * 2 * c.rowf, 0, (size_t)3 * s * 2 * c.rowf * 8, ctx->stream));
-    if (c.packed_mask) SFG_TRY(launch_rot_sum(ctx, dst, (size_t)s * 2, ng * d, c.L, c.rotsum + (size_t)buf * s * 2 * c.rowf));
     return 0;
 }
 // B_mode (MacStrides): 0: the launch transposes its panel by the pass into the MAC's own buffers; 1: the riding movers have transposed it into the ride's tile
@@ -437,13 +438,13 @@ static int run_mac(const MmCall &c, const MacJob &m, int B_mode) {
     PhaseTimer t(ctx, "mac");
     MacStrides st;
     if (c.rideBs) { st.B_small = c.rideBs; st.B_big = c.rideBb; st.B_mode = B_mode; }
-    if (c.pre8) { st.A_small = c.pre8->As[m.gi]; st.A_big = c.pre8->Ab[m.gi]; }
+    if (c.rot.tiles) { st.A_small = c.rot.tiles->As[m.gi]; st.A_big = c.rot.tiles->Ab[m.gi]; }       // (then m.rotf_grp is null)
     st.rot_k = (size_t)c.s * c.ctw; st.rot_r = (size_t)c.nl * N;          // rotc[baby][i][poly][nl][N]: row r = i*2+poly
     st.pt_k = p.plw; st.pt_n = (size_t)m.gsn * d * p.plw; st.pt_half = c.dma; st.pt_packed = c.packed_mask != 0; st.pt_digits = st.i8 = p.use_i8; st.i8_big = st.pt_digits_big = p.use_i8_big;   // pt[giant][g][baby]: k = g*91 + baby
     st.pt_layout = p.pt_layout; st.pt_L = c.L;
     st.out_n = c.accw; st.out_r = (size_t)c.L * N;                        // acc[j][giant][r]
     int rc;
-    if (c.dma) rc = launch_mac_dma(ctx, c.pre8 ? nullptr : m.rotf_grp, (size_t)c.s * 2, m.ptp, m.accj, m.gsn * d, 2 * c.s, d, c.L, m.acc_flag, st, m.rotsum_grp);
+    if (c.dma) rc = launch_mac_dma(ctx, m.rotf_grp, (size_t)c.s * 2, m.ptp, m.accj, m.gsn * d, 2 * c.s, d, c.L, m.acc_flag, st);
 #ifdef SFG_AB
     else rc = launch_mac_strided(ctx, c.rotc, m.ptp, m.accj, d, 2 * c.s, d, c.L, m.acc_flag, st);      // ab/mac_reg.hip
 #else
@@ -529,34 +530,39 @@ static int ride_launch_count(const MmCall &c, int bg, int ng, int nc) {
     return launches;
 }
 
-// acc_dev: [(j - j0)][giant < d][i < s][2][L][N] canonical residues (zero-initialised here unless accumulate != 0)
-// for operand block rows [b0, b1) and block columns [j0, j1).
-static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, int max_level, const Shape &sh, unsigned flags,
-                             int b0, int b1, int j0, int j1, int accumulate, u64 *acc, const double *rotf_pre = nullptr, const double *rotsum_pre = nullptr,
-                             const I8RotPre *pre8 = nullptr, size_t acc_col_words = 0) {          // acc_col_words: words between the accumulators of consecutive block columns (0: dense, 91 giants)
-    const int N = SFG_N, d = SFG_D, L = max_level;
-    if (pre8 && (rotf_pre || !mac_use_dma(ctx) || b0 != 0 || b1 != pre8->nbr || sh.nbr != pre8->nbr || s != pre8->s || L != pre8->L))
-        SFG_FAIL(ctx, "matmul: internal: the int8 rot tiles were built for another product (block rows %d, s = %d, level %d)", pre8->nbr, pre8->s, pre8->L);
+int RotOperand::validate(sfg_ctx *ctx, int s, int L, int nbr, int b0, int b1) const {
+    if (src == RotSrc::f64_cache && !mac_use_dma(ctx)) SFG_FAIL(ctx, "matmul: a prebuilt rotation cache needs the LDS-DMA MAC (the A/B build selected the register-staged kernel)");
+    if (src == RotSrc::i8_tiles) {
+        if (!tiles || !tiles->G) SFG_FAIL(ctx, "matmul: no int8 rot tiles");
+        if (!mac_use_dma(ctx) || b0 != 0 || b1 != tiles->nbr || nbr != tiles->nbr || s != tiles->s || L != tiles->L)
+            SFG_FAIL(ctx, "matmul: internal: the int8 rot tiles were built for another product (block rows %d, s = %d, level %d)", tiles->nbr, tiles->s, tiles->L);
+    }
+    return 0;
+}
+// the accumulate phase (kernels.hpp MmArgs) on the shape of a.g
+static int accumulate_blocks(sfg_ctx *ctx, const RotOperand &rot, const Shape &sh, const MmArgs &a) {
+    const int N = SFG_N, d = SFG_D, s = a.s, max_level = a.max_level, L = max_level, in_level = rot.level_in(max_level);
+    const int b0 = a.b0, b1 = a.b1, j0 = a.j0, j1 = a.j1, accumulate = a.accumulate; u64 *const acc = (u64 *)a.acc;
+    SFG_TRY(rot.validate(ctx, s, L, sh.nbr, b0, b1));
     const int lev = in_level > max_level ? max_level : in_level, nl = lev + 1, nl_in = in_level + 1;
     if (L < 1 || L > ctx->nq) SFG_FAIL(ctx, "matmul: max_level out of range");
     if (nl < L) SFG_FAIL(ctx, "matmul: input level %d has fewer than max_level = %d moduli", in_level, max_level);
     if (b0 < 0 || b1 > sh.nbr || b0 > b1 || j0 < 0 || j1 > sh.m_ct || j0 > j1) SFG_FAIL(ctx, "matmul: block range out of bounds");
     const size_t ctw = (size_t)2 * nl * N, accw = (size_t)s * 2 * L * N;
     const int ncolb = j1 - j0;
-    const size_t acc_col = acc_col_words ? acc_col_words : (size_t)d * accw;
+    const size_t acc_col = a.acc_col_words ? a.acc_col_words : (size_t)d * accw;
     if (acc_col < (size_t)d * accw) SFG_FAIL(ctx, "matmul: internal: accumulator column stride below 91 giant steps");
     if (b0 == b1 || j0 == j1) {
         if (!accumulate) for (int c = 0; c < ncolb; c++) SFG_HIP(ctx, hipMemsetAsync(acc + (size_t)c * acc_col, 0, (size_t)d * accw * 8, ctx->stream));
         return 0;
     }
     // ---- the plan
-    const MmPlanIn in = plan_input(ctx, s, L, b1 - b0, ncolb, rotf_pre ? RotSrc::f64_cache : pre8 ? RotSrc::i8_tiles : RotSrc::own, pre8 ? pre8->G : 0);
+    const MmPlanIn in = plan_input(ctx, s, L, b1 - b0, ncolb, rot);
     if (in.dma && in.mods.too_big) SFG_FAIL(ctx, "sfg_mac: modulus >= 2^47 unsupported by the fp64 limb schedule");
-    MmCall c{ctx, sh, flags, A, pre8, s, L, lev, nl, nl_in, in.dma, in.packed_mask, ctw, accw};
+    MmCall c{ctx, sh, a.flags, rot, s, L, lev, nl, nl_in, in.dma, in.packed_mask, ctw, accw};
     c.plan = mm_plan(in);
     MmPlan &plan = c.plan;
     const int G = plan.G; const bool dma = in.dma, rot_ext = in.rot != RotSrc::own;        // rot_ext: the caller holds the rotations of every block row
-    if (rotsum_pre && G < rotsum_group_size(in.mm_group, in.nblockrows)) SFG_FAIL(ctx, "matmul: internal: fewer rot-sum groups than MAC groups");      // (see rotsum_group_size)
     // ---- the buffers
     u64 *pt = nullptr;
     SFG_TRY(sfg_scratch(ctx, "mm.a_row", (size_t)s * ctw * 8, (void **)&c.a_row));
@@ -574,9 +580,8 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
     if (dma) {
         c.rowf = (size_t)in.mods.fp64_planes * N;
         if (!rot_ext) SFG_TRY(sfg_scratch(ctx, "mm.rotf", plan.grp_slices * s * 2 * c.rowf * 8 * (plan.pipelined ? 2 : 1), (void **)&c.rotf));
-        if (!rot_ext && in.packed_mask) SFG_TRY(sfg_scratch(ctx, "mm.rotsum", (size_t)2 * s * 2 * c.rowf * 8, (void **)&c.rotsum));     // one per ring half
     }
-    const size_t rot_half = plan.grp_slices * s * 2 * c.rowf, rotsum_half = (size_t)s * 2 * c.rowf;
+    const size_t rot_half = plan.grp_slices * s * 2 * c.rowf;
     // ---- the schedule
     // With several groups the key switching of group k+1 runs on the auxiliary stream beside the encode + MAC of group k
     // (those kernels leave registers and wave slots free; the MAC does not, so nothing overlaps it).
@@ -592,11 +597,11 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
         const int ng = std::min(G, b1 - bg);
         // (the delayed launch of the previous group reads a rot operand buffer that is rebuilt below: it goes first, transposing by the pass - unless the rot tiles
         //  of all groups are the caller's)
-        if (held.on && !pre8) { SFG_TRY(run_mac(c, held, 2)); held.on = false; }
+        if (held.on && in.rot != RotSrc::i8_tiles) { SFG_TRY(run_mac(c, held, 2)); held.on = false; }
         // ---- rotation caches of the group's block rows (or the product-wide cache built by the caller)
-        const double *rotf_grp = c.rotf, *rotsum_grp = c.rotsum;
-        if (rotf_pre) { rotf_grp = rotf_pre + (size_t)(bg - b0) * d * s * 2 * c.rowf; rotsum_grp = rotsum_pre ? rotsum_pre + (size_t)gi * rotsum_half : nullptr; }
-        else if (pre8) { rotf_grp = nullptr; rotsum_grp = nullptr; }            // group gi multiplies from pre8->As[gi] / Ab[gi]
+        const double *rotf_grp = c.rotf;
+        if (in.rot == RotSrc::f64_cache) rotf_grp = rot.rows + (size_t)(bg - b0) * d * s * 2 * c.rowf;
+        else if (in.rot == RotSrc::i8_tiles) rotf_grp = nullptr;               // group gi multiplies from the tiles As[gi] / Ab[gi]
         else if (plan.pipelined) {
             if (bg + G < b1) {                                                   // next group: its half was last read by group gi-1
                 SFG_TRY(sfg_stream_after(ctx, ctx->aux_stream, main_stream));
@@ -605,7 +610,6 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
             }
             SFG_HIP(ctx, hipStreamWaitEvent(main_stream, ctx->ev_pipe[gi & 1], 0));
             rotf_grp = c.rotf + (size_t)(gi & 1) * rot_half;
-            if (c.rotsum) rotsum_grp = c.rotsum + (size_t)(gi & 1) * rotsum_half;
         } else SFG_TRY(build_group(c, bg, b1, 0));
         for (int bj = j0; bj < j1; bj++, it++) {
             pt = pt_base + (size_t)(plan.ride_want ? (it & 1) : 0) * plan.panel_words;
@@ -622,7 +626,7 @@ static int matmul_accumulate(sfg_ctx *ctx, const u64 *A, int s, int in_level, in
             if (held.on) { SFG_TRY(i8_ride_finish(ctx, ride)); SFG_TRY(run_mac(c, held, 1)); held.on = false; }
             MacJob m; m.on = true; m.ptp = pt; m.gsn = ng; m.gi = gi;
             m.acc_flag = (accumulate || bg != b0) ? 1 : 0;              // the first launch of a fresh call overwrites
-            m.accj = acc + (size_t)(bj - j0) * acc_col; m.rotf_grp = rotf_grp; m.rotsum_grp = rotsum_grp;
+            m.accj = acc + (size_t)(bj - j0) * acc_col; m.rotf_grp = rotf_grp;
             if (plan.ride_want && c.rideBs) held = m;                                 // multiplied after the next launch's encode has transposed this panel
             else SFG_TRY(run_mac(c, m, c.rideBs ? 2 : 0));
         }
@@ -671,12 +675,14 @@ static void giant_table(const Shape &sh, std::vector<uint8_t> &giant_t) {
     }
 }
 
-extern "C" int sfg_matmul_accumulate_dev(sfg_ctx *ctx, const uint64_t *A, int s, int in_level, int max_level, const sfg_geno *g, unsigned flags,
-                                         int b0, int b1, int j0, int j1, int accumulate, uint64_t *acc) {
+int matmul_accumulate(sfg_ctx *ctx, const RotOperand &rot, const MmArgs &a) {
     ApiScope api_scope(ctx);
     SFG_HIP(ctx, hipSetDevice(ctx->device));
-    Shape sh = make_shape(g, flags);
-    return matmul_accumulate(ctx, (const u64 *)A, s, in_level, max_level, sh, flags, b0, b1, j0, j1, accumulate, (u64 *)acc);
+    return accumulate_blocks(ctx, rot, make_shape(a.g, a.flags), a);
+}
+extern "C" int sfg_matmul_accumulate_dev(sfg_ctx *ctx, const uint64_t *A, int s, int in_level, int max_level, const sfg_geno *g, unsigned flags,
+                                         int b0, int b1, int j0, int j1, int accumulate, uint64_t *acc) {
+    return matmul_accumulate(ctx, RotOperand::own((const u64 *)A, in_level), {g, flags, s, max_level, b0, b1, j0, j1, accumulate, acc, 0});
 }
 extern "C" int sfg_matmul_finalize_dev(sfg_ctx *ctx, const uint64_t *acc, int s, int max_level, int ncolb, int g0, int g1, int accumulate, uint64_t *out) {
     ApiScope api_scope(ctx);
@@ -694,86 +700,56 @@ extern "C" int sfg_matmul_finalize_slots_dev(sfg_ctx *ctx, const uint64_t *acc, 
     return matmul_finalize(ctx, (const u64 *)acc, s, max_level, ncolb, ncolb, 0, g0, g1, nullptr, accumulate, (u64 *)out, acc_giants, giant_base);
 }
 
-// SNP-block range [blk0, blk1) over the block columns of the STORED matrix: output columns for X, contraction rows for X^T
-static int matmul_resident_range(sfg_ctx *ctx, const uint64_t *A, int s, int in_level, int max_level, const sfg_geno *g, unsigned flags,
-                                 int blk0, int blk1, uint64_t *out, const double *rotf_ext, const I8RotPre *pre8 = nullptr) {
+// The whole product over an SNP-block range (kernels.hpp MmRangeArgs): the executor of mm_range_plan (mm_plan.hpp)
+int matmul_resident_range(sfg_ctx *ctx, const RotOperand &rot_in, const MmRangeArgs &a) {
+    ApiScope api_scope(ctx);
     SFG_HIP(ctx, hipSetDevice(ctx->device));
     ctx->phases.clear();
-    if (!rotf_ext && !pre8) ctx->i8_gen++;                               // a product that builds its own rot operands: whatever the int8 MAC had transposed is stale
-    Shape sh = make_shape(g, flags);
-    const int d = SFG_D, L = max_level, N = SFG_N;
-    const size_t accw = (size_t)s * 2 * L * N;
+    if (rot_in.src == RotSrc::own) ctx->i8_gen++;                        // a product that builds its own rot operands: whatever the int8 MAC had transposed is stale
+    const Shape sh = make_shape(a.g, a.flags);
+    const int d = SFG_D, s = a.s, L = a.max_level;
     std::vector<uint8_t> giant_t; giant_table(sh, giant_t);
     int b0 = 0, b1 = sh.nbr, j0 = 0, j1 = sh.m_ct;
-    if (sh.transposed) { b0 = blk0; b1 = blk1; } else { j0 = blk0; j1 = blk1; }
+    if (sh.transposed) { b0 = a.blk0; b1 = a.blk1; } else { j0 = a.blk0; j1 = a.blk1; }
     if (b0 < 0 || b1 > sh.nbr || j0 < 0 || j1 > sh.m_ct || b0 > b1 || j0 > j1) SFG_FAIL(ctx, "matmul: SNP-block range out of bounds");
+    if (L < 1 || L > ctx->nq) SFG_FAIL(ctx, "matmul: max_level out of range");
+    SFG_TRY(rot_in.validate(ctx, s, L, sh.nbr, b0, b1));
     const int m_out = j1 - j0;
-    // column groups bounded by an accumulator budget (default 24 GiB)
-    const size_t budget = ctx->cfg.acc_budget;
-    int jg = (int)(budget / ((size_t)d * accw * 8)); if (jg < 1) jg = 1;
-    // Several column groups would each rebuild the rotation cache of every block row (91 key switches per input
-    // ciphertext).  When the whole cache fits (48 GiB; Q*X at 100k x 1M: 13 block rows = 28 GB) it is built once here.
-    const double *rotf_all = rotf_ext, *rotsum_all = nullptr;
-    if (rotf_ext && !mac_use_dma(ctx)) SFG_FAIL(ctx, "matmul: a prebuilt rotation cache needs the LDS-DMA MAC (the A/B build selected the register-staged kernel)");
-    if (!rotf_ext && !pre8 && mac_use_dma(ctx) && j1 - j0 > jg && b1 > b0) {
-        std::vector<int> plane_of, is_big; const int nplanes = mac_dma_planes(ctx, L, plane_of, is_big);
-        if (nplanes < 0) return 1;
-        const size_t rowf = (size_t)nplanes * N, per_row = (size_t)d * s * 2 * rowf;       // doubles per block row
-        const int lev = in_level > max_level ? max_level : in_level, nl = lev + 1;
-        if (nl >= L && ((size_t)(b1 - b0) * per_row + 3 * (size_t)s * 2 * rowf) * 8 <= (48ULL << 30)) {
-            double *buf = nullptr; u64 *a_row = nullptr, *rotc = nullptr;
-            const size_t ctw = (size_t)2 * nl * N;
-            SFG_TRY(sfg_scratch(ctx, "mm.rotf", ((size_t)(b1 - b0) * per_row + 3 * (size_t)s * 2 * rowf) * 8, (void **)&buf));
-            SFG_TRY(sfg_scratch(ctx, "mm.a_row", (size_t)s * ctw * 8, (void **)&a_row));
-            SFG_TRY(sfg_scratch(ctx, "mm.rotc", 8, (void **)&rotc));                         // unused: the key switch writes the fp64 operand rows itself
-            for (int bi = b0; bi < b1; bi++) SFG_TRY(build_rot_row(ctx, (const u64 *)A, s, in_level + 1, nl, lev, L, sh, bi, a_row, rotc, true, buf + (size_t)(bi - b0) * per_row));
-            SFG_HIP(ctx, hipMemsetAsync(buf + (size_t)(b1 - b0) * per_row, 0, 3 * (size_t)s * 2 * rowf * 8, ctx->stream));   // k-slices read by a ragged last chunk
-            rotf_all = buf;
-            if (mac_dma_packed_mask(ctx, L)) {             // per group of rotsum_group_size (mm_plan.hpp) block rows: sum of its k-slices
-                const int G = rotsum_group_size(ctx->cfg.mm_group, b1 - b0), ngrp = (b1 - b0 + G - 1) / G;
-                double *rs = nullptr;
-                SFG_TRY(sfg_scratch(ctx, "mm.rotsum_all", (size_t)ngrp * s * 2 * rowf * 8, (void **)&rs));
-                for (int gi = 0; gi < ngrp; gi++) {
-                    const int ng = std::min(G, b1 - b0 - gi * G);
-                    SFG_TRY(launch_rot_sum(ctx, buf + (size_t)gi * G * per_row, (size_t)s * 2, ng * d, L, rs + (size_t)gi * s * 2 * rowf));
-                }
-                rotsum_all = rs;
-            }
-        }
+    MmRangeIn in;
+    in.s = s; in.L = L; in.nl = std::min(rot_in.level_in(L), L) + 1; in.rows = b1 - b0; in.cols = j1 - j0; in.fp64_planes = ModSplit(ctx->q, L).fp64_planes;
+    in.acc_budget = ctx->cfg.acc_budget; in.no_overlap = ctx->cfg.no_overlap; in.dma = mac_use_dma(ctx); in.rot = rot_in.src;
+    const MmRangePlan plan = mm_range_plan(in);
+    RotOperand rot = rot_in;
+    if (plan.whole_cache) {                       // the rotations of every block row of the range, once for all passes: from here on a product on an fp64 cache
+        double *buf = nullptr;
+        SFG_TRY(sfg_scratch(ctx, "mm.rotf", plan.cache_bytes, (void **)&buf));
+        std::vector<std::vector<uint8_t>> tabs;
+        for (int bi = b0; bi < b1; bi++) tabs.push_back(baby_table(sh, bi));
+        SFG_TRY(rotcache_build_rows_tab(ctx, rot_in.A, s, rot_in.in_level, L, sh.nbr, b0, b1, &tabs, buf));
+        rot = RotOperand::f64_cache(buf, rot_in.in_level);
     }
-    // With the product-wide cache the accumulate passes do no key switching, so the giant-step alignment of pass k runs on the
-    // auxiliary stream beside the encode + MAC of pass k+1 (two accumulator buffers of half the budget each).
-    const bool overlap = (rotf_all || pre8) && !ctx->cfg.no_overlap;
-    if (overlap) { jg = (jg + 1) / 2; }
+    const int jg = plan.jg; const size_t accw = (size_t)s * 2 * L * SFG_N;
     hipStream_t main_stream = ctx->stream;
     int k = 0;
     for (int ja = j0; ja < j1; ja += jg, k++) {
         const int jb = std::min(j1, ja + jg);
         u64 *acc = nullptr;
-        SFG_TRY(sfg_scratch(ctx, "mm.acc", (size_t)jg * d * accw * 8 * (overlap ? 2 : 1), (void **)&acc));
-        if (overlap) {
+        SFG_TRY(sfg_scratch(ctx, "mm.acc", plan.acc_bytes, (void **)&acc));
+        if (plan.overlap) {
             acc += (size_t)(k & 1) * jg * d * accw;
             if (k >= 2) SFG_HIP(ctx, hipStreamWaitEvent(main_stream, ctx->ev_pipe[2 + (k & 1)], 0));    // pass k-2 has been aligned out of this buffer
         }
-        int rc = matmul_accumulate(ctx, (const u64 *)A, s, in_level, max_level, sh, flags, b0, b1, ja, jb, 0, acc, rotf_all, rotsum_all, pre8);
-        if (rc) return rc;
-        if (overlap) {
-            SFG_TRY(sfg_stream_after(ctx, ctx->aux_stream, main_stream));
-            { AuxScope aux(ctx); rc = matmul_finalize(ctx, acc, s, max_level, jb - ja, m_out, ja - j0, 0, d, &giant_t, 0, (u64 *)out); }
-            if (rc) return rc;
-            SFG_HIP(ctx, hipEventRecord(ctx->ev_pipe[2 + (k & 1)], ctx->aux_stream));
-        } else {
-            rc = matmul_finalize(ctx, acc, s, max_level, jb - ja, m_out, ja - j0, 0, d, &giant_t, 0, (u64 *)out);
-            if (rc) return rc;
-        }
+        SFG_TRY(accumulate_blocks(ctx, rot, sh, {a.g, a.flags, s, L, b0, b1, ja, jb, 0, (uint64_t *)acc, 0}));
+        if (plan.overlap) SFG_TRY(sfg_stream_after(ctx, ctx->aux_stream, main_stream));
+        { AuxScope aux(ctx, plan.overlap); SFG_TRY(matmul_finalize(ctx, acc, s, L, jb - ja, m_out, ja - j0, 0, d, &giant_t, 0, (u64 *)a.out)); }
+        if (plan.overlap) SFG_HIP(ctx, hipEventRecord(ctx->ev_pipe[2 + (k & 1)], ctx->aux_stream));
     }
-    if (overlap) SFG_TRY(sfg_stream_after(ctx, main_stream, ctx->aux_stream));      // outputs are complete in main-stream order
+    if (plan.overlap) SFG_TRY(sfg_stream_after(ctx, main_stream, ctx->aux_stream));      // outputs are complete in main-stream order
     return 0;
 }
 extern "C" int sfg_matmul_resident_range_dev(sfg_ctx *ctx, const uint64_t *A, int s, int in_level, int max_level, const sfg_geno *g, unsigned flags,
                                              int blk0, int blk1, uint64_t *out) {
-    ApiScope api_scope(ctx);
-    return matmul_resident_range(ctx, A, s, in_level, max_level, g, flags, blk0, blk1, out, nullptr);
+    return matmul_resident_range(ctx, RotOperand::own((const u64 *)A, in_level), {g, flags, s, max_level, blk0, blk1, out});
 }
 
 // ---------------------------------------------------------------- the rotation cache as an object (multi-GPU runs)
@@ -877,12 +853,9 @@ int i8_rotpre_build(sfg_ctx *ctx, const u64 *A, int s, int in_level, int max_lev
     const ModSplit m(ctx->q, L);
     const int l_big = m.l_big, l_s0 = m.l_small0, n_s = m.nsmall; const int *plane_of = m.plane_of;
     const size_t rowf = (size_t)m.fp64_planes * SFG_N;
-    size_t have = 0, tot = 0; bool mem_failed = false;
-    if (c.mm_group_auto && nbr > c.mm_group) {
-        mem_failed = hipMemGetInfo(&have, &tot) != hipSuccess;
-        for (const auto &kv : ctx->pool) if (kv.first.rfind(prefix, 0) == 0 || kv.first == "mm.pt" || kv.first == "mm.rotf" || kv.first.rfind("mi8.", 0) == 0) have += kv.second.second;
-    }
-    int G = i8pre_group_size(m, c.mm_group, c.mm_group_auto, s, nbr, mem_failed, have, budget_bytes);
+    PoolMemory mem;                                          // (the tile buffers of an earlier call under `prefix` are regrown in place too)
+    if (c.mm_group_auto && nbr > c.mm_group) mem = pool_memory(ctx, prefix);
+    int G = i8pre_group_size(m, c.mm_group, c.mm_group_auto, s, nbr, mem.failed, mem.search, budget_bytes);
     if (!G) return 0;
     // every buffer first (the fp64 rows of one group in the product's own mm.rotf, the tile buffers of all groups); where the larger groups do not fit after
     // all - another context on the device - the default group size is tried before the caller is told to fall back
@@ -920,36 +893,16 @@ int i8_rotpre_build(sfg_ctx *ctx, const u64 *A, int s, int in_level, int max_lev
     pre.G = G; pre.nbr = nbr; pre.s = s; pre.L = L;
     return 0;
 }
-int matmul_resident_range_i8pre(sfg_ctx *ctx, const I8RotPre &pre, int s, int max_level, const sfg_geno *g, unsigned flags, int blk0, int blk1, uint64_t *out) {
-    ApiScope api_scope(ctx);
-    if (!pre.G) SFG_FAIL(ctx, "matmul: no int8 rot tiles");
-    return matmul_resident_range(ctx, nullptr, s, max_level, max_level, g, flags, blk0, blk1, out, nullptr, &pre);
-}
-// accumulate phase of a product (sfg_matmul_accumulate_rc_dev) against int8 rot tiles that cover ALL operand block rows of the (possibly transposed) matrix: the
-// multi-GPU engine's Q' X^T multiplies one output block column per call against the tiles of the rank's own block rows (mgpu.hip)
-int matmul_accumulate_i8pre(sfg_ctx *ctx, const I8RotPre &pre, int s, int max_level, const sfg_geno *g, unsigned flags, int j0, int j1, int accumulate, uint64_t *acc, size_t acc_col_words) {
-    ApiScope api_scope(ctx);
-    SFG_HIP(ctx, hipSetDevice(ctx->device));
-    if (!pre.G) SFG_FAIL(ctx, "matmul: no int8 rot tiles");
-    Shape sh = make_shape(g, flags);
-    return matmul_accumulate(ctx, nullptr, s, max_level, max_level, sh, flags, 0, pre.nbr, j0, j1, accumulate, (u64 *)acc, nullptr, nullptr, &pre, acc_col_words);
-}
-// GetDiagBool (matmult.go:627-631) for other translation units
 // the products on a prebuilt cache that covers exactly the operand block rows the call contracts over ([0, nbr) for X, [blk0, blk1) / [b0, b1) for X^T)
 extern "C" int sfg_matmul_resident_range_rc_dev(sfg_ctx *ctx, const double *cache, int s, int max_level, const sfg_geno *g, unsigned flags,
                                                 int blk0, int blk1, uint64_t *out) {
-    ApiScope api_scope(ctx);
     if (!cache) SFG_FAIL(ctx, "matmul: null rotation cache");
-    return matmul_resident_range(ctx, nullptr, s, max_level, max_level, g, flags, blk0, blk1, out, cache);
+    return matmul_resident_range(ctx, RotOperand::f64_cache(cache), {g, flags, s, max_level, blk0, blk1, out});
 }
 extern "C" int sfg_matmul_accumulate_rc_dev(sfg_ctx *ctx, const double *cache, int s, int max_level, const sfg_geno *g, unsigned flags,
                                             int b0, int b1, int j0, int j1, int accumulate, uint64_t *acc) {
-    ApiScope api_scope(ctx);
-    SFG_HIP(ctx, hipSetDevice(ctx->device));
     if (!cache) SFG_FAIL(ctx, "matmul: null rotation cache");
-    if (!mac_use_dma(ctx)) SFG_FAIL(ctx, "matmul: a prebuilt rotation cache needs the LDS-DMA MAC (the A/B build selected the register-staged kernel)");
-    Shape sh = make_shape(g, flags);
-    return matmul_accumulate(ctx, nullptr, s, max_level, max_level, sh, flags, b0, b1, j0, j1, accumulate, (u64 *)acc, cache, nullptr);
+    return matmul_accumulate(ctx, RotOperand::f64_cache(cache), {g, flags, s, max_level, b0, b1, j0, j1, accumulate, acc, 0});
 }
 
 extern "C" int sfg_matmul_resident_dev(sfg_ctx *ctx, const uint64_t *A, int s, int in_level, int max_level, const sfg_geno *g, unsigned flags, uint64_t *out) {
@@ -1167,12 +1120,12 @@ extern "C" int sfg_matmul_from_cache(sfg_ctx *ctx, const uint64_t *A, int s, int
     const size_t rowf = (size_t)nplanes * N;
     const unsigned packed_mask = mac_dma_packed_mask(ctx, L);
     int jp = (int)(ctx->cfg.acc_budget / ((size_t)d * accw * 8)); if (jp < 1) jp = 1; if (jp > m_ct) jp = m_ct;
-    u64 *a_row = nullptr, *rotc = nullptr, *acc = nullptr, *panel = nullptr, *raw_d = nullptr, *inv_d = nullptr; double *rotf = nullptr, *rotsum = nullptr;
+    u64 *a_row = nullptr, *rotc = nullptr, *acc = nullptr, *panel = nullptr, *raw_d = nullptr, *inv_d = nullptr; double *rotf = nullptr;
     uint8_t *present_d = nullptr; unsigned long long *asym_d = nullptr; u64 *raw_h = nullptr;
     int rc = 0;
     auto bail = [&](int r) { close_all(); if (raw_h) (void)hipHostFree(raw_h); return r; };
     if (sfg_scratch(ctx, "mm.a_row", (size_t)s * ctw * 8, (void **)&a_row) || sfg_scratch(ctx, "mm.rotc", 8, (void **)&rotc) ||
-        sfg_scratch(ctx, "mm.rotf", ((size_t)d + 3) * s * 2 * rowf * 8, (void **)&rotf) || sfg_scratch(ctx, "mm.rotsum", (size_t)2 * s * 2 * rowf * 8, (void **)&rotsum) ||
+        sfg_scratch(ctx, "mm.rotf", ((size_t)d + 3) * s * 2 * rowf * 8, (void **)&rotf) ||
         sfg_scratch(ctx, "mm.acc", (size_t)jp * d * accw * 8, (void **)&acc) || sfg_scratch(ctx, "dc.panel", (size_t)jp * d * plw * 8, (void **)&panel) ||
         sfg_scratch(ctx, "dc.raw", (size_t)d * jp * L * N * 8 + (size_t)d * jp + 64 + 8 * SFG_MAXMOD, (void **)&raw_d)) return bail(1);
     present_d = (uint8_t *)(raw_d + (size_t)d * jp * L * N);
@@ -1195,7 +1148,6 @@ extern "C" int sfg_matmul_from_cache(sfg_ctx *ctx, const uint64_t *A, int s, int
             try { rec.resize(h.rowSize); } catch (const std::exception &) { ctx->err = "matmul_from_cache: out of host memory for a record"; rc = 1; break; }
             rc = build_rot_row_tab(ctx, (const u64 *)A, s, nl_in, nl, lev, L, nbr, bi, h.baby, a_row, rotc, true, rotf);       // matmult.go:1083-1119
             if (!rc && hipMemsetAsync(rotf + (size_t)d * s * 2 * rowf, 0, (size_t)3 * s * 2 * rowf * 8, ctx->stream) != hipSuccess) rc = 1;
-            if (!rc && packed_mask) rc = launch_rot_sum(ctx, rotf, (size_t)s * 2, d, L, rotsum);
             int cur_giant = -1; bool any = false;
             auto flush = [&]() -> int {                      // the buffered records of giant cur_giant -> panel -> one MAC launch
                 if (!any) return 0;
@@ -1209,7 +1161,7 @@ extern "C" int sfg_matmul_from_cache(sfg_ctx *ctx, const uint64_t *A, int s, int
                 st.pt_k = plw; st.pt_n = (size_t)d * plw; st.pt_half = true; st.pt_packed = packed_mask != 0; st.i8 = ctx->cfg.mac_i8 && packed_mask; st.i8_big = st.i8 && ctx->cfg.mac_i8_big;     // panel[j][baby]
                 st.out_n = (size_t)d * accw; st.out_r = (size_t)L * N;                                           // acc[j][giant][r], column n = j
                 PhaseTimer t(ctx, "mac");
-                int r2 = launch_mac_dma(ctx, rotf, (size_t)s * 2, panel, acc + (size_t)cur_giant * accw, d, 2 * s, jn, L, 1, st, rotsum);
+                int r2 = launch_mac_dma(ctx, rotf, (size_t)s * 2, panel, acc + (size_t)cur_giant * accw, d, 2 * s, jn, L, 1, st);
                 t.stop(1);
                 SFG_HIP(ctx, hipStreamSynchronize(ctx->stream));               // raw_h is refilled next
                 any = false;

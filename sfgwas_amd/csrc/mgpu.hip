@@ -693,15 +693,14 @@ static int rank_contract(sfg_mgpu *mg, MgRank &R, int li, const uint64_t *A, int
     const I8RotPre &pre8 = rot8.pre;
     MgContractPlan P;                                    // every size, offset and step below (mg_plan.hpp); made in prepare(), once the form of the rank's rotations is known
     uint64_t *acc_mine = nullptr, *acc2 = nullptr; double *cache = nullptr;
+    RotOperand rot = RotOperand::own((const u64 *)A, in_level); size_t acc_pitch = 0;      // the rank's rotations and the column pitch of its products: prepare() replaces them where it builds tiles or a cache
     hipStream_t cs = ctx->stream;
     // columns [st.j, st.je) of the rank's partial product into their place of mg.acc2.  With int8 rot tiles a pipelined step is TWO columns, so that the second column's
     // encode carries the first one's plaintext transposition (kernels.hpp PtRide; a one-column call of one MAC group has nothing to ride in)
     auto multiply = [&](const MgStep &st) -> int {
         uint64_t *buf = acc2 + P.buf_words(st);
         if (!nloc) return 0;
-        if (!P.pipe) R_CTX(R, sfg_matmul_accumulate_dev(ctx, A, s, in_level, L, shard, fl, 0, nloc, st.j, st.je, 0, buf));
-        else if (pre8.G) R_CTX(R, matmul_accumulate_i8pre(ctx, pre8, s, L, shard, fl, st.j, st.je, 0, buf, P.colp));
-        else R_CTX(R, sfg_matmul_accumulate_rc_dev(ctx, cache, s, L, shard, fl, 0, nloc, st.j, st.je, 0, buf));
+        R_CTX(R, matmul_accumulate(ctx, rot, {shard, fl, s, L, 0, nloc, st.j, st.je, 0, buf, acc_pitch}));
         return 0;
     };
     // ---- everything that allocates or can fail on this rank's own account, BEFORE the first exchange
@@ -716,6 +715,7 @@ static int rank_contract(sfg_mgpu *mg, MgRank &R, int li, const uint64_t *A, int
         // they would not, the library's grouped rotation cache and the reduce-scatters after the whole product (P.pipe == false)
         if (nloc) R_CTX(R, i8_rotpre_build(ctx, (const u64 *)A, s, in_level, L, nloc, nullptr, mg->cache_budget, "mg.rot8", rot8.pre));
         P = mg_contract_plan({mg->world, R.rank, s, L, nbr_x, nloc, mg->direct, pre8.G != 0, (size_t)nloc * s * jobw + tailw, mg->cache_budget});
+        if (pre8.G) { rot = RotOperand::i8_tiles(&pre8); acc_pitch = P.colp; }
         R_CTX(R, sfg_scratch(ctx, "mg.mine", P.mine_bytes, (void **)&acc_mine));
         if (P.ar_bytes) { uint64_t *tmp = nullptr; R_CTX(R, sfg_scratch(ctx, "mg.ar", P.ar_bytes, (void **)&tmp)); }      // (the direct all-reduce's private copy: not after the agreement)
         // (the collectives' queue must not start before earlier work of the compute queue that still reads these buffers: previous call's finalize)
@@ -727,6 +727,7 @@ static int rank_contract(sfg_mgpu *mg, MgRank &R, int li, const uint64_t *A, int
         if (P.cache_bytes) {
             R_CTX(R, sfg_scratch(ctx, "mg.cache", P.cache_bytes, (void **)&cache));
             R_CTX(R, sfg_rotcache_build_rows_dev(ctx, A, s, in_level, L, nloc, 0, nloc, cache));
+            rot = RotOperand::f64_cache(cache);
         }
         // the first step is multiplied before the agreement too: that grows the product's own scratch pools (panel, tiles, accumulators) to their final shape
         if (multiply(P.steps.front())) return 1;

@@ -1,5 +1,5 @@
 // mm_plan.hpp — the launch plan of the matrix product (matmul.hip) as pure functions: which MAC kernel multiplies, how many block rows share a launch, the layout
-// and size of the plaintext panel, whether the transposition rides.  Arithmetic on the moduli, four integers, the configuration and two byte counts: standard
+// and size of the plaintext panel, whether the transposition rides; and the passes of a whole product (mm_range_plan).  Arithmetic on the moduli, four integers, the configuration and two byte counts: standard
 // library only, so that every decision runs on a CPU (tests/host/host_mmplan_test.cpp).  matmul.hip asks the device for the two byte counts and executes the plan.
 #pragma once
 #include "consts.hpp"
@@ -143,11 +143,31 @@ inline bool mm_plan_reads_memory(const MmPlanIn &in) {
     return in.dma && ((in.rot != RotSrc::i8_tiles && in.mm_group_auto && in.nblockrows > in.mm_group) || (in.rot == RotSrc::f64_cache && in.mac_i8 && in.packed_mask));
 }
 
-// The groups matmul_resident_range sums its product-wide rotation cache over ("mm.rotsum_all"): the configured group size.  mm_plan may pick a larger automatic
-// G for the same call (four block columns or more), so these sums can belong to other groups than the MAC launches - harmless, because no MAC kernel reads them:
-// the bias-free packed limbs need no rot sums (launch_rot_sum is empty, launch_mac_bc ignores its rotsum argument); only the buffer's name and size remain.
-// mm_plan's G is never smaller, so the pointer matmul_accumulate forms for group gi stays inside the buffer; it asserts that.
-inline int rotsum_group_size(int mm_group, int nblockrows) { return std::min(mm_group, nblockrows); }
+// ---------------------------------------------------------------- the plan of one matmul_resident_range call: the accumulate + finalize passes over block columns
+// Several passes would each rebuild the rotation cache of every block row (91 key switches per input ciphertext): when the cache of the whole range fits the
+// cap (Q*X at 100k x 1M: 13 block rows = 28 GB) the call builds it once and multiplies as with a caller's cache.  Without key switching in the passes the
+// giant-step alignment of pass k runs on the auxiliary stream beside the encode + MAC of pass k + 1: two accumulator buffers of half the budget each.
+struct MmRangeIn {
+    int s = 0, L = 0, nl = 0, rows = 0, cols = 0, fp64_planes = 0;   // nl: the operand's moduli after the level drop; block rows and columns of the range; ModSplit::fp64_planes
+    size_t acc_budget = 0; bool no_overlap = true, dma = true; RotSrc rot = RotSrc::own;      // SfgConfig: acc_budget, no_overlap
+};
+struct MmRangePlan {
+    int jg = 1, npasses = 0;              // block columns per pass, passes
+    bool whole_cache = false, overlap = false;         // the call builds the fp64 rotation cache of all its block rows first
+    size_t cache_bytes = 0, acc_bytes = 0;             // that cache (3 k-slices of tail included); "mm.acc"
+};
+inline MmRangePlan mm_range_plan(const MmRangeIn &in) {
+    const size_t N = SFG_N, d = SFG_D, per_col = d * in.s * 2 * in.L * N * 8, rowf = (size_t)in.fp64_planes * N;
+    MmRangePlan p;
+    int jg0 = (int)(in.acc_budget / per_col); if (jg0 < 1) jg0 = 1;
+    p.cache_bytes = ((size_t)in.rows * d * in.s * 2 * rowf + 3 * (size_t)in.s * 2 * rowf) * 8;
+    p.whole_cache = in.rot == RotSrc::own && in.dma && in.cols > jg0 && in.rows > 0 && in.nl >= in.L && p.cache_bytes <= SFG_MM_WHOLE_CACHE_CAP;
+    p.overlap = (p.whole_cache || in.rot != RotSrc::own) && !in.no_overlap;
+    p.jg = p.overlap ? (jg0 + 1) / 2 : jg0;
+    p.npasses = in.cols > 0 ? (in.cols + p.jg - 1) / p.jg : 0;
+    p.acc_bytes = (size_t)p.jg * per_col * (p.overlap ? 2 : 1);
+    return p;
+}
 
 // The group size of a caller's rotation cache held as int8 rot tiles (i8_rotpre_build), or 0: not taken - the moduli are not one run of small ones plus at most one
 // big one, or the tiles of all nbr block rows exceed budget_bytes or one MAC launch.  16 (12) block rows per group where the HBM (mem_search: free + the pool's own

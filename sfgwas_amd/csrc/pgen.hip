@@ -341,7 +341,7 @@ extern "C" int sfg_assoc_pgen(sfg_ctx *ctx, const uint8_t *pgen_host, size_t pge
         sfg_geno *g = nullptr;
         SFG_TRY(sfg_geno_from_pgen(ctx, pgen_host, pgen_bytes, b.snp0, b.snp0 + b.nsnp, row_filter, col_filter ? col_filter + b.snp0 : nullptr, &g));
         const size_t nct = assoc_cts(b.kept);
-        rc = assoc_product(ctx, rot.r, A_dev, s, in_level, max_level, g, flags, (int)nct, (uint64_t *)tmp.h);
+        rc = assoc_product(ctx, rot.r, s, max_level, g, flags, (int)nct, (uint64_t *)tmp.h);
         if (!rc) rc = assoc_batch_tail(ctx, (const u64 *)tmp.h, g, s, nct, ctw, out_dev, out_ct_capacity, plan.shift_of[k], sum_host, sqsum_host);
         sfg_geno_free(ctx, g);                                            // synchronises the queue: tmp and the batch matrix are done with
     }

@@ -80,18 +80,21 @@ int assoc_build_rotcache(sfg_ctx *ctx, const u64 *A_dev, int s, int in_level, in
 // fp64 kernel, the cache shrinks from 1.86 to 1.3 GB per block row at s = 13), else the fp64 operand rows, else nothing (every product rotates for itself).
 int assoc_build_rot(sfg_ctx *ctx, const u64 *A_dev, int s, int in_level, int max_level, size_t nr, const std::vector<size_t> &widths, AssocRot &out) {
     out = AssocRot();
+    out.op = RotOperand::own(A_dev, in_level);
     if (ctx->cfg.assoc_cache_budget) {
         std::vector<std::vector<uint8_t>> tabs; assoc_baby_tabs(nr, widths, tabs);
         SFG_TRY(i8_rotpre_build(ctx, A_dev, s, in_level, max_level, (int)tabs.size(), &tabs, ctx->cfg.assoc_cache_budget, "assoc.rot8", out.pre));
-        if (out.pre.G) return 0;
+        if (out.pre.G) { out.op = RotOperand::i8_tiles(&out.pre); return 0; }
     }
-    return assoc_build_rotcache(ctx, A_dev, s, in_level, max_level, nr, widths, &out.f64);
+    double *rows = nullptr;
+    SFG_TRY(assoc_build_rotcache(ctx, A_dev, s, in_level, max_level, nr, widths, &rows));
+    if (rows) out.op = RotOperand::f64_cache(rows);
+    return 0;
 }
 void assoc_free_rot(AssocRot &r) { i8_rotpre_free(r.pre); r = AssocRot(); }        // (the buffers are the context's scratch: see i8_rotpre_free)
-int assoc_product(sfg_ctx *ctx, const AssocRot &r, const uint64_t *A_dev, int s, int in_level, int max_level, const sfg_geno *g, unsigned flags, int nct, uint64_t *out) {
-    if (r.pre.G) return matmul_resident_range_i8pre(ctx, r.pre, s, max_level, g, flags, 0, nct, out);
-    if (r.f64) return sfg_matmul_resident_range_rc_dev(ctx, r.f64, s, max_level, g, flags, 0, nct, out);
-    return sfg_matmul_resident_dev(ctx, A_dev, s, in_level, max_level, g, flags, out);
+// the product of one batch: all nct block columns of the batch's matrix
+int assoc_product(sfg_ctx *ctx, const AssocRot &r, int s, int max_level, const sfg_geno *g, unsigned flags, int nct, uint64_t *out) {
+    return matmul_resident_range(ctx, r.op, {g, flags, s, max_level, 0, nct, out});
 }
 
 // The tail of a batch, shared by the streamed scan and sfg_assoc_pgen: the s rows of the product (tmp: [s][nct] ciphertexts of ctw words) copied to their place
@@ -208,7 +211,7 @@ int assoc_stream_part(sfg_ctx *ctx, int fmt, const char *path, size_t num_sample
         {
             const auto t0 = std::chrono::steady_clock::now();
             SFG_TRY(assoc_build_rot(ctx, (const u64 *)A_dev, s, in_level, max_level, nr, plan.widths, rot.r));
-            if (trace) { (void)hipStreamSynchronize(ctx->stream); fprintf(stderr, "[assoc] rotation cache (%s): %.1f ms\n", rot.r.pre.G ? "int8 tiles" : rot.r.f64 ? "fp64 rows" : "none",
+            if (trace) { (void)hipStreamSynchronize(ctx->stream); fprintf(stderr, "[assoc] rotation cache (%s): %.1f ms\n", rot.r.op.src == RotSrc::i8_tiles ? "int8 tiles" : rot.r.op.src == RotSrc::f64_cache ? "fp64 rows" : "none",
                                                                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); }
         }
         for (size_t k = 0; k < bt.size(); k++) {
@@ -237,7 +240,7 @@ int assoc_stream_part(sfg_ctx *ctx, int fmt, const char *path, size_t num_sample
             SFG_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev_ready[sl].h, 0));
             sfg_geno g; g.dev = gb[sl]; g.nrow = nr; g.ncol = b.kept; g.ld = b.kept; g.owned = false;
             const auto tb = std::chrono::steady_clock::now();
-            SFG_TRY(assoc_product(ctx, rot.r, A_dev, s, in_level, max_level, &g, flags, (int)nct, (uint64_t *)tmp));
+            SFG_TRY(assoc_product(ctx, rot.r, s, max_level, &g, flags, (int)nct, (uint64_t *)tmp));
             if (trace) { const double t_enq = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count(); (void)hipStreamSynchronize(ctx->stream);
                          fprintf(stderr, "[assoc] batch %zu: enqueued in %.1f ms, done after %.1f ms\n", k, t_enq, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count()); }
             SFG_TRY(assoc_batch_tail(ctx, tmp, &g, s, nct, ctw, out_dev, out_ct_capacity, out_shift, sum_host, sqsum_host));

@@ -1,5 +1,5 @@
-// The product's launch plan (sfgwas_amd/csrc/mm_plan.hpp) on the CPU: the full MmPlan of a table of named cases, the invariants every plan keeps, and the two
-// other group-size choosers.  Stand-alone: includes the header, links nothing of the library.
+// The product's launch plan (sfgwas_amd/csrc/mm_plan.hpp) on the CPU: the full MmPlan of a table of named cases, the invariants every plan keeps, the group-size
+// chooser of a caller's int8 tiles, and the range plan of a whole product (mm_range_plan).  Stand-alone: includes the header, links nothing of the library.
 // The expected rows were recorded from the decision statements matmul_accumulate held inline before they moved into the header.
 #include "../../sfgwas_amd/csrc/mm_plan.hpp"
 #include <cstdio>
@@ -45,7 +45,7 @@ static std::vector<Case> cases() {
     { MmPlanIn c = b; c.nblockrows = 0; add("17a no block rows", c); }
     { MmPlanIn c = b; c.ncolb = 0; add("17b no block columns", c); }
     { MmPlanIn c = b; c.mem_failed = true; add("21 memory query failed", c); }
-    { MmPlanIn c = b; c.rot = RotSrc::f64_cache; c.ncolb = 5; add("22 product-wide cache, five columns: automatic group above the rot-sum group", c); }
+    { MmPlanIn c = b; c.rot = RotSrc::f64_cache; c.ncolb = 5; add("22 product-wide cache, five columns: automatic group", c); }
     { MmPlanIn c = b; c.mac_i8 = false; add("23 mac_i8 off", c); }
     return v;
 }
@@ -72,12 +72,62 @@ static const Want WANT[] = {
     {0, 0, false, false, false, false, false, 0, 0, 0, 0, 0, 0, false, false, 0x0u},      // 17a no block rows (the parent returns before deciding)
     {0, 0, false, false, false, false, false, 0, 0, 0, 0, 0, 0, false, false, 0x0u},      // 17b no block columns (the parent returns before deciding)
     {8, 2, false, true, true, true, true, 2, 26, 8192, 26624, 1763786752ULL, 731, false, true, 0xf000001eu},      // 21 memory query failed
-    {13, 1, true, true, true, true, true, 2, 26, 8192, 26624, 2866153472ULL, 1186, false, true, 0xf000001eu},      // 22 product-wide cache, five columns: automatic group above the rot-sum group
+    {13, 1, true, true, true, true, true, 2, 26, 8192, 26624, 2866153472ULL, 1186, false, true, 0xf000001eu},      // 22 product-wide cache, five columns: automatic group
     {13, 1, false, false, false, false, false, 0, 0, 8192, 40960, 4409466880ULL, 1186, false, false, 0x1eu},      // 23 mac_i8 off
 };
 
 static int fails = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { fails++; printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } while (0)
+
+// mm_range_plan, derived by hand from its statements.  N = 16384, s = 15, L = nl = 5, 6 fp64 planes (one 46-bit + four small moduli), a 24 GiB budget:
+//   per_col = 91 * 15 * 2 * 5 * 16384 * 8 = 1 789 132 800;  jg0 = floor(25 769 803 776 / 1 789 132 800) = 14;  rowf = 6 * 16384 = 98 304
+//   cache_bytes(rows) = (rows * 91 * 15 * 2 * 98304 + 3 * 15 * 2 * 98304) * 8 = (rows * 2730 + 90) * 786 432;  the cap is 48 GiB = 51 539 607 552
+static MmRangePlan range_case(const char *n, const MmRangeIn &in) {
+    const MmRangePlan p = mm_range_plan(in);
+    const size_t per_col = (size_t)91 * in.s * 2 * in.L * 16384 * 8;
+    CHECK(p.jg >= 1, "%s: jg = %d", n, p.jg);
+    CHECK(p.npasses == (in.cols + p.jg - 1) / p.jg, "%s: %d passes of %d columns over %d", n, p.npasses, p.jg, in.cols);
+    CHECK(p.acc_bytes == (size_t)p.jg * per_col * (p.overlap ? 2 : 1), "%s: acc bytes %zu", n, p.acc_bytes);
+    CHECK(!p.whole_cache || in.rot == RotSrc::own, "%s: a whole-range cache beside a caller's rotations", n);
+    return p;
+}
+static void range_plan_cases() {
+    MmRangeIn b;
+    b.s = 15; b.L = b.nl = 5; b.rows = 13; b.cols = 123; b.fp64_planes = 6; b.acc_budget = 24ULL << 30; b.no_overlap = true; b.dma = true; b.rot = RotSrc::own;
+#define RANGE(name, in, WC, CB, OV, JG, NP, AB) do { const MmRangePlan p = range_case(name, in); \
+        CHECK(p.whole_cache == (WC) && p.overlap == (OV) && p.jg == (JG) && p.npasses == (NP) && p.acc_bytes == (size_t)(AB) && (!(CB) || p.cache_bytes == (size_t)(CB)), \
+              "%s: whole_cache %d (%zu bytes), overlap %d, jg %d, %d passes, acc %zu", name, p.whole_cache, p.cache_bytes, p.overlap, p.jg, p.npasses, p.acc_bytes); } while (0)
+    // R1: 13 x 123, one queue.  123 > 14 columns, cache (13 * 2730 + 90) * 786432 = 35580 * 786432 = 27 981 250 560 <= cap: taken.  no_overlap: jg = 14,
+    // ceil(123 / 14) = 9 passes, acc 14 * 1 789 132 800 = 25 047 859 200
+    RANGE("R1 13 x 123, one queue", b, true, 27981250560ULL, false, 14, 9, 25047859200ULL);
+    // R2: two queues: overlap, jg = (14 + 1) / 2 = 7, ceil(123 / 7) = 18 passes, acc 7 * per_col * 2 = 25 047 859 200
+    MmRangeIn two = b; two.no_overlap = false;
+    RANGE("R2 13 x 123, two queues", two, true, 27981250560ULL, true, 7, 18, 25047859200ULL);
+    // R3: the cap's edge.  23 rows: (62790 + 90) * 786432 = 49 450 844 160 <= 51 539 607 552; 24 rows: (65520 + 90) * 786432 = 51 597 803 520 > cap
+    { MmRangeIn c = b; c.rows = 23; RANGE("R3a 23 rows: at the cap", c, true, 49450844160ULL, false, 14, 9, 25047859200ULL); }
+    { MmRangeIn c = b; c.rows = 24; RANGE("R3b 24 rows: past the cap", c, false, 51597803520ULL, false, 14, 9, 25047859200ULL); }
+    { MmRangeIn c = two; c.rows = 24; RANGE("R3c 24 rows, two queues: own rotations in every pass, no overlap", c, false, 51597803520ULL, false, 14, 9, 25047859200ULL); }
+    // R4: 14 columns fit one pass (cols > jg0 fails): no cache; 1 pass
+    { MmRangeIn c = b; c.cols = 14; RANGE("R4a 14 columns", c, false, 0, false, 14, 1, 25047859200ULL); }
+    { MmRangeIn c = two; c.cols = 5; RANGE("R4b 5 columns, two queues", c, false, 0, false, 14, 1, 25047859200ULL); }
+    // R5: the operand has fewer moduli than the product after the level drop (the accumulate phase refuses it): no cache
+    { MmRangeIn c = b; c.nl = 4; RANGE("R5 nl < L", c, false, 0, false, 14, 9, 25047859200ULL); }
+    // R6: a caller's rotations: never a cache of the call's own; overlap is !no_overlap alone
+    for (RotSrc r : {RotSrc::f64_cache, RotSrc::i8_tiles}) {
+        MmRangeIn c = b; c.rot = r; RANGE("R6a caller's rotations, one queue", c, false, 0, false, 14, 9, 25047859200ULL);
+        c.no_overlap = false; RANGE("R6b caller's rotations, two queues", c, false, 0, true, 7, 18, 25047859200ULL);
+        c.cols = 1; RANGE("R6c caller's rotations, one column, two queues", c, false, 0, true, 7, 1, 25047859200ULL);
+    }
+    // R7: the register-staged MAC has no fp64 operand rows: no cache
+    { MmRangeIn c = two; c.dma = false; RANGE("R7 dma off", c, false, 0, false, 14, 9, 25047859200ULL); }
+    // R8: a budget below one column (1 GiB < 1 789 132 800): jg = 1, 123 passes of one column; with the cache and two queues (1 + 1) / 2 = 1, two buffers
+    { MmRangeIn c = b; c.acc_budget = 1ULL << 30; RANGE("R8a budget below one column", c, true, 27981250560ULL, false, 1, 123, 1789132800ULL);
+      c.no_overlap = false; RANGE("R8b the same, two queues", c, true, 27981250560ULL, true, 1, 123, 3578265600ULL); }
+    // R9: no block rows (an empty X^T range): no cache; no block columns: no pass
+    { MmRangeIn c = two; c.rows = 0; RANGE("R9a no rows", c, false, 0, false, 14, 9, 25047859200ULL); }
+    { MmRangeIn c = b; c.cols = 0; RANGE("R9b no columns", c, false, 0, false, 14, 0, 25047859200ULL); }
+#undef RANGE
+}
 
 int main() {
     const std::vector<Case> cs = cases();
@@ -98,9 +148,8 @@ int main() {
         CHECK(!p.pipelined || in.rot == RotSrc::own, "%s: pipelined with a caller's rotations", n);
         CHECK(p.pt_layout == (p.kmajor ? 2 : p.compact ? 1 : 0), "%s: pt_layout", n);
         if (in.L == 5 && in.dma && p.G) CHECK(p.plw * 8 == (p.compact ? 208u : 320u) * 1024u, "%s: %zu bytes per plaintext", n, p.plw * 8);     // the figures README and DESIGN state
-        // mm_plan is plan_at of the chosen group size, and never groups fewer block rows than the rot sums of a product-wide cache
+        // mm_plan is plan_at of the chosen group size
         if (p.G) { const MmPlan a = plan_at(in, p.G); CHECK(a.enc_flags == p.enc_flags && a.panel_words == p.panel_words && a.use_i8 == p.use_i8, "%s: plan_at(G) differs", n); }
-        if (p.G && in.dma) CHECK(p.G >= rotsum_group_size(in.mm_group, in.nblockrows), "%s: G below the rot-sum group", n);
     }
     // 18: i8pre_group_size, 20 block rows of the product's moduli at s = 13: the candidates 16 and 12, the fallback, a budget below the tiles
     const ModSplit prod(Q_PRODUCT, 5);
@@ -116,8 +165,7 @@ int main() {
     // 19: not one run of small moduli plus at most one big one
     CHECK(i8pre_group_size(ModSplit(Q_TWO_BIG, 3), 8, true, 13, 20, false, 300 * GB, 200 * GB) == 0, "19: two 46-bit moduli");
     CHECK(i8pre_group_size(ModSplit(Q_TWO_RUNS, 3), 8, true, 13, 20, false, 300 * GB, 200 * GB) == 0, "19: two runs of small moduli");
-    // 20
-    CHECK(rotsum_group_size(8, 13) == 8 && rotsum_group_size(8, 5) == 5, "20: rotsum_group_size");
+    range_plan_cases();
     // ModSplit of the product's moduli
     CHECK(prod.nsmall == 4 && prod.nbig == 1 && prod.l_big == 0 && prod.l_small0 == 1 && prod.small_runs == 1 && prod.fp64_planes == 6 && prod.digit_planes == 26 &&
           prod.packed_mask_all == 0x1eu && !prod.too_big && prod.plane_of[1] == 2 && prod.is_big[0] == 1, "ModSplit of the product's moduli");

@@ -1,6 +1,6 @@
 """The launch plan of the matrix product (sfgwas_amd/csrc/mm_plan.hpp) is pure host arithmetic: tests/host/host_mmplan_test.cpp holds the plan of every
-named case against the rows recorded from the statements matmul_accumulate held inline before, checks the invariants of every plan and the two other
-group-size choosers.  No GPU, nothing of the library linked; built with AddressSanitizer + UBSan where the compiler has the runtimes."""
+named case against the rows recorded from the statements matmul_accumulate held inline before, checks the invariants of every plan, the group-size
+chooser of a caller's int8 tiles and the range plan of a whole product (mm_range_plan) against cases derived by hand.  No GPU, nothing of the library linked; built with AddressSanitizer + UBSan where the compiler has the runtimes."""
 import os
 import subprocess
 
