@@ -1,6 +1,6 @@
 // gring.hip - the general ring: evaluator operations for logN 12..16 and any NTT-friendly modulus below 2^61, in integer arithmetic.
 // A second path beside the PN14QP438 context (whose kernels are specialised for N = 16384 and residues held exactly in fp64): nothing here is shared with it
-// but the C-ABI's layouts.  Arithmetic and bounds: gring_arith.hpp.  Stage split and digits: gring_plan.hpp.  DESIGN.md section 13.
+// but the C-ABI's layouts.  Arithmetic and bounds: gring_arith.hpp.  Stage split, digits, launch caps, workspace layouts and chunks: gring_plan.hpp.  DESIGN.md section 13.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -9,7 +9,7 @@
 #include <map>
 #include <string>
 #include <vector>
-#include "gring_dev.hpp"      // the device-side tables, struct sfg_ring and the error macros, shared with gring_io.hip
+#include "gring_dev.hpp"      // the device-side tables, the owners, struct sfg_ring and the error macros, shared with gring_io.hip
 
 // ---------------------------------------------------------------- the transform: two launches, logN = a + b (gring_plan.hpp)
 // Twiddle tables tw[mod][4][N]: psi^brev forward, its Shoup quotients, psi^-brev inverse, its Shoup quotients - lattigo's and the oracle's order
@@ -183,11 +183,6 @@ __global__ __launch_bounds__(GR_T) void k_gr_from_mont(u64 *rows, const GrMod *m
 // ---------------------------------------------------------------- host side
 static thread_local std::string g_ring_create_error;
 
-static u64 hm_mul(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
-static u64 hm_pow(u64 a, u64 e, u64 q) { u64 r = 1 % q; a %= q; while (e) { if (e & 1) r = hm_mul(r, a, q); a = hm_mul(a, a, q); e >>= 1; } return r; }
-static u64 hm_inv(u64 a, u64 q) { return hm_pow(a, q - 2, q); }
-static u64 hm_shoup(u64 w, u64 q) { return (u64)(((u128)w << 64) / q); }
-static uint32_t hm_brev(uint32_t x, int bits) { uint32_t r = 0; for (int i = 0; i < bits; i++) { r = (r << 1) | (x & 1); x >>= 1; } return r; }
 static bool hm_is_prime(u64 n) {            // Miller-Rabin, deterministic below 2^64 with the first twelve primes as bases
     if (n < 2) return false;
     for (u64 p : {2ULL, 3ULL, 5ULL, 7ULL, 11ULL, 13ULL, 17ULL, 19ULL, 23ULL, 29ULL, 31ULL, 37ULL}) { if (n % p == 0) return n == p; }
@@ -217,23 +212,25 @@ int gr_upload(sfg_ring *r, void *dst, const void *src, size_t bytes) {
     const size_t need = (bytes + 255) & ~(size_t)255;
     if (need > r->pin_bytes) { GR_HIP(r, hipStreamSynchronize(r->stream)); GR_HIP(r, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return 0; }
     if (r->pin_head + need > r->pin_bytes) { GR_HIP(r, hipStreamSynchronize(r->stream)); r->pin_head = 0; }
-    unsigned char *slot = r->pin + r->pin_head; r->pin_head += need;
+    unsigned char *slot = (unsigned char *)r->pin.h + r->pin_head; r->pin_head += need;
     memcpy(slot, src, bytes);
     GR_HIP(r, hipMemcpyAsync(dst, slot, bytes, hipMemcpyHostToDevice, r->stream));
     return 0;
 }
-int gr_reserve(sfg_ring *r, void **buf, size_t *have, size_t bytes) {
-    if (bytes <= *have) return 0;
+int gr_reserve(sfg_ring *r, GrMem &buf, size_t bytes) {
+    if (bytes <= buf.bytes) return 0;
     GR_HIP(r, hipStreamSynchronize(r->stream));
-    if (*buf) GR_HIP(r, hipFree(*buf));
-    *buf = nullptr; *have = 0;
-    if (hipMalloc(buf, bytes) != hipSuccess) { (void)hipGetLastError(); *buf = nullptr; GR_FAIL(r, "out of device memory: %zu bytes of workspace", bytes); }
-    *have = bytes;
+    if (buf.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); GR_FAIL(r, "out of device memory: %zu bytes of workspace", bytes); }
+    return 0;
+}
+int gr_table(sfg_ring *r, GrMem &dst, const void *host, size_t bytes) {
+    GR_HIP(r, dst.alloc(bytes));
+    GR_HIP(r, hipMemcpy(dst.p, host, bytes, hipMemcpyHostToDevice));
     return 0;
 }
 
 static int gr_build_ext(sfg_ring *r, GrExtOwner &o, const std::vector<int> &src, int alpha, const std::vector<int> &tgt) {
-    const int nsrc = (int)src.size(), ntgt = (int)tgt.size(), ndig = (nsrc + alpha - 1) / alpha;
+    const int nsrc = (int)src.size(), ntgt = (int)tgt.size(), ndig = gr_digits(nsrc - 1, alpha).beta;
     std::vector<u64> inv((size_t)nsrc * 2), tab((size_t)ndig * ntgt * (1 + alpha), 0);
     std::vector<int> tsrc((size_t)ndig * ntgt, -1);
     for (int i = 0; i < ndig; i++) {
@@ -263,9 +260,8 @@ static int gr_build_ext(sfg_ring *r, GrExtOwner &o, const std::vector<int> &src,
     std::vector<unsigned char> host(total, 0);
     memcpy(host.data() + o_inv, inv.data(), b_inv); memcpy(host.data() + o_tab, tab.data(), b_tab); memcpy(host.data() + o_src, src.data(), b_src);
     memcpy(host.data() + o_tm, tgt.data(), b_tm); memcpy(host.data() + o_ts, tsrc.data(), b_ts);
-    GR_HIP(r, hipMalloc(&o.buf, total));
-    GR_HIP(r, hipMemcpy(o.buf, host.data(), total, hipMemcpyHostToDevice));
-    unsigned char *d = (unsigned char *)o.buf;
+    GR_TRY(gr_table(r, o.buf, host.data(), total));
+    unsigned char *d = (unsigned char *)o.buf.p;
     o.e.nsrc = nsrc; o.e.ndig = ndig; o.e.alpha = alpha; o.e.tgt_cap = ntgt;
     o.e.inv = (const u64 *)(d + o_inv); o.e.tgt_tab = (const u64 *)(d + o_tab); o.e.src_mod = (const int *)(d + o_src);
     o.e.tgt_mod = (const int *)(d + o_tm); o.e.tgt_src = (const int *)(d + o_ts);
@@ -283,9 +279,8 @@ static int gr_level(sfg_ring *r, int level, GrLevel **out) {
         std::vector<u64> tab((size_t)3 * std::max(level, 1), 0);
         const u64 qL = r->q[level], half = (qL - 1) >> 1;
         for (int m = 0; m < level; m++) { const u64 q = r->q[m], li = hm_inv(qL % q, q); tab[3 * m] = q - half % q; tab[3 * m + 1] = li; tab[3 * m + 2] = hm_shoup(li, q); }
-        GR_HIP(r, hipMalloc((void **)&L.rescale_tab, tab.size() * 8));
-        GR_HIP(r, hipMemcpy(L.rescale_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-        it = r->levels.emplace(level, L).first;
+        GR_TRY(gr_table(r, L.rescale_tab, tab.data(), tab.size() * 8));
+        it = r->levels.emplace(level, std::move(L)).first;                   // complete: a failure above let the local tables go
     }
     *out = &it->second;
     return 0;
@@ -293,8 +288,8 @@ static int gr_level(sfg_ring *r, int level, GrLevel **out) {
 
 int gr_transform(sfg_ring *r, u64 *rows, size_t nrows, GrRowMap map, bool inv) {
     const GrNttPlan &p = r->plan;
-    for (size_t row0 = 0; row0 < nrows; row0 += 32768) {
-        dim3 grid((unsigned)p.tiles_per_row, (unsigned)std::min<size_t>(32768, nrows - row0));
+    gr_split(nrows, kGrLaunchCap, [&](size_t row0, size_t n) {
+        dim3 grid((unsigned)p.tiles_per_row, (unsigned)n);
         if (!inv) {
             hipLaunchKernelGGL(k_gr_cols<false>, grid, dim3(GR_T), 0, r->stream, rows, row0, map, r->modc, r->tw, p.logN, p.a, p.b);
             hipLaunchKernelGGL(k_gr_contig<false>, grid, dim3(GR_T), 0, r->stream, rows, row0, map, r->modc, r->tw, p.logN, p.a, p.b);
@@ -302,7 +297,8 @@ int gr_transform(sfg_ring *r, u64 *rows, size_t nrows, GrRowMap map, bool inv) {
             hipLaunchKernelGGL(k_gr_contig<true>, grid, dim3(GR_T), 0, r->stream, rows, row0, map, r->modc, r->tw, p.logN, p.a, p.b);
             hipLaunchKernelGGL(k_gr_cols<true>, grid, dim3(GR_T), 0, r->stream, rows, row0, map, r->modc, r->tw, p.logN, p.a, p.b);
         }
-    }
+        return 0;
+    });
     GR_HIP(r, hipGetLastError());
     return 0;
 }
@@ -318,25 +314,11 @@ int gr_extend(sfg_ring *r, const GrExt &e, const u64 *src, u64 *Y, uint32_t *V, 
     return 0;
 }
 
-// workspace of one chunk of key switches
+// workspace of one chunk of key switches: the regions of gr_ks_layout (gring_plan.hpp) in the ring's workspace
 struct GrKsWs { u64 *c2, *Y, *ext, *accQ, *accP, *Y2, *ext2; uint32_t *V, *V2; GrJob *jobs; };
-static size_t gr_ks_words_per_job(const sfg_ring *r, int level) {
-    const size_t nl = level + 1, np = r->np, nt = nl + np, beta = (nl + np - 1) / np;
-    return nl * 2 + beta * nt + 2 * nl + 2 * np + 2 * np + 2 * nl + (beta + 2 + 1) / 2 + 1;     // c2, Y, ext, accQ, accP, Y2, ext2, V + V2 (32-bit)
-}
-static int gr_ks_chunk_jobs(sfg_ring *r, int level, size_t njobs) {
-    const size_t per = gr_ks_words_per_job(r, level) * r->N * 8 + sizeof(GrJob);
-    return (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(njobs, 32767), r->ws_budget / per));
-}
-static int gr_ks_workspace(sfg_ring *r, int level, size_t J, GrKsWs &w) {
-    const size_t nl = level + 1, np = r->np, nt = nl + np, beta = (nl + np - 1) / np, N = r->N;
-    GR_TRY(gr_reserve(r, &r->ws, &r->ws_bytes, J * (gr_ks_words_per_job(r, level) * N * 8 + sizeof(GrJob)) + 256));
-    u64 *p = (u64 *)r->ws;
-    w.c2 = p; p += J * nl * N; w.Y = p; p += J * nl * N; w.ext = p; p += J * beta * nt * N; w.accQ = p; p += J * 2 * nl * N; w.accP = p; p += J * 2 * np * N;
-    w.Y2 = p; p += J * 2 * np * N; w.ext2 = p; p += J * 2 * nl * N;
-    w.V = (uint32_t *)p; w.V2 = w.V + J * beta * N; p += (J * (beta + 2) * N + 1) / 2;
-    w.jobs = (GrJob *)p;
-    return 0;
+static GrKsWs gr_ks_ws(void *ws, const GrKsLayout &l) {
+    u64 *p = (u64 *)ws;
+    return GrKsWs{p + l.c2, p + l.Y, p + l.ext, p + l.accQ, p + l.accP, p + l.Y2, p + l.ext2, (uint32_t *)(p + l.V), (uint32_t *)(p + l.V2), (GrJob *)(p + l.jobs)};
 }
 // lattigo switchKeysInPlace on J jobs whose c2 rows (NTT domain) are in w.c2 and whose job list is uploaded: out[ct][p] = d_p (+ add[ct][p] where add_mask says so),
 // read through the job's automorphism index
@@ -353,6 +335,21 @@ static int gr_keyswitch(sfg_ring *r, int level, size_t J, const GrKsWs &w, const
     GR_TRY(gr_transform(r, w.ext2, J * 2 * nl, gr_map(nl, nl, 0, 0), false));
     hipLaunchKernelGGL(k_gr_ks_finish, dim3(gx, nl, (unsigned)(J * 2)), dim3(GR_T), 0, r->stream, w.accQ, w.ext2, w.jobs, r->pinv, add, add_mask, out, r->modc, nl, N);
     GR_HIP(r, hipGetLastError());
+    return 0;
+}
+// a batch of key switches in the chunks of gr_ks_plan: per chunk the job list is uploaded, front(first job, jobs, workspace) launches what fills the chunk's c2
+// rows (a job's ciphertext index is absolute, its workspace rows are the chunk's), and the key switch runs
+template <class Front>
+static int gr_ks_batch(sfg_ring *r, int level, const std::vector<GrJob> &jobs, const u64 *add, int add_mask, u64 *out, Front front) {
+    const GrChunks plan = gr_ks_plan(jobs.size(), level, r->np, (size_t)r->N, r->ws_budget);
+    GR_TRY(gr_reserve(r, r->ws, plan.bytes));
+    const GrKsWs w = gr_ks_ws(r->ws.p, gr_ks_layout(level, r->np, (size_t)r->N, plan.chunk));
+    for (size_t c = 0; c < plan.nchunks; c++) {
+        const size_t j0 = plan.first(c), n = plan.count(c, jobs.size());
+        GR_TRY(gr_upload(r, w.jobs, jobs.data() + j0, n * sizeof(GrJob)));
+        front(j0, n, w);
+        GR_TRY(gr_keyswitch(r, level, n, w, add, add_mask, out));
+    }
     return 0;
 }
 
@@ -375,25 +372,20 @@ static int gr_apply_galois(sfg_ring *r, const char *what, const u64 *in, u64 *ou
         jobs.push_back(GrJob{it->second.key, it->second.idx, j});
     }
     for (int j = 0; j < nct; j++) if (gal[j] == 0) GR_HIP(r, hipMemcpyAsync(out + j * ctw, in + j * ctw, ctw * 8, hipMemcpyDeviceToDevice, r->stream));
-    const size_t J = jobs.empty() ? 0 : gr_ks_chunk_jobs(r, level, jobs.size());
-    for (size_t j0 = 0; j0 < jobs.size(); j0 += J) {
-        const size_t n = std::min(J, jobs.size() - j0); GrKsWs w;
-        GR_TRY(gr_ks_workspace(r, level, J, w));
-        GR_TRY(gr_upload(r, w.jobs, jobs.data() + j0, n * sizeof(GrJob)));
+    return gr_ks_batch(r, level, jobs, in, 1, out, [&](size_t, size_t n, const GrKsWs &w) {
         hipLaunchKernelGGL(k_gr_gather_c1, dim3(N / GR_T, nl, (unsigned)n), dim3(GR_T), 0, r->stream, in, w.c2, w.jobs, nl, N);
-        GR_TRY(gr_keyswitch(r, level, n, w, in, 1, out));
-    }
-    return 0;
+    });
 }
 
 template <int OP>
 static int gr_ew(sfg_ring *r, const u64 *a, const u64 *b, u64 *out, const GrScalars &sc, size_t pt_stride, int nct, int nl_in, int nl_out) {
-    for (int c0 = 0; c0 < nct; c0 += 16384) {
-        const int n = std::min(16384, nct - c0); const size_t oi = (size_t)c0 * 2 * nl_in * r->N, oo = (size_t)c0 * 2 * nl_out * r->N;
+    gr_split((size_t)nct, kGrEwCap, [&](size_t c0, size_t n) {
+        const size_t oi = c0 * 2 * nl_in * r->N, oo = c0 * 2 * nl_out * r->N;
         const bool pt = OP == GR_ADDP || OP == GR_MULP;
-        hipLaunchKernelGGL(k_gr_ew<OP>, dim3(r->N / GR_T, nl_out, (unsigned)n * 2), dim3(GR_T), 0, r->stream, a + oi, b ? (pt ? b + (size_t)c0 * pt_stride : b + oi) : nullptr,
+        hipLaunchKernelGGL(k_gr_ew<OP>, dim3(r->N / GR_T, nl_out, (unsigned)n * 2), dim3(GR_T), 0, r->stream, a + oi, b ? (pt ? b + c0 * pt_stride : b + oi) : nullptr,
                            out + oo, sc, pt_stride, r->modc, nl_in, nl_out, r->N);
-    }
+        return 0;
+    });
     GR_HIP(r, hipGetLastError());
     return 0;
 }
@@ -408,13 +400,7 @@ extern "C" void sfg_ring_destroy(sfg_ring *r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
     if (r->stream) (void)hipStreamSynchronize(r->stream);
-    for (auto &kv : r->rotkeys) { (void)hipFree(kv.second.key); (void)hipFree(kv.second.idx); }
-    (void)hipFree(r->rlk.key);
-    for (auto &kv : r->levels) { (void)hipFree(kv.second.up.buf); (void)hipFree(kv.second.rescale_tab); }
-    (void)hipFree(r->down.buf); (void)hipFree(r->modc); (void)hipFree(r->tw); (void)hipFree(r->pinv); (void)hipFree(r->ws); (void)hipFree(r->modidx); (void)hipFree(r->small);
-    gr_io_destroy(r);
-    if (r->pin) (void)hipHostFree(r->pin);
-    if (r->stream) (void)hipStreamDestroy(r->stream);
+    volatile uint32_t *k = r->io.enc_key; for (int i = 0; i < 8; i++) k[i] = 0;      // the host copy of the ChaCha20 key; the device's secrets are wiped by their owners
     delete r;
 }
 extern "C" int sfg_ring_create(sfg_ring **out, int device, int logN, int nq, int np, const uint64_t *moduli, const uint64_t *psi) {
@@ -438,13 +424,13 @@ extern "C" int sfg_ring_create(sfg_ring **out, int device, int logN, int nq, int
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); g_ring_create_error = "no HIP device: libsfgwas_hip has no CPU fallback"; return 1; }
     if (device < 0 || device >= ndev) { g_ring_create_error = "bad device index"; return 1; }
     sfg_ring *r = new sfg_ring();
-    r->device = device; r->logN = logN; r->N = N; r->nq = nq; r->np = np; r->nmod = nmod; r->beta = (nq + np - 1) / np; r->plan = plan;
+    r->device = device; r->logN = logN; r->N = N; r->nq = nq; r->np = np; r->nmod = nmod; r->beta = gr_digits(nq - 1, np).beta; r->plan = plan;
     if (const char *e = getenv("SFG_ENABLE_TEST_HOOKS")) r->test_hooks = atoi(e) == 1;
     auto fail = [&](const char *m) { std::string msg = m; sfg_ring_destroy(r); g_ring_create_error = msg; return 1; };
     if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice failed");
-    if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
+    if (hipStreamCreateWithFlags(&r->stream.h, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
     r->pin_bytes = 1u << 20;
-    if (hipHostMalloc((void **)&r->pin, r->pin_bytes, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc failed");
+    if (hipHostMalloc(&r->pin.h, r->pin_bytes, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc failed");
     std::vector<GrMod> mc(nmod); std::vector<u64> tw((size_t)nmod * 4 * N);
     for (int m = 0; m < nmod; m++) {
         const u64 q = moduli[m]; r->q[m] = q; r->psi[m] = ps[m];
@@ -460,8 +446,7 @@ extern "C" int sfg_ring_create(sfg_ring **out, int device, int logN, int nq, int
     }
     std::vector<u64> pinv((size_t)2 * nq);
     for (int t = 0; t < nq; t++) { const u64 q = r->q[t]; u64 P = 1; for (int p = 0; p < np; p++) P = hm_mul(P, r->q[nq + p] % q, q); P = hm_inv(P, q); pinv[2 * t] = P; pinv[2 * t + 1] = hm_shoup(P, q); }
-    if (hipMalloc((void **)&r->modc, mc.size() * sizeof(GrMod)) != hipSuccess || hipMalloc((void **)&r->tw, tw.size() * 8) != hipSuccess ||
-        hipMalloc((void **)&r->pinv, pinv.size() * 8) != hipSuccess) return fail("hipMalloc of tables failed");
+    if (r->modc.alloc(mc.size() * sizeof(GrMod)) != hipSuccess || r->tw.alloc(tw.size() * 8) != hipSuccess || r->pinv.alloc(pinv.size() * 8) != hipSuccess) return fail("hipMalloc of tables failed");
     if (hipMemcpy(r->modc, mc.data(), mc.size() * sizeof(GrMod), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(r->tw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(r->pinv, pinv.data(), pinv.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return fail("table upload failed");
     std::vector<int> src(np), tgt(nq);
@@ -488,9 +473,7 @@ static int gr_rows(sfg_ring *r, const char *what, uint64_t *rows, int nrows, con
     if (nrows == 0) return 0;
     if (!rows || !mod_idx) GR_FAIL(r, "%s: null argument", what);
     for (int i = 0; i < nrows; i++) if (mod_idx[i] < 0 || mod_idx[i] >= r->nmod) GR_FAIL(r, "%s: modulus index %d of row %d out of range 0..%d", what, mod_idx[i], i, r->nmod - 1);
-    size_t cap = r->modidx_cap * sizeof(int);
-    GR_TRY(gr_reserve(r, (void **)&r->modidx, &cap, (size_t)nrows * sizeof(int)));
-    r->modidx_cap = cap / sizeof(int);
+    GR_TRY(gr_reserve(r, r->modidx, (size_t)nrows * sizeof(int)));
     GR_TRY(gr_upload(r, r->modidx, mod_idx, (size_t)nrows * sizeof(int)));
     GrRowMap map = gr_map(1, 1, 0, 0); map.table = r->modidx;
     return gr_transform(r, (u64 *)rows, (size_t)nrows, map, inv);
@@ -499,14 +482,16 @@ extern "C" int sfg_ring_ntt_rows(sfg_ring *r, uint64_t *rows, int nrows, const i
 extern "C" int sfg_ring_intt_rows(sfg_ring *r, uint64_t *rows, int nrows, const int *mod_idx) { return gr_rows(r, "sfg_ring_intt_rows", rows, nrows, mod_idx, true); }
 
 int gr_rows_from_mont(sfg_ring *r, u64 *rows, size_t nrows) {
-    for (size_t r0 = 0; r0 < nrows; r0 += 32768 / r->nmod * r->nmod)       // whole groups of nmod rows per launch: blockIdx.y % nmod stays the row's modulus
-        hipLaunchKernelGGL(k_gr_from_mont, dim3(r->N / GR_T, (unsigned)std::min<size_t>(32768 / r->nmod * r->nmod, nrows - r0)), dim3(GR_T), 0, r->stream, rows + r0 * r->N, r->modc, r->nmod, r->N);
+    gr_split(nrows, gr_from_mont_cap(r->nmod), [&](size_t r0, size_t n) {
+        hipLaunchKernelGGL(k_gr_from_mont, dim3(r->N / GR_T, (unsigned)n), dim3(GR_T), 0, r->stream, rows + r0 * r->N, r->modc, r->nmod, r->N);
+        return 0;
+    });
     GR_HIP(r, hipGetLastError());
     return 0;
 }
 static int gr_load_key(sfg_ring *r, GrKey &k, const uint64_t *key_host, int mont) {
     const size_t words = (size_t)r->beta * 2 * r->nmod * r->N;
-    if (!k.key) GR_HIP(r, hipMalloc((void **)&k.key, words * 8));
+    if (!k.key) GR_HIP(r, k.key.alloc(words * 8));
     GR_HIP(r, hipMemcpyAsync(k.key, key_host, words * 8, hipMemcpyHostToDevice, r->stream));
     if (mont) hipLaunchKernelGGL(k_gr_from_mont, dim3(r->N / GR_T, (unsigned)(r->beta * 2 * r->nmod)), dim3(GR_T), 0, r->stream, k.key, r->modc, r->nmod, r->N);
     GR_HIP(r, hipStreamSynchronize(r->stream));
@@ -517,13 +502,14 @@ extern "C" int sfg_ring_load_rotkey(sfg_ring *r, uint64_t g, const uint64_t *key
     const int N = r->N;
     if (!key_host) GR_FAIL(r, "sfg_ring_load_rotkey: null key");
     if (!(g & 1) || g >= 2ULL * N) GR_FAIL(r, "sfg_ring_load_rotkey: galois element %llu is not an odd number below 2N", (unsigned long long)g);
-    GrKey k; auto it = r->rotkeys.find(g); if (it != r->rotkeys.end()) k = it->second;
+    GrKey fresh; const auto it = r->rotkeys.find(g);                        // a new element's key enters the map only when it is complete
+    GrKey &k = it != r->rotkeys.end() ? it->second : fresh;
     GR_TRY(gr_load_key(r, k, key_host, mont));
-    if (!k.idx) GR_HIP(r, hipMalloc((void **)&k.idx, (size_t)N * 4));
+    if (!k.idx) GR_HIP(r, k.idx.alloc((size_t)N * 4));
     std::vector<uint32_t> idx(N); const u64 mask = 2ULL * N - 1;             // lattigo ring.PermuteNTTIndex: out[i] = in[index[i]]
     for (int i = 0; i < N; i++) { u64 t1 = 2ULL * hm_brev((uint32_t)i, r->logN) + 1, t2 = ((g * t1 & mask) - 1) >> 1; idx[i] = hm_brev((uint32_t)t2, r->logN); }
     GR_HIP(r, hipMemcpy(k.idx, idx.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-    r->rotkeys[g] = k;
+    if (it == r->rotkeys.end()) r->rotkeys.emplace(g, std::move(fresh));
     return 0;
 }
 extern "C" int sfg_ring_has_rotkey(const sfg_ring *r, uint64_t g) { return r->rotkeys.count(g) ? 1 : 0; }
@@ -605,17 +591,11 @@ extern "C" int sfg_ring_ct_mulrelin_dev(sfg_ring *r, const uint64_t *a, const ui
     const int nl = level + 1, N = r->N; const size_t ctw = (size_t)2 * nl * N, bytes = (size_t)nct * ctw * 8;
     if (gr_overlap(a, bytes, out, bytes) || gr_overlap(b, bytes, out, bytes)) GR_FAIL(r, "sfg_ring_ct_mulrelin_dev: out may alias neither input");
     if (!r->rlk.key) GR_FAIL(r, "sfg_ring_ct_mulrelin_dev: no relinearisation key loaded");
-    const size_t J = gr_ks_chunk_jobs(r, level, nct);
-    std::vector<GrJob> jobs(J);
-    for (size_t j0 = 0; j0 < (size_t)nct; j0 += J) {
-        const size_t n = std::min(J, (size_t)nct - j0); GrKsWs w;
-        GR_TRY(gr_ks_workspace(r, level, J, w));
-        for (size_t j = 0; j < n; j++) jobs[j] = GrJob{r->rlk.key, nullptr, (long long)(j0 + j)};
-        GR_TRY(gr_upload(r, w.jobs, jobs.data(), n * sizeof(GrJob)));
+    std::vector<GrJob> jobs(nct);
+    for (int j = 0; j < nct; j++) jobs[j] = GrJob{r->rlk.key, nullptr, j};
+    return gr_ks_batch(r, level, jobs, (const u64 *)out, 3, (u64 *)out, [&](size_t j0, size_t n, const GrKsWs &w) {
         hipLaunchKernelGGL(k_gr_tensor, dim3(N / GR_T, nl, (unsigned)n), dim3(GR_T), 0, r->stream, (const u64 *)a + j0 * ctw, (const u64 *)b + j0 * ctw, (u64 *)out + j0 * ctw, w.c2, r->modc, nl, N);
-        GR_TRY(gr_keyswitch(r, level, n, w, (const u64 *)out, 3, (u64 *)out));
-    }
-    return 0;
+    });
 }
 extern "C" int sfg_ring_ct_rescale_dev(sfg_ring *r, const uint64_t *in, uint64_t *out, int nct, int level) {
     GR_EW_ENTRY("sfg_ring_ct_rescale_dev", !in || !out)
@@ -623,11 +603,12 @@ extern "C" int sfg_ring_ct_rescale_dev(sfg_ring *r, const uint64_t *in, uint64_t
     const int nl = level + 1, N = r->N;
     if (gr_overlap(in, (size_t)nct * 2 * nl * N * 8, out, (size_t)nct * 2 * level * N * 8)) GR_FAIL(r, "sfg_ring_ct_rescale_dev: in and out may not alias");
     GrLevel *L; GR_TRY(gr_level(r, level, &L));
-    const size_t per = (size_t)2 * (level + 1) * N * 8, J = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(nct, 16384), r->ws_budget / per));
-    GR_TRY(gr_reserve(r, &r->ws, &r->ws_bytes, J * per));
-    u64 *T = (u64 *)r->ws, *tmp = T + J * 2 * N;
-    for (size_t j0 = 0; j0 < (size_t)nct; j0 += J) {
-        const size_t n = std::min(J, (size_t)nct - j0); const u64 *src = (const u64 *)in + j0 * 2 * nl * N; const unsigned gx = N / GR_T;
+    const GrChunks plan = gr_rescale_plan((size_t)nct, level, (size_t)N, r->ws_budget);
+    GR_TRY(gr_reserve(r, r->ws, plan.bytes));
+    const GrRescaleLayout lay = gr_rescale_layout(level, (size_t)N, plan.chunk);
+    u64 *T = (u64 *)r->ws.p + lay.T, *tmp = (u64 *)r->ws.p + lay.tmp;
+    for (size_t c = 0; c < plan.nchunks; c++) {
+        const size_t j0 = plan.first(c), n = plan.count(c, (size_t)nct); const u64 *src = (const u64 *)in + j0 * 2 * nl * N; const unsigned gx = N / GR_T;
         hipLaunchKernelGGL(k_gr_copy_last, dim3(gx, 1, (unsigned)n * 2), dim3(GR_T), 0, r->stream, src, T, nl, N);
         GR_TRY(gr_transform(r, T, n * 2, gr_map(1, 1, level, 0), true));
         hipLaunchKernelGGL(k_gr_rescale_prep, dim3(gx, level, (unsigned)n * 2), dim3(GR_T), 0, r->stream, T, tmp, L->rescale_tab, r->modc, level, N);
@@ -645,8 +626,8 @@ extern "C" int sfg_ring_ct_innersum_dev(sfg_ring *r, const uint64_t *in, int nct
     const int nl = level + 1, N = r->N; const size_t ctw = (size_t)2 * nl * N;
     if (gr_overlap(in, (size_t)nct * ctw * 8, out, ctw * 8)) GR_FAIL(r, "sfg_ring_ct_innersum_dev: in and out may not alias");
     for (int rot = 1; rot < N / 2; rot *= 2) if (!r->rotkeys.count(gr_galois(r, rot))) GR_FAIL(r, "sfg_ring_ct_innersum_dev: no key loaded for the left rotation by %d", rot);
-    GR_TRY(gr_reserve(r, &r->small, &r->small_bytes, ctw * 8));
-    u64 *rt = (u64 *)r->small;
+    GR_TRY(gr_reserve(r, r->small, ctw * 8));
+    u64 *rt = r->small;
     GR_HIP(r, hipMemcpyAsync(out, in, ctw * 8, hipMemcpyDeviceToDevice, r->stream));
     for (int i = 1; i < nct; i++) GR_TRY(gr_ew<GR_ADD>(r, (const u64 *)in + i * ctw, (const u64 *)out, (u64 *)out, GrScalars(), 0, 1, nl, nl));
     for (int rot = 1; rot < N / 2; rot *= 2) {

@@ -1,10 +1,12 @@
 // gring_dev.hpp - what the general ring's translation units share (gring.hip: the ring, its transform, its evaluator; gring_io.hip: keys, sampler, encryption,
-// collective decryption): the device-side tables, struct sfg_ring, the error macros and the host helpers gring.hip defines.  Included by .hip files only.
+// collective decryption): the device-side tables, the owners of what a ring holds, struct sfg_ring, the error macros, the host modular helpers and the host
+// functions gring.hip defines.  Included by .hip files only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <map>
 #include <string>
+#include <utility>
 #include "../../include/sfgwas_hip.h"
 #include "gring_arith.hpp"
 #include "gring_plan.hpp"
@@ -31,38 +33,65 @@ struct GrExt {
     const u64 *tgt_tab;       // [ndig][tgt_cap][1 + alpha]   D mod qt, then (D / q_m) mod qt
 };
 struct GrJob { const u64 *key; const uint32_t *idx; long long ct; };     // one key switch of a batch: its key, its automorphism index (or null), its ciphertext
+static_assert(sizeof(GrJob) == kGrJobBytes, "gring_plan.hpp sizes the key switch's job list");
 struct GrScalars { u64 s[gr::kMaxMod]; };
 
 constexpr int GR_T = 256;
 
+// ---------------------------------------------------------------- owners (move-only; the ring's device must be current when one lets go)
+// one device allocation; a wiping one is zeroed, and the device synchronised, before it is freed
+struct GrMem {
+    void *p = nullptr; size_t bytes = 0; bool wipe = false;
+    GrMem() {}
+    GrMem(GrMem &&o) : p(o.p), bytes(o.bytes), wipe(o.wipe) { o.p = nullptr; o.bytes = 0; }
+    GrMem &operator=(GrMem &&o) { if (this != &o) { reset(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
+    GrMem(const GrMem &) = delete; GrMem &operator=(const GrMem &) = delete;
+    ~GrMem() { reset(); }
+    void reset() {
+        if (!p) return;
+        if (wipe) { (void)hipMemset(p, 0, bytes); (void)hipDeviceSynchronize(); }
+        (void)hipFree(p); p = nullptr; bytes = 0;
+    }
+    hipError_t alloc(size_t n) { reset(); const hipError_t e = hipMalloc(&p, n); if (e == hipSuccess) bytes = n; else p = nullptr; return e; }
+};
+template <class T> struct GrBuf : GrMem { operator T *() const { return (T *)p; } };
+template <class T> struct GrSecret : GrBuf<T> { GrSecret() { this->wipe = true; } };
+template <class T, hipError_t (*Free)(T)> struct GrHandle {             // the stream, the pinned staging buffer
+    T h = T();
+    GrHandle() {}
+    GrHandle(const GrHandle &) = delete; GrHandle &operator=(const GrHandle &) = delete;
+    ~GrHandle() { if (h) (void)Free(h); }
+    operator T() const { return h; }
+};
+
 // ---------------------------------------------------------------- host side
-struct GrKey { u64 *key = nullptr; uint32_t *idx = nullptr; };
-struct GrExtOwner { GrExt e{}; void *buf = nullptr; };
-struct GrLevel { GrExtOwner up; u64 *rescale_tab = nullptr; };
+struct GrKey { GrBuf<u64> key; GrBuf<uint32_t> idx; };
+struct GrExtOwner { GrExt e{}; GrBuf<void> buf; };
+struct GrLevel { GrExtOwner up; GrBuf<u64> rescale_tab; };
 // keys and sampler of gring_io.hip: the public key [2][nmod][N], the secret key [nq][N] (both NTT domain, canonical), the ChaCha20 key and the encryption index
 struct GrIo {
-    u64 *pk = nullptr, *sk = nullptr;
-    uint32_t enc_key[8] = {}; uint32_t *enc_key_dev = nullptr; bool enc_seeded = false;
+    GrBuf<u64> pk; GrSecret<u64> sk;
+    uint32_t enc_key[8] = {}; GrSecret<uint32_t> enc_key_dev; bool enc_seeded = false;
     unsigned long long enc_next = 0;                   // ONE atomic counter per ring
-    void *ws = nullptr; size_t ws_bytes = 0;           // grow-only workspace of the encryption core and of the decoder
-    std::map<int, void *> dec_tabs;                    // the decoder's tables of a level (mixed-radix constants, the digits of floor(Q / 2)), built at its first use
-    void *dd_tab = nullptr;                            // the double-double transform's tables (twiddles, twist, slot permutation), built at first use
-    void *pt = nullptr; size_t pt_bytes = 0;           // grow-only plaintext rows between the encoder and the encryption core, and between decryption and the decoder
+    GrSecret<void> ws;                                 // grow-only workspace of the encryption core, the encoder and the decoders: lifted samples
+    std::map<int, GrBuf<u64>> dec_tabs;                // the decoder's tables of a level (mixed-radix constants, the digits of floor(Q / 2)), built at its first use
+    GrBuf<void> dd_tab;                                // the double-double transform's tables (twiddles, twist, slot permutation), built at first use
+    GrSecret<u64> pt;                                  // grow-only plaintext rows between the encoder and the encryption core, and between decryption and the decoder
     size_t ws_budget = 512ull << 20;
 };
 struct sfg_ring {
     int device = 0, logN = 0, N = 0, nq = 0, np = 0, nmod = 0, beta = 0;
     u64 q[gr::kMaxMod] = {}, psi[gr::kMaxMod] = {};
     GrNttPlan plan;
-    hipStream_t stream = nullptr;
-    GrMod *modc = nullptr; u64 *tw = nullptr; u64 *pinv = nullptr;
+    GrHandle<hipStream_t, hipStreamDestroy> stream;    // declared before every allocation: destroyed after them
+    GrHandle<void *, hipHostFree> pin; size_t pin_bytes = 0, pin_head = 0;  // pinned staging of small uploads
+    GrBuf<GrMod> modc; GrBuf<u64> tw, pinv;
     GrExtOwner down;                                   // ModDown: P -> Q
     std::map<int, GrLevel> levels;
     std::map<u64, GrKey> rotkeys; GrKey rlk;
-    void *ws = nullptr; size_t ws_bytes = 0;           // grow-only workspace of the key switch and the rescale
-    int *modidx = nullptr; size_t modidx_cap = 0;      // sfg_ring_ntt_rows' modulus table
-    unsigned char *pin = nullptr; size_t pin_bytes = 0, pin_head = 0;       // pinned staging of small uploads
-    void *small = nullptr; size_t small_bytes = 0;     // the inner sum's rotated ciphertext
+    GrBuf<void> ws;                                    // grow-only workspace of the key switch and the rescale
+    GrBuf<int> modidx;                                 // sfg_ring_ntt_rows' modulus table
+    GrBuf<u64> small;                                  // the inner sum's rotated ciphertext
     size_t ws_budget = 768ull << 20;
     bool test_hooks = false;                           // SFG_ENABLE_TEST_HOOKS=1 when the ring was made: the *_for_test entry points may be called
     GrIo io;
@@ -73,13 +102,19 @@ struct sfg_ring {
     snprintf(_b, sizeof _b, "HIP call failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); (r)->err = _b; return 1; } } while (0)
 #define GR_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 
+// host modular helpers of both translation units
+static inline u64 hm_mul(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
+static inline u64 hm_pow(u64 a, u64 e, u64 q) { u64 r = 1 % q; a %= q; while (e) { if (e & 1) r = hm_mul(r, a, q); a = hm_mul(a, a, q); e >>= 1; } return r; }
+static inline u64 hm_inv(u64 a, u64 q) { return hm_pow(a, q - 2, q); }
+static inline u64 hm_shoup(u64 w, u64 q) { return (u64)(((u128)w << 64) / q); }
+static inline uint32_t hm_brev(uint32_t x, int bits) { uint32_t r = 0; for (int i = 0; i < bits; i++) { r = (r << 1) | (x & 1); x >>= 1; } return r; }
+
 // gring.hip
 int gr_upload(sfg_ring *r, void *dst, const void *src, size_t bytes);
-int gr_reserve(sfg_ring *r, void **buf, size_t *have, size_t bytes);
+int gr_reserve(sfg_ring *r, GrMem &buf, size_t bytes);             // grow-only: a buffer too small is let go (a wiping one wiped) and allocated anew
+int gr_table(sfg_ring *r, GrMem &dst, const void *host, size_t bytes);   // a table allocated and filled; the caller moves it into the ring when it is complete
 int gr_transform(sfg_ring *r, u64 *rows, size_t nrows, GrRowMap map, bool inv);
 GrRowMap gr_map(int period, int split, int base0, int base1);
 int gr_extend(sfg_ring *r, const GrExt &e, const u64 *src, u64 *Y, uint32_t *V, u64 *out, int ntgt, size_t npoly);
 int gr_check_level(sfg_ring *r, const char *what, int nct, int level);
 int gr_rows_from_mont(sfg_ring *r, u64 *rows, size_t nrows);      // lattigo ring.InvMForm on key rows [.][nmod][N], enqueued on the ring's stream
-// gring_io.hip: wipes and frees the keys and the sampler (sfg_ring_destroy)
-void gr_io_destroy(sfg_ring *r);

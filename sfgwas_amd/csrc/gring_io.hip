@@ -142,41 +142,20 @@ __global__ __launch_bounds__(GR_T) void k_gri_add_c0(const u64 *ct, const u64 *h
 }
 
 // ---------------------------------------------------------------- host side
-static void gri_wipe(volatile void *p, size_t n) { volatile unsigned char *b = (volatile unsigned char *)p; for (size_t i = 0; i < n; i++) b[i] = 0; }
-void gr_io_destroy(sfg_ring *r) {
-    GrIo &io = r->io;
-    gri_wipe(io.enc_key, sizeof io.enc_key);
-    if (io.enc_key_dev) (void)hipMemset(io.enc_key_dev, 0, 32);
-    if (io.sk) (void)hipMemset(io.sk, 0, (size_t)r->nq * r->N * 8);
-    if (io.ws) (void)hipMemset(io.ws, 0, io.ws_bytes);                            // the lifted samples u, e0, e1 of the last call
-    if (io.enc_key_dev || io.sk || io.ws) (void)hipDeviceSynchronize();
-    (void)hipFree(io.enc_key_dev); (void)hipFree(io.sk); (void)hipFree(io.pk); (void)hipFree(io.ws);
-    for (auto &kv : io.dec_tabs) (void)hipFree(kv.second);
-    if (io.pt) { (void)hipMemset(io.pt, 0, io.pt_bytes); (void)hipDeviceSynchronize(); }      // plaintexts
-    (void)hipFree(io.pt); (void)hipFree(io.dd_tab);
-    io = GrIo();
-}
-
 // the workspace of a call, reserved before the call spends an encryption index: a failed allocation leaves the counter where it was
-static int gri_reserve(sfg_ring *r, int npoly, int nct, int level, bool with_u) {
-    const GriPlan plan = gri_plan(nct, level + 1, r->np, npoly, with_u, (size_t)r->N, r->io.ws_budget);
-    return gr_reserve(r, &r->io.ws, &r->io.ws_bytes, plan.bytes + 64);
+static int gri_reserve(sfg_ring *r, int npoly, int nct, int level, bool with_u, GriPlan &plan) {
+    plan = gri_plan(nct, level + 1, r->np, npoly, with_u, (size_t)r->N, r->io.ws_budget);
+    return gr_reserve(r, r->io.ws, plan.reserve());
 }
-// the core for nct ciphertexts, in the chunks of gri_plan.  pk null: u drops out.  mode GRI_OUT (aux = plaintext rows or null), GRI_ADD, GRI_SHARE (aux = ciphertexts)
-static int gri_core(sfg_ring *r, const GriSrc &src0, const u64 *pk, int npoly, int nct, int level, int mode, const u64 *aux, u64 *out0, u64 *out1, bool reserved = false) {
-    const int nl = level + 1, np = r->np, N = r->N; const size_t Nw = (size_t)N;
+// the core for nct ciphertexts, in the chunks of the plan gri_reserve made.  pk null: u drops out.  mode GRI_OUT (aux = plaintext rows or null), GRI_ADD, GRI_SHARE (aux = ciphertexts)
+static int gri_core(sfg_ring *r, const GriPlan &plan, const GriSrc &src0, const u64 *pk, int npoly, int nct, int level, int mode, const u64 *aux, u64 *out0, u64 *out1) {
+    const int nl = level + 1, np = r->np, N = r->N;
     const bool with_u = pk != nullptr;
-    const GriPlan plan = gri_plan(nct, nl, np, npoly, with_u, Nw, r->io.ws_budget);
-    if (!reserved) GR_TRY(gri_reserve(r, npoly, nct, level, with_u));          // (the sampled forms reserve before they take their indices)
-    const size_t J = plan.chunk;
-    u64 *p = (u64 *)r->io.ws;
-    u64 *UQ = nullptr, *UP = nullptr;
-    if (with_u) { UQ = p; p += J * nl * Nw; UP = p; p += J * np * Nw; }
-    u64 *TQ = p; p += J * npoly * nl * Nw;
-    u64 *TP = p; p += J * npoly * np * Nw;
-    u64 *Y2 = p; p += J * npoly * np * Nw;
-    u64 *ext = p; p += J * npoly * nl * Nw;
-    uint32_t *V2 = (uint32_t *)p;
+    const GriCoreLayout lay = gri_core_layout(nl, np, npoly, with_u, (size_t)N, (size_t)plan.chunk);
+    u64 *ws = (u64 *)r->io.ws.p;
+    u64 *UQ = with_u ? ws + lay.UQ : nullptr, *UP = with_u ? ws + lay.UP : nullptr;
+    u64 *TQ = ws + lay.TQ, *TP = ws + lay.TP, *Y2 = ws + lay.Y2, *ext = ws + lay.ext;
+    uint32_t *V2 = (uint32_t *)(ws + lay.V2);
     const unsigned gx = N / GR_T, gs = N / 8 / GR_T;
     for (int c = 0; c < plan.nchunks; c++) {
         const int c0 = plan.first(c), nb = plan.count(c, nct); const size_t n = nb, z = n * npoly;
@@ -202,7 +181,7 @@ static int gri_core(sfg_ring *r, const GriSrc &src0, const u64 *pk, int npoly, i
         else if (mode == GRI_ADD) hipLaunchKernelGGL(k_gri_finish<GRI_ADD>, gf, dim3(GR_T), 0, r->stream, (const u64 *)TQ, (const u64 *)ext, (const u64 *)r->pinv, (const u64 *)nullptr,
                                                      (const u64 *)nullptr, out0 + (size_t)c0 * 2 * nl * N, (u64 *)nullptr, r->modc, npoly, nl, N);
         else hipLaunchKernelGGL(k_gri_finish<GRI_SHARE>, gf, dim3(GR_T), 0, r->stream, (const u64 *)TQ, (const u64 *)ext, (const u64 *)r->pinv, aux + (size_t)c0 * 2 * nl * N,
-                                (const u64 *)r->io.sk, out0 + (size_t)c0 * nl * N, out1 ? out1 + (size_t)c0 * nl * N : nullptr, r->modc, npoly, nl, N);
+                                r->io.sk, out0 + (size_t)c0 * nl * N, out1 ? out1 + (size_t)c0 * nl * N : nullptr, r->modc, npoly, nl, N);
         GR_HIP(r, hipGetLastError());
     }
     return 0;
@@ -231,7 +210,7 @@ extern "C" int sfg_ring_load_public_key(sfg_ring *r, const uint64_t *pk_host, in
     if (!pk_host) GR_FAIL(r, "sfg_ring_load_public_key: null key");
     const size_t rows = (size_t)2 * r->nmod, words = rows * r->N;
     GR_HIP(r, hipStreamSynchronize(r->stream));                                // launches that still read the previous key
-    if (!r->io.pk) GR_HIP(r, hipMalloc((void **)&r->io.pk, words * 8));
+    if (!r->io.pk) GR_HIP(r, r->io.pk.alloc(words * 8));
     GR_HIP(r, hipMemcpyAsync(r->io.pk, pk_host, words * 8, hipMemcpyHostToDevice, r->stream));
     if (mont) GR_TRY(gr_rows_from_mont(r, r->io.pk, rows));
     GR_HIP(r, hipStreamSynchronize(r->stream));
@@ -243,7 +222,7 @@ extern "C" int sfg_ring_load_secret_key(sfg_ring *r, const uint64_t *sk_host, in
     if (!sk_host) GR_FAIL(r, "sfg_ring_load_secret_key: null key");
     const size_t rows = (size_t)r->nq, words = rows * r->N;
     GR_HIP(r, hipStreamSynchronize(r->stream));
-    if (!r->io.sk) GR_HIP(r, hipMalloc((void **)&r->io.sk, words * 8));
+    if (!r->io.sk) GR_HIP(r, r->io.sk.alloc(words * 8));
     GR_HIP(r, hipMemcpyAsync(r->io.sk, sk_host, words * 8, hipMemcpyHostToDevice, r->stream));
     if (mont) GR_TRY(gr_rows_from_mont(r, r->io.sk, rows));                    // rows 0..nq-1 of one group of nmod: row m is modulus m
     GR_HIP(r, hipStreamSynchronize(r->stream));
@@ -254,7 +233,7 @@ extern "C" int sfg_ring_seed_encryptor(sfg_ring *r, const uint8_t *key32) {
     if (!key32) GR_FAIL(r, "sfg_ring_seed_encryptor: null key");
     GrIo &io = r->io;
     GR_HIP(r, hipStreamSynchronize(r->stream));                                // launches that still read the previous key
-    if (!io.enc_key_dev) GR_HIP(r, hipMalloc((void **)&io.enc_key_dev, 32));
+    if (!io.enc_key_dev) GR_HIP(r, io.enc_key_dev.alloc(32));
     for (int i = 0; i < 8; i++) io.enc_key[i] = (uint32_t)key32[4 * i] | (uint32_t)key32[4 * i + 1] << 8 | (uint32_t)key32[4 * i + 2] << 16 | (uint32_t)key32[4 * i + 3] << 24;
     GR_HIP(r, hipMemcpy(io.enc_key_dev, io.enc_key, 32, hipMemcpyHostToDevice));
     __atomic_store_n(&io.enc_next, 0ULL, __ATOMIC_RELEASE);
@@ -273,16 +252,17 @@ extern "C" int sfg_ring_encrypt_explicit_dev(sfg_ring *r, const uint64_t *pt, in
     if (!r->io.pk) GR_FAIL(r, "sfg_ring_encrypt_explicit_dev: no public key loaded (sfg_ring_load_public_key)");
     if (!u || !e0 || !e1 || !out) GR_FAIL(r, "sfg_ring_encrypt_explicit_dev: null polynomial or output");
     GriSrc src{u, e0, e1, nullptr, 0};
-    return gri_core(r, src, r->io.pk, 2, nct, level, GRI_OUT, (const u64 *)pt, (u64 *)out, nullptr);
+    GriPlan plan; GR_TRY(gri_reserve(r, 2, nct, level, true, plan));
+    return gri_core(r, plan, src, r->io.pk, 2, nct, level, GRI_OUT, (const u64 *)pt, (u64 *)out, nullptr);
 }
 extern "C" int sfg_ring_ct_add_fresh_zero_dev(sfg_ring *r, uint64_t *ct, int nct, int level) {
     GRI_ENTRY("sfg_ring_ct_add_fresh_zero_dev")
     if (!r->io.pk) GR_FAIL(r, "sfg_ring_ct_add_fresh_zero_dev: no public key loaded (sfg_ring_load_public_key)");
     if (!ct) GR_FAIL(r, "sfg_ring_ct_add_fresh_zero_dev: null ciphertexts");
-    GR_TRY(gri_reserve(r, 2, nct, level, true));
+    GriPlan plan; GR_TRY(gri_reserve(r, 2, nct, level, true, plan));          // before an index is taken: a failed allocation leaves the counter where it was
     u64 first; GR_TRY(gri_take_indices(r, "sfg_ring_ct_add_fresh_zero_dev", nct, &first));
     GriSrc src{nullptr, nullptr, nullptr, r->io.enc_key_dev, first};
-    return gri_core(r, src, r->io.pk, 2, nct, level, GRI_ADD, nullptr, (u64 *)ct, nullptr, true);
+    return gri_core(r, plan, src, r->io.pk, 2, nct, level, GRI_ADD, nullptr, (u64 *)ct, nullptr);
 }
 extern "C" int sfg_ring_encrypt_transcript_for_test(sfg_ring *r, uint64_t first_index, int nct, int8_t *u, int32_t *e0, int32_t *e1) {
     if (!r->test_hooks) GR_FAIL(r, "sfg_ring_encrypt_transcript_for_test: test hook, enabled only in a process that set the test switch before creating the ring");
@@ -292,11 +272,11 @@ extern "C" int sfg_ring_encrypt_transcript_for_test(sfg_ring *r, uint64_t first_
     if (nct == 0) return 0;
     if (!u || !e0 || !e1) GR_FAIL(r, "sfg_ring_encrypt_transcript_for_test: null output");
     if (first_index > ~0ULL - (u64)nct) GR_FAIL(r, "sfg_ring_encrypt_transcript_for_test: indices beyond 2^64");
-    for (int c0 = 0; c0 < nct; c0 += 32768) {
-        const int nb = std::min(32768, nct - c0);
+    gr_split((size_t)nct, kGrLaunchCap, [&](size_t c0, size_t nb) {
         hipLaunchKernelGGL(k_gri_transcript, dim3(r->N / 8 / GR_T, 1, (unsigned)nb), dim3(GR_T), 0, r->stream, (const unsigned *)r->io.enc_key_dev, (u64)first_index + c0,
-                           u + (size_t)c0 * r->N, e0 + (size_t)c0 * r->N, e1 + (size_t)c0 * r->N, r->N);
-    }
+                           u + c0 * r->N, e0 + c0 * r->N, e1 + c0 * r->N, r->N);
+        return 0;
+    });
     GR_HIP(r, hipGetLastError());
     return 0;
 }
@@ -307,17 +287,18 @@ extern "C" int sfg_ring_pcks_gen_share_dev(sfg_ring *r, const uint64_t *ct, int 
     if (!r->io.sk) GR_FAIL(r, "sfg_ring_pcks_gen_share_dev: no secret-key shard loaded (sfg_ring_load_secret_key)");
     if (!ct || !e0 || !h0 || (h1 && !e1)) GR_FAIL(r, "sfg_ring_pcks_gen_share_dev: null ciphertexts, errors or output");
     GriSrc src{nullptr, e0, h1 ? e1 : nullptr, nullptr, 0};
-    return gri_core(r, src, nullptr, h1 ? 2 : 1, nct, level, GRI_SHARE, (const u64 *)ct, (u64 *)h0, (u64 *)h1);
+    GriPlan plan; GR_TRY(gri_reserve(r, h1 ? 2 : 1, nct, level, false, plan));
+    return gri_core(r, plan, src, nullptr, h1 ? 2 : 1, nct, level, GRI_SHARE, (const u64 *)ct, (u64 *)h0, (u64 *)h1);
 }
 extern "C" int sfg_ring_pcks_finish_dev(sfg_ring *r, const uint64_t *ct, int nct, int level, const uint64_t *h0agg, uint64_t *pt) {
     GRI_ENTRY("sfg_ring_pcks_finish_dev")
     if (!ct || !h0agg || !pt) GR_FAIL(r, "sfg_ring_pcks_finish_dev: null ciphertexts, shares or output");
     const int nl = level + 1, N = r->N;
-    for (int c0 = 0; c0 < nct; c0 += 32768) {
-        const int nb = std::min(32768, nct - c0);
-        hipLaunchKernelGGL(k_gri_add_c0, dim3(N / GR_T, nl, (unsigned)nb), dim3(GR_T), 0, r->stream, (const u64 *)ct + (size_t)c0 * 2 * nl * N, (const u64 *)h0agg + (size_t)c0 * nl * N,
-                           (u64 *)pt + (size_t)c0 * nl * N, r->modc, nl, N);
-    }
+    gr_split((size_t)nct, kGrLaunchCap, [&](size_t c0, size_t nb) {
+        hipLaunchKernelGGL(k_gri_add_c0, dim3(N / GR_T, nl, (unsigned)nb), dim3(GR_T), 0, r->stream, (const u64 *)ct + c0 * 2 * nl * N, (const u64 *)h0agg + c0 * nl * N,
+                           (u64 *)pt + c0 * nl * N, r->modc, nl, N);
+        return 0;
+    });
     GR_HIP(r, hipGetLastError());
     return 0;
 }
@@ -342,8 +323,6 @@ __global__ __launch_bounds__(GR_T) void k_gri_decode_fin(u64 *X, double *out, Gr
                                                          [&](int i) { return modc[i].q; }, [&](int i) { return t.half[i]; }, scale);
 }
 
-static u64 gri_mulm(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
-static u64 gri_powm(u64 a, u64 e, u64 q) { u64 r = 1 % q; a %= q; while (e) { if (e & 1) r = gri_mulm(r, a, q); a = gri_mulm(a, a, q); e >>= 1; } return r; }
 static int gri_dec_tab(sfg_ring *r, int level, GriDecTab *out) {
     const int nl = level + 1;
     auto it = r->io.dec_tabs.find(level);
@@ -352,18 +331,16 @@ static int gri_dec_tab(sfg_ring *r, int level, GriDecTab *out) {
         u64 *qmod = h.data(), *winv = qmod + (size_t)nl * nl, *half = winv + 2 * nl;
         for (int i = 0; i < nl; i++) {
             const u64 qi = r->q[i]; u64 W = 1 % qi;
-            for (int j = 0; j < i; j++) { qmod[i * nl + j] = r->q[j] % qi; W = gri_mulm(W, r->q[j] % qi, qi); }
-            winv[2 * i] = gri_powm(W, qi - 2, qi); winv[2 * i + 1] = (u64)(((u128)winv[2 * i] << 64) / qi);
+            for (int j = 0; j < i; j++) { qmod[i * nl + j] = r->q[j] % qi; W = hm_mul(W, r->q[j] % qi, qi); }
+            winv[2 * i] = hm_inv(W, qi); winv[2 * i + 1] = hm_shoup(winv[2 * i], qi);
         }
         // floor(Q / 2) = (Q - 1) / 2 and Q - 1 has the digits q_i - 1: halve from the top, the remainder of digit i + 1 entering digit i as q_i
         u64 rem = 0;
         for (int i = nl - 1; i >= 0; i--) { const u128 cur = (u128)rem * r->q[i] + (r->q[i] - 1); half[i] = (u64)(cur >> 1); rem = (u64)(cur & 1); }
-        void *d = nullptr;
-        GR_HIP(r, hipMalloc(&d, h.size() * 8));
-        GR_HIP(r, hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-        it = r->io.dec_tabs.emplace(level, d).first;
+        GrBuf<u64> d; GR_TRY(gr_table(r, d, h.data(), h.size() * 8));
+        it = r->io.dec_tabs.emplace(level, std::move(d)).first;
     }
-    const u64 *d = (const u64 *)it->second;
+    const u64 *d = it->second;
     out->qmod = d; out->winv = d + (size_t)nl * nl; out->half = out->winv + 2 * nl;
     return 0;
 }
@@ -387,11 +364,12 @@ static int gri_digits(sfg_ring *r, const u64 *src, size_t stride, int nb, int le
 extern "C" int sfg_ring_decode_coeffs(sfg_ring *r, const uint64_t *pt, size_t pt_stride, int nct, int level, double scale, double *coeffs_host) {
     GRI_ENTRY("sfg_ring_decode_coeffs")
     GR_TRY(gri_decode_checks(r, "sfg_ring_decode_coeffs", pt, coeffs_host, pt_stride, level, scale));
-    const int nl = level + 1, N = r->N; const size_t rowsw = (size_t)nl * N;
+    const int nl = level + 1, N = r->N;
     GriDecTab tab; GR_TRY(gri_dec_tab(r, level, &tab));
     const GriPlan plan = gri_decode_plan(nct, nl, (size_t)N, r->io.ws_budget);
-    GR_TRY(gr_reserve(r, &r->io.ws, &r->io.ws_bytes, plan.bytes + 64));
-    u64 *X = (u64 *)r->io.ws; double *out = (double *)(X + (size_t)plan.chunk * rowsw);
+    GR_TRY(gr_reserve(r, r->io.ws, plan.reserve()));
+    const GriDecodeLayout lay = gri_decode_layout(nl, (size_t)N, (size_t)plan.chunk);
+    u64 *X = (u64 *)r->io.ws.p + lay.X; double *out = (double *)r->io.ws.p + lay.out;
     for (int c = 0; c < plan.nchunks; c++) {
         const int c0 = plan.first(c), nb = plan.count(c, nct);
         GR_TRY(gri_digits(r, (const u64 *)pt + (size_t)c0 * pt_stride, pt_stride, nb, level, X, tab));
@@ -528,12 +506,10 @@ static int gri_dd_tab(sfg_ring *r, GriDdTab *out) {
             for (int i = 0; i < logn; i++) rev |= ((m >> i) & 1u) << (logn - 1 - i);
             sm[t] = m; sp[t] = rev; g = g * 5 % (2ULL * N);
         }
-        void *d = nullptr;
-        GR_HIP(r, hipMalloc(&d, h.size()));
-        GR_HIP(r, hipMemcpy(d, h.data(), h.size(), hipMemcpyHostToDevice));
-        r->io.dd_tab = d;
+        GrBuf<void> d; GR_TRY(gr_table(r, d, h.data(), h.size()));
+        r->io.dd_tab = std::move(d);
     }
-    const unsigned char *d = (const unsigned char *)r->io.dd_tab;
+    const unsigned char *d = (const unsigned char *)r->io.dd_tab.p;
     out->W = (const double4 *)d; out->Z = (const double4 *)(d + (size_t)(n / 2) * 32);
     out->slot_m = (const uint32_t *)(d + (size_t)(n / 2) * 32 + (size_t)n * 32); out->slot_pos = out->slot_m + n;
     return 0;
@@ -558,12 +534,12 @@ static int gri_encode(sfg_ring *r, const char *what, const double *values, int n
         band[v] = gio::enc_band(s1 * (scale / n) * (1.0 + 0x1p-40));           // S with its own rounding covered (n + 1 roundings of 2^-53 each)
     }
     GriDdTab tab; GR_TRY(gri_dd_tab(r, &tab));
-    const size_t per = (size_t)n + 4 * (size_t)n + (size_t)nl * N;              // values, A, R in words
-    const GriPlan plan = gri_plan_words(nvec, per + 8, r->io.ws_budget);
-    GR_TRY(gr_reserve(r, &r->io.ws, &r->io.ws_bytes, plan.bytes + 64));
-    const size_t J = plan.chunk;
-    double4 *A = (double4 *)r->io.ws; double *vals = (double *)(A + J * n); u64 *R = (u64 *)(vals + J * n);
-    double *bandd = (double *)(R + J * nl * N); unsigned *flags = (unsigned *)(bandd + J);                  // J * 8 words of tail: J doubles, then two counters
+    const GriPlan plan = gri_encode_plan(nvec, nl, (size_t)N, r->io.ws_budget);
+    GR_TRY(gr_reserve(r, r->io.ws, plan.reserve()));
+    const GriEncodeLayout lay = gri_encode_layout(nl, (size_t)N, (size_t)plan.chunk);
+    u64 *ws = (u64 *)r->io.ws.p;
+    double4 *A = (double4 *)(ws + lay.A); double *vals = (double *)(ws + lay.vals); u64 *R = ws + lay.R;
+    double *bandd = (double *)(ws + lay.band); unsigned *flags = (unsigned *)(ws + lay.flags);
     for (int pass = plan.nchunks > 1 ? 0 : 1; pass < 2; pass++)                  // several chunks: a checking pass over all of them first, then the writing pass
         for (int c = 0; c < plan.nchunks; c++) {
             const int c0 = plan.first(c), nb = plan.count(c, nvec);
@@ -588,13 +564,14 @@ static int gri_encode(sfg_ring *r, const char *what, const double *values, int n
 }
 // plaintext rows (stride words apart) -> slot values; re / im on the device when dev_out, else on the host (the call then synchronises).  im may be null.
 static int gri_decode_vectors(sfg_ring *r, const u64 *src, size_t stride, int nct, int level, double scale, double *re, double *im, bool dev_out) {
-    const int nl = level + 1, N = r->N, n = N / 2; const size_t rowsw = (size_t)nl * N;
+    const int nl = level + 1, N = r->N, n = N / 2;
     GriDecTab dtab; GR_TRY(gri_dec_tab(r, level, &dtab));
     GriDdTab tab; GR_TRY(gri_dd_tab(r, &tab));
-    const GriPlan plan = gri_plan_words(nct, rowsw + 2 * (size_t)N + 4 * (size_t)n + (size_t)N, r->io.ws_budget);      // X, Wd, A, re + im
-    GR_TRY(gr_reserve(r, &r->io.ws, &r->io.ws_bytes, plan.bytes + 64));
-    const size_t J = plan.chunk;
-    double4 *A = (double4 *)r->io.ws; double2 *Wd = (double2 *)(A + J * n); u64 *X = (u64 *)(Wd + J * N); double *ore = (double *)(X + J * rowsw), *oim = ore + J * n;
+    const GriPlan plan = gri_vectors_plan(nct, nl, (size_t)N, r->io.ws_budget);
+    GR_TRY(gr_reserve(r, r->io.ws, plan.reserve()));
+    const GriVectorsLayout lay = gri_vectors_layout(nl, (size_t)N, (size_t)plan.chunk);
+    u64 *ws = (u64 *)r->io.ws.p;
+    double4 *A = (double4 *)(ws + lay.A); double2 *Wd = (double2 *)(ws + lay.Wd); u64 *X = ws + lay.X; double *ore = (double *)(ws + lay.re), *oim = (double *)(ws + lay.im);
     for (int c = 0; c < plan.nchunks; c++) {
         const int c0 = plan.first(c), nb = plan.count(c, nct);
         GR_TRY(gri_digits(r, src + (size_t)c0 * stride, stride, nb, level, X, dtab));
@@ -624,12 +601,12 @@ extern "C" int sfg_ring_encrypt_vectors_dev(sfg_ring *r, const double *values_ho
     if (!r->io.pk) GR_FAIL(r, "sfg_ring_encrypt_vectors_dev: no public key loaded (sfg_ring_load_public_key)");
     if (!values_host || !out) GR_FAIL(r, "sfg_ring_encrypt_vectors_dev: null values or output");
     if (!r->io.enc_seeded) GR_FAIL(r, "sfg_ring_encrypt_vectors_dev: the encryptor has no key (sfg_ring_seed_encryptor); there is no default");
-    GR_TRY(gr_reserve(r, &r->io.pt, &r->io.pt_bytes, (size_t)nct * (level + 1) * r->N * 8));
-    GR_TRY(gri_encode(r, "sfg_ring_encrypt_vectors_dev", values_host, nct, level, scale, (u64 *)r->io.pt));      // the encoder's rows and its refusals, before an index is spent
-    GR_TRY(gri_reserve(r, 2, nct, level, true));
+    GR_TRY(gr_reserve(r, r->io.pt, (size_t)nct * (level + 1) * r->N * 8));
+    GR_TRY(gri_encode(r, "sfg_ring_encrypt_vectors_dev", values_host, nct, level, scale, r->io.pt));      // the encoder's rows and its refusals, before an index is spent
+    GriPlan plan; GR_TRY(gri_reserve(r, 2, nct, level, true, plan));
     u64 first; GR_TRY(gri_take_indices(r, "sfg_ring_encrypt_vectors_dev", nct, &first));
     GriSrc src{nullptr, nullptr, nullptr, r->io.enc_key_dev, first};
-    return gri_core(r, src, r->io.pk, 2, nct, level, GRI_OUT, (const u64 *)r->io.pt, (u64 *)out, nullptr, true);
+    return gri_core(r, plan, src, r->io.pk, 2, nct, level, GRI_OUT, r->io.pt, (u64 *)out, nullptr);
 }
 extern "C" int sfg_ring_decode_vectors(sfg_ring *r, const uint64_t *pt, size_t pt_stride, int nct, int level, double scale, double *re_host, double *im_host) {
     GRI_ENTRY("sfg_ring_decode_vectors")
@@ -646,11 +623,11 @@ extern "C" int sfg_ring_decrypt_vectors(sfg_ring *r, const uint64_t *ct, int nct
     if (!r->io.sk) GR_FAIL(r, "sfg_ring_decrypt_vectors: no secret key loaded (sfg_ring_load_secret_key)");
     const int nl = level + 1, N = r->N; const size_t rowsw = (size_t)nl * N;
     GR_TRY(gri_decode_checks(r, "sfg_ring_decrypt_vectors", ct, re_host, rowsw, level, scale));
-    GR_TRY(gr_reserve(r, &r->io.pt, &r->io.pt_bytes, (size_t)nct * rowsw * 8));
-    for (int c0 = 0; c0 < nct; c0 += 32768) {
-        const int nb = std::min(32768, nct - c0);
-        hipLaunchKernelGGL(k_gri_decrypt, dim3(N / GR_T, nl, (unsigned)nb), dim3(GR_T), 0, r->stream, (const u64 *)ct + (size_t)c0 * 2 * rowsw, (const u64 *)r->io.sk, (u64 *)r->io.pt + (size_t)c0 * rowsw, r->modc, nl, N);
-    }
+    GR_TRY(gr_reserve(r, r->io.pt, (size_t)nct * rowsw * 8));
+    gr_split((size_t)nct, kGrLaunchCap, [&](size_t c0, size_t nb) {
+        hipLaunchKernelGGL(k_gri_decrypt, dim3(N / GR_T, nl, (unsigned)nb), dim3(GR_T), 0, r->stream, (const u64 *)ct + c0 * 2 * rowsw, r->io.sk, r->io.pt + c0 * rowsw, r->modc, nl, N);
+        return 0;
+    });
     GR_HIP(r, hipGetLastError());
-    return gri_decode_vectors(r, (const u64 *)r->io.pt, rowsw, nct, level, scale, re_host, im_host, false);
+    return gri_decode_vectors(r, r->io.pt, rowsw, nct, level, scale, re_host, im_host, false);
 }

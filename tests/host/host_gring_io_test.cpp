@@ -9,7 +9,9 @@
 //   G k q_0..q_(k-1) x_0..x_(k-1) bits      one decoded coefficient from its residues and the scale (a double's bits): the mixed-radix digits, the sign, the
 //                                          magnitude's digits, the bits of the double returned
 //   K nct nl N budget                      the decoder's chunks
-//   R hi lo band                           (bits of three doubles) the encoder's rounding of the pair hi + lo with its band test: status, p
+//   CL nct nl np npoly with_u N budget     the encryption core's workspace: its plan, the layout at the plan's chunk, first and count of every chunk
+//   KL | EL | VL  nct nl N budget          likewise the coefficient decoder's, the encoder's and the vector decoder's
+//   R hi lo band                          (bits of three doubles) the encoder's rounding of the pair hi + lo with its band test: status, p
 //   Q p q                                  the signed integer p, |p| < 2^62, modulo q
 //   B S                                    (bits) the band of a vector whose scaled slot sum is S
 #include "gring_io_arith.hpp"
@@ -82,6 +84,30 @@ int main(int argc, char **argv) {
             if (fscanf(f, "%d %d %zu %zu", &nct, &nl, &N, &budget) != 4) return 3;
             const GriPlan p = gri_decode_plan(nct, nl, N, budget);
             printf("K %d %d %zu %zu %zu %d %d %zu\n", nct, nl, N, budget, p.words_per_ct, p.chunk, p.nchunks, p.bytes);
+        } else if (!strcmp(op, "CL") || !strcmp(op, "KL") || !strcmp(op, "EL") || !strcmp(op, "VL")) {
+            // a workspace's plan, then its layout at the plan's chunk, then first and count of every chunk
+            int nct, nl, np = 0, npoly = 0, with_u = 0; size_t N, budget;
+            if (fscanf(f, "%d %d", &nct, &nl) != 2) return 3;
+            if (op[0] == 'C' && fscanf(f, "%d %d %d", &np, &npoly, &with_u) != 3) return 3;
+            if (fscanf(f, "%zu %zu", &N, &budget) != 2) return 3;
+            GriPlan p; std::vector<size_t> at;
+            if (op[0] == 'C') {
+                p = gri_plan(nct, nl, np, npoly, with_u != 0, N, budget);
+                const GriCoreLayout l = gri_core_layout(nl, np, npoly, with_u != 0, N, (size_t)p.chunk); at = {l.UQ, l.UP, l.TQ, l.TP, l.Y2, l.ext, l.V2, l.end};
+            } else if (op[0] == 'K') {
+                p = gri_decode_plan(nct, nl, N, budget);
+                const GriDecodeLayout l = gri_decode_layout(nl, N, (size_t)p.chunk); at = {l.X, l.out, l.end};
+            } else if (op[0] == 'E') {
+                p = gri_encode_plan(nct, nl, N, budget);
+                const GriEncodeLayout l = gri_encode_layout(nl, N, (size_t)p.chunk); at = {l.A, l.vals, l.R, l.band, l.flags, l.end};
+            } else {
+                p = gri_vectors_plan(nct, nl, N, budget);
+                const GriVectorsLayout l = gri_vectors_layout(nl, N, (size_t)p.chunk); at = {l.A, l.Wd, l.X, l.re, l.im, l.end};
+            }
+            printf("%s %d %d %d %d %d %zu %zu %zu %d %d %zu %zu %zu", op, nct, nl, np, npoly, with_u, N, budget, p.words_per_ct, p.chunk, p.nchunks, p.bytes, p.reserve(), at.size());
+            for (size_t o : at) printf(" %zu", o);
+            for (int c = 0; c < p.nchunks; c++) printf(" %d %d", p.first(c), p.count(c, nct));
+            printf("\n");
         } else if (!strcmp(op, "R")) {
             u64 b[3]; double v[3];
             if (fscanf(f, "%llu %llu %llu", &b[0], &b[1], &b[2]) != 3) return 3;

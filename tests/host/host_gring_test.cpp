@@ -5,6 +5,11 @@
 //   E k q_1..q_k x_1..x_k qt         one basis-extension element: y_1..y_k, v, the residue at qt
 //   D y                              the bits of (double)y
 //   P logN                           the transform's stage split
+//   G level np                       the digits of the key switch
+//   W njobs level np N budget        the key switch's workspace: bytes of an item, chunk, chunks, bytes to reserve; the layout at that chunk; first and count of every chunk
+//   Z nct level N budget             the rescale's workspace, likewise
+//   X n cap                          the pieces of gr_split
+//   U nmod                           the launch caps
 #include "gring_arith.hpp"
 #include "gring_plan.hpp"
 #include <cinttypes>
@@ -88,6 +93,35 @@ int main(int argc, char **argv) {
             int logN; if (fscanf(f, "%d", &logN) != 1) return 3;
             const GrNttPlan p = gr_ntt_plan(logN);
             printf("P %d %d %d %d %d %d %d %zu %zu\n", logN, p.ok ? 1 : 0, p.a, p.b, p.col_run, p.chunks, p.tiles_per_row, p.col_stride, p.lds_bytes);
+        } else if (!strcmp(op, "G")) {
+            int level, np; if (fscanf(f, "%d %d", &level, &np) != 2) return 3;
+            const GrDigits d = gr_digits(level, np);
+            printf("G %d %d %d %d %d\n", level, np, d.alpha, d.beta, d.nl);
+        } else if (!strcmp(op, "W")) {
+            size_t njobs, N, budget; int level, np;
+            if (fscanf(f, "%zu %d %d %zu %zu", &njobs, &level, &np, &N, &budget) != 5) return 3;
+            const GrChunks p = gr_ks_plan(njobs, level, np, N, budget);
+            const GrKsLayout l = gr_ks_layout(level, np, N, p.chunk);
+            printf("W %zu %d %d %zu %zu %zu %zu %zu %zu", njobs, level, np, N, budget, p.per_item, p.chunk, p.nchunks, p.bytes);
+            printf(" %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu", l.c2, l.Y, l.ext, l.accQ, l.accP, l.Y2, l.ext2, l.V, l.V2, l.jobs, l.end);
+            for (size_t c = 0; c < p.nchunks; c++) printf(" %zu %zu", p.first(c), p.count(c, njobs));
+            printf("\n");
+        } else if (!strcmp(op, "Z")) {
+            size_t nct, N, budget; int level;
+            if (fscanf(f, "%zu %d %zu %zu", &nct, &level, &N, &budget) != 4) return 3;
+            const GrChunks p = gr_rescale_plan(nct, level, N, budget);
+            const GrRescaleLayout l = gr_rescale_layout(level, N, p.chunk);
+            printf("Z %zu %d %zu %zu %zu %zu %zu %zu %zu %zu %zu", nct, level, N, budget, p.per_item, p.chunk, p.nchunks, p.bytes, l.T, l.tmp, l.end);
+            for (size_t c = 0; c < p.nchunks; c++) printf(" %zu %zu", p.first(c), p.count(c, nct));
+            printf("\n");
+        } else if (!strcmp(op, "X")) {
+            size_t n, cap; if (fscanf(f, "%zu %zu", &n, &cap) != 2 || cap < 1) return 3;
+            printf("X %zu %zu", n, cap);
+            gr_split(n, cap, [](size_t i0, size_t cnt) { printf(" %zu %zu", i0, cnt); return 0; });
+            printf("\n");
+        } else if (!strcmp(op, "U")) {
+            int nmod; if (fscanf(f, "%d", &nmod) != 1 || nmod < 1) return 3;
+            printf("U %d %zu %zu %zu %zu\n", nmod, kGrLaunchCap, kGrEwCap, kGrKsJobCap, gr_from_mont_cap(nmod));
         } else return 3;
     }
     fclose(f);

@@ -1,6 +1,8 @@
 """The general ring (sfgwas_amd/csrc/gring.hip, capi.Ring) on the GPU, word for word against the CPU oracle on the chains of tests/ring_cases.py:
 transforms, rotations, conjugation, the evaluator operations, the 19-modulus chain against the Python-integer key switch of tests/ring_ref.py, the PN14 chain
-against the specialised Context, an end-to-end rotate / square / rescale on two wide chains, and every refusal with its message.
+against the specialised Context, an end-to-end rotate / square / rescale on two wide chains, every refusal with its message, and the rotation, the product
+and the rescale on batches that need a second chunk of the workspace.  The launch splits at 16384 ciphertexts and at 32768 rows need gigabytes per operand and
+are not run here: tests/test_ring_ref.py holds the split helper and the caps on the CPU.
 One device ring, one oracle ring and one key set per chain for the module."""
 import atexit
 import ctypes as C
@@ -381,3 +383,52 @@ def test_montgomery_form_key_loads_to_the_same_words():
     e.dev.load_relinkey(rmont, montgomery=True)
     assert np.array_equal(e.dev.mulrelin(two, two, top), want)
     e.dev.load_relinkey(rlk)
+
+
+# ---------------------------------------------------------------- the evaluator's chunk loops with a second chunk
+# The ring's workspace budget is fixed (768 MiB), so a second chunk needs a batch beyond the chunk sizes tests/test_ring_ref.py pins on the CPU - the literals
+# below, not read from the library: 1638 key switches at G12 level 0, 6144 rescales at G12 level 1.  Each batch tiles four distinct ciphertexts, so four oracle
+# calls cover every output word: got[j] must equal the oracle's result for j % 4.  The launch splits at 16384 ciphertexts and 32768 rows would need gigabytes per
+# operand; they are left to the CPU plan test (the X and U lines of tests/host/host_gring_test.cpp).
+KS_CHUNK_G12_L0, RESCALE_CHUNK_G12_L1 = 1638, 6144
+
+
+def four_cts(e, level, seed):
+    return np.concatenate([e.cts(level, seed), e.cts(level, seed + 2)])
+
+
+def assert_tiled(got, want4, what):
+    t = got.reshape((-1, 4) + got.shape[1:])
+    for k in range(4):
+        bad = np.nonzero((t[:, k] != want4[k]).reshape(t.shape[0], -1).any(axis=1))[0]
+        assert bad.size == 0, (what, k, "first wrong ciphertexts", (bad[:5] * 4 + k).tolist())
+
+
+def test_rotation_across_the_chunk_boundary_equals_the_oracle():
+    """2192 ciphertexts, amounts 0, 1, 7, 1 tiled: 1644 jobs, a second chunk of 6, and every job's ciphertext index differs from its job index past the first copy"""
+    e = env("G12")
+    nct, amounts = 2192, [0, 1, 7, 1]
+    assert nct * 3 // 4 == KS_CHUNK_G12_L0 + 6
+    e.need_right(*amounts)
+    four = four_cts(e, 0, 110)
+    got = e.dev.rotate_right(np.tile(four, (nct // 4, 1, 1, 1)), 0, amounts * (nct // 4))
+    assert_tiled(got, [ol.rotate_right(e.ring, e.keys, 0, four[k], amounts[k]) for k in range(4)], "rotate_right")
+
+
+def test_mulrelin_across_the_chunk_boundary_equals_the_oracle():
+    e = env("G12")
+    nct = 1640
+    assert KS_CHUNK_G12_L0 < nct < 2 * KS_CHUNK_G12_L0
+    rlk = e.need_rlk()
+    a, b = four_cts(e, 0, 120), four_cts(e, 0, 130)
+    got = e.dev.mulrelin(np.tile(a, (nct // 4, 1, 1, 1)), np.tile(b, (nct // 4, 1, 1, 1)), 0)
+    assert_tiled(got, [orc("orc_mulrelin", e.ring, a[k].shape, 0, c64(a[k]), c64(b[k]), c64(rlk)) for k in range(4)], "mulrelin")
+
+
+def test_rescale_across_the_chunk_boundary_equals_the_oracle():
+    e = env("G12")
+    nct = 6148
+    assert RESCALE_CHUNK_G12_L1 < nct < 2 * RESCALE_CHUNK_G12_L1
+    four = four_cts(e, 1, 140)
+    got = e.dev.rescale(np.tile(four, (nct // 4, 1, 1, 1)), 1)
+    assert_tiled(got, [orc("orc_rescale", e.ring, (2, 1, e.N), 1, c64(four[k])) for k in range(4)], "rescale")

@@ -2,7 +2,7 @@
 against the PN14 statements they generalise, and the per-element arithmetic and host planner of sfgwas_amd/csrc/gring_io_arith.hpp / gring_io_plan.hpp.
 
 tests/host/host_gring_io_test.cpp includes the two headers - the functions the kernels of gring_io.hip run - compiled for the host, built once with
-AddressSanitizer + UBSan as a plain executable and run as a child process.  Every word it prints is compared here with Python integers.  Ten planted mistakes
+AddressSanitizer + UBSan as a plain executable and run as a child process.  Every word it prints is compared here with Python integers.  Twelve planted mistakes
 must change the output of the directed operands alone.
 """
 import functools
@@ -128,6 +128,58 @@ PLAN_CASES = [(1, 1, 1, 2, 1, 4096, 512 << 20), (3, 4, 3, 2, 1, 32768, 512 << 20
 
 DECODE_PLAN_CASES = [(1, 1, 4096, 512 << 20), (3, 47, 65536, 512 << 20), (300, 2, 4096, 512 << 20), (40, 17, 4096, 1 << 20), (0, 3, 4096, 1 << 20)]
 
+# ---------------------------------------------------------------- the four workspaces, restated from the executors as they stood before the layouts existed
+IO_BUDGET = 512 << 20                    # struct GrIo's default
+HUGE = 1 << 60                           # a budget under which only the chunk cap binds
+MAX_CHUNK, SLACK = 256, 64
+
+
+def ws_parent(kind, nl, np_, npoly, with_u, N):
+    """-> (words that size one item, [bytes of one item's share of each region, in order; None = a region of one word a call])"""
+    n, nt = N // 2, nl + np_
+    if kind == "CL":
+        words = ((nt if with_u else 0) + npoly * nt + npoly * np_ + npoly * nl) * N + (npoly * N + 1) // 2
+        return words, [nl * N * 8 * with_u, np_ * N * 8 * with_u, npoly * nl * N * 8, npoly * np_ * N * 8, npoly * np_ * N * 8, npoly * nl * N * 8, npoly * N * 4]
+    if kind == "KL":
+        return (nl + 1) * N, [nl * N * 8, N * 8]
+    if kind == "EL":
+        return n + 4 * n + nl * N + 8, [n * 32, n * 8, nl * N * 8, 8, None]           # A, values, R; the tail: a band a vector, two counters
+    return nl * N + 2 * N + 4 * n + N, [n * 32, N * 16, nl * N * 8, n * 8, n * 8]     # A, Wd, X, re, im
+
+
+def ws_cases():
+    """(kind, nct, nl, np, npoly, with_u, N, budget) on every level of every chain: 1, chunk - 1, chunk, chunk + 1 and 3 chunk + 2 items of the default budget's
+    chunk, a count above the cap under a budget that does not bind, and budgets below one item"""
+    cases = []
+    for name in rc.NAMES:
+        logN, q, p = rc.chain(name)
+        N = 1 << logN
+        for nl in range(1, len(q) + 1):
+            for kind, np_, npoly, with_u in [("CL", len(p), 2, 1), ("CL", len(p), 1, 0), ("CL", len(p), 2, 0), ("KL", 0, 0, 0), ("EL", 0, 0, 0), ("VL", 0, 0, 0)]:
+                words = ws_parent(kind, nl, np_, npoly, with_u, N)[0]
+                chunk = max(1, min(MAX_CHUNK, IO_BUDGET // (words * 8)))
+                counts = sorted({c for c in (1, chunk - 1, chunk, chunk + 1, 3 * chunk + 2) if c >= 1})
+                cases += [(kind, c, nl, np_, npoly, with_u, N, IO_BUDGET) for c in counts]
+                cases += [(kind, 3 * MAX_CHUNK + 2, nl, np_, npoly, with_u, N, HUGE), (kind, 3, nl, np_, npoly, with_u, N, words * 8 - 1), (kind, 2, nl, np_, npoly, with_u, N, 0)]
+    return cases
+
+
+def ws_line_ok(kind, v):
+    nct, nl, np_, npoly, with_u, N, budget, words, chunk, nchunks, nbytes, reserve, nat = v[:13]
+    at, spans = v[13:13 + nat], list(zip(v[13 + nat::2], v[14 + nat::2]))
+    want_words, shares = ws_parent(kind, nl, np_, npoly, with_u, N)
+    J = min(nct, MAX_CHUNK, max(1, budget // (want_words * 8)))
+    ok = (words, chunk, nbytes, reserve) == (want_words, J, J * want_words * 8, J * want_words * 8 + SLACK) and len(at) == len(shares) + 1 and len(spans) == nchunks
+    sizes = [8 if b is None else J * b for b in shares]
+    if kind == "CL":
+        sizes[-1] = (sizes[-1] + 7) // 8 * 8                # the 32-bit region ends the layout on a whole word
+    p = 0
+    for off, size in zip(at, sizes):                        # each region where the executor's pointer arithmetic put it: behind the one before, on a word
+        ok = ok and off * 8 == p and p % 8 == 0
+        p += size
+    ok = ok and at[-1] * 8 == p and p <= reserve
+    return ok and [s for s, _ in spans] == [c * J for c in range(nchunks)] and sum(c for _, c in spans) == nct and all(1 <= c <= J <= MAX_CHUNK for _, c in spans)
+
 
 def lift_values(q):
     vals = {0, 1, -1, 2, -2, 19, -19, 38, -38, (1 << 31) - 1, -(1 << 31), -(1 << 31) + 1}
@@ -207,6 +259,8 @@ def write_script(path):
             f.write(f"G {len(qs)} {' '.join(map(str, qs))} {' '.join(map(str, xs))} {struct.unpack('<Q', struct.pack('<d', scale))[0]}\n")
         for c in DECODE_PLAN_CASES:
             f.write("K " + " ".join(map(str, c)) + "\n")
+        for kind, nct, nl, np_, npoly, with_u, N, budget in ws_cases():
+            f.write(f"{kind} {nct} {nl} " + (f"{np_} {npoly} {with_u} " if kind == "CL" else "") + f"{N} {budget}\n")
         for hi, lo, band in ROUND_CASES:
             f.write(f"R {_bits(hi)} {_bits(lo)} {_bits(band)}\n")
         for q in REDUCE_MODULI:
@@ -260,6 +314,8 @@ def mismatches(lines):
             nct, nl, N, budget, words, chunk, nchunks, nbytes = v
             ok = words == (nl + 1) * N and nbytes == chunk * words * 8
             ok = ok and ((nct == 0 and chunk == 0 and nchunks == 0) or (1 <= chunk <= min(nct, 256) and nchunks == -(-nct // chunk) and (nbytes <= budget or chunk == 1)))
+        elif op in ("CL", "KL", "EL", "VL"):
+            ok = ws_line_ok(op, v)
         elif op == "R":
             hi, lo, band = (struct.unpack("<d", struct.pack("<Q", b))[0] for b in v[:3])
             st, pp = v[3], v[4]
@@ -303,8 +359,9 @@ def run(exe, script):
 def test_arithmetic_matches_python_integers_under_the_sanitizers(tmp_path, script):
     lines = run(_compile(str(tmp_path / "host_gring_io_test"), CSRC, sanitize=True), script)
     assert len(lines) == sum(1 for _ in open(script)) + 1
-    assert sum(ln[0] == "G" for ln in lines) == len(decode_cases()) and sum(ln[0] == "K" for ln in lines) == len(DECODE_PLAN_CASES)
-    assert sum(ln[0] == "L" for ln in lines) >= 12 * len(LIFT_MODULI) and sum(ln[0] == "C" for ln in lines) == len(PLAN_CASES)
+    assert sum(ln[0] == "G" for ln in lines) == len(decode_cases()) and sum(ln.split()[0] == "K" for ln in lines) == len(DECODE_PLAN_CASES)
+    assert sum(ln[:2] in ("CL", "KL", "EL", "VL") for ln in lines) == len(ws_cases()) > 1000
+    assert sum(ln.split()[0] == "L" for ln in lines) >= 12 * len(LIFT_MODULI) and sum(ln.split()[0] == "C" for ln in lines) == len(PLAN_CASES)
     bad = mismatches(lines)
     assert not bad, bad[:10]
 
@@ -357,6 +414,8 @@ MUTANTS = {
     "the lift of a negative multiple of q left at q": ("gring_io_arith.hpp", "return (w < 0 && m) ? q - m : m;", "return (w < 0) ? q - m : m;"),
     "the u shift taken modulo 16 coefficients": ("gring_io_arith.hpp", "GR_HD int samp_u_shift(int a) { return 2 * (a & 31); }", "GR_HD int samp_u_shift(int a) { return 2 * (a & 15); }"),
     "an off-by-one in the Gaussian block index": ("gring_io_arith.hpp", "return (unsigned)(t + kSampT * (a >> 3));", "return (unsigned)(t + kSampT * ((a + 1) >> 3));"),
+    "a region left out of the encryption core's layout": ("gring_io_plan.hpp", "l.Y2 = c.take(J * npoly * np * N);", "l.Y2 = c.at;"),
+    "the encoder's tail carved from the slack": ("gring_io_plan.hpp", "(size_t)nl * N + 8, budget_bytes); }", "(size_t)nl * N, budget_bytes); }"),
     "the chunk cap dropped": ("gring_io_plan.hpp", "if (fit > (size_t)GriPlan::kMaxChunk) fit = GriPlan::kMaxChunk;", ""),
 }
 
