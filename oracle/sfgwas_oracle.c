@@ -1188,6 +1188,7 @@ int orc_pgen_index(const uint8_t *f, size_t bytes, uint32_t *nv_out, uint32_t *n
     const uint32_t nv = (uint32_t)f[3] | (uint32_t)f[4] << 8 | (uint32_t)f[5] << 16 | (uint32_t)f[6] << 24;
     const uint32_t ns = (uint32_t)f[7] | (uint32_t)f[8] << 8 | (uint32_t)f[9] << 16 | (uint32_t)f[10] << 24;
     *nv_out = nv; *ns_out = ns;
+    if (!nv || !ns) return -1;                                                 /* an empty file is refused, as the device refuses it */
     uint64_t *o = malloc(sizeof(uint64_t) * (nv + 1)); uint32_t *l = malloc(sizeof(uint32_t) * (nv + 1)); uint8_t *t = malloc(nv + 1);
     *off = o; *len = l; *vrt = t;
     if (f[2] == 0x02) {                                                        /* fixed-width 2-bit records after a 12-byte header */
@@ -1217,6 +1218,7 @@ int orc_pgen_index(const uint8_t *f, size_t bytes, uint32_t *nv_out, uint32_t *n
         if (nonref == 3) p += (cnt + 7) / 8;
     }
     if (cur > bytes) return -1;
+    for (uint32_t b = 0; b < nblk; b++) if (o[(size_t)b * 65536u] < p) return -1;   /* a block of records that starts inside the header tables (p: their end) */
     return 0;
 }
 /* genovec[v][bps] 2-bit codes (ALT allele count, 3 = missing), bps = ceil(ns/4), for variants [v0, v1) */
@@ -1229,6 +1231,7 @@ int orc_pgen_decode_codes(const uint8_t *f, size_t bytes, uint32_t v0, uint32_t 
     /* the LD base of the first variants of the window may precede it */
     uint32_t start = v0;
     while (start > 0 && (vrt[start] & 6) == 2) start--;
+    if (v0 < v1 && (vrt[start] & 6) == 2) rc = -1;                             /* the first variant of a file has no base to be LD-compressed against */
     for (uint32_t v = start; v < v1 && !rc; v++) {
         const unsigned vt = vrt[v], mt = vt & 7;
         const uint8_t *p = f + off[v], *end = p + len[v];
