@@ -8,6 +8,8 @@
 #include <vector>
 #include <map>
 #include <set>
+#include <initializer_list>
+#include <type_traits>
 #include <unistd.h>
 #include "../../include/sfgwas_hip.h"
 #include "fp64mod.hpp"         // mulmod_lazy, canon, pred, ...: the fp64-held integer arithmetic
@@ -234,6 +236,13 @@ struct FdOwner {                                          // a file descriptor
     ~FdOwner() { reset(); }
     void reset(int fd_ = -1) { if (fd >= 0) close(fd); fd = fd_; }
 };
+// the sampled (std::true_type) or explicit (std::false_type) instance of a kernel family, chosen in one place: f launches K<decltype(tag)::value> with its one argument list
+template <class F> inline void sfg_by_sampled(bool sampled, F &&f) { if (sampled) f(std::true_type()); else f(std::false_type()); }
+// the dynamic-LDS limit of every kernel of a module's table (its *_set_attrs)
+inline hipError_t sfg_raise_lds(std::initializer_list<const void *> kernels, size_t bytes) {
+    for (const void *k : kernels) { const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); if (e != hipSuccess) return e; }
+    return hipSuccess;
+}
 // order `waiter` after everything enqueued so far on `signaller` (no host wait)
 int sfg_stream_after(sfg_ctx *ctx, hipStream_t waiter, hipStream_t signaller);
 // named grow-only scratch buffers owned by the context (avoids hipMalloc/hipFree of multi-GB buffers per call)

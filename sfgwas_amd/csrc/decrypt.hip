@@ -156,15 +156,16 @@ __global__ void __launch_bounds__(512) k_fft_decode(const double2 *wdd, const do
 }
 
 int decrypt_set_attrs(sfg_ctx *ctx) {
-    SFG_HIP(ctx, hipFuncSetAttribute((const void *)k_fft_decode, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEC_LDS_BYTES));
+    SFG_HIP(ctx, sfg_raise_lds({(const void *)k_fft_decode}, DEC_LDS_BYTES));
     return 0;
 }
 
 // ---------------------------------------------------------------- host side
-static int dec_check_level(sfg_ctx *ctx, const char *what, int nct, int level) {
-    if (level < 0 || level >= ctx->nq) SFG_FAIL(ctx, "%s: level %d out of range (0..%d)", what, level, ctx->nq - 1);
-    if (level + 1 > RF_MAXL) SFG_FAIL(ctx, "%s: more than %d moduli at the input level", what, RF_MAXL);
-    if (nct < 0) SFG_FAIL(ctx, "%s: negative count %d", what, nct);
+int check_level_count(sfg_ctx *ctx, const char *what, int nct, int level, int maxl, int min_count) {
+    if (level < 0 || level >= ctx->nq) SFG_FAIL(ctx, "%s: level %d out of range", what, level);
+    if (maxl && level + 1 > maxl) SFG_FAIL(ctx, "%s: more than %d moduli at the input level", what, maxl);
+    if (nct < 0) SFG_FAIL(ctx, "%s: negative ciphertext count", what);
+    if (nct < min_count) SFG_FAIL(ctx, "%s: ciphertext count %d must be positive", what, nct);
     return 0;
 }
 static int dec_check_scale(sfg_ctx *ctx, const char *what, double scale) {
@@ -175,19 +176,19 @@ static int dec_check_scale(sfg_ctx *ctx, const char *what, double scale) {
 // GenShare(skShard, zeroPk, ct, share) for nct ciphertexts [nct][2][level+1][N]
 extern "C" int sfg_pcks_gen_share_dev(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, const int32_t *e0, const int32_t *e1, uint64_t *h0, uint64_t *h1) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(dec_check_level(ctx, "pcks_gen_share", nct, level));
+    SFG_TRY(check_level_count(ctx, "pcks_gen_share", nct, level, RF_MAXL));
     if (!ctx->sh->sk_dev) SFG_FAIL(ctx, "pcks_gen_share: no secret-key shard loaded (sfg_ctx_load_secret_key)");
     if (!nct) return 0;
     if (!ct || !e0 || !h0 || (h1 && !e1)) SFG_FAIL(ctx, "pcks_gen_share: NULL ciphertexts, errors or output");
     ApiScope scope(ctx);
     const int N = SFG_N, nl = level + 1;
-    const size_t ctw = (size_t)2 * nl * N, roww = (size_t)nl * N;
-    const int chunk = nct < 256 ? nct : 256;
+    const size_t ctw = pcks_share_words(nl, (size_t)N), roww = (size_t)nl * N;
+    const BatchPlan plan = pcks_share_plan(nct, nl, (size_t)N);
     void *tp = nullptr;
-    SFG_TRY(sfg_scratch(ctx, "decrypt.share", (size_t)chunk * ctw * 8, &tp));
+    SFG_TRY(sfg_scratch(ctx, "decrypt.share", plan.bytes, &tp));
     u64 *T = (u64 *)tp;
-    for (int c0 = 0; c0 < nct; c0 += chunk) {
-        const int nb = nct - c0 < chunk ? nct - c0 : chunk;
+    for (int c = 0; c < plan.nchunks; c++) {
+        const int c0 = plan.first(c), nb = plan.count(c, nct);
         const int32_t *e0c = e0 + (size_t)c0 * N, *e1c = h1 ? e1 + (size_t)c0 * N : e0c;         // (h1 not wanted: polynomial 1 of T is not read)
         SFG_TRY(encrypt_errors_moddown(ctx, e0c, e1c, nb, level, T));
         SFG_TRY(launch_share(ctx, T, ctw, (const u64 *)ct + (size_t)c0 * ctw + roww, ctw, (u64 *)h0 + (size_t)c0 * roww, nl, nb));
@@ -199,61 +200,66 @@ extern "C" int sfg_pcks_gen_share_dev(sfg_ctx *ctx, const uint64_t *ct, int nct,
 // KeySwitch + .Plaintext(): pt = c0 + h0agg
 extern "C" int sfg_pcks_finish_dev(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, const uint64_t *h0agg, uint64_t *pt) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(dec_check_level(ctx, "pcks_finish", nct, level));
+    SFG_TRY(check_level_count(ctx, "pcks_finish", nct, level, RF_MAXL));
     if (!nct) return 0;
     if (!ct || !h0agg || !pt) SFG_FAIL(ctx, "pcks_finish: NULL ciphertexts, shares or output");
     const int N = SFG_N, nl = level + 1;
-    for (int c0 = 0; c0 < nct; c0 += 32768) {
-        const int nb = nct - c0 < 32768 ? nct - c0 : 32768;
+    const BatchPlan plan = grid_rows_plan(nct);
+    for (int c = 0; c < plan.nchunks; c++) {
+        const int c0 = plan.first(c), nb = plan.count(c, nct);
         SFG_TRY(launch_add_rows(ctx, (const u64 *)ct + (size_t)c0 * 2 * nl * N, (size_t)2 * nl * N, (const u64 *)h0agg + (size_t)c0 * nl * N, (size_t)nl * N,
                                 (u64 *)pt + (size_t)c0 * nl * N, (size_t)nl * N, nl, nb));
     }
     return 0;
 }
 
-enum DecSrc { DEC_PT, DEC_FINISH, DEC_DECRYPT };
-// the three stages for nvec plaintexts, in chunks of 512.  src: plaintext rows (DEC_PT, `stride` words apart) or ciphertexts [nvec][2][nl][N]; outputs on the host
+// the decryption front end (kernels.hpp): the one place that turns a source into coefficient rows, for the decoder here, the ring-vector decoder (rvec.hip) and
+// the collective bootstrap's finish (refresh.hip)
+int launch_dec_front(sfg_ctx *ctx, const DecSrc &s, int first, int nb, int nl, u64 *x, int *launches) {
+    const size_t ctw = (size_t)2 * nl * SFG_N, roww = (size_t)nl * SFG_N;
+    const ModPattern p0 = mod_pattern_run(0, nl);
+    if (s.kind == DecSrc::ROWS) {
+        RowMap rm; rm.rpg = nl; rm.gstride_in = s.stride; rm.gstride_out = roww;
+        return launch_ntt_inv_map(ctx, s.src + (size_t)first * s.stride, x, (size_t)nb * nl, p0, rm);
+    }
+    const u64 *ct = s.src + (size_t)first * ctw;
+    if (s.kind == DecSrc::FINISH) SFG_TRY(launch_add_rows(ctx, ct, ctw, s.h0agg + (size_t)first * roww, roww, x, roww, nl, nb));
+    else SFG_TRY(launch_share(ctx, ct, ctw, ct + roww, ctw, x, nl, nb));                       // c0 + sk (.) c1
+    if (launches) ++*launches;
+    return launch_ntt_inv(ctx, x, x, (size_t)nb * nl, p0);
+}
+
+// the three stages for nvec plaintexts, in the chunks of decode_plan (batch_plan.hpp).  src: plaintext rows or ciphertexts [nvec][2][nl][N]; outputs on the host
 // (host_out: the call synchronises) or on the device; coeffs != nullptr: stages 1 and 2 only.
-static int decode_run(sfg_ctx *ctx, const char *what, DecSrc mode, const u64 *src, size_t stride, const u64 *h0agg, int nvec, int level, double scale,
-                      double *re, double *im, double *coeffs, bool host_out) {
+static int decode_run(sfg_ctx *ctx, const char *what, const DecSrc &src, int nvec, int level, double scale, double *re, double *im, double *coeffs, bool host_out) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(dec_check_level(ctx, what, nvec, level));
+    SFG_TRY(check_level_count(ctx, what, nvec, level, RF_MAXL));
     SFG_TRY(dec_check_scale(ctx, what, scale));
-    if (mode == DEC_DECRYPT && !ctx->sh->sk_dev) SFG_FAIL(ctx, "%s: no secret key loaded (sfg_ctx_load_secret_key)", what);
+    if (src.kind == DecSrc::DECRYPT && !ctx->sh->sk_dev) SFG_FAIL(ctx, "%s: no secret key loaded (sfg_ctx_load_secret_key)", what);
     const int N = SFG_N, n = SFG_SLOTS, nl = level + 1;
-    if (mode == DEC_PT && stride < (size_t)nl * N) SFG_FAIL(ctx, "%s: plaintext stride %zu below (level + 1) * N", what, stride);
+    if (src.kind == DecSrc::ROWS && src.stride < (size_t)nl * N) SFG_FAIL(ctx, "%s: plaintext stride %zu below (level + 1) * N", what, src.stride);
     if (host_out) {       // results leave the device here: refused, with nothing launched, while an unprovable encoder rounding is outstanding
         SFG_TRY(sfg_sync_all(ctx));
         SFG_TRY(sfg_encoder_check(ctx));
     }
     if (!nvec) return 0;
-    if (!src || (!coeffs && !re) || (mode == DEC_FINISH && !h0agg)) SFG_FAIL(ctx, "%s: NULL input or output", what);
+    if (!src.src || (!coeffs && !re) || (src.kind == DecSrc::FINISH && !src.h0agg)) SFG_FAIL(ctx, "%s: NULL input or output", what);
     ApiScope scope(ctx);
     EncTables *et = (EncTables *)ctx->enc_tables();
-    const int chunk = nvec < 512 ? nvec : 512;
     const int parts = im ? 2 : 1;
+    const DecodeWords dw = decode_words(nl, (size_t)N, coeffs != nullptr, host_out, parts);
+    const BatchPlan plan = decode_plan(nvec, dw);
     void *xp = nullptr, *wp = nullptr, *op = nullptr;
-    SFG_TRY(sfg_scratch(ctx, "decrypt.x", (size_t)chunk * nl * N * 8, &xp));
-    if (!coeffs) SFG_TRY(sfg_scratch(ctx, "decrypt.w", (size_t)chunk * N * sizeof(double2), &wp));
-    if (host_out) SFG_TRY(sfg_scratch(ctx, "decrypt.out", (size_t)chunk * (coeffs ? (size_t)N : (size_t)n * parts) * 8, &op));
+    SFG_TRY(sfg_scratch(ctx, "decrypt.x", plan.bytes_of(dw.x), &xp));
+    if (dw.w) SFG_TRY(sfg_scratch(ctx, "decrypt.w", plan.bytes_of(dw.w), &wp));
+    if (dw.out) SFG_TRY(sfg_scratch(ctx, "decrypt.out", plan.bytes_of(dw.out), &op));
     u64 *x = (u64 *)xp; double2 *wdd = (double2 *)wp; double *ob = (double *)op;
     RecodeConst rc; recode_constants(ctx, level, rc);
-    ModPattern p0; p0.period = nl; for (int j = 0; j < nl; j++) p0.m[j] = (int8_t)j;
-    const size_t ctw = (size_t)2 * nl * N, roww = (size_t)nl * N;
     PhaseTimer timer(ctx, "decode");
     int launches = 0;
-    for (int c0 = 0; c0 < nvec; c0 += chunk) {
-        const int nb = nvec - c0 < chunk ? nvec - c0 : chunk;
-        if (mode == DEC_PT) {
-            RowMap rm; rm.rpg = nl; rm.gstride_in = stride; rm.gstride_out = roww;
-            SFG_TRY(launch_ntt_inv_map(ctx, src + (size_t)c0 * stride, x, (size_t)nb * nl, p0, rm));
-        } else {
-            const u64 *ct = src + (size_t)c0 * ctw;
-            if (mode == DEC_FINISH) SFG_TRY(launch_add_rows(ctx, ct, ctw, h0agg + (size_t)c0 * roww, roww, x, roww, nl, nb));
-            else SFG_TRY(launch_share(ctx, ct, ctw, ct + roww, ctw, x, nl, nb));                   // c0 + sk (.) c1
-            SFG_TRY(launch_ntt_inv(ctx, x, x, (size_t)nb * nl, p0));
-            launches++;
-        }
+    for (int c = 0; c < plan.nchunks; c++) {
+        const int c0 = plan.first(c), nb = plan.count(c, nvec);
+        SFG_TRY(launch_dec_front(ctx, src, c0, nb, nl, x, &launches));
         double *cdst = coeffs ? (host_out ? ob : coeffs + (size_t)c0 * N) : nullptr;
         hipLaunchKernelGGL(k_dec_coeffs, dim3(N / 256, nb), dim3(256), 0, ctx->stream, (const u64 *)x, rc, scale, coeffs ? (double2 *)nullptr : wdd, cdst, ctx->modc);
         SFG_HIP(ctx, hipGetLastError());
@@ -261,11 +267,11 @@ static int decode_run(sfg_ctx *ctx, const char *what, DecSrc mode, const u64 *sr
         if (coeffs) {
             if (host_out) {
                 SFG_HIP(ctx, hipMemcpyAsync(coeffs + (size_t)c0 * N, ob, (size_t)nb * N * 8, hipMemcpyDeviceToHost, ctx->stream));
-                if (c0 + chunk < nvec) SFG_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (the staging buffer is reused by the next chunk)
+                if (c + 1 < plan.nchunks) SFG_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (the staging buffer is reused by the next chunk)
             }
             continue;
         }
-        double *rdst = host_out ? ob : re + (size_t)c0 * n, *idst = !im ? nullptr : host_out ? ob + (size_t)chunk * n : im + (size_t)c0 * n;
+        double *rdst = host_out ? ob : re + (size_t)c0 * n, *idst = !im ? nullptr : host_out ? ob + (size_t)plan.chunk * n : im + (size_t)c0 * n;
         hipLaunchKernelGGL(k_fft_decode, dim3(nb, parts), dim3(512), DEC_LDS_BYTES, ctx->stream, (const double2 *)wdd, (const double4 *)et->tb, (const double4 *)et->dec,
                            (const uint16_t *)et->tinv, rdst, idst);
         SFG_HIP(ctx, hipGetLastError());
@@ -273,7 +279,7 @@ static int decode_run(sfg_ctx *ctx, const char *what, DecSrc mode, const u64 *sr
         if (host_out) {
             SFG_HIP(ctx, hipMemcpyAsync(re + (size_t)c0 * n, rdst, (size_t)nb * n * 8, hipMemcpyDeviceToHost, ctx->stream));
             if (im) SFG_HIP(ctx, hipMemcpyAsync(im + (size_t)c0 * n, idst, (size_t)nb * n * 8, hipMemcpyDeviceToHost, ctx->stream));
-            if (c0 + chunk < nvec) SFG_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (the staging buffer is reused by the next chunk)
+            if (c + 1 < plan.nchunks) SFG_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (the staging buffer is reused by the next chunk)
         }
     }
     timer.stop(launches);
@@ -282,19 +288,19 @@ static int decode_run(sfg_ctx *ctx, const char *what, DecSrc mode, const u64 *sr
 }
 
 extern "C" int sfg_decode_vectors(sfg_ctx *ctx, const uint64_t *pt, size_t pt_stride, int nct, int level, double scale, double *re_host, double *im_host) {
-    return decode_run(ctx, "decode_vectors", DEC_PT, (const u64 *)pt, pt_stride, nullptr, nct, level, scale, re_host, im_host, nullptr, true);
+    return decode_run(ctx, "decode_vectors", DecSrc::rows((const u64 *)pt, pt_stride), nct, level, scale, re_host, im_host, nullptr, true);
 }
 extern "C" int sfg_decode_vectors_dev(sfg_ctx *ctx, const uint64_t *pt, size_t pt_stride, int nct, int level, double scale, double *re_dev, double *im_dev) {
-    return decode_run(ctx, "decode_vectors_dev", DEC_PT, (const u64 *)pt, pt_stride, nullptr, nct, level, scale, re_dev, im_dev, nullptr, false);
+    return decode_run(ctx, "decode_vectors_dev", DecSrc::rows((const u64 *)pt, pt_stride), nct, level, scale, re_dev, im_dev, nullptr, false);
 }
 extern "C" int sfg_decode_coeffs(sfg_ctx *ctx, const uint64_t *pt, size_t pt_stride, int nct, int level, double scale, double *coeffs_host) {
     if (nct > 0 && !coeffs_host) SFG_FAIL(ctx, "decode_coeffs: NULL output");
     static double none;       // (nct == 0: the argument checks still run; nothing is written)
-    return decode_run(ctx, "decode_coeffs", DEC_PT, (const u64 *)pt, pt_stride, nullptr, nct, level, scale, nullptr, nullptr, coeffs_host ? coeffs_host : &none, true);
+    return decode_run(ctx, "decode_coeffs", DecSrc::rows((const u64 *)pt, pt_stride), nct, level, scale, nullptr, nullptr, coeffs_host ? coeffs_host : &none, true);
 }
 extern "C" int sfg_pcks_finish_decode(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, double scale, const uint64_t *h0agg, double *re_host, double *im_host) {
-    return decode_run(ctx, "pcks_finish_decode", DEC_FINISH, (const u64 *)ct, 0, (const u64 *)h0agg, nct, level, scale, re_host, im_host, nullptr, true);
+    return decode_run(ctx, "pcks_finish_decode", DecSrc::finish((const u64 *)ct, (const u64 *)h0agg), nct, level, scale, re_host, im_host, nullptr, true);
 }
 extern "C" int sfg_decrypt_vectors(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, double scale, double *re_host, double *im_host) {
-    return decode_run(ctx, "decrypt_vectors", DEC_DECRYPT, (const u64 *)ct, 0, nullptr, nct, level, scale, re_host, im_host, nullptr, true);
+    return decode_run(ctx, "decrypt_vectors", DecSrc::decrypt((const u64 *)ct), nct, level, scale, re_host, im_host, nullptr, true);
 }

@@ -144,11 +144,8 @@ __global__ void __launch_bounds__(512) k_enc_transcript(const unsigned *keyp, u6
 }
 
 int encrypt_set_attrs(sfg_ctx *ctx) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_enc_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_enc_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_enc_tail<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_enc_tail<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
-    if (e != hipSuccess) SFG_FAIL(ctx, "cannot raise dynamic LDS limit for the encryption kernels");
+    if (sfg_raise_lds({(const void *)k_enc_fwd<false>, (const void *)k_enc_fwd<true>, (const void *)k_enc_tail<0>, (const void *)k_enc_tail<1>}, LDS_DOUBLES * 8) != hipSuccess)
+        SFG_FAIL(ctx, "cannot raise dynamic LDS limit for the encryption kernels");
     return 0;
 }
 static void wipe(volatile void *p, size_t n) { volatile unsigned char *b = (volatile unsigned char *)p; for (size_t i = 0; i < n; i++) b[i] = 0; }
@@ -160,28 +157,28 @@ void sfg_encrypt_destroy(SfgShared *sh) {
 }
 
 // ---------------------------------------------------------------- host side
-// the three steps for nct ciphertexts, in chunks whose T rows fit 1 GiB of scratch.  mode 0: out = Enc(pt) (pt nullable: zero); mode 1: out += Enc(0)
+// the three steps for nct ciphertexts, in the chunks of enc_core_plan (batch_plan.hpp: the T rows of a chunk fit its budget).  mode 0: out = Enc(pt) (pt nullable: zero); mode 1: out += Enc(0)
 static int encrypt_run(sfg_ctx *ctx, const EncSrc &src0, const u64 *pk, const u64 *pt, int nct, int level, int mode, u64 *out) {
     const int N = SFG_N, nl = level + 1, np = ctx->np, nt = nl + np;
     const KswConst *kcd, *kc;
     SFG_TRY(get_ksw(ctx, level, &kcd, &kc));
     ApiScope scope(ctx);
-    const size_t per_ct = (size_t)2 * nt * N * 8;
-    int chunk = (int)((1ULL << 30) / per_ct); if (chunk < 1) chunk = 1; if (chunk > nct) chunk = nct;
+    const BatchPlan plan = enc_core_plan(nct, nl, np, (size_t)N);
     void *Tp = nullptr;
-    SFG_TRY(sfg_scratch(ctx, "encrypt.T", (size_t)chunk * per_ct, &Tp));
+    SFG_TRY(sfg_scratch(ctx, "encrypt.T", plan.bytes, &Tp));
     u64 *T = (u64 *)Tp;
-    ModPattern pp; pp.period = np; for (int p = 0; p < np; p++) pp.m[p] = (int8_t)(ctx->nq + p);
+    const ModPattern pp = mod_pattern_run(ctx->nq, np);
     RowMap rm; rm.rpg = np; rm.gstride_in = (size_t)nt * N; rm.gstride_out = (size_t)nt * N;
     PhaseTimer timer(ctx, "encrypt");
     int launches = 0;
-    for (int c0 = 0; c0 < nct; c0 += chunk) {
-        const int nb = nct - c0 < chunk ? nct - c0 : chunk;
+    for (int c = 0; c < plan.nchunks; c++) {
+        const int c0 = plan.first(c), nb = plan.count(c, nct);
         EncSrc src = src0;
         if (src.key) src.index0 += (u64)c0;
         else { if (src.u) src.u += (size_t)c0 * N; src.e0 += (size_t)c0 * N; src.e1 += (size_t)c0 * N; }
-        if (src.key) hipLaunchKernelGGL(k_enc_fwd<true>, dim3(nb), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, pk, T, nl, np, ctx->nq, ctx->nmod, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
-        else hipLaunchKernelGGL(k_enc_fwd<false>, dim3(nb), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, pk, T, nl, np, ctx->nq, ctx->nmod, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
+        sfg_by_sampled(src.key != nullptr, [&](auto sampled) {
+            hipLaunchKernelGGL(k_enc_fwd<decltype(sampled)::value>, dim3(nb), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, pk, T, nl, np, ctx->nq, ctx->nmod, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
+        });
         SFG_HIP(ctx, hipGetLastError());
         SFG_TRY(launch_ntt_inv_map(ctx, T + (size_t)nl * N, T + (size_t)nl * N, (size_t)nb * 2 * np, pp, rm));
         u64 *o = out + (size_t)c0 * 2 * nl * N;
@@ -197,8 +194,7 @@ static int encrypt_run(sfg_ctx *ctx, const EncSrc &src0, const u64 *pk, const u6
 
 static int enc_check_common(sfg_ctx *ctx, const char *what, int nct, int level) {
     if (!ctx->sh->pk_dev) SFG_FAIL(ctx, "%s: no public key loaded (sfg_ctx_load_public_key)", what);
-    if (level < 0 || level >= ctx->nq) SFG_FAIL(ctx, "%s: level %d out of range (0..%d)", what, level, ctx->nq - 1);
-    if (nct <= 0) SFG_FAIL(ctx, "%s: ciphertext count %d must be positive", what, nct);
+    SFG_TRY(check_level_count(ctx, what, nct, level, 0, 1));
     if (ctx->np < 1 || ctx->np > KSW_MAXA) SFG_FAIL(ctx, "%s: needs 1..%d special primes", what, KSW_MAXA);
     return 0;
 }

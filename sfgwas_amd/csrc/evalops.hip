@@ -152,7 +152,7 @@ extern "C" int sfg_ct_rescale_dev(sfg_ctx *ctx, const uint64_t *in, uint64_t *ou
     SFG_TRY(launch_ntt_inv_map(ctx, (const u64 *)in + (size_t)level * N, tl, np2, pl, rm));
     hipLaunchKernelGGL(k_rescale_prep, dim3(N / 256, level, (unsigned)np2), dim3(256), 0, ctx->stream, tl, tmp, level, rc);
     SFG_HIP(ctx, hipGetLastError());
-    ModPattern pq; pq.period = level; for (int m = 0; m < level; m++) pq.m[m] = (int8_t)m;
+    const ModPattern pq = mod_pattern_run(0, level);
     SFG_TRY(launch_ntt_fwd(ctx, tmp, tmp, np2 * level, pq));
     hipLaunchKernelGGL(k_rescale_fin, dim3(N / 256, level, (unsigned)np2), dim3(256), 0, ctx->stream, (const u64 *)in, tmp, (u64 *)out, level, rc, ctx->modc);
     SFG_HIP(ctx, hipGetLastError());

@@ -3,11 +3,14 @@
 #include "common.hpp"
 #include "mm_plan.hpp"            // the product's launch plan; the byte models mac_i8_stream_bytes / mac_i8_tile_bytes / mac_i8_rot_tile_bytes
 #include "assoc_plan.hpp"         // the association scan's batch plan, filter maps, diag_bool, the active-baby tables
+#include "batch_plan.hpp"         // the one chunk rule and the per-family figures of the fixed-ring protocol ends
 
 // row r of a batch uses modulus m[r % period] (ciphertext rows, plaintext rows, key-switch rows are all periodic)
 // m < 0 marks a row the kernel must leave untouched
 constexpr int SFG_MAXPATTERN = 128;   // >= KSW_MAXDIG * SFG_MAXMOD
 struct ModPattern { int period; int8_t m[SFG_MAXPATTERN]; };
+// the pattern of `count` consecutive moduli from `first`: row r uses modulus first + r % count
+inline ModPattern mod_pattern_run(int first, int count) { ModPattern p; p.period = count; for (int j = 0; j < count; j++) p.m[j] = (int8_t)(first + j); return p; }
 // row r of a launch lives at base + (r / rpg) * gstride + (r % rpg) * N  (strides in words)
 struct RowMap { int rpg; size_t gstride_in, gstride_out; };
 // where the plaintext of diagonal `shift` (= shift0 + index in the batch) of block row g lands inside a panel that holds G
@@ -58,9 +61,21 @@ int i8_ride_tiles(sfg_ctx *ctx, int K, int L, int8_t **Bs, int8_t **Bb);        
 struct I8Args;                                                      // i8_move.hpp
 void launch_i8_pack_pt_digits(hipStream_t q, const I8Args &a, unsigned items, bool big);      // the transposition pass of digit-plane panel rows
 void launch_move_alone(hipStream_t q, const MoveJob &j);           // the same by mover workgroups alone on queue q
-// refresh.hip: h = rows + sk (.) xr and out = a + b over [nct][nl][N] rows taken from strided sources (the loaded secret-key shard)
-int launch_share(sfg_ctx *ctx, const u64 *rows, size_t rows_ct_stride, const u64 *xr, size_t x_ct_stride, u64 *h, int nl, int nct);
+// refresh.hip: h = rows + sk (.) xr (negated if neg) and out = a + b over [nct][nl][N] rows taken from strided sources (the loaded secret-key shard)
+int launch_share(sfg_ctx *ctx, const u64 *rows, size_t rows_ct_stride, const u64 *xr, size_t x_ct_stride, u64 *h, int nl, int nct, int neg = 0);
 int launch_add_rows(sfg_ctx *ctx, const u64 *a, size_t a_ct_stride, const u64 *b, size_t b_ct_stride, u64 *out, size_t out_ct_stride, int nl, int nct);
+// decrypt.hip: the decryption front end - x [nb][nl][N] = the coefficient rows of plaintexts first .. first + nb - 1 of the source: NTT rows `stride` words apart,
+// c0 + h0agg, or c0 + sk (.) c1 of ciphertexts [..][2][nl][N].  *launches (nullable) grows by the launches made beyond the inverse NTT
+struct DecSrc {
+    enum Kind { ROWS, FINISH, DECRYPT } kind; const u64 *src; size_t stride; const u64 *h0agg;
+    static DecSrc rows(const u64 *pt, size_t stride) { return DecSrc{ROWS, pt, stride, nullptr}; }
+    static DecSrc finish(const u64 *ct, const u64 *h0agg) { return DecSrc{FINISH, ct, 0, h0agg}; }
+    static DecSrc decrypt(const u64 *ct) { return DecSrc{DECRYPT, ct, 0, nullptr}; }
+};
+int launch_dec_front(sfg_ctx *ctx, const DecSrc &s, int first, int nb, int nl, u64 *x, int *launches = nullptr);
+// decrypt.hip: the level and the count of a protocol entry point.  what: the caller's prefix; maxl: the module's modulus cap at the input level (RF_MAXL; 0: none);
+// min_count: 0, or 1 where an empty call is refused
+int check_level_count(sfg_ctx *ctx, const char *what, int nct, int level, int maxl, int min_count = 0);
 // encrypt.hip: the deterministic encryption core for the zero public key: out [nct][2][level+1][N] = (ModDown_P(NTT_QP(e0)), ModDown_P(NTT_QP(e1)))
 int encrypt_errors_moddown(sfg_ctx *ctx, const int32_t *e0, const int32_t *e1, int nct, int level, u64 *out);
 // genoio.hip: dense int8 copy [nr][ld_out] of the stored sub-block (r0.., c0..) of a 2-bit packed matrix (c0 a multiple of 4)

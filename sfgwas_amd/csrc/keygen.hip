@@ -177,13 +177,9 @@ __global__ void __launch_bounds__(256) k_crp_fill(CrpKey key, u64 first_row, con
 }
 
 int keygen_set_attrs(sfg_ctx *ctx) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_kg_share<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_kg_share<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_kg_rkg<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_kg_rkg<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_kg_rkg<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_kg_rkg<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * 8);
-    if (e != hipSuccess) SFG_FAIL(ctx, "cannot raise dynamic LDS limit for the key-generation kernels");
+    if (sfg_raise_lds({(const void *)k_kg_share<false>, (const void *)k_kg_share<true>, (const void *)k_kg_rkg<1, false>, (const void *)k_kg_rkg<1, true>,
+                       (const void *)k_kg_rkg<2, false>, (const void *)k_kg_rkg<2, true>}, LDS_DOUBLES * 8) != hipSuccess)
+        SFG_FAIL(ctx, "cannot raise dynamic LDS limit for the key-generation kernels");
     return 0;
 }
 void sfg_keygen_destroy(SfgShared *sh) {
@@ -260,50 +256,42 @@ static int kg_run_shares(sfg_ctx *ctx, const KgShareSrc &src, const uint64_t *ga
     }
     const unsigned npoly = pubkey ? 1u : (unsigned)nkeys * (unsigned)ctx->beta;
     PhaseTimer timer(ctx, "keygen");
-    if (src.key) hipLaunchKernelGGL(k_kg_share<true>, dim3(npoly), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, kc, (const u64 *)ctx->sh->skqp_dev, crp, idx_dev, pubkey ? 0 : 1, out, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
-    else hipLaunchKernelGGL(k_kg_share<false>, dim3(npoly), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, kc, (const u64 *)ctx->sh->skqp_dev, crp, idx_dev, pubkey ? 0 : 1, out, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
+    sfg_by_sampled(src.key != nullptr, [&](auto sampled) {
+        hipLaunchKernelGGL(k_kg_share<decltype(sampled)::value>, dim3(npoly), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, kc, (const u64 *)ctx->sh->skqp_dev, crp, idx_dev, pubkey ? 0 : 1, out, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
+    });
     SFG_HIP(ctx, hipGetLastError());
     timer.stop(1, (double)npoly * ctx->nmod * SFG_N * 8 * 2);
     return 0;
 }
 
-extern "C" int sfg_ckg_gen_share_dev(sfg_ctx *ctx, const uint64_t *crp, const int32_t *e, uint64_t *share) {
+// The four share entry points, each in its explicit form (the caller's small polynomials) and its sampled form (none given: they come from the encryptor's
+// stream, `nidx` consecutive encryption indices are taken and the first is reported through first_index, nullable).  kg_sample is the sampled form's step.
+static int kg_sample(sfg_ctx *ctx, const char *what, int nidx, const unsigned **key, u64 *index0, uint64_t *first_index) {
+    SFG_TRY(enc_take_indices(ctx, what, nidx, index0));           // (refuses an unseeded encryptor)
+    if (first_index) *first_index = *index0;
+    *key = ctx->sh->enc_key_dev;
+    return 0;
+}
+static int kg_ckg(sfg_ctx *ctx, const char *what, bool sampled, const uint64_t *crp, const int32_t *e, uint64_t *share, uint64_t *first_index) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(kg_check_sk(ctx, "ckg_gen_share"));
-    if (!crp || !e || !share) SFG_FAIL(ctx, "ckg_gen_share: NULL polynomial or output");
+    SFG_TRY(kg_check_sk(ctx, what));
+    if (!crp || (!sampled && !e) || !share) SFG_FAIL(ctx, "%s: NULL polynomial or output", what);
     KgShareSrc src{e, nullptr, 0};
+    if (sampled) SFG_TRY(kg_sample(ctx, what, 1, &src.key, &src.index0, first_index));
     return kg_run_shares(ctx, src, nullptr, 1, true, (const u64 *)crp, (u64 *)share);
 }
-extern "C" int sfg_ckg_gen_share_sampled_dev(sfg_ctx *ctx, const uint64_t *crp, uint64_t *share, uint64_t *first_index) {
+static int kg_rtg(sfg_ctx *ctx, const char *what, bool sampled, const uint64_t *galois_host, int nkeys, const uint64_t *crp, const int32_t *e, uint64_t *shares, uint64_t *first_index) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(kg_check_sk(ctx, "ckg_gen_share_sampled"));
-    if (!crp || !share) SFG_FAIL(ctx, "ckg_gen_share_sampled: NULL polynomial or output");
-    SFG_TRY(kg_check_seeded(ctx, "ckg_gen_share_sampled"));
-    u64 first; SFG_TRY(enc_take_indices(ctx, "ckg_gen_share_sampled", 1, &first));
-    if (first_index) *first_index = first;
-    KgShareSrc src{nullptr, ctx->sh->enc_key_dev, first};
-    return kg_run_shares(ctx, src, nullptr, 1, true, (const u64 *)crp, (u64 *)share);
-}
-extern "C" int sfg_rtg_gen_shares_dev(sfg_ctx *ctx, const uint64_t *galois_host, int nkeys, const uint64_t *crp, const int32_t *e, uint64_t *shares) {
-    SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(kg_check_sk(ctx, "rtg_gen_shares"));
-    SFG_TRY(kg_check_galois(ctx, "rtg_gen_shares", galois_host, nkeys));
+    SFG_TRY(kg_check_sk(ctx, what));
+    SFG_TRY(kg_check_galois(ctx, what, galois_host, nkeys));
+    if (sampled) SFG_TRY(kg_check_seeded(ctx, what));             // (before the empty call returns)
     if (!nkeys) return 0;
-    if (!crp || !e || !shares) SFG_FAIL(ctx, "rtg_gen_shares: NULL polynomial or output");
+    if (!crp || (!sampled && !e) || !shares) SFG_FAIL(ctx, "%s: NULL polynomial or output", what);
     KgShareSrc src{e, nullptr, 0};
-    return kg_run_shares(ctx, src, galois_host, nkeys, false, (const u64 *)crp, (u64 *)shares);
-}
-extern "C" int sfg_rtg_gen_shares_sampled_dev(sfg_ctx *ctx, const uint64_t *galois_host, int nkeys, const uint64_t *crp, uint64_t *shares, uint64_t *first_index) {
-    SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(kg_check_sk(ctx, "rtg_gen_shares_sampled"));
-    SFG_TRY(kg_check_galois(ctx, "rtg_gen_shares_sampled", galois_host, nkeys));
-    SFG_TRY(kg_check_seeded(ctx, "rtg_gen_shares_sampled"));
-    if (!nkeys) return 0;
-    if (!crp || !shares) SFG_FAIL(ctx, "rtg_gen_shares_sampled: NULL polynomial or output");
-    if ((long long)nkeys * ctx->beta > 0x7FFFFFFFLL) SFG_FAIL(ctx, "rtg_gen_shares_sampled: too many keys in one call");
-    u64 first; SFG_TRY(enc_take_indices(ctx, "rtg_gen_shares_sampled", nkeys * ctx->beta, &first));
-    if (first_index) *first_index = first;
-    KgShareSrc src{nullptr, ctx->sh->enc_key_dev, first};
+    if (sampled) {
+        if ((long long)nkeys * ctx->beta > 0x7FFFFFFFLL) SFG_FAIL(ctx, "%s: too many keys in one call", what);
+        SFG_TRY(kg_sample(ctx, what, nkeys * ctx->beta, &src.key, &src.index0, first_index));
+    }
     return kg_run_shares(ctx, src, galois_host, nkeys, false, (const u64 *)crp, (u64 *)shares);
 }
 
@@ -311,56 +299,56 @@ template <int ROUND>
 static int kg_run_rkg(sfg_ctx *ctx, const KgRkgSrc &src, const u64 *A, const u64 *B, u64 *out0, u64 *out1) {
     KgConst kc; kg_const(ctx, kc);
     PhaseTimer timer(ctx, "keygen");
-    if (src.key) hipLaunchKernelGGL((k_kg_rkg<ROUND, true>), dim3(ctx->beta), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, kc, (const u64 *)ctx->sh->skqp_dev, A, B, out0, out1, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
-    else hipLaunchKernelGGL((k_kg_rkg<ROUND, false>), dim3(ctx->beta), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, kc, (const u64 *)ctx->sh->skqp_dev, A, B, out0, out1, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
+    sfg_by_sampled(src.key != nullptr, [&](auto sampled) {
+        hipLaunchKernelGGL((k_kg_rkg<ROUND, decltype(sampled)::value>), dim3(ctx->beta), dim3(512), LDS_DOUBLES * 8, ctx->stream, src, kc, (const u64 *)ctx->sh->skqp_dev, A, B, out0, out1, ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
+    });
     SFG_HIP(ctx, hipGetLastError());
     timer.stop(1);
     return 0;
 }
-extern "C" int sfg_rkg_round1_dev(sfg_ctx *ctx, const uint64_t *crp, const int8_t *u, const int32_t *e0, const int32_t *e1, uint64_t *h0, uint64_t *h1) {
+// round 1 takes beta + 1 indices (the last is u's, reported through u_index: round 2 needs it); round 2 takes beta and reads u at u_index
+static int kg_rkg1(sfg_ctx *ctx, const char *what, bool sampled, const uint64_t *crp, const int8_t *u, const int32_t *e0, const int32_t *e1, uint64_t *h0, uint64_t *h1,
+                   uint64_t *first_index, uint64_t *u_index) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(kg_check_sk(ctx, "rkg_round1"));
-    if (!crp || !u || !e0 || !e1 || !h0 || !h1) SFG_FAIL(ctx, "rkg_round1: NULL polynomial or output");
+    SFG_TRY(kg_check_sk(ctx, what));
+    if (!crp || !h0 || !h1 || (sampled ? !u_index : (!u || !e0 || !e1))) SFG_FAIL(ctx, "%s: NULL polynomial or output%s", what, sampled ? " or u_index (round 2 needs it)" : "");
     KgRkgSrc src{u, e0, e1, nullptr, 0, 0};
+    if (sampled) {
+        SFG_TRY(kg_sample(ctx, what, ctx->beta + 1, &src.key, &src.index0, first_index));
+        *u_index = src.u_index = src.index0 + (u64)ctx->beta;
+    }
     return kg_run_rkg<1>(ctx, src, (const u64 *)crp, nullptr, (u64 *)h0, (u64 *)h1);
 }
-extern "C" int sfg_rkg_round1_sampled_dev(sfg_ctx *ctx, const uint64_t *crp, uint64_t *h0, uint64_t *h1, uint64_t *first_index, uint64_t *u_index) {
+static int kg_rkg2(sfg_ctx *ctx, const char *what, bool sampled, const uint64_t *h0agg, const uint64_t *h1agg, const int8_t *u, const int32_t *e2, const int32_t *e3,
+                   uint64_t u_index, uint64_t *out, uint64_t *first_index) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(kg_check_sk(ctx, "rkg_round1_sampled"));
-    if (!crp || !h0 || !h1 || !u_index) SFG_FAIL(ctx, "rkg_round1_sampled: NULL polynomial, output or u_index (round 2 needs it)");
-    SFG_TRY(kg_check_seeded(ctx, "rkg_round1_sampled"));
-    u64 first; SFG_TRY(enc_take_indices(ctx, "rkg_round1_sampled", ctx->beta + 1, &first));
-    if (first_index) *first_index = first;
-    *u_index = first + (u64)ctx->beta;
-    KgRkgSrc src{nullptr, nullptr, nullptr, ctx->sh->enc_key_dev, first, first + (u64)ctx->beta};
-    return kg_run_rkg<1>(ctx, src, (const u64 *)crp, nullptr, (u64 *)h0, (u64 *)h1);
-}
-extern "C" int sfg_rkg_round2_dev(sfg_ctx *ctx, const uint64_t *h0agg, const uint64_t *h1agg, const int8_t *u, const int32_t *e2, const int32_t *e3, uint64_t *out) {
-    SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(kg_check_sk(ctx, "rkg_round2"));
-    if (!h0agg || !h1agg || !u || !e2 || !e3 || !out) SFG_FAIL(ctx, "rkg_round2: NULL polynomial or output");
-    KgRkgSrc src{u, e2, e3, nullptr, 0, 0};
+    SFG_TRY(kg_check_sk(ctx, what));
+    if (!h0agg || !h1agg || !out || (!sampled && (!u || !e2 || !e3))) SFG_FAIL(ctx, "%s: NULL polynomial or output", what);
+    KgRkgSrc src{u, e2, e3, nullptr, 0, (u64)u_index};
+    if (sampled) SFG_TRY(kg_sample(ctx, what, ctx->beta, &src.key, &src.index0, first_index));
     return kg_run_rkg<2>(ctx, src, (const u64 *)h0agg, (const u64 *)h1agg, (u64 *)out, nullptr);
 }
-extern "C" int sfg_rkg_round2_sampled_dev(sfg_ctx *ctx, const uint64_t *h0agg, const uint64_t *h1agg, uint64_t u_index, uint64_t *out, uint64_t *first_index) {
-    SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(kg_check_sk(ctx, "rkg_round2_sampled"));
-    if (!h0agg || !h1agg || !out) SFG_FAIL(ctx, "rkg_round2_sampled: NULL polynomial or output");
-    SFG_TRY(kg_check_seeded(ctx, "rkg_round2_sampled"));
-    u64 first; SFG_TRY(enc_take_indices(ctx, "rkg_round2_sampled", ctx->beta, &first));
-    if (first_index) *first_index = first;
-    KgRkgSrc src{nullptr, nullptr, nullptr, ctx->sh->enc_key_dev, first, (u64)u_index};
-    return kg_run_rkg<2>(ctx, src, (const u64 *)h0agg, (const u64 *)h1agg, (u64 *)out, nullptr);
-}
+extern "C" int sfg_ckg_gen_share_dev(sfg_ctx *ctx, const uint64_t *crp, const int32_t *e, uint64_t *share) { return kg_ckg(ctx, "ckg_gen_share", false, crp, e, share, nullptr); }
+extern "C" int sfg_ckg_gen_share_sampled_dev(sfg_ctx *ctx, const uint64_t *crp, uint64_t *share, uint64_t *first_index) { return kg_ckg(ctx, "ckg_gen_share_sampled", true, crp, nullptr, share, first_index); }
+extern "C" int sfg_rtg_gen_shares_dev(sfg_ctx *ctx, const uint64_t *galois_host, int nkeys, const uint64_t *crp, const int32_t *e, uint64_t *shares) { return kg_rtg(ctx, "rtg_gen_shares", false, galois_host, nkeys, crp, e, shares, nullptr); }
+extern "C" int sfg_rtg_gen_shares_sampled_dev(sfg_ctx *ctx, const uint64_t *galois_host, int nkeys, const uint64_t *crp, uint64_t *shares, uint64_t *first_index) { return kg_rtg(ctx, "rtg_gen_shares_sampled", true, galois_host, nkeys, crp, nullptr, shares, first_index); }
+extern "C" int sfg_rkg_round1_dev(sfg_ctx *ctx, const uint64_t *crp, const int8_t *u, const int32_t *e0, const int32_t *e1, uint64_t *h0, uint64_t *h1) { return kg_rkg1(ctx, "rkg_round1", false, crp, u, e0, e1, h0, h1, nullptr, nullptr); }
+extern "C" int sfg_rkg_round1_sampled_dev(sfg_ctx *ctx, const uint64_t *crp, uint64_t *h0, uint64_t *h1, uint64_t *first_index, uint64_t *u_index) { return kg_rkg1(ctx, "rkg_round1_sampled", true, crp, nullptr, nullptr, nullptr, h0, h1, first_index, u_index); }
+extern "C" int sfg_rkg_round2_dev(sfg_ctx *ctx, const uint64_t *h0agg, const uint64_t *h1agg, const int8_t *u, const int32_t *e2, const int32_t *e3, uint64_t *out) { return kg_rkg2(ctx, "rkg_round2", false, h0agg, h1agg, u, e2, e3, 0, out, nullptr); }
+extern "C" int sfg_rkg_round2_sampled_dev(sfg_ctx *ctx, const uint64_t *h0agg, const uint64_t *h1agg, uint64_t u_index, uint64_t *out, uint64_t *first_index) { return kg_rkg2(ctx, "rkg_round2_sampled", true, h0agg, h1agg, nullptr, nullptr, nullptr, u_index, out, first_index); }
 
 // ---------------------------------------------------------------- installation from device memory
 // key storage [beta][2][nmod][N] (sfg_ctx_load_rotkey's, normal form: the words are kept as they are) from b = agg [beta][nmod][N], a = crp [beta][nmod][N]
 static int kg_install_key(sfg_ctx *ctx, u64 g, const u64 *b, const u64 *a) {
     const int N = SFG_N; const size_t row = (size_t)ctx->nmod * N * 8, words = (size_t)ctx->beta * 2 * ctx->nmod * N;
     RotKey rk;
+    DevMem key_new, index_new;                                  // a new key's storage: owned here until the key is installed
     auto it = ctx->rotkeys().find(g);
     if (it != ctx->rotkeys().end()) rk = it->second;
-    else { SFG_HIP(ctx, hipMalloc(&rk.key_dev, words * 8)); SFG_HIP(ctx, hipMalloc(&rk.index_dev, N * sizeof(uint16_t))); }
+    else {
+        SFG_HIP(ctx, hipMalloc(&key_new.h, words * 8)); SFG_HIP(ctx, hipMalloc(&index_new.h, N * sizeof(uint16_t)));
+        rk.key_dev = (decltype(rk.key_dev))key_new.h; rk.index_dev = (decltype(rk.index_dev))index_new.h;
+    }
     for (int i = 0; i < ctx->beta; i++) {
         SFG_HIP(ctx, hipMemcpyAsync((char *)rk.key_dev + (size_t)(2 * i) * row, (const char *)b + (size_t)i * row, row, hipMemcpyDeviceToDevice, ctx->stream));
         SFG_HIP(ctx, hipMemcpyAsync((char *)rk.key_dev + (size_t)(2 * i + 1) * row, (const char *)a + (size_t)i * row, row, hipMemcpyDeviceToDevice, ctx->stream));
@@ -368,6 +356,7 @@ static int kg_install_key(sfg_ctx *ctx, u64 g, const u64 *b, const u64 *a) {
     std::vector<uint16_t> idx(N); kg_index_table(g, idx.data());
     SFG_TRY(sfg_upload_small(ctx, rk.index_dev, idx.data(), N * sizeof(uint16_t)));
     ctx->rotkeys()[g] = rk;
+    (void)key_new.release(); (void)index_new.release();
     return 0;
 }
 extern "C" int sfg_ctx_install_public_key_dev(sfg_ctx *ctx, const uint64_t *agg, const uint64_t *crp) {
@@ -402,6 +391,7 @@ extern "C" int sfg_crp_fill_dev(sfg_ctx *ctx, const uint8_t *key32, uint64_t fir
     SFG_HIP(ctx, hipSetDevice(ctx->device));
     if (!key32 || (nrows && (!mod_idx_host || !out))) SFG_FAIL(ctx, "crp_fill: NULL key, modulus indices or output");
     if (first_row > ~0ULL - nrows) SFG_FAIL(ctx, "crp_fill: row numbers beyond 2^64");
+    if (nrows > 0x7FFFFFFFu) SFG_FAIL(ctx, "crp_fill: more than 2^31 - 1 rows in one call");        // (256 TiB of output: the plan counts in int)
     for (size_t r = 0; r < nrows; r++) if (mod_idx_host[r] < 0 || mod_idx_host[r] >= ctx->nmod) SFG_FAIL(ctx, "crp_fill: modulus index %d of row %zu out of range", mod_idx_host[r], r);
     if (!nrows) return 0;
     ApiScope scope(ctx);
@@ -411,8 +401,9 @@ extern "C" int sfg_crp_fill_dev(sfg_ctx *ctx, const uint8_t *key32, uint64_t fir
     CrpKey key;                                     // passed by value: the context keeps no copy of the seed
     for (int i = 0; i < 8; i++) key.k[i] = (uint32_t)key32[4 * i] | (uint32_t)key32[4 * i + 1] << 8 | (uint32_t)key32[4 * i + 2] << 16 | (uint32_t)key32[4 * i + 3] << 24;
     PhaseTimer timer(ctx, "crp_fill");
-    for (size_t r0 = 0; r0 < nrows; r0 += 32768) {      // (the grid's second dimension ends at 65535)
-        const size_t nr = nrows - r0 < 32768 ? nrows - r0 : 32768;
+    const BatchPlan plan = grid_rows_plan((int)nrows);  // (the grid's second dimension)
+    for (int c = 0; c < plan.nchunks; c++) {
+        const size_t r0 = (size_t)plan.first(c), nr = (size_t)plan.count(c, (int)nrows);
         hipLaunchKernelGGL(k_crp_fill, dim3(SFG_N / 256, (unsigned)nr), dim3(256), 0, ctx->stream, key, (u64)first_row + r0, (const int *)mp + r0, ctx->modc, (u64 *)out + r0 * SFG_N);
         SFG_HIP(ctx, hipGetLastError());
     }

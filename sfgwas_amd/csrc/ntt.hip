@@ -555,7 +555,7 @@ int launch_ntt_fwd_staged(sfg_ctx *ctx, const u64 *in, u64 *out, size_t nrows, c
 }
 int launch_ntt_plain(sfg_ctx *ctx, const double *pc, u64 *out, size_t nplain, int L) {
     if (!nplain) return 0;
-    ModPattern pat; pat.period = L; for (int l = 0; l < L; l++) pat.m[l] = (int8_t)l;
+    const ModPattern pat = mod_pattern_run(0, L);
     hipLaunchKernelGGL(k_ntt_fwd<1>, dim3((unsigned)(nplain * L)), dim3(512), LDS_DOUBLES * 8, ctx->stream, (const void *)pc, out, pat, dense_map(), ctx->tw_fwd, ctx->pack_fwd, ctx->modc);
     SFG_HIP(ctx, hipGetLastError());
     return 0;

@@ -199,13 +199,6 @@ static int scale_ratio(sfg_ctx *ctx, int level, double ct_scale, double target_s
     return 0;
 }
 
-static int refresh_check(sfg_ctx *ctx, int nct, int level) {
-    if (level < 0 || level >= ctx->nq) SFG_FAIL(ctx, "refresh: level %d out of range", level);
-    if (level + 1 > RF_MAXL) SFG_FAIL(ctx, "refresh: more than %d moduli at the input level", RF_MAXL);
-    if (nct < 0) SFG_FAIL(ctx, "refresh: negative ciphertext count");
-    return 0;
-}
-
 static int refresh_gen_shares(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, const uint64_t *crs, const uint64_t *mask, int W,
                               const int32_t *e0, const int32_t *e1, uint64_t *h0, uint64_t *h1, const ScaleRatio *sr);
 extern "C" int sfg_refresh_gen_shares_dev(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, const uint64_t *crs, const uint64_t *mask, int W,
@@ -214,7 +207,7 @@ extern "C" int sfg_refresh_gen_shares_dev(sfg_ctx *ctx, const uint64_t *ct, int 
 }
 extern "C" int sfg_refresh_gen_shares_scaled_dev(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, double ct_scale, double target_scale, const uint64_t *crs,
                                                  const uint64_t *mask, int W, const int32_t *e0, const int32_t *e1, uint64_t *h0, uint64_t *h1) {
-    if (level < 0 || level >= ctx->nq) SFG_FAIL(ctx, "refresh: level %d out of range", level);
+    SFG_TRY(check_level_count(ctx, "refresh", 0, level, 0));                 // (the level alone: scale_ratio reads the moduli up to it)
     if (ct_scale == target_scale) return refresh_gen_shares(ctx, ct, nct, level, crs, mask, W, e0, e1, h0, h1, nullptr);     // ratio 1: the unscaled kernels (Quo(mask * x, x) = mask)
     ScaleRatio sr; SFG_TRY(scale_ratio(ctx, level, ct_scale, target_scale, sr));
     if (W > BG) SFG_FAIL(ctx, "refresh: mask limb count %d exceeds %d in the target-scale form", W, BG);
@@ -226,26 +219,28 @@ extern "C" int sfg_refresh_gen_shares_scaled_dev(sfg_ctx *ctx, const uint64_t *c
 static int refresh_gen_shares(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, const uint64_t *crs, const uint64_t *mask, int W,
                               const int32_t *e0, const int32_t *e1, uint64_t *h0, uint64_t *h1, const ScaleRatio *sr) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(refresh_check(ctx, nct, level));
+    SFG_TRY(check_level_count(ctx, "refresh", nct, level, RF_MAXL));
     if (!ctx->sh->sk_dev) SFG_FAIL(ctx, "refresh: no secret-key shard loaded (sfg_ctx_load_secret_key)");
     if (W < 1 || W > 16) SFG_FAIL(ctx, "refresh: mask limb count %d out of range", W);
-    if (!nct) return 0;
     const int N = SFG_N, nl = level + 1, nq = ctx->nq;
-    const u64 *sk = ctx->sh->sk_dev;
-    // h0: rows (mask + e0) mod q_j, j <= level -> NTT -> + sk (.) c1
-    hipLaunchKernelGGL(k_bigint_rows, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const u64 *)mask, W, (const int *)e0, (u64 *)h0, nl, ctx->modc);
-    SFG_HIP(ctx, hipGetLastError());
-    ModPattern p0; p0.period = nl; for (int j = 0; j < nl; j++) p0.m[j] = (int8_t)j;
-    SFG_TRY(launch_ntt_fwd(ctx, (const u64 *)h0, (u64 *)h0, (size_t)nct * nl, p0));
-    hipLaunchKernelGGL(k_share, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const u64 *)h0, (size_t)nl * N, sk, (const u64 *)ct + (size_t)nl * N, (size_t)2 * nl * N, (u64 *)h0, nl, 0, ctx->modc);
-    // h1: all nq moduli, against the common reference polynomial, negated
-    if (sr) hipLaunchKernelGGL(k_bigint_rows_scaled, dim3(N / 256, nct), dim3(256), 0, ctx->stream, (const u64 *)mask, W, (const int *)e1, (u64 *)h1, nq, *sr, ctx->modc);
-    else hipLaunchKernelGGL(k_bigint_rows, dim3(N / 256, nq, nct), dim3(256), 0, ctx->stream, (const u64 *)mask, W, (const int *)e1, (u64 *)h1, nq, ctx->modc);
-    SFG_HIP(ctx, hipGetLastError());
-    ModPattern p1; p1.period = nq; for (int j = 0; j < nq; j++) p1.m[j] = (int8_t)j;
-    SFG_TRY(launch_ntt_fwd(ctx, (const u64 *)h1, (u64 *)h1, (size_t)nct * nq, p1));
-    hipLaunchKernelGGL(k_share, dim3(N / 256, nq, nct), dim3(256), 0, ctx->stream, (const u64 *)h1, (size_t)nq * N, sk, (const u64 *)crs, (size_t)nq * N, (u64 *)h1, nq, 1, ctx->modc);
-    SFG_HIP(ctx, hipGetLastError());
+    const size_t mw = (size_t)N * W, ctw = (size_t)2 * nl * N, r0w = (size_t)nl * N, r1w = (size_t)nq * N;     // words of one item: mask, ciphertext, h0, h1 and crs
+    const BatchPlan plan = grid_rows_plan(nct);
+    for (int c = 0; c < plan.nchunks; c++) {
+        const size_t c0 = (size_t)plan.first(c); const int nb = plan.count(c, nct);
+        const u64 *maskc = (const u64 *)mask + c0 * mw;
+        u64 *h0c = (u64 *)h0 + c0 * r0w, *h1c = (u64 *)h1 + c0 * r1w;
+        // h0: rows (mask + e0) mod q_j, j <= level -> NTT -> + sk (.) c1
+        hipLaunchKernelGGL(k_bigint_rows, dim3(N / 256, nl, nb), dim3(256), 0, ctx->stream, maskc, W, (const int *)e0 + c0 * N, h0c, nl, ctx->modc);
+        SFG_HIP(ctx, hipGetLastError());
+        SFG_TRY(launch_ntt_fwd(ctx, h0c, h0c, (size_t)nb * nl, mod_pattern_run(0, nl)));
+        SFG_TRY(launch_share(ctx, h0c, r0w, (const u64 *)ct + c0 * ctw + r0w, ctw, h0c, nl, nb));
+        // h1: all nq moduli, against the common reference polynomial, negated
+        if (sr) hipLaunchKernelGGL(k_bigint_rows_scaled, dim3(N / 256, nb), dim3(256), 0, ctx->stream, maskc, W, (const int *)e1 + c0 * N, h1c, nq, *sr, ctx->modc);
+        else hipLaunchKernelGGL(k_bigint_rows, dim3(N / 256, nq, nb), dim3(256), 0, ctx->stream, maskc, W, (const int *)e1 + c0 * N, h1c, nq, ctx->modc);
+        SFG_HIP(ctx, hipGetLastError());
+        SFG_TRY(launch_ntt_fwd(ctx, h1c, h1c, (size_t)nb * nq, mod_pattern_run(0, nq)));
+        SFG_TRY(launch_share(ctx, h1c, r1w, (const u64 *)crs + c0 * r1w, r1w, h1c, nq, nb, 1));
+    }
     return 0;
 }
 
@@ -256,24 +251,31 @@ static int refresh_gen_shares(sfg_ctx *ctx, const uint64_t *ct, int nct, int lev
 extern "C" int sfg_ckks_to_ss_share_dev(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, const uint64_t *mask, int W, const int32_t *e0,
                                         uint64_t *h0, uint64_t *mask_ntt) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(refresh_check(ctx, nct, level));
+    SFG_TRY(check_level_count(ctx, "refresh", nct, level, RF_MAXL));
     if (!ctx->sh->sk_dev) SFG_FAIL(ctx, "CMatToSS: no secret-key shard loaded (sfg_ctx_load_secret_key)");
     if (W < 1 || W > 16) SFG_FAIL(ctx, "CMatToSS: mask limb count %d out of range", W);
     if (!nct) return 0;
+    ApiScope scope(ctx);
     const int N = SFG_N, nl = level + 1;
+    const size_t mw = (size_t)N * W, ctw = (size_t)2 * nl * N, roww = (size_t)nl * N;
+    const RefreshWords rw = refresh_words(nl, (size_t)N);
+    const BatchPlan plan = grid_rows_plan(nct, rw.zero_e);
     int *zero = nullptr;
-    SFG_TRY(sfg_scratch(ctx, "refresh.zero_e", (size_t)nct * N * sizeof(int), (void **)&zero));
-    SFG_HIP(ctx, hipMemsetAsync(zero, 0, (size_t)nct * N * sizeof(int), ctx->stream));
-    ModPattern p0; p0.period = nl; for (int j = 0; j < nl; j++) p0.m[j] = (int8_t)j;
-    hipLaunchKernelGGL(k_bigint_rows, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const u64 *)mask, W, (const int *)zero, (u64 *)mask_ntt, nl, ctx->modc);
-    SFG_HIP(ctx, hipGetLastError());
-    SFG_TRY(launch_ntt_fwd(ctx, (const u64 *)mask_ntt, (u64 *)mask_ntt, (size_t)nct * nl, p0));
-    hipLaunchKernelGGL(k_small_rows, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const int *)e0, (u64 *)h0, nl, ctx->modc);
-    SFG_HIP(ctx, hipGetLastError());
-    SFG_TRY(launch_ntt_fwd(ctx, (const u64 *)h0, (u64 *)h0, (size_t)nct * nl, p0));
-    hipLaunchKernelGGL(k_add_rows, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const u64 *)h0, (size_t)nl * N, (const u64 *)mask_ntt, (size_t)nl * N, (u64 *)h0, (size_t)nl * N, ctx->modc);
-    hipLaunchKernelGGL(k_share, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const u64 *)h0, (size_t)nl * N, ctx->sh->sk_dev, (const u64 *)ct + (size_t)nl * N, (size_t)2 * nl * N, (u64 *)h0, nl, 0, ctx->modc);
-    SFG_HIP(ctx, hipGetLastError());
+    SFG_TRY(sfg_scratch(ctx, "refresh.zero_e", plan.bytes, (void **)&zero));
+    SFG_HIP(ctx, hipMemsetAsync(zero, 0, plan.bytes, ctx->stream));
+    const ModPattern p0 = mod_pattern_run(0, nl);
+    for (int c = 0; c < plan.nchunks; c++) {
+        const size_t c0 = (size_t)plan.first(c); const int nb = plan.count(c, nct);
+        u64 *mc = (u64 *)mask_ntt + c0 * roww, *h0c = (u64 *)h0 + c0 * roww;
+        hipLaunchKernelGGL(k_bigint_rows, dim3(N / 256, nl, nb), dim3(256), 0, ctx->stream, (const u64 *)mask + c0 * mw, W, (const int *)zero, mc, nl, ctx->modc);
+        SFG_HIP(ctx, hipGetLastError());
+        SFG_TRY(launch_ntt_fwd(ctx, mc, mc, (size_t)nb * nl, p0));
+        hipLaunchKernelGGL(k_small_rows, dim3(N / 256, nl, nb), dim3(256), 0, ctx->stream, (const int *)e0 + c0 * N, h0c, nl, ctx->modc);
+        SFG_HIP(ctx, hipGetLastError());
+        SFG_TRY(launch_ntt_fwd(ctx, h0c, h0c, (size_t)nb * nl, p0));
+        SFG_TRY(launch_add_rows(ctx, h0c, roww, mc, roww, h0c, roww, nl, nb));
+        SFG_TRY(launch_share(ctx, h0c, roww, (const u64 *)ct + c0 * ctw + roww, ctw, h0c, nl, nb));
+    }
     return 0;
 }
 
@@ -309,7 +311,7 @@ extern "C" int sfg_refresh_finish_dev(sfg_ctx *ctx, const uint64_t *ct, int nct,
 }
 extern "C" int sfg_refresh_finish_scaled_dev(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, double ct_scale, double target_scale, const uint64_t *h0agg,
                                              const uint64_t *h1agg, const uint64_t *crs, uint64_t *out) {
-    if (level < 0 || level >= ctx->nq) SFG_FAIL(ctx, "refresh: level %d out of range", level);
+    SFG_TRY(check_level_count(ctx, "refresh", 0, level, 0));
     if (ct_scale == target_scale) return refresh_finish(ctx, ct, nct, level, h0agg, h1agg, crs, out, nullptr);
     ScaleRatio sr; SFG_TRY(scale_ratio(ctx, level, ct_scale, target_scale, sr));
     return refresh_finish(ctx, ct, nct, level, h0agg, h1agg, crs, out, &sr);
@@ -317,37 +319,41 @@ extern "C" int sfg_refresh_finish_scaled_dev(sfg_ctx *ctx, const uint64_t *ct, i
 static int refresh_finish(sfg_ctx *ctx, const uint64_t *ct, int nct, int level, const uint64_t *h0agg, const uint64_t *h1agg, const uint64_t *crs,
                           uint64_t *out, const ScaleRatio *sr) {
     SFG_HIP(ctx, hipSetDevice(ctx->device));
-    SFG_TRY(refresh_check(ctx, nct, level));
+    SFG_TRY(check_level_count(ctx, "refresh", nct, level, RF_MAXL));
     if (!nct) return 0;
+    ApiScope scope(ctx);
     const int N = SFG_N, nl = level + 1, nq = ctx->nq;
+    const BatchPlan plan = grid_rows_plan(nct, refresh_words(nl, (size_t)N).x);
     u64 *x = nullptr;
-    SFG_TRY(sfg_scratch(ctx, "refresh.x", (size_t)nct * nl * N * 8, (void **)&x));
-    // Decrypt: c0 + h0agg, then to the coefficient domain
-    hipLaunchKernelGGL(k_add_rows, dim3(N / 256, nl, nct), dim3(256), 0, ctx->stream, (const u64 *)ct, (size_t)2 * nl * N, (const u64 *)h0agg, (size_t)nl * N, x, (size_t)nl * N, ctx->modc);
-    SFG_HIP(ctx, hipGetLastError());
-    ModPattern p0; p0.period = nl; for (int j = 0; j < nl; j++) p0.m[j] = (int8_t)j;
-    SFG_TRY(launch_ntt_inv(ctx, x, x, (size_t)nct * nl, p0));
-    // Recode into all nq moduli
+    SFG_TRY(sfg_scratch(ctx, "refresh.x", plan.bytes, (void **)&x));
+    const DecSrc src = DecSrc::finish((const u64 *)ct, (const u64 *)h0agg);
     RecodeConst rc; recode_constants(ctx, level, rc);
+    RecodeBig rb; memset(&rb, 0, sizeof rb);
     if (sr) {
-        RecodeBig rb; memset(&rb, 0, sizeof rb);
         HBig Q(1); for (int i = 0; i < nl; i++) { Q.mul_small(ctx->q[i]); rb.qi[i] = ctx->q[i]; }
         for (size_t i = 0; i < Q.w.size() && i < (size_t)BG; i++) rb.Q[i] = Q.w[i];
-        hipLaunchKernelGGL(k_recode_scaled, dim3(N / 256, nct), dim3(256), 0, ctx->stream, (const u64 *)x, (u64 *)out, rc, rb, *sr, ctx->modc);
-    } else hipLaunchKernelGGL(k_recode, dim3(N / 256, nct), dim3(256), 0, ctx->stream, (const u64 *)x, (u64 *)out, rc, ctx->modc);
-    SFG_HIP(ctx, hipGetLastError());
-    ModPattern p1; p1.period = nq; for (int j = 0; j < nq; j++) p1.m[j] = (int8_t)j;
+    }
     RowMap rm; rm.rpg = nq; rm.gstride_in = rm.gstride_out = (size_t)2 * nq * N;           // polynomial 0 of every output ciphertext
-    SFG_TRY(launch_ntt_fwd_map(ctx, (const u64 *)out, (u64 *)out, (size_t)nct * nq, p1, rm));
-    // Recrypt
-    hipLaunchKernelGGL(k_recrypt, dim3(N / 256, nq, nct), dim3(256), 0, ctx->stream, (u64 *)out, (const u64 *)h1agg, (const u64 *)crs, nq, ctx->modc);
-    SFG_HIP(ctx, hipGetLastError());
+    for (int c = 0; c < plan.nchunks; c++) {
+        const size_t c0 = (size_t)plan.first(c); const int nb = plan.count(c, nct);
+        u64 *outc = (u64 *)out + c0 * 2 * nq * N;
+        // Decrypt: c0 + h0agg, then to the coefficient domain
+        SFG_TRY(launch_dec_front(ctx, src, (int)c0, nb, nl, x));
+        // Recode into all nq moduli
+        if (sr) hipLaunchKernelGGL(k_recode_scaled, dim3(N / 256, nb), dim3(256), 0, ctx->stream, (const u64 *)x, outc, rc, rb, *sr, ctx->modc);
+        else hipLaunchKernelGGL(k_recode, dim3(N / 256, nb), dim3(256), 0, ctx->stream, (const u64 *)x, outc, rc, ctx->modc);
+        SFG_HIP(ctx, hipGetLastError());
+        SFG_TRY(launch_ntt_fwd_map(ctx, outc, outc, (size_t)nb * nq, mod_pattern_run(0, nq), rm));
+        // Recrypt
+        hipLaunchKernelGGL(k_recrypt, dim3(N / 256, nq, nb), dim3(256), 0, ctx->stream, outc, (const u64 *)h1agg + c0 * nq * N, (const u64 *)crs + c0 * nq * N, nq, ctx->modc);
+        SFG_HIP(ctx, hipGetLastError());
+    }
     return 0;
 }
 
-// ---- launch interface for decrypt.hip (the kernels above, strided)
-int launch_share(sfg_ctx *ctx, const u64 *rows, size_t rows_ct_stride, const u64 *xr, size_t x_ct_stride, u64 *h, int nl, int nct) {
-    hipLaunchKernelGGL(k_share, dim3(SFG_N / 256, nl, nct), dim3(256), 0, ctx->stream, rows, rows_ct_stride, (const u64 *)ctx->sh->sk_dev, xr, x_ct_stride, h, nl, 0, ctx->modc);
+// ---- launch interface (the kernels above, strided): the entry points here, decrypt.hip and rvec.hip
+int launch_share(sfg_ctx *ctx, const u64 *rows, size_t rows_ct_stride, const u64 *xr, size_t x_ct_stride, u64 *h, int nl, int nct, int neg) {
+    hipLaunchKernelGGL(k_share, dim3(SFG_N / 256, nl, nct), dim3(256), 0, ctx->stream, rows, rows_ct_stride, (const u64 *)ctx->sh->sk_dev, xr, x_ct_stride, h, nl, neg, ctx->modc);
     SFG_HIP(ctx, hipGetLastError());
     return 0;
 }

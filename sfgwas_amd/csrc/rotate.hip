@@ -370,11 +370,11 @@ static int launch_keyswitch_jobs(sfg_ctx *ctx, const KswBatch &bt, const KswJobs
         return 0;
     };
     ModPattern pq; pq.period = nl; for (int m = 0; m < nl; m++) pq.m[m] = m < nq_out ? (int8_t)m : (int8_t)-2;
-    ModPattern pin; pin.period = nl; for (int m = 0; m < nl; m++) pin.m[m] = (int8_t)m;
+    const ModPattern pin = mod_pattern_run(0, nl);
     ModPattern pext; pext.period = kc.beta * kc.nt;
     for (int i = 0; i < kc.beta; i++) for (int t = 0; t < kc.nt; t++)           // in-digit rows and the targets the finish does not store: nobody reads them
         pext.m[i * kc.nt + t] = (kc.digit_of[t] == i || (t >= nq_out && t < nl)) ? (int8_t)-2 : (int8_t)kc.tmod[t];
-    ModPattern pp; pp.period = kc.np; for (int p = 0; p < kc.np; p++) pp.m[p] = (int8_t)(ctx->nq + p);
+    const ModPattern pp = mod_pattern_run(ctx->nq, kc.np);
     RowMap rm_dense; rm_dense.rpg = 1; rm_dense.gstride_in = N; rm_dense.gstride_out = N;
     for (const KswGroup &g : groups) {
         const int i0 = g.i0, ni = g.ni;

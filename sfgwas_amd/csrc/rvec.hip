@@ -25,7 +25,7 @@
 //     pre-pass's store address, the twist is inside the pre-pass (decode) or the post-pass (encode), the slot permutation is the pre-pass's (encode) or the
 //     post-pass's (decode) address: no pass of its own for any of them;
 //   * HBM and LDS images are limb-planar, [re, im][word][point]: the loads of one word by a wave are consecutive.
-// Scratch, from the context's pool and per ciphertext of a chunk of at most 64: 2 W 65,536 B ("rvec.fft") + (level + 1) 131,072 B ("rvec.coef").
+// Scratch, from the context's pool and per ciphertext of a chunk (rvec_batch_plan, batch_plan.hpp): 2 W 65,536 B ("rvec.fft") + (level + 1) 131,072 B ("rvec.coef").
 //
 // Error, in units of 2^-g (derivation: DESIGN.md 12).  A complex product truncates two real products per component: below 2 units per component, 2 sqrt 2 in modulus.
 // Point errors add through the butterflies with unit gain, so an output collects the truncations of every product of its tree, the twist's included: fewer than
@@ -203,16 +203,15 @@ int sfg_rvec_init(sfg_ctx *ctx) {
     std::vector<uint16_t> sm(RV_n);
     u64 g = 1;
     for (int t = 0; t < RV_n; t++) { sm[t] = (uint16_t)(((g - 1) / 4) % RV_n); g = (g * 5) % (2ULL * RV_N); }
-    u64 *roots_dev = nullptr;
+    DevMem roots_dev;                                           // the base roots: needed until the table is built
     SFG_HIP(ctx, hipMalloc(&rt->tw, (size_t)2 * T * RV_TWN * 8));
     SFG_HIP(ctx, hipMalloc(&rt->slot_m, RV_n * sizeof(uint16_t)));
-    SFG_HIP(ctx, hipMalloc(&roots_dev, roots.size() * 8));
-    hipError_t e = hipMemcpy(roots_dev, roots.data(), roots.size() * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(rt->slot_m, sm.data(), RV_n * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) { hipLaunchKernelGGL(k_rvec_table, dim3(RV_TWN / 64), dim3(64), 0, 0, (const u64 *)roots_dev, rt->tw); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(roots_dev);
-    SFG_HIP(ctx, e);
+    SFG_HIP(ctx, hipMalloc(&roots_dev.h, roots.size() * 8));
+    SFG_HIP(ctx, hipMemcpy(roots_dev.h, roots.data(), roots.size() * 8, hipMemcpyHostToDevice));
+    SFG_HIP(ctx, hipMemcpy(rt->slot_m, sm.data(), RV_n * sizeof(uint16_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_rvec_table, dim3(RV_TWN / 64), dim3(64), 0, 0, (const u64 *)roots_dev.h, rt->tw);
+    SFG_HIP(ctx, hipGetLastError());
+    SFG_HIP(ctx, hipDeviceSynchronize());
     return 0;
 }
 void sfg_rvec_destroy(SfgShared *sh) {
@@ -221,8 +220,6 @@ void sfg_rvec_destroy(SfgShared *sh) {
     (void)hipFree(rt->tw); (void)hipFree(rt->slot_m);
     delete rt; sh->rvec_tables = nullptr;
 }
-
-constexpr int RVEC_CHUNK = 64;
 
 #define RVEC_BY_W(W_, ...) do { switch (W_) { case 2: { constexpr int W = 2; __VA_ARGS__; } break; case 3: { constexpr int W = 3; __VA_ARGS__; } break; \
     case 4: { constexpr int W = 4; __VA_ARGS__; } break; case 5: { constexpr int W = 5; __VA_ARGS__; } break; case 6: { constexpr int W = 6; __VA_ARGS__; } break; \
@@ -239,22 +236,24 @@ extern "C" int sfg_rvec_encode_dev(sfg_ctx *ctx, int limbs, const uint64_t *modu
     SFG_HIP(ctx, hipSetDevice(ctx->device));
     RvecPlan pl;
     if (const char *e = rvec_plan_encode(limbs, modulus_host, (const uint64_t *)ctx->q, ctx->nq, n_elem, level, scale, frac_bits, pl)) SFG_FAIL(ctx, "rvec_encode: %s", e);
-    if (nct < 0) SFG_FAIL(ctx, "rvec_encode: negative count %d", nct);
+    SFG_TRY(check_level_count(ctx, "rvec_encode", nct, level, 0));
     if (!nct) return 0;
     if (!share_dev || !pt_dev) SFG_FAIL(ctx, "rvec_encode: NULL shares or output");
     ApiScope scope(ctx);
     const RvecTables *rt = (const RvecTables *)ctx->sh->rvec_tables;
     RvecField f; rvec_field(limbs, modulus_host, f);
-    const int nl = level + 1, chunk = nct < RVEC_CHUNK ? nct : RVEC_CHUNK;
+    const int nl = level + 1;
+    const RvecWords rw = rvec_words(pl.W, nl, (size_t)RV_N);
+    const BatchPlan plan = rvec_batch_plan(nct, rw);
     void *bp = nullptr, *cp = nullptr;
-    SFG_TRY(sfg_scratch(ctx, "rvec.fft", (size_t)chunk * 2 * pl.W * RV_n * 8, &bp));
-    SFG_TRY(sfg_scratch(ctx, "rvec.coef", (size_t)chunk * nl * RV_N * 8, &cp));
+    SFG_TRY(sfg_scratch(ctx, "rvec.fft", plan.bytes_of(rw.fft), &bp));
+    SFG_TRY(sfg_scratch(ctx, "rvec.coef", plan.bytes_of(rw.coef), &cp));
     u64 *buf = (u64 *)bp, *coef = (u64 *)cp;
-    ModPattern p0; p0.period = nl; for (int j = 0; j < nl; j++) p0.m[j] = (int8_t)j;
+    const ModPattern p0 = mod_pattern_run(0, nl);
     PhaseTimer timer(ctx, "rvec_encode");
     int launches = 0;
-    for (int c0 = 0; c0 < nct; c0 += chunk) {
-        const int nb = nct - c0 < chunk ? nct - c0 : chunk;
+    for (int c = 0; c < plan.nchunks; c++) {
+        const int c0 = plan.first(c), nb = plan.count(c, nct);
         const u64 *src = (const u64 *)share_dev + (size_t)c0 * n_elem * limbs;
         RVEC_BY_W(pl.W, {
             hipLaunchKernelGGL(k_rvec_enc_pre<W>, dim3(RV_n / 256, nb), dim3(256), 0, ctx->stream, src, f, n_elem, pl.g, (const uint16_t *)rt->slot_m, buf);
@@ -270,33 +269,24 @@ extern "C" int sfg_rvec_encode_dev(sfg_ctx *ctx, int limbs, const uint64_t *modu
     return 0;
 }
 
-enum RvecSrc { RVEC_PT, RVEC_FINISH };
-// INTT (of the rows, or of c0 + h0agg) and the decoder, for nct plaintexts, in chunks
-static int rvec_decode_run(sfg_ctx *ctx, const char *what, RvecSrc mode, const RvecPlan &pl, const RvecField &f, const u64 *src, size_t stride, const u64 *h0agg,
-                           int nct, int level, int n_elem, u64 *out) {
+// the decryption front end (decrypt.hip: INTT of the rows, or of c0 + h0agg) and the decoder, for nct plaintexts, in the chunks of rvec_batch_plan
+static int rvec_decode_run(sfg_ctx *ctx, const char *what, const DecSrc &src, const RvecPlan &pl, const RvecField &f, int nct, int level, int n_elem, u64 *out) {
     ApiScope scope(ctx);
     const RvecTables *rt = (const RvecTables *)ctx->sh->rvec_tables;
-    const int nl = level + 1, chunk = nct < RVEC_CHUNK ? nct : RVEC_CHUNK;
-    if (nl > RF_MAXL) SFG_FAIL(ctx, "%s: more than %d moduli at the input level", what, RF_MAXL);
+    const int nl = level + 1;
+    SFG_TRY(check_level_count(ctx, what, nct, level, RF_MAXL));
+    const RvecWords rw = rvec_words(pl.W, nl, (size_t)RV_N);
+    const BatchPlan plan = rvec_batch_plan(nct, rw);
     void *bp = nullptr, *cp = nullptr;
-    SFG_TRY(sfg_scratch(ctx, "rvec.fft", (size_t)chunk * 2 * pl.W * RV_n * 8, &bp));
-    SFG_TRY(sfg_scratch(ctx, "rvec.coef", (size_t)chunk * nl * RV_N * 8, &cp));
+    SFG_TRY(sfg_scratch(ctx, "rvec.fft", plan.bytes_of(rw.fft), &bp));
+    SFG_TRY(sfg_scratch(ctx, "rvec.coef", plan.bytes_of(rw.coef), &cp));
     u64 *buf = (u64 *)bp, *x = (u64 *)cp;
     RecodeConst rc; recode_constants(ctx, level, rc);
-    ModPattern p0; p0.period = nl; for (int j = 0; j < nl; j++) p0.m[j] = (int8_t)j;
-    const size_t ctw = (size_t)2 * nl * RV_N, roww = (size_t)nl * RV_N;
     PhaseTimer timer(ctx, "rvec_decode");
     int launches = 0;
-    for (int c0 = 0; c0 < nct; c0 += chunk) {
-        const int nb = nct - c0 < chunk ? nct - c0 : chunk;
-        if (mode == RVEC_PT) {
-            RowMap rm; rm.rpg = nl; rm.gstride_in = stride; rm.gstride_out = roww;
-            SFG_TRY(launch_ntt_inv_map(ctx, src + (size_t)c0 * stride, x, (size_t)nb * nl, p0, rm));
-        } else {
-            SFG_TRY(launch_add_rows(ctx, src + (size_t)c0 * ctw, ctw, h0agg + (size_t)c0 * roww, roww, x, roww, nl, nb));
-            SFG_TRY(launch_ntt_inv(ctx, x, x, (size_t)nb * nl, p0));
-            launches++;
-        }
+    for (int c = 0; c < plan.nchunks; c++) {
+        const int c0 = plan.first(c), nb = plan.count(c, nct);
+        SFG_TRY(launch_dec_front(ctx, src, c0, nb, nl, x, &launches));
         RVEC_BY_W(pl.W, {
             hipLaunchKernelGGL(k_rvec_dec_pre<W>, dim3(RV_n / 256, nb), dim3(256), 0, ctx->stream, (const u64 *)x, rc, (const ModConst *)ctx->modc, (const u64 *)rt->tw, pl.g, buf);
             rvec_fft_launch<W>(ctx, buf, rt->tw, nb, 0);
@@ -316,12 +306,12 @@ extern "C" int sfg_rvec_decode_dev(sfg_ctx *ctx, int limbs, const uint64_t *modu
     SFG_HIP(ctx, hipSetDevice(ctx->device));
     RvecPlan pl;
     if (const char *e = rvec_plan_decode(limbs, modulus_host, (const uint64_t *)ctx->q, ctx->nq, n_elem, level, scale, frac_bits, pl)) SFG_FAIL(ctx, "rvec_decode: %s", e);
-    if (nct < 0) SFG_FAIL(ctx, "rvec_decode: negative count %d", nct);
+    SFG_TRY(check_level_count(ctx, "rvec_decode", nct, level, 0));
     if (pt_stride < (size_t)(level + 1) * RV_N) SFG_FAIL(ctx, "rvec_decode: plaintext stride %zu below (level + 1) * N", pt_stride);
     if (!nct) return 0;
     if (!pt_dev || !out_dev) SFG_FAIL(ctx, "rvec_decode: NULL plaintexts or output");
     RvecField f; rvec_field(limbs, modulus_host, f);
-    return rvec_decode_run(ctx, "rvec_decode", RVEC_PT, pl, f, (const u64 *)pt_dev, pt_stride, nullptr, nct, level, n_elem, (u64 *)out_dev);
+    return rvec_decode_run(ctx, "rvec_decode", DecSrc::rows((const u64 *)pt_dev, pt_stride), pl, f, nct, level, n_elem, (u64 *)out_dev);
 }
 
 // mpc/ss.go:239-279: KeySwitch + Plaintext() on the hub, DecodeRVec of the result and of NTT(mask), the field subtraction
@@ -330,7 +320,7 @@ extern "C" int sfg_ckks_to_ss_finish_dev(sfg_ctx *ctx, int limbs, const uint64_t
     SFG_HIP(ctx, hipSetDevice(ctx->device));
     RvecPlan pl;
     if (const char *e = rvec_plan_decode(limbs, modulus_host, (const uint64_t *)ctx->q, ctx->nq, n_elem, level, scale, frac_bits, pl)) SFG_FAIL(ctx, "ckks_to_ss_finish: %s", e);
-    if (nct < 0) SFG_FAIL(ctx, "ckks_to_ss_finish: negative count %d", nct);
+    SFG_TRY(check_level_count(ctx, "ckks_to_ss_finish", nct, level, 0));
     if (!nct) return 0;
     if (!mask_ntt_dev || !out_dev || (is_hub && (!ct_dev || !h0agg_dev))) SFG_FAIL(ctx, "ckks_to_ss_finish: NULL ciphertexts, shares, masks or output");
     ApiScope scope(ctx);
@@ -338,10 +328,10 @@ extern "C" int sfg_ckks_to_ss_finish_dev(sfg_ctx *ctx, int limbs, const uint64_t
     const size_t cnt = (size_t)nct * n_elem;
     void *ap = nullptr, *mp = nullptr;
     SFG_TRY(sfg_scratch(ctx, "rvec.mask", cnt * limbs * 8, &mp));
-    SFG_TRY(rvec_decode_run(ctx, "ckks_to_ss_finish", RVEC_PT, pl, f, (const u64 *)mask_ntt_dev, (size_t)(level + 1) * RV_N, nullptr, nct, level, n_elem, (u64 *)mp));
+    SFG_TRY(rvec_decode_run(ctx, "ckks_to_ss_finish", DecSrc::rows((const u64 *)mask_ntt_dev, (size_t)(level + 1) * RV_N), pl, f, nct, level, n_elem, (u64 *)mp));
     if (is_hub) {
         SFG_TRY(sfg_scratch(ctx, "rvec.hub", cnt * limbs * 8, &ap));
-        SFG_TRY(rvec_decode_run(ctx, "ckks_to_ss_finish", RVEC_FINISH, pl, f, (const u64 *)ct_dev, 0, (const u64 *)h0agg_dev, nct, level, n_elem, (u64 *)ap));
+        SFG_TRY(rvec_decode_run(ctx, "ckks_to_ss_finish", DecSrc::finish((const u64 *)ct_dev, (const u64 *)h0agg_dev), pl, f, nct, level, n_elem, (u64 *)ap));
     }
     hipLaunchKernelGGL(k_rvec_field_sub, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, (const u64 *)ap, (const u64 *)mp, (u64 *)out_dev, f, cnt);
     SFG_HIP(ctx, hipGetLastError());

@@ -271,3 +271,68 @@ def test_refusals_are_clean_errors(env):
     assert np.array_equal(out, sentinel)                                 # nothing was written by any refused call
     assert L.sfg_decrypt_vectors(ctx.h, d.p, 1, 4, 2.0 ** 34, po, None) == 0 and not np.array_equal(out, sentinel)
     d.free()
+
+
+# ---------------------------------------------------------------- a second chunk at the smallest shapes that reach one (level 0; batch_plan.hpp holds the chunk rules)
+# The refresh entry points (sfg_refresh_gen_shares_dev, sfg_refresh_finish_dev, sfg_ckks_to_ss_share_dev) chunk at 32768 ciphertexts: their second chunk needs
+# more than 8 GB of input and has no GPU test; tests/test_proto_plan.py holds that rule on the CPU.
+def test_shares_second_chunk_at_257_ciphertexts(env):
+    """sfg_pcks_gen_share_dev takes 256 ciphertexts a chunk.  Every item has its own ciphertext and errors; items 255 and 256 against the big-integer statement
+    as in test_shares_every_word_against_big_integers, every item against two calls split at the boundary; h1 = NULL gives the same h0"""
+    ctx, ring, s = env
+    level, nct, cut = 0, 257, 256
+    rnd = np.random.default_rng(257)
+    q = ring.moduli[0]
+    cts = rnd.integers(0, q, (nct, 2, 1, N), dtype=np.uint64)
+    e0 = rnd.integers(-38, 39, (nct, N)).astype(np.int32)
+    e1 = rnd.integers(-38, 39, (nct, N)).astype(np.int32)
+    h0, h1 = ctx.pcks_gen_share(cts, level, e0, e1)
+    assert h0.shape == h1.shape == (nct, 1, N)
+    zero_pk = np.zeros((2, NQ + NP, N), dtype=np.uint64)
+    zero_u = np.zeros(N, dtype=np.int64)
+    sk = ol.secret_ntt(ring, s)
+    for i in (cut - 1, cut):
+        ref = er.encrypt_bigint(ring, level, zero_pk, zero_u, e0[i], e1[i])
+        w0 = np.array([(int(a) + int(b) * int(c)) % q for a, b, c in zip(ref[0][0], sk[0], cts[i, 1, 0])], dtype=np.uint64)
+        assert np.array_equal(h0[i, 0], w0), (i, "h0")
+        assert np.array_equal(h1[i, 0], np.array(ref[0][1], dtype=np.uint64)), (i, "h1")
+    for a, b in ((0, cut), (cut, nct)):
+        p0, p1 = ctx.pcks_gen_share(cts[a:b], level, e0[a:b], e1[a:b])
+        assert np.array_equal(h0[a:b], p0) and np.array_equal(h1[a:b], p1), a
+    h0_only, none = ctx.pcks_gen_share(cts, level, e0)
+    assert none is None and np.array_equal(h0_only, h0)
+
+
+def test_decoder_second_chunk_at_513_plaintexts(env):
+    """the decoder takes 512 plaintexts a chunk.  513 plaintexts of planted centred integers, every one different: sfg_decode_coeffs of items 511 and 512 bit for
+    bit against Python's correctly rounded division (no tolerance), every item against two calls split at the boundary; sfg_decode_vectors, real and complex, of
+    items 511 and 512 against the exact decoder within the header's bound B max|E|, and every item against the split calls"""
+    ctx, ring, s = env
+    level, nct, cut, scale = 0, 513, 512, 2.0 ** 34
+    q = ring.moduli[0]
+    half = q // 2
+    rnd = np.random.default_rng(513)
+    p = rnd.integers(half - q, half, (nct, N))                              # the represented values: floor(Q/2) itself is negative by the Cmp rule
+    p[cut - 1, :4] = [half - q, half - 1, 0, -1]
+    p[cut, :4] = [half - 1, half - q, 1, -2]
+    assert len({row.tobytes() for row in p}) == nct
+    rows = np.stack([ring.ntt(0, (pi % q).astype(np.uint64)) for pi in p])[:, None]          # rows_of, without a Python integer per word
+    assert np.array_equal(rows[cut], rows_of(ring, level, p[cut]))
+    coeffs = ctx.decode_coeffs(rows, level, scale)
+    fs = Fraction(scale)
+    for i in (cut - 1, cut):
+        want = np.array([float(Fraction(int(x)) / fs) for x in p[i]])
+        assert np.array_equal(coeffs[i], want), i
+    assert np.array_equal(coeffs[:cut], ctx.decode_coeffs(rows[:cut], level, scale)) and np.array_equal(coeffs[cut:], ctx.decode_coeffs(rows[cut:], level, scale))
+    re = ctx.decode_vectors(rows, level, scale)
+    re2, im = ctx.decode_vectors(rows, level, scale, want_imag=True)
+    assert np.array_equal(re, re2)
+    for i in (cut - 1, cut):
+        E_re, E_im, _ = decode_ref.decode([int(x) for x in p[i]], N, fs)
+        emax = max(math.hypot(float(a), float(b)) for a, b in zip(E_re, E_im))
+        err = slot_errors(re[i], im[i], E_re, E_im)
+        print(f"item {i}: err_dev = {err:.3e}, B max|E| = {B * emax:.3e}")
+        assert emax > 0 and err <= B * emax, i
+    for a, b in ((0, cut), (cut, nct)):
+        pr, pi_ = ctx.decode_vectors(rows[a:b], level, scale, want_imag=True)
+        assert np.array_equal(re[a:b], pr) and np.array_equal(im[a:b], pi_), a

@@ -240,3 +240,26 @@ def test_refusals_are_clean_errors(env):
             other.encrypt_transcript(0, 1)
     finally:
         other.close()
+
+
+def test_core_second_chunk_at_1366_ciphertexts(env):
+    """level 0: the core's chunk is 2^30 // (2 * 3 * N * 8) = 1365 ciphertexts (batch_plan.hpp enc_core_plan), so 1366 is the smallest call with a second chunk.
+    Every item has its own u, e0, e1 and plaintext.  Items 1364 and 1365, either side of the boundary, word for word against the big-integer statement; every
+    item against the same inputs submitted as two calls split at the boundary (one chunk each)."""
+    ctx, ring, s, pk = env
+    level, nct, cut = 0, 1366, 1365
+    assert cut == (1 << 30) // (2 * (level + 1 + NP) * N * 8)
+    rnd = np.random.default_rng(1366)
+    q = ring.moduli[0]
+    u = rnd.integers(-1, 2, (nct, N)).astype(np.int8)
+    e0 = rnd.integers(-19, 20, (nct, N)).astype(np.int32)
+    e1 = rnd.integers(-19, 20, (nct, N)).astype(np.int32)
+    pt = rnd.integers(0, q, (nct, 1, N), dtype=np.uint64)
+    got = ctx.encrypt_explicit(pt, level, u, e0, e1)
+    assert got.shape == (nct, 2, 1, N) and got.max() < q
+    for i in (cut - 1, cut):
+        c0, c1 = er.encrypt_bigint(ring, level, pk, u[i], e0[i], e1[i])[0]             # {row: (c0 row, c1 row)}
+        assert np.array_equal(got[i, 0, 0], (np.array(c0, dtype=np.uint64) + pt[i, 0]) % np.uint64(q)), i
+        assert np.array_equal(got[i, 1, 0], np.array(c1, dtype=np.uint64)), i
+    assert np.array_equal(got[:cut], ctx.encrypt_explicit(pt[:cut], level, u[:cut], e0[:cut], e1[:cut]))
+    assert np.array_equal(got[cut:], ctx.encrypt_explicit(pt[cut:], level, u[cut:], e0[cut:], e1[cut:]))

@@ -332,3 +332,43 @@ def test_two_parties_shares_to_ciphertext_and_back(two_parties, limbs):
     assert bound_ct < 2 ** 30 and bound_ss < 2 ** 30                    # the bounds mean something against |x| up to 2^50: below one unit of x / 2^f
     assert dev_ct <= bound_ct
     assert dev_ss <= bound_ss
+
+
+# ---------------------------------------------------------------- a second chunk: the encoder and the decoder take 64 plaintexts a chunk (batch_plan.hpp)
+def test_encode_second_chunk_at_65_share_vectors(ctx):
+    """65 share vectors of 100 seeded elements, every one different, at the lowest level the 128-bit field is accepted at (the encoder refuses level 0 for it:
+    test_refusals_launch_nothing).  Items 63 and 64, either side of the boundary, word for word against rvec_ref; every item against two calls split there"""
+    limbs, level, nct, cut, n_elem = 2, LOWEST[2], 65, 64, 100
+    p = rc.FIELDS[limbs]
+    mod = rc.modulus_words(p, limbs)
+    xs = [rc.uniform_elems(p, n_elem, 1000 + k) for k in range(nct)]
+    shares = np.stack([rc.limbs_of(x, limbs) for x in xs])
+    assert len({s.tobytes() for s in shares}) == nct
+    got = ctx.rvec_encode(mod, shares, level, float(rc.SCALE), F)
+    wants = []
+    for i in (cut - 1, cut):
+        want, tie, err = rr.encode(xs[i], p, N, rc.SCALE, F)
+        assert min(tie) > rc.TIE_BAND + err, i                                    # nothing is excluded by the near-tie rule
+        wants.append(want)
+    rows = ntt_rows(wants, level)
+    assert np.array_equal(got[cut - 1], rows[0]) and np.array_equal(got[cut], rows[1])
+    assert np.array_equal(got[:cut], ctx.rvec_encode(mod, shares[:cut], level, float(rc.SCALE), F))
+    assert np.array_equal(got[cut:], ctx.rvec_encode(mod, shares[cut:], level, float(rc.SCALE), F))
+
+
+def test_decode_second_chunk_at_65_plaintexts(ctx):
+    """level 0, 65 plaintexts of uniform residues, every one different, n_elem = 100: items 63 and 64 against rvec_ref, every item against two calls split at 64"""
+    limbs, level, nct, cut, n_elem = 2, 0, 65, 64, 100
+    p = rc.FIELDS[limbs]
+    mod = rc.modulus_words(p, limbs)
+    Ql = rr.q_product(Q, level)
+    res = np.random.default_rng(65).integers(0, Q[0], (nct, N), dtype=np.uint64)
+    rows = ntt_rows([[int(v) for v in r] for r in res], level)
+    assert rows.shape == (nct, 1, N) and len({r.tobytes() for r in rows}) == nct
+    got = ctx.rvec_decode(mod, rows, level, float(rc.SCALE), F, n_elem)
+    for i in (cut - 1, cut):
+        want, tie, err = rr.decode_int([rr.centred_crt(int(v), Ql) for v in res[i]], N, rc.SCALE, F, n_elem)
+        assert min(tie) > rc.TIE_BAND + err, i
+        assert rc.ints_of(got[i]) == [v % p for v in want], i
+    assert np.array_equal(got[:cut], ctx.rvec_decode(mod, rows[:cut], level, float(rc.SCALE), F, n_elem))
+    assert np.array_equal(got[cut:], ctx.rvec_decode(mod, rows[cut:], level, float(rc.SCALE), F, n_elem))
