@@ -863,6 +863,51 @@ int sfg_ring_decode_vectors_dev(sfg_ring *ring, const uint64_t *pt_dev, size_t p
 /* crypto.DecryptFloatVector (crypto.go:489-510), as sfg_decrypt_vectors: pt = c0 + sk (.) c1 under the loaded (whole) secret key, then sfg_ring_decode_vectors */
 int sfg_ring_decrypt_vectors(sfg_ring *ring, const uint64_t *ct_dev, int nct, int level, double scale, double *re_host, double *im_host);
 
+/* ---- the general ring's collective key generation (gring_keygen.hip): the local halves of mpc.CollectiveInit (mpc/mhe.go:24-81) at every ring sfg_ring_create accepts ----
+ * The twins of the sfg_ckg_* / sfg_rtg_* / sfg_rkg_* / sfg_ctx_install_*_dev / sfg_crp_fill_dev block above, call for call: the same layouts (rows [nmod = nq + np][N],
+ * NTT domain, canonical words, device memory; shares [nkeys][beta][nmod][N]; errors int32 [..][N]; u int8 [N]), the same key convention (beta = ceil(nq / np); g_i at
+ * modulus m is P mod q_m when m < nq && m / np == i, else 0; a rotation key for Galois element g switches from phi_{g^-1}(s)) and the same three equations.
+ * PARITY UNPINNED, as there: restated from the published lattigo v2.1 dckks / drlwe; with fresh randomness bit parity with the Go binary cannot exist.  What IS pinned
+ * (tests/test_gpu_ring_keygen.py): every share word against the Python-integer statement tests/keygen_ref.py, the PN14 parameters against the specialised context, the
+ * sampled forms against the explicit cores on the sampler's transcript, and keys made here carrying a ciphertext through a rotation and a relinearisation.
+ * Each call returns 1 with the cause in sfg_ring_last_error and launches nothing: without a QP secret key, with an unseeded encryptor (sampled forms), on a null
+ * argument, nkeys < 0, an even Galois element or one >= 2N, a modulus index out of range, an export of an element that has no key.  nkeys == 0 and nrows == 0 return 0. */
+/* cryptoParams.Sk.Value over Q and P (crypto.go:44), as sfg_ctx_load_secret_key_qp: sk_host [nq+np][N], NTT domain.  Also provides what sfg_ring_load_secret_key
+ * provides.  Wiped from device memory in sfg_ring_destroy. */
+int sfg_ring_load_secret_key_qp(sfg_ring *ring, const uint64_t *sk_host, int montgomery_form);
+/* CKGProtocol.GenShare (CollectivePubKeyGen, mhe.go:83-105), as sfg_ckg_gen_share_dev: share = -crp (.) sk + NTT(e) */
+int sfg_ring_ckg_gen_share_dev(sfg_ring *ring, const uint64_t *crp_dev, const int32_t *e_dev, uint64_t *share_dev);
+/* RTGProtocol.GenShare for nkeys Galois elements at once (CollectiveRotKeyGen, mhe.go:381-476), as sfg_rtg_gen_shares_dev:
+ *   h_{k,i} = -crp_{k,i} (.) phi_{g_k^-1}(sk) + NTT(e_{k,i}) + g_i sk.  Any nkeys: the call runs in chunks of at most 1024 keys (gring_keygen_plan.hpp). */
+int sfg_ring_rtg_gen_shares_dev(sfg_ring *ring, const uint64_t *galois_host, int nkeys, const uint64_t *crp_dev, const int32_t *e_dev, uint64_t *shares_dev);
+/* RKGProtocol.GenShareRoundOne (CollectiveRelinKeyGen, mhe.go:478-502), as sfg_rkg_round1_dev: h0_i = -NTT(u) (.) crp_i + g_i sk + NTT(e0_i), h1_i = sk (.) crp_i + NTT(e1_i) */
+int sfg_ring_rkg_round1_dev(sfg_ring *ring, const uint64_t *crp_dev, const int8_t *u_dev, const int32_t *e0_dev, const int32_t *e1_dev, uint64_t *h0_dev, uint64_t *h1_dev);
+/* RKGProtocol.GenShareRoundTwo (mhe.go:478-502), as sfg_rkg_round2_dev: out_i = sk (.) H0agg_i + NTT(e2_i) + (NTT(u) - sk) (.) H1agg_i + NTT(e3_i) */
+int sfg_ring_rkg_round2_dev(sfg_ring *ring, const uint64_t *h0agg_dev, const uint64_t *h1agg_dev, const int8_t *u_dev, const int32_t *e2_dev, const int32_t *e3_dev, uint64_t *out_dev);
+/* The sampled forms (the CKG / RTG / RKG protocols' own ring.GaussianSampler and TernarySampler reads, mhe.go:83-105, 381-502), as sfg_*_sampled_dev: errors and u from the
+ * ring's encryptor stream (sfg_ring_seed_encryptor; the one counter of sfg_ring_encryptor_next_index).  Public key share: 1 index, e = polynomial id 1; rotation
+ * shares: nkeys * beta indices, (k, i) at first + k beta + i, e = id 1; round 1: beta + 1 indices (e0, e1 = ids 1, 2), u = id 0 of index first + beta, returned in
+ * *u_index (required); round 2: beta indices (e2, e3 = ids 1, 2), u redrawn from u_index and never stored.  *first_index (may be NULL) states the first index taken:
+ * sfg_ring_encrypt_transcript_for_test reproduces every sample from it.  Bit-identical to the explicit core on those samples.  The workspace is reserved before an
+ * index is taken: a call that fails spends none. */
+int sfg_ring_ckg_gen_share_sampled_dev(sfg_ring *ring, const uint64_t *crp_dev, uint64_t *share_dev, uint64_t *first_index);
+int sfg_ring_rtg_gen_shares_sampled_dev(sfg_ring *ring, const uint64_t *galois_host, int nkeys, const uint64_t *crp_dev, uint64_t *shares_dev, uint64_t *first_index);
+int sfg_ring_rkg_round1_sampled_dev(sfg_ring *ring, const uint64_t *crp_dev, uint64_t *h0_dev, uint64_t *h1_dev, uint64_t *first_index, uint64_t *u_index);
+int sfg_ring_rkg_round2_sampled_dev(sfg_ring *ring, const uint64_t *h0agg_dev, const uint64_t *h1agg_dev, uint64_t u_index, uint64_t *out_dev, uint64_t *first_index);
+/* Installation of the aggregated keys from device memory (replaces the evaluation-key assembly after the aggregation, mhe.go:60-81), as sfg_ctx_install_*_dev: device
+ * to device, no host copy of key words, the words kept as given.  public key = (agg, crp); rotation key k = (agg_{k,i}, crp_{k,i}) under galois_host[k], with its
+ * automorphism index; relinearisation key = (round2agg_i, H1agg_i).  As in sfg_ring_load_rotkey a new element's key enters the ring only when it is complete. */
+int sfg_ring_install_public_key_dev(sfg_ring *ring, const uint64_t *agg_dev, const uint64_t *crp_dev);
+int sfg_ring_install_rotkeys_dev(sfg_ring *ring, const uint64_t *galois_host, int nkeys, const uint64_t *agg_dev, const uint64_t *crp_dev);
+int sfg_ring_install_relinkey_dev(sfg_ring *ring, const uint64_t *round2agg_dev, const uint64_t *h1agg_dev);
+/* the stored key of a Galois element (what a party would send on, mhe.go:60-81), as sfg_ctx_export_rotkey: exactly (agg, crp) as key_host [beta][2][nmod][N];
+ * galois_el 1 = the relinearisation key */
+int sfg_ring_export_rotkey(sfg_ring *ring, uint64_t galois_el, uint64_t *key_host);
+/* The common reference polynomials (replaces ring.UniformSampler over the fork's frand, mhe.go:49-59), sfg_crp_fill_dev's exact map at any N and any modulus below
+ * 2^61 (bitlen(q) up to 61): on PN14's parameters it gives the same words.  out_dev [nrows][N]; row r is global row first_row + r at modulus mod_idx_host[r].  The
+ * seed is not retained by the ring. */
+int sfg_ring_crp_fill_dev(sfg_ring *ring, const uint8_t *key32_host, uint64_t first_row, size_t nrows, const int *mod_idx_host, uint64_t *out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1526,3 +1526,113 @@ func (r *Ring) DecryptFloatVector(flat []uint64, nct, level int, scale float64) 
 	r.check(C.sfg_ring_decrypt_vectors(r.p, d, C.int(nct), C.int(level), C.double(scale), (*C.double)(unsafe.Pointer(&out[0])), nil), "ring_decrypt_vectors")
 	return out
 }
+
+// ---- the ring's collective key generation, local halves (mpc/mhe.go:24-105, 381-502; gring_keygen.hip): the twins of Ctx's methods of the same names, at the
+// presets the specialised context does not serve.  PARITY UNPINNED against lattigo's dckks / drlwe protocols.  Shares come back as host words for
+// mpc/aggregate.go; the aggregated words go back in and are installed from device memory.  SeedEncryptor first; the common reference polynomials come from the
+// seed every party shares, through the one map of INTEGRATION.md.
+
+// RingBuf is device memory of a ring that the caller frees.
+type RingBuf struct {
+	r     *Ring
+	p     *C.uint64_t
+	Words int
+}
+
+func (b *RingBuf) Free() {
+	if b.p != nil {
+		b.r.free(b.p)
+		b.p = nil
+	}
+}
+
+// LoadSecretKeyQP gives the ring skShard.Value over Q and P (mhe.go:31-46, NTT + Montgomery form); it also serves as LoadSecretKey.
+func (r *Ring) LoadSecretKeyQP(sk *ckks.SecretKey) {
+	nmod := r.NQ + r.NP
+	flat := make([]uint64, nmod*r.N)
+	for m := 0; m < nmod; m++ {
+		copy(flat[m*r.N:(m+1)*r.N], sk.Value.Coeffs[m])
+	}
+	r.check(C.sfg_ring_load_secret_key_qp(r.p, (*C.uint64_t)(unsafe.Pointer(&flat[0])), 1), "ring_load_secret_key_qp")
+}
+
+func (r *Ring) keyBeta() int { return (r.NQ + r.NP - 1) / r.NP }
+
+// CommonReferencePolys: crpGen.ReadNew() (mhe.go:49-59) for npoly consecutive polynomials over Q and P, starting at polynomial firstPoly of the stream under seed32.
+func (r *Ring) CommonReferencePolys(seed32 []byte, firstPoly uint64, npoly int) *RingBuf {
+	nmod := r.NQ + r.NP
+	mod := make([]int32, npoly*nmod)
+	for i := range mod {
+		mod[i] = int32(i % nmod)
+	}
+	d := &RingBuf{r: r, p: r.alloc(npoly * nmod * r.N), Words: npoly * nmod * r.N}
+	r.check(C.sfg_ring_crp_fill_dev(r.p, (*C.uint8_t)(unsafe.Pointer(&seed32[0])), C.uint64_t(firstPoly*uint64(nmod)), C.size_t(len(mod)), (*C.int)(unsafe.Pointer(&mod[0])), d.p), "ring_crp_fill")
+	return d
+}
+
+// CollectivePubKeyGenShare: ckgProtocol.GenShare(sk, crp, pkShare) (mhe.go:91).
+func (r *Ring) CollectivePubKeyGenShare(crp *RingBuf) []uint64 {
+	words := (r.NQ + r.NP) * r.N
+	d := r.alloc(words)
+	defer r.free(d)
+	r.check(C.sfg_ring_ckg_gen_share_sampled_dev(r.p, crp.p, d, nil), "ring_ckg_gen_share")
+	return r.download(d, words)
+}
+
+// CollectivePubKeyGenFinish: ckgProtocol.GenPublicKey(pkAgg, crp, pk) (mhe.go:103); the key stays on the device.
+func (r *Ring) CollectivePubKeyGenFinish(agg []uint64, crp *RingBuf) {
+	d := r.upload(agg)
+	defer r.free(d)
+	r.check(C.sfg_ring_install_public_key_dev(r.p, d, crp.p), "ring_install_public_key")
+}
+
+// CollectiveRotKeyGenShares: rtgProtocol.GenShare for a batch of Galois elements (mhe.go:457-465); crp and the result are [len(gElems)][beta][nq+np][N].
+func (r *Ring) CollectiveRotKeyGenShares(gElems []uint64, crp *RingBuf) []uint64 {
+	d := r.alloc(crp.Words)
+	defer r.free(d)
+	r.check(C.sfg_ring_rtg_gen_shares_sampled_dev(r.p, (*C.uint64_t)(unsafe.Pointer(&gElems[0])), C.int(len(gElems)), crp.p, d, nil), "ring_rtg_gen_shares")
+	return r.download(d, crp.Words)
+}
+
+// CollectiveRotKeyGenFinish: rtgProtocol.GenRotationKey for the batch (mhe.go:469).
+func (r *Ring) CollectiveRotKeyGenFinish(gElems []uint64, agg []uint64, crp *RingBuf) {
+	d := r.upload(agg)
+	defer r.free(d)
+	r.check(C.sfg_ring_install_rotkeys_dev(r.p, (*C.uint64_t)(unsafe.Pointer(&gElems[0])), C.int(len(gElems)), d, crp.p), "ring_install_rotkeys")
+}
+
+// CollectiveRelinKeyGenRound1: prot.GenShareRoundOne (mhe.go:492); uIndex names the ephemeral secret for round 2 (it is never stored).
+func (r *Ring) CollectiveRelinKeyGenRound1(crp *RingBuf) (h0, h1 []uint64, uIndex uint64) {
+	d0, d1 := r.alloc(crp.Words), r.alloc(crp.Words)
+	defer r.free(d0)
+	defer r.free(d1)
+	var ui C.uint64_t
+	r.check(C.sfg_ring_rkg_round1_sampled_dev(r.p, crp.p, d0, d1, nil, &ui), "ring_rkg_round1")
+	return r.download(d0, crp.Words), r.download(d1, crp.Words), uint64(ui)
+}
+
+// CollectiveRelinKeyGenRound2: prot.GenShareRoundTwo on the aggregated round-one shares (mhe.go:495).
+func (r *Ring) CollectiveRelinKeyGenRound2(h0agg, h1agg []uint64, uIndex uint64) []uint64 {
+	a, b := r.upload(h0agg), r.upload(h1agg)
+	defer r.free(a)
+	defer r.free(b)
+	d := r.alloc(len(h0agg))
+	defer r.free(d)
+	r.check(C.sfg_ring_rkg_round2_sampled_dev(r.p, a, b, C.uint64_t(uIndex), d, nil), "ring_rkg_round2")
+	return r.download(d, len(h0agg))
+}
+
+// CollectiveRelinKeyGenFinish: prot.GenRelinearizationKey(outRound1, outRound2, evk) (mhe.go:498).
+func (r *Ring) CollectiveRelinKeyGenFinish(round2agg, h1agg []uint64) {
+	a, b := r.upload(round2agg), r.upload(h1agg)
+	defer r.free(a)
+	defer r.free(b)
+	r.check(C.sfg_ring_install_relinkey_dev(r.p, a, b), "ring_install_relinkey")
+}
+
+// ExportRotKey: the stored key of a Galois element as [beta][2][nq+np][N] words, exactly (agg, crp); galEl 1 is the relinearisation key (mhe.go:60-81).
+func (r *Ring) ExportRotKey(galEl uint64) []uint64 {
+	out := make([]uint64, r.keyBeta()*2*(r.NQ+r.NP)*r.N)
+	r.check(C.sfg_ring_export_rotkey(r.p, C.uint64_t(galEl), (*C.uint64_t)(unsafe.Pointer(&out[0]))), "ring_export_rotkey")
+	return out
+}

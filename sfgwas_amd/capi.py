@@ -103,6 +103,20 @@ def _ring_sig():
         "sfg_ring_decode_vectors": (i, [vp, vp, sz, i, i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "sfg_ring_decode_vectors_dev": (i, [vp, vp, sz, i, i, C.c_double, vp, vp]),
         "sfg_ring_decrypt_vectors": (i, [vp, vp, i, i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "sfg_ring_load_secret_key_qp": (i, [vp, u64p, i]),
+        "sfg_ring_ckg_gen_share_dev": (i, [vp, vp, vp, vp]),
+        "sfg_ring_rtg_gen_shares_dev": (i, [vp, u64p, i, vp, vp, vp]),
+        "sfg_ring_rkg_round1_dev": (i, [vp, vp, vp, vp, vp, vp, vp]),
+        "sfg_ring_rkg_round2_dev": (i, [vp, vp, vp, vp, vp, vp, vp]),
+        "sfg_ring_ckg_gen_share_sampled_dev": (i, [vp, vp, vp, u64p]),
+        "sfg_ring_rtg_gen_shares_sampled_dev": (i, [vp, u64p, i, vp, vp, u64p]),
+        "sfg_ring_rkg_round1_sampled_dev": (i, [vp, vp, vp, vp, u64p, u64p]),
+        "sfg_ring_rkg_round2_sampled_dev": (i, [vp, vp, vp, u64, vp, u64p]),
+        "sfg_ring_install_public_key_dev": (i, [vp, vp, vp]),
+        "sfg_ring_install_rotkeys_dev": (i, [vp, u64p, i, vp, vp]),
+        "sfg_ring_install_relinkey_dev": (i, [vp, vp, vp]),
+        "sfg_ring_export_rotkey": (i, [vp, u64, u64p]),
+        "sfg_ring_crp_fill_dev": (i, [vp, C.c_char_p, u64, sz, ip, vp]),
     }
 
 
@@ -1808,3 +1822,92 @@ class Ring:
         finally:
             self.free(d)
         return (re, im) if want_imag else re
+
+    # ---- collective key generation (gring_keygen.hip).  A polynomial argument is a host array (uploaded for the call) or a device pointer of malloc / to_device
+    # (used in place).  Results come back as host arrays, or stay on the device (`keep`: the pointers, for the caller to free); `out` supplies the result buffers.
+    def _kg(self, name, ins, out_shapes, call, keep=False, out=None):
+        own_in = [not isinstance(a, C.c_void_p) and a is not None for a, _ in ins]
+        devs = [self.to_device(np.ascontiguousarray(a, dtype=dt)) if o else a for (a, dt), o in zip(ins, own_in)]
+        outs = list(out) if out is not None else [self.malloc(int(np.prod(s)) * 8) for s in out_shapes]
+        ok = False
+        try:
+            self.check(call(devs, outs), name)
+            ok = True
+            return outs if keep or out is not None else [self.to_host(o, s) for o, s in zip(outs, out_shapes)]
+        finally:
+            for d_, o in zip(devs, own_in):
+                if o:
+                    self.free(d_)
+            if out is None and not (keep and ok):
+                for o in outs:
+                    self.free(o)
+
+    def load_secret_key_qp(self, sk, montgomery=False):
+        sk = np.ascontiguousarray(sk, dtype=np.uint64)
+        assert sk.shape == (len(self.moduli), self.N)
+        self.check(lib().sfg_ring_load_secret_key_qp(self.h, p64(sk), int(montgomery)), "sfg_ring_load_secret_key_qp")
+
+    def ckg_gen_share(self, crp, e=None, sampled=False, keep=False, out=None):
+        """crp [nmod][N]; e int32 [N] -> share [nmod][N]; sampled: -> (share, first index)"""
+        shp, L = [(len(self.moduli), self.N)], lib()
+        if not sampled:
+            return self._kg("sfg_ring_ckg_gen_share_dev", [(crp, np.uint64), (e, np.int32)], shp, lambda d, o: L.sfg_ring_ckg_gen_share_dev(self.h, d[0], d[1], o[0]), keep, out)[0]
+        first = C.c_uint64()
+        r = self._kg("sfg_ring_ckg_gen_share_sampled_dev", [(crp, np.uint64)], shp, lambda d, o: L.sfg_ring_ckg_gen_share_sampled_dev(self.h, d[0], o[0], C.byref(first)), keep, out)
+        return r[0], first.value
+
+    def rtg_gen_shares(self, galois, crp, e=None, sampled=False, keep=False, out=None):
+        """galois: nkeys elements; crp [nkeys][beta][nmod][N]; e int32 [nkeys][beta][N] -> shares like crp; sampled: -> (shares, first index)"""
+        g, gp = _galois_arr(galois); nk, L = int(g.size), lib()
+        shp = [(max(nk, 1), self.beta, len(self.moduli), self.N)]
+        if not sampled:
+            return self._kg("sfg_ring_rtg_gen_shares_dev", [(crp, np.uint64), (e, np.int32)], shp, lambda d, o: L.sfg_ring_rtg_gen_shares_dev(self.h, gp, nk, d[0], d[1], o[0]), keep, out)[0]
+        first = C.c_uint64()
+        r = self._kg("sfg_ring_rtg_gen_shares_sampled_dev", [(crp, np.uint64)], shp, lambda d, o: L.sfg_ring_rtg_gen_shares_sampled_dev(self.h, gp, nk, d[0], o[0], C.byref(first)), keep, out)
+        return r[0], first.value
+
+    def rkg_round1(self, crp, u=None, e0=None, e1=None, sampled=False, keep=False, out=None):
+        """crp [beta][nmod][N]; u int8 [N], e0, e1 int32 [beta][N] -> (h0, h1); sampled: -> (h0, h1, first index, u index)"""
+        shp, L = [(self.beta, len(self.moduli), self.N)] * 2, lib()
+        if not sampled:
+            return tuple(self._kg("sfg_ring_rkg_round1_dev", [(crp, np.uint64), (u, np.int8), (e0, np.int32), (e1, np.int32)], shp,
+                                  lambda d, o: L.sfg_ring_rkg_round1_dev(self.h, d[0], d[1], d[2], d[3], o[0], o[1]), keep, out))
+        first, ui = C.c_uint64(), C.c_uint64()
+        h0, h1 = self._kg("sfg_ring_rkg_round1_sampled_dev", [(crp, np.uint64)], shp, lambda d, o: L.sfg_ring_rkg_round1_sampled_dev(self.h, d[0], o[0], o[1], C.byref(first), C.byref(ui)), keep, out)
+        return h0, h1, first.value, ui.value
+
+    def rkg_round2(self, h0agg, h1agg, u=None, e2=None, e3=None, u_index=None, sampled=False, keep=False, out=None):
+        """H0agg, H1agg [beta][nmod][N]; (u, e2, e3) -> share; sampled with u_index (from round 1): -> (share, first index)"""
+        shp, L = [(self.beta, len(self.moduli), self.N)], lib()
+        if not sampled:
+            return self._kg("sfg_ring_rkg_round2_dev", [(h0agg, np.uint64), (h1agg, np.uint64), (u, np.int8), (e2, np.int32), (e3, np.int32)], shp,
+                            lambda d, o: L.sfg_ring_rkg_round2_dev(self.h, d[0], d[1], d[2], d[3], d[4], o[0]), keep, out)[0]
+        first = C.c_uint64()
+        r = self._kg("sfg_ring_rkg_round2_sampled_dev", [(h0agg, np.uint64), (h1agg, np.uint64)], shp,
+                     lambda d, o: L.sfg_ring_rkg_round2_sampled_dev(self.h, d[0], d[1], int(u_index), o[0], C.byref(first)), keep, out)
+        return r[0], first.value
+
+    def install_public_key(self, agg, crp):
+        self._kg("sfg_ring_install_public_key_dev", [(agg, np.uint64), (crp, np.uint64)], [], lambda d, o: lib().sfg_ring_install_public_key_dev(self.h, d[0], d[1]))
+
+    def install_rotkeys(self, galois, agg, crp):
+        g, gp = _galois_arr(galois)
+        self._kg("sfg_ring_install_rotkeys_dev", [(agg, np.uint64), (crp, np.uint64)], [], lambda d, o: lib().sfg_ring_install_rotkeys_dev(self.h, gp, int(g.size), d[0], d[1]))
+
+    def install_relinkey(self, round2agg, h1agg):
+        self._kg("sfg_ring_install_relinkey_dev", [(round2agg, np.uint64), (h1agg, np.uint64)], [], lambda d, o: lib().sfg_ring_install_relinkey_dev(self.h, d[0], d[1]))
+
+    def export_rotkey(self, galois):
+        """-> [beta][2][nmod][N]: exactly (agg, crp); galois 1 = the relinearisation key"""
+        out = np.empty((self.beta, 2, len(self.moduli), self.N), dtype=np.uint64)
+        self.check(lib().sfg_ring_export_rotkey(self.h, int(galois), p64(out)), "sfg_ring_export_rotkey")
+        return out
+
+    def crp_fill(self, key32, first_row, mod_idx, keep=False, out=None):
+        """rows first_row .. first_row + len(mod_idx) - 1 of the common reference stream under the 32-byte seed -> [nrows][N]"""
+        key32 = bytes(key32)
+        if len(key32) != 32:
+            raise ValueError("the common reference seed is 32 bytes")
+        n = len(mod_idx)
+        mi = (C.c_int * max(n, 1))(*[int(x) for x in mod_idx])
+        return self._kg("sfg_ring_crp_fill_dev", [], [(max(n, 1), self.N)], lambda d, o: lib().sfg_ring_crp_fill_dev(self.h, key32, int(first_row), n, mi, o[0]), keep, out)[0]

@@ -302,6 +302,15 @@ int gr_transform(sfg_ring *r, u64 *rows, size_t nrows, GrRowMap map, bool inv) {
     GR_HIP(r, hipGetLastError());
     return 0;
 }
+int gr_transform_cols_fwd(sfg_ring *r, u64 *rows, size_t nrows, GrRowMap map) {
+    const GrNttPlan &p = r->plan;
+    gr_split(nrows, kGrLaunchCap, [&](size_t row0, size_t n) {
+        hipLaunchKernelGGL(k_gr_cols<false>, dim3((unsigned)p.tiles_per_row, (unsigned)n), dim3(GR_T), 0, r->stream, rows, row0, map, r->modc, r->tw, p.logN, p.a, p.b);
+        return 0;
+    });
+    GR_HIP(r, hipGetLastError());
+    return 0;
+}
 GrRowMap gr_map(int period, int split, int base0, int base1) { GrRowMap m; m.table = nullptr; m.period = period; m.split = split; m.base0 = base0; m.base1 = base1; return m; }
 
 // basis extension of npoly polynomials: src [npoly][nsrc][N] (coefficient domain) -> out [npoly][ndig][ntgt][N] (coefficient domain)

@@ -79,6 +79,13 @@ struct GrIo {
     GrSecret<u64> pt;                                  // grow-only plaintext rows between the encoder and the encryption core, and between decryption and the decoder
     size_t ws_budget = 512ull << 20;
 };
+// key generation (gring_keygen.hip): the secret key over Q and P [nmod][N] (NTT domain, canonical), P mod q_m with its Shoup quotient [nmod][2] (the rows of P zero), the index
+// tables of a chunk of rotation keys, and NTT(u) of a relinearisation round
+struct GrKeygen {
+    GrSecret<u64> skqp; GrBuf<u64> pmod;
+    GrBuf<void> index;                                 // grow-only
+    GrSecret<u64> u;                                   // grow-only, wiping
+};
 struct sfg_ring {
     int device = 0, logN = 0, N = 0, nq = 0, np = 0, nmod = 0, beta = 0;
     u64 q[gr::kMaxMod] = {}, psi[gr::kMaxMod] = {};
@@ -95,6 +102,7 @@ struct sfg_ring {
     size_t ws_budget = 768ull << 20;
     bool test_hooks = false;                           // SFG_ENABLE_TEST_HOOKS=1 when the ring was made: the *_for_test entry points may be called
     GrIo io;
+    GrKeygen kg;
     std::string err;
 };
 #define GR_FAIL(r, ...) do { char _b[512]; snprintf(_b, sizeof _b, __VA_ARGS__); (r)->err = _b; return 1; } while (0)
@@ -114,7 +122,10 @@ int gr_upload(sfg_ring *r, void *dst, const void *src, size_t bytes);
 int gr_reserve(sfg_ring *r, GrMem &buf, size_t bytes);             // grow-only: a buffer too small is let go (a wiping one wiped) and allocated anew
 int gr_table(sfg_ring *r, GrMem &dst, const void *host, size_t bytes);   // a table allocated and filled; the caller moves it into the ring when it is complete
 int gr_transform(sfg_ring *r, u64 *rows, size_t nrows, GrRowMap map, bool inv);
+int gr_transform_cols_fwd(sfg_ring *r, u64 *rows, size_t nrows, GrRowMap map);   // the forward transform's first launch alone (the caller runs its own contiguous pass)
 GrRowMap gr_map(int period, int split, int base0, int base1);
 int gr_extend(sfg_ring *r, const GrExt &e, const u64 *src, u64 *Y, uint32_t *V, u64 *out, int ntgt, size_t npoly);
 int gr_check_level(sfg_ring *r, const char *what, int nct, int level);
 int gr_rows_from_mont(sfg_ring *r, u64 *rows, size_t nrows);      // lattigo ring.InvMForm on key rows [.][nmod][N], enqueued on the ring's stream
+// gring_io.hip
+int gri_take_indices(sfg_ring *r, const char *what, int nct, u64 *first);       // nct consecutive encryption indices from the ring's one counter; refuses an unseeded encryptor

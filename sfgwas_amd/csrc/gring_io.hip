@@ -22,40 +22,11 @@
 #include "gring_io_arith.hpp"
 #include "gring_io_plan.hpp"
 #include "ddfft.hpp"          // host only: the double-double Taylor series the transform's tables are built with (dd_sincos_small)
-#include "sampler.hpp"        // chacha20_block, gauss_from_bits and the Gaussian table: shared with encrypt.hip and keygen.hip, not forked
+#include "gring_sampler.hpp"  // gri_sample8 (shared with gring_keygen.hip) over sampler.hpp: chacha20_block, gauss_from_bits and the Gaussian table, not forked
 
 // ---------------------------------------------------------------- sampling and lifting
 struct GriSrc { const int8_t *u; const int32_t *e0, *e1; const unsigned *key; u64 index0; };     // key != nullptr: the sampler; else the caller's polynomials [nct][N] (u nullable: zero)
 
-// words idx, idx + 1 of a block without a dynamically indexed register array (idx even, < 16)
-__device__ __forceinline__ u64 gri_pick(const unsigned (&w)[16], int idx) {
-    unsigned lo = 0, hi = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) if (idx == 2 * i) { lo = w[2 * i]; hi = w[2 * i + 1]; }
-    return ((u64)hi << 32) | lo;
-}
-// Thread (t, g), t < 512, g < N / 4096, owns the 8 coefficients j = 512 (8 g + k) + t, k < 8: one block of each Gaussian polynomial serves exactly these 8 (word pair
-// k), and one block of u holds their 8 bit pairs.  Three ChaCha20 blocks a thread.
-__device__ __forceinline__ void gri_sample8(const unsigned (&key)[8], u64 index, int t, int g, bool want_u, int npoly, int (&su)[8], int (&s0)[8], int (&s1)[8]) {
-    const unsigned n0 = (unsigned)index, n1 = (unsigned)(index >> 32);
-    unsigned w[16];
-    if (want_u) {
-        chacha20_block(key, gio::samp_u_block(t, 8 * g), n0, n1, 0u, w);
-        const u64 r = gri_pick(w, gio::samp_u_word(t));
-#pragma unroll
-        for (int k = 0; k < 8; k++) su[k] = gio::samp_ternary(r, gio::samp_u_shift(8 * g + k));
-    }
-#pragma unroll 1
-    for (int pol = 0; pol < npoly; pol++) {
-        chacha20_block(key, gio::samp_e_block(t, 8 * g), n0, n1, (unsigned)(1 + pol), w);
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const u64 r = gri_pick(w, gio::samp_e_word(8 * g + k));
-            const int v = gauss_from_bits((unsigned)r, (unsigned)(r >> 32));
-            if (pol == 0) s0[k] = v; else s1[k] = v;
-        }
-    }
-}
 // grid (N / 8 / 256, 1, chunk).  U: UQ [chunk][nl][N], UP [chunk][np][N] (both null when u drops out); T: TQ [chunk][npoly][nl][N], TP [chunk][npoly][np][N].
 // j = 512 (8 g + k) + t < 4096 (g + 1) <= N since g < N / 4096 by the grid.
 template <bool SAMPLE>
@@ -188,7 +159,7 @@ static int gri_core(sfg_ring *r, const GriPlan &plan, const GriSrc &src0, const 
 }
 
 // takes nct consecutive encryption indices from the ring's one counter
-static int gri_take_indices(sfg_ring *r, const char *what, int nct, u64 *first) {
+int gri_take_indices(sfg_ring *r, const char *what, int nct, u64 *first) {
     GrIo &io = r->io;
     if (!io.enc_seeded) GR_FAIL(r, "%s: the encryptor has no key (sfg_ring_seed_encryptor); there is no default", what);
     unsigned long long cur = __atomic_load_n(&io.enc_next, __ATOMIC_ACQUIRE);

@@ -13,6 +13,7 @@
 //   gwas::MatMult4Stream / MatMult4StreamPreprocess / MatMult4StreamCompute   gwas/matmult.go:914,1043,1238
 //   mpc::BeaverMultElemVec / BeaverMultMat                               mpc/beavermult.go:108-147
 //   mpc::CollectivePubKeyGen / RotKeyGen / RelinKeyGen Share(s) / Round / Finish, crypto::GenerateRotKeys   mpc/mhe.go:24-105, 381-502, crypto/crypto.go:232-275
+//   the same on crypto::RingParams (the general ring: the other CKKS presets)                         mpc/mhe.go:24-105, 381-502
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -1561,5 +1562,97 @@ inline KeyShares CollectiveRelinKeyGenRound2(crypto::CryptoParams *cps, const Re
 }
 inline void CollectiveRelinKeyGenFinish(crypto::CryptoParams *cps, const uint64_t *round2agg_dev, const uint64_t *h1agg_dev) {
     cps->check(sfg_ctx_install_relinkey_dev(cps->ctx, round2agg_dev, h1agg_dev), "RKGProtocol.GenRelinearizationKey");
+}
+}  // namespace mpc
+
+// ---- the same at the other CKKS presets (gwas/gwas.go:164-177: PN12QP109 .. PN16QP1761): the general ring's twins (gring_keygen.hip).
+//      Same protocol steps, same layouts, same common-reference map; the aggregation stays in Go as above.  PARITY UNPINNED (see include/sfgwas_hip.h).
+namespace crypto {
+// the ring of one preset: ring moduli Q then P, lattigo's 2N-th roots (or nullptr).  Owns the sfg_ring.
+struct RingParams {
+    sfg_ring *ring = nullptr; int logN = 0, nq = 0, np = 0;
+    RingParams(int device, int logN_, const std::vector<uint64_t> &q, const std::vector<uint64_t> &p, const uint64_t *psi = nullptr) : logN(logN_), nq((int)q.size()), np((int)p.size()) {
+        std::vector<uint64_t> mods(q); mods.insert(mods.end(), p.begin(), p.end());
+        if (sfg_ring_create(&ring, device, logN, nq, np, mods.data(), psi)) throw std::runtime_error(std::string("sfg_ring_create: ") + sfg_ring_last_error(nullptr));
+    }
+    RingParams(const RingParams &) = delete; RingParams &operator=(const RingParams &) = delete;
+    ~RingParams() { if (ring) sfg_ring_destroy(ring); }
+    int N() const { return 1 << logN; }
+    int GetSlots() const { return N() / 2; }
+    void check(int rc, const char *what) const { if (rc) throw std::runtime_error(std::string(what) + ": " + sfg_ring_last_error(ring)); }
+};
+// a device buffer of a ring that frees itself
+struct RingBuf {
+    RingParams *rp; void *p = nullptr;
+    RingBuf(RingParams *rp_, size_t bytes) : rp(rp_) { rp->check(sfg_ring_malloc(rp->ring, &p, bytes ? bytes : 8), "sfg_ring_malloc"); }
+    RingBuf(const RingBuf &) = delete; RingBuf &operator=(const RingBuf &) = delete;
+    ~RingBuf() { if (p) (void)sfg_ring_free(rp->ring, p); }
+    uint64_t *u() const { return (uint64_t *)p; }
+};
+// mhe.go:384-411 for a ring: the distinct left shifts, their Galois elements, the conjugate, sorted so that every party agrees on the order
+inline std::vector<uint64_t> GaloisElementsForRotKeys(const RingParams *rp, const std::vector<RotationType> &rotTypes) {
+    const int slots = rp->GetSlots();
+    std::map<int, bool> shiftMap;
+    for (const RotationType &r : rotTypes) shiftMap[r.Side == SideRight ? slots - r.Value : r.Value] = true;
+    std::vector<uint64_t> gElems;
+    for (const auto &kv : shiftMap) gElems.push_back(sfg_ring_galois_for_rotation(rp->ring, kv.first));
+    gElems.push_back(2ULL * (uint64_t)rp->N() - 1);
+    std::sort(gElems.begin(), gElems.end());
+    gElems.erase(std::unique(gElems.begin(), gElems.end()), gElems.end());
+    return gElems;
+}
+// skShard.Value over Q and P (mhe.go:31-46): [nq+np][N], NTT domain; also what sfg_ring_load_secret_key stores
+inline void LoadSecretKeyQP(RingParams *rp, const std::vector<uint64_t> &sk, bool montgomeryForm) {
+    if (sk.size() != (size_t)(rp->nq + rp->np) * rp->N()) throw std::runtime_error("LoadSecretKeyQP: expected [nq+np][N] words");
+    rp->check(sfg_ring_load_secret_key_qp(rp->ring, sk.data(), montgomeryForm ? 1 : 0), "LoadSecretKeyQP");
+}
+}  // namespace crypto
+namespace mpc {
+using RingKeyBuf = std::shared_ptr<crypto::RingBuf>;
+inline size_t keyPolyWords(const crypto::RingParams *rp) { return (size_t)(rp->nq + rp->np) * rp->N(); }
+inline int keyBeta(const crypto::RingParams *rp) { return (rp->nq + rp->np - 1) / rp->np; }
+// crpGen.ReadNew() (mhe.go:49-59) for npoly consecutive polynomials: the map of sfg_crp_fill_dev, at this ring's N and moduli
+inline RingKeyBuf CommonReferencePolys(crypto::RingParams *rp, const std::vector<uint8_t> &seed32, uint64_t firstPoly, size_t npoly) {
+    if (seed32.size() != 32) throw std::runtime_error("CommonReferencePolys: the seed is 32 bytes");
+    const int nmod = rp->nq + rp->np;
+    std::vector<int> mod(npoly * nmod); for (size_t r = 0; r < mod.size(); r++) mod[r] = (int)(r % nmod);
+    RingKeyBuf out = std::make_shared<crypto::RingBuf>(rp, npoly * keyPolyWords(rp) * 8);
+    rp->check(sfg_ring_crp_fill_dev(rp->ring, seed32.data(), firstPoly * (uint64_t)nmod, mod.size(), mod.data(), out->u()), "CommonReferencePolys");
+    return out;
+}
+struct RingKeyShares { RingKeyBuf h; uint64_t firstIndex = 0; };
+// mhe.go:83-105 CollectivePubKeyGen up to the aggregation, and ckgProtocol.GenPublicKey after it
+inline RingKeyShares CollectivePubKeyGenShare(crypto::RingParams *rp, const uint64_t *crp_dev) {
+    RingKeyShares s; s.h = std::make_shared<crypto::RingBuf>(rp, keyPolyWords(rp) * 8);
+    rp->check(sfg_ring_ckg_gen_share_sampled_dev(rp->ring, crp_dev, s.h->u(), &s.firstIndex), "CKGProtocol.GenShare");
+    return s;
+}
+inline void CollectivePubKeyGenFinish(crypto::RingParams *rp, const uint64_t *agg_dev, const uint64_t *crp_dev) {
+    rp->check(sfg_ring_install_public_key_dev(rp->ring, agg_dev, crp_dev), "CKGProtocol.GenPublicKey");
+}
+// mhe.go:381-476 CollectiveRotKeyGen for a batch of Galois elements (the library runs any batch in chunks of at most 1024 keys); crp, shares [len][beta][nq+np][N]
+inline RingKeyShares CollectiveRotKeyGenShares(crypto::RingParams *rp, const std::vector<uint64_t> &gElems, const uint64_t *crp_dev) {
+    RingKeyShares s; s.h = std::make_shared<crypto::RingBuf>(rp, gElems.size() * keyBeta(rp) * keyPolyWords(rp) * 8);
+    rp->check(sfg_ring_rtg_gen_shares_sampled_dev(rp->ring, gElems.data(), (int)gElems.size(), crp_dev, s.h->u(), &s.firstIndex), "RTGProtocol.GenShare");
+    return s;
+}
+inline void CollectiveRotKeyGenFinish(crypto::RingParams *rp, const std::vector<uint64_t> &gElems, const uint64_t *agg_dev, const uint64_t *crp_dev) {
+    rp->check(sfg_ring_install_rotkeys_dev(rp->ring, gElems.data(), (int)gElems.size(), agg_dev, crp_dev), "RTGProtocol.GenRotationKey");
+}
+// mhe.go:478-502 CollectiveRelinKeyGen: round 1 -> aggregation -> round 2 -> aggregation -> GenRelinearizationKey; the ephemeral secret is redrawn from uIndex
+struct RingRelinRound1Shares { RingKeyBuf h0, h1; uint64_t firstIndex = 0, uIndex = 0; };
+inline RingRelinRound1Shares CollectiveRelinKeyGenRound1(crypto::RingParams *rp, const uint64_t *crp_dev) {
+    RingRelinRound1Shares s; const size_t bytes = keyBeta(rp) * keyPolyWords(rp) * 8;
+    s.h0 = std::make_shared<crypto::RingBuf>(rp, bytes); s.h1 = std::make_shared<crypto::RingBuf>(rp, bytes);
+    rp->check(sfg_ring_rkg_round1_sampled_dev(rp->ring, crp_dev, s.h0->u(), s.h1->u(), &s.firstIndex, &s.uIndex), "RKGProtocol.GenShareRoundOne");
+    return s;
+}
+inline RingKeyShares CollectiveRelinKeyGenRound2(crypto::RingParams *rp, const RingRelinRound1Shares &round1, const uint64_t *h0agg_dev, const uint64_t *h1agg_dev) {
+    RingKeyShares s; s.h = std::make_shared<crypto::RingBuf>(rp, keyBeta(rp) * keyPolyWords(rp) * 8);
+    rp->check(sfg_ring_rkg_round2_sampled_dev(rp->ring, h0agg_dev, h1agg_dev, round1.uIndex, s.h->u(), &s.firstIndex), "RKGProtocol.GenShareRoundTwo");
+    return s;
+}
+inline void CollectiveRelinKeyGenFinish(crypto::RingParams *rp, const uint64_t *round2agg_dev, const uint64_t *h1agg_dev) {
+    rp->check(sfg_ring_install_relinkey_dev(rp->ring, round2agg_dev, h1agg_dev), "RKGProtocol.GenRelinearizationKey");
 }
 }  // namespace mpc
