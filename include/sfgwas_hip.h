@@ -908,6 +908,34 @@ int sfg_ring_export_rotkey(sfg_ring *ring, uint64_t galois_el, uint64_t *key_hos
  * seed is not retained by the ring. */
 int sfg_ring_crp_fill_dev(sfg_ring *ring, const uint8_t *key32_host, uint64_t first_row, size_t nrows, const int *mod_idx_host, uint64_t *out_dev);
 
+/* ---- the general ring's collective bootstrap, local halves (gring_refresh.hip): mpc.BootstrapMatAll / CollectiveBootstrapMat / CollectiveBootstrapVec
+ * (mpc/mhe.go:222-376) at every ring sfg_ring_create accepts ----
+ * The twins of the four sfg_refresh_* calls above, call for call, with the ring's N and nq: ct [nct][2][level+1][N]; crs, h1, h1agg [nct][nq][N]; h0, h0agg
+ * [nct][level+1][N]; mask [nct][N][mask_limbs] two's-complement 64-bit limbs, 1 <= mask_limbs <= 48; e0, e1 [nct][N] int32; out [nct][2][nq][N] at level nq - 1.
+ * All rows NTT domain, canonical, device memory.  The secret key is the one sfg_ring_load_secret_key holds.  Randomness (mask, errors, crs) is an input and the
+ * aggregation of the shares stays in Go, as for PN14.  Any nct: a call runs in chunks of at most 1024 ciphertexts (gring_refresh_plan.hpp).
+ * PARITY UNPINNED, as there: dckks.RefreshProtocol lives in the absent lattigo fork; restated from the published lattigo v2.1.0 / v2.2.0 dckks/refresh.go as
+ * orc_refresh_gen_shares / orc_refresh_finish and their _scaled forms state it (oracle/sfgwas_oracle.c).  What IS pinned (tests/test_gpu_ring_refresh.py): every
+ * word of h0, h1 and out against Python integers (tests/ring_refresh_ref.py), and PN14's parameters against the specialised context word for word.
+ * The device big integer has 48 limbs (3072 bits).  The target-scale forms require bits(Q_level) + 54 + max(sh, 0) <= 3070, and the share form
+ * 64 mask_limbs + 54 + max(sh, 0) <= 3072 as well, sh = the exponent of Int(target scale) minus that of Int(ct scale): every ring fits at the reference's pairs.
+ * Each call returns 1 with the cause in sfg_ring_last_error and launches nothing: without a secret key (the share forms), on a null pointer, a level out of range,
+ * nct < 0, mask_limbs outside 1..48, a scale that is not finite, below 1 or above 2^400, a product that does not fit.  nct == 0 returns 0. */
+/* RefreshProtocol.GenShares (mhe.go:251,315), as sfg_refresh_gen_shares_dev: h0 = NTT_level(mask + e0) + sk (.) c1; h1 = -(NTT(mask + e1) + sk (.) crs) over all nq moduli */
+int sfg_ring_refresh_gen_shares_dev(sfg_ring *ring, const uint64_t *ct_dev, int nct, int level, const uint64_t *crs_dev, const uint64_t *mask_dev, int mask_limbs,
+                                    const int32_t *e0_dev, const int32_t *e1_dev, uint64_t *h0_dev, uint64_t *h1_dev);
+/* RefreshProtocol.Decrypt, Recode, Recrypt (mhe.go:256-258,329-331), as sfg_refresh_finish_dev: x = INTT_level(c0 + h0agg) as a big integer, negative when
+ * x >= floor(Q_level / 2), reduced into all nq moduli; c0' = NTT(x) + h1agg, c1' = crs */
+int sfg_ring_refresh_finish_dev(sfg_ring *ring, const uint64_t *ct_dev, int nct, int level, const uint64_t *h0agg_dev, const uint64_t *h1agg_dev, const uint64_t *crs_dev,
+                                uint64_t *out_dev);
+/* The target-scale forms the reference calls (mhe.go:251,315 GenShares(..., parameters.Scale(), ...); mhe.go:256-258,329-331 Recode(ct, parameters.Scale())), as
+ * sfg_refresh_gen_shares_scaled_dev / sfg_refresh_finish_scaled_dev: h1 from Quo(mask Int(target), Int(ct scale)); x <- Quo(x Int(target), Int(ct scale)) before
+ * the re-reduction; Quo truncates towards zero.  ct_scale == target_scale takes the unscaled path. */
+int sfg_ring_refresh_gen_shares_scaled_dev(sfg_ring *ring, const uint64_t *ct_dev, int nct, int level, double ct_scale, double target_scale, const uint64_t *crs_dev,
+                                           const uint64_t *mask_dev, int mask_limbs, const int32_t *e0_dev, const int32_t *e1_dev, uint64_t *h0_dev, uint64_t *h1_dev);
+int sfg_ring_refresh_finish_scaled_dev(sfg_ring *ring, const uint64_t *ct_dev, int nct, int level, double ct_scale, double target_scale, const uint64_t *h0agg_dev,
+                                       const uint64_t *h1agg_dev, const uint64_t *crs_dev, uint64_t *out_dev);
+
 #ifdef __cplusplus
 }
 #endif

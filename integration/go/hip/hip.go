@@ -1499,6 +1499,43 @@ func (r *Ring) PCKSFinish(flat []uint64, nct, level int, h0agg []uint64) []uint6
 	return r.download(dOut, nct*(level+1)*r.N)
 }
 
+// RefreshGenShares: the local half of BootstrapMatAll / CollectiveBootstrapMat / CollectiveBootstrapVec before the aggregation (mpc/mhe.go:251,315:
+// refProtocol.GenShares(skShard, levelStart, nParties, ct, parameters.Scale(), crp, ...)) for nct ciphertexts of one level: h0 [nct][level+1][N] and
+// h1 [nct][nq][N] from this party's key shard, its masks ([nct][N][maskLimbs] two's-complement limbs, ring.RandInt below Q_level / (2 nParties) recentred), its
+// error polynomials e0, e1 [nct][N] and the common reference polynomials crs [nct][nq][N].  ctScale is the scale the ciphertexts carry, the target is always
+// Params.Scale(), as the reference passes it.  PARITY UNPINNED (see include/sfgwas_hip.h).
+func (r *Ring) RefreshGenShares(flat []uint64, nct, level int, ctScale float64, crs, masks []uint64, maskLimbs int, e0, e1 []int32) (h0, h1 []uint64) {
+	d, dc, dm := r.upload(flat), r.upload(crs), r.upload(masks)
+	defer r.free(d)
+	defer r.free(dc)
+	defer r.free(dm)
+	d0, d1 := r.allocBytes(4*len(e0)), r.allocBytes(4*len(e1))
+	defer r.freeBytes(d0)
+	defer r.freeBytes(d1)
+	r.check(C.sfg_ring_memcpy_h2d(r.p, d0, unsafe.Pointer(&e0[0]), C.size_t(4*len(e0))), "ring_memcpy_h2d")
+	r.check(C.sfg_ring_memcpy_h2d(r.p, d1, unsafe.Pointer(&e1[0]), C.size_t(4*len(e1))), "ring_memcpy_h2d")
+	dh0, dh1 := r.alloc(nct*(level+1)*r.N), r.alloc(nct*r.NQ*r.N)
+	defer r.free(dh0)
+	defer r.free(dh1)
+	r.check(C.sfg_ring_refresh_gen_shares_scaled_dev(r.p, d, C.int(nct), C.int(level), C.double(ctScale), C.double(r.Params.Scale()), dc, dm, C.int(maskLimbs),
+		(*C.int32_t)(d0), (*C.int32_t)(d1), dh0, dh1), "ring_refresh_gen_shares")
+	return r.download(dh0, nct*(level+1)*r.N), r.download(dh1, nct*r.NQ*r.N)
+}
+
+// RefreshFinish: the local half after the aggregation (mpc/mhe.go:256-258,329-331: Decrypt, Recode(ct, parameters.Scale()), Recrypt): the refreshed ciphertexts
+// [nct][2][nq][N] at level nq - 1 and scale Params.Scale() from the aggregated shares h0agg [nct][level+1][N], h1agg [nct][nq][N] and crs.
+func (r *Ring) RefreshFinish(flat []uint64, nct, level int, ctScale float64, h0agg, h1agg, crs []uint64) []uint64 {
+	d, d0, d1, dc := r.upload(flat), r.upload(h0agg), r.upload(h1agg), r.upload(crs)
+	defer r.free(d)
+	defer r.free(d0)
+	defer r.free(d1)
+	defer r.free(dc)
+	dOut := r.alloc(nct * 2 * r.NQ * r.N)
+	defer r.free(dOut)
+	r.check(C.sfg_ring_refresh_finish_scaled_dev(r.p, d, C.int(nct), C.int(level), C.double(ctScale), C.double(r.Params.Scale()), d0, d1, dc, dOut), "ring_refresh_finish")
+	return r.download(dOut, nct*2*r.NQ*r.N)
+}
+
 // DecodeCoeffs: the first half of crypto.DecodeFloatVector (crypto.go:525-536 -> encoder.Decode) for nvec NTT-domain plaintexts ([nvec][level+1][N] words): inverse
 // NTT, the centred CRT and the division by the scale: [nvec][N] doubles.
 func (r *Ring) DecodeCoeffs(flat []uint64, nvec, level int, scale float64) []float64 {

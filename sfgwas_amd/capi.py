@@ -117,6 +117,10 @@ def _ring_sig():
         "sfg_ring_install_relinkey_dev": (i, [vp, vp, vp]),
         "sfg_ring_export_rotkey": (i, [vp, u64, u64p]),
         "sfg_ring_crp_fill_dev": (i, [vp, C.c_char_p, u64, sz, ip, vp]),
+        "sfg_ring_refresh_gen_shares_dev": (i, [vp, vp, i, i, vp, vp, i, vp, vp, vp, vp]),
+        "sfg_ring_refresh_finish_dev": (i, [vp, vp, i, i, vp, vp, vp, vp]),
+        "sfg_ring_refresh_gen_shares_scaled_dev": (i, [vp, vp, i, i, C.c_double, C.c_double, vp, vp, i, vp, vp, vp, vp]),
+        "sfg_ring_refresh_finish_scaled_dev": (i, [vp, vp, i, i, C.c_double, C.c_double, vp, vp, vp, vp]),
     }
 
 
@@ -1754,6 +1758,33 @@ class Ring:
         nct = cts.shape[0]
         return self._run_mixed("sfg_ring_pcks_finish_dev", [cts, np.ascontiguousarray(h0agg, dtype=np.uint64)], [(nct, level + 1, self.N)],
                                lambda d, o: lib().sfg_ring_pcks_finish_dev(self.h, d[0], nct, level, d[1], o[0]))[0]
+
+    # ---- collective bootstrap, local halves (gring_refresh.hip)
+    def refresh_gen_shares(self, cts, level, crs, mask_limbs, e0, e1, scales=None):
+        """cts [nct][2][level+1][N], crs [nct][nq][N], mask_limbs [nct][N][W] uint64 two's complement, e0 / e1 [nct][N] int32 -> (h0 [nct][level+1][N], h1 [nct][nq][N]);
+        scales = (ciphertext scale, target scale) selects the target-scale form"""
+        cts, crs = np.ascontiguousarray(cts, dtype=np.uint64), np.ascontiguousarray(crs, dtype=np.uint64)
+        mask_limbs = np.ascontiguousarray(mask_limbs, dtype=np.uint64)
+        nct, W = cts.shape[0], mask_limbs.shape[-1]
+        ins = [cts, crs, mask_limbs, np.ascontiguousarray(e0, dtype=np.int32), np.ascontiguousarray(e1, dtype=np.int32)]
+        shapes = [(nct, level + 1, self.N), (nct, self.nq, self.N)]
+        if scales is None:
+            return tuple(self._run_mixed("sfg_ring_refresh_gen_shares_dev", ins, shapes,
+                                         lambda d, o: lib().sfg_ring_refresh_gen_shares_dev(self.h, d[0], nct, level, d[1], d[2], W, d[3], d[4], o[0], o[1])))
+        return tuple(self._run_mixed("sfg_ring_refresh_gen_shares_scaled_dev", ins, shapes,
+                                     lambda d, o: lib().sfg_ring_refresh_gen_shares_scaled_dev(self.h, d[0], nct, level, float(scales[0]), float(scales[1]), d[1], d[2], W,
+                                                                                               d[3], d[4], o[0], o[1])))
+
+    def refresh_finish(self, cts, level, h0agg, h1agg, crs, scales=None):
+        """cts [nct][2][level+1][N], h0agg [nct][level+1][N], h1agg, crs [nct][nq][N] -> [nct][2][nq][N] at level nq - 1"""
+        ins = [np.ascontiguousarray(a, dtype=np.uint64) for a in (cts, h0agg, h1agg, crs)]
+        nct = ins[0].shape[0]
+        shapes = [(nct, 2, self.nq, self.N)]
+        if scales is None:
+            return self._run_mixed("sfg_ring_refresh_finish_dev", ins, shapes,
+                                   lambda d, o: lib().sfg_ring_refresh_finish_dev(self.h, d[0], nct, level, d[1], d[2], d[3], o[0]))[0]
+        return self._run_mixed("sfg_ring_refresh_finish_scaled_dev", ins, shapes,
+                               lambda d, o: lib().sfg_ring_refresh_finish_scaled_dev(self.h, d[0], nct, level, float(scales[0]), float(scales[1]), d[1], d[2], d[3], o[0]))[0]
 
     def decode_coeffs(self, pt, level, scale, poly0_of_cts=False):
         """pt [nct][level+1][N] NTT-domain rows -> float64 [nct][N]: centred coefficient / scale.  poly0_of_cts: pt is [nct][2][level+1][N], polynomial 0 read in place"""

@@ -103,6 +103,7 @@ struct sfg_ring {
     bool test_hooks = false;                           // SFG_ENABLE_TEST_HOOKS=1 when the ring was made: the *_for_test entry points may be called
     GrIo io;
     GrKeygen kg;
+    std::map<int, GrBuf<u64>> rf_tabs;                 // gring_refresh.hip: the recode's tables of a level, built at its first use
     std::string err;
 };
 #define GR_FAIL(r, ...) do { char _b[512]; snprintf(_b, sizeof _b, __VA_ARGS__); (r)->err = _b; return 1; } while (0)
@@ -128,4 +129,8 @@ int gr_extend(sfg_ring *r, const GrExt &e, const u64 *src, u64 *Y, uint32_t *V, 
 int gr_check_level(sfg_ring *r, const char *what, int nct, int level);
 int gr_rows_from_mont(sfg_ring *r, u64 *rows, size_t nrows);      // lattigo ring.InvMForm on key rows [.][nmod][N], enqueued on the ring's stream
 // gring_io.hip
+struct GriDecTab { const u64 *qmod, *winv, *half; };               // the decoder's tables of a level
+int gri_dec_tab(sfg_ring *r, int level, GriDecTab *out);           // built at the level's first use, kept by the ring
+int gri_add_c0(sfg_ring *r, const u64 *ct, const u64 *h, u64 *pt, int nb, int level);          // pt [nb][nl][N] = c0 + h, one launch
+int gri_digits_inplace(sfg_ring *r, u64 *X, int nb, int level, const GriDecTab &tab);          // NTT-domain rows -> mixed-radix digits in place
 int gri_take_indices(sfg_ring *r, const char *what, int nct, u64 *first);       // nct consecutive encryption indices from the ring's one counter; refuses an unseeded encryptor

@@ -113,6 +113,13 @@ __global__ __launch_bounds__(GR_T) void k_gri_add_c0(const u64 *ct, const u64 *h
 }
 
 // ---------------------------------------------------------------- host side
+// pt [nb][nl][N] = c0 + h for nb <= kGrLaunchCap ciphertexts: one launch (the collective decryption's finish, the front of the collective bootstrap's)
+int gri_add_c0(sfg_ring *r, const u64 *ct, const u64 *h, u64 *pt, int nb, int level) {
+    const int nl = level + 1, N = r->N;
+    hipLaunchKernelGGL(k_gri_add_c0, dim3(N / GR_T, nl, (unsigned)nb), dim3(GR_T), 0, r->stream, ct, h, pt, r->modc, nl, N);
+    GR_HIP(r, hipGetLastError());
+    return 0;
+}
 // the workspace of a call, reserved before the call spends an encryption index: a failed allocation leaves the counter where it was
 static int gri_reserve(sfg_ring *r, int npoly, int nct, int level, bool with_u, GriPlan &plan) {
     plan = gri_plan(nct, level + 1, r->np, npoly, with_u, (size_t)r->N, r->io.ws_budget);
@@ -265,20 +272,15 @@ extern "C" int sfg_ring_pcks_finish_dev(sfg_ring *r, const uint64_t *ct, int nct
     GRI_ENTRY("sfg_ring_pcks_finish_dev")
     if (!ct || !h0agg || !pt) GR_FAIL(r, "sfg_ring_pcks_finish_dev: null ciphertexts, shares or output");
     const int nl = level + 1, N = r->N;
-    gr_split((size_t)nct, kGrLaunchCap, [&](size_t c0, size_t nb) {
-        hipLaunchKernelGGL(k_gri_add_c0, dim3(N / GR_T, nl, (unsigned)nb), dim3(GR_T), 0, r->stream, (const u64 *)ct + c0 * 2 * nl * N, (const u64 *)h0agg + c0 * nl * N,
-                           (u64 *)pt + c0 * nl * N, r->modc, nl, N);
-        return 0;
+    return gr_split((size_t)nct, kGrLaunchCap, [&](size_t c0, size_t nb) {
+        return gri_add_c0(r, (const u64 *)ct + c0 * 2 * nl * N, (const u64 *)h0agg + c0 * nl * N, (u64 *)pt + c0 * nl * N, (int)nb, level);
     });
-    GR_HIP(r, hipGetLastError());
-    return 0;
 }
 
 // ---------------------------------------------------------------- the decoder's coefficients (sfg_ring_decode_coeffs)
 // INTT of the rows; mixed-radix digits, one launch per digit, the digits taking the place of the residues row by row (rows of digits in the workspace, no per-thread
 // array: level + 1 may be 47); then one thread per coefficient walks its column of digits three times (gio::decode_digits).
-// tables of a level: qmod [nl][nl] (q_j mod q_i, j < i), winv [nl][2] (W_i^-1 mod q_i and its Shoup quotient), half [nl] (the digits of floor(Q / 2))
-struct GriDecTab { const u64 *qmod, *winv, *half; };
+// tables of a level (GriDecTab, gring_dev.hpp): qmod [nl][nl] (q_j mod q_i, j < i), winv [nl][2] (W_i^-1 mod q_i and its Shoup quotient), half [nl] (the digits of floor(Q / 2))
 // digit i of every coefficient: grid (N / 256, 1, chunk); X [chunk][nl][N], rows 0 .. i-1 digits already, row i the residue
 __global__ __launch_bounds__(GR_T) void k_gri_garner(u64 *X, GriDecTab t, const GrMod *modc, int i, int nl, int N) {
     const int x = blockIdx.x * GR_T + threadIdx.x; u64 *col = X + (size_t)blockIdx.z * nl * N + x;
@@ -294,7 +296,7 @@ __global__ __launch_bounds__(GR_T) void k_gri_decode_fin(u64 *X, double *out, Gr
                                                          [&](int i) { return modc[i].q; }, [&](int i) { return t.half[i]; }, scale);
 }
 
-static int gri_dec_tab(sfg_ring *r, int level, GriDecTab *out) {
+int gri_dec_tab(sfg_ring *r, int level, GriDecTab *out) {
     const int nl = level + 1;
     auto it = r->io.dec_tabs.find(level);
     if (it == r->io.dec_tabs.end()) {
@@ -323,14 +325,19 @@ static int gri_decode_checks(sfg_ring *r, const char *what, const void *src, con
     if (stride < rowsw) GR_FAIL(r, "%s: pt_stride %zu is below the (level + 1) * N = %zu words of a plaintext", what, stride, rowsw);
     return 0;
 }
-// residues of nb plaintexts (stride words apart) -> their mixed-radix digits in X [nb][nl][N]
-static int gri_digits(sfg_ring *r, const u64 *src, size_t stride, int nb, int level, u64 *X, const GriDecTab &tab) {
-    const int nl = level + 1, N = r->N; const size_t rowsw = (size_t)nl * N;
-    GR_HIP(r, hipMemcpy2DAsync(X, rowsw * 8, src, stride * 8, rowsw * 8, nb, hipMemcpyDeviceToDevice, r->stream));
+// NTT-domain residue rows X [nb][nl][N] -> their mixed-radix digits in place (nl == 1: the inverse transform alone, no Garner launch)
+int gri_digits_inplace(sfg_ring *r, u64 *X, int nb, int level, const GriDecTab &tab) {
+    const int nl = level + 1, N = r->N;
     GR_TRY(gr_transform(r, X, (size_t)nb * nl, gr_map(nl, nl, 0, 0), true));
     for (int i = 1; i < nl; i++) hipLaunchKernelGGL(k_gri_garner, dim3(N / GR_T, 1, (unsigned)nb), dim3(GR_T), 0, r->stream, X, tab, r->modc, i, nl, N);
     GR_HIP(r, hipGetLastError());
     return 0;
+}
+// residues of nb plaintexts (stride words apart) -> their mixed-radix digits in X [nb][nl][N]
+static int gri_digits(sfg_ring *r, const u64 *src, size_t stride, int nb, int level, u64 *X, const GriDecTab &tab) {
+    const int nl = level + 1, N = r->N; const size_t rowsw = (size_t)nl * N;
+    GR_HIP(r, hipMemcpy2DAsync(X, rowsw * 8, src, stride * 8, rowsw * 8, nb, hipMemcpyDeviceToDevice, r->stream));
+    return gri_digits_inplace(r, X, nb, level, tab);
 }
 extern "C" int sfg_ring_decode_coeffs(sfg_ring *r, const uint64_t *pt, size_t pt_stride, int nct, int level, double scale, double *coeffs_host) {
     GRI_ENTRY("sfg_ring_decode_coeffs")

@@ -1656,3 +1656,29 @@ inline void CollectiveRelinKeyGenFinish(crypto::RingParams *rp, const uint64_t *
     rp->check(sfg_ring_install_relinkey_dev(rp->ring, round2agg_dev, h1agg_dev), "RKGProtocol.GenRelinearizationKey");
 }
 }  // namespace mpc
+
+// ---- collective bootstrap at the other CKKS presets: the general ring's twins of CollectiveBootstrapGenShares / Finish above (gring_refresh.hip; DESIGN.md
+//      section 17; mpc/mhe.go:222-376 BootstrapMatAll, CollectiveBootstrapMat, CollectiveBootstrapVec).  Same randomness record, same layouts with the ring's N and
+//      nq; the aggregation of the shares stays in Go.  PARITY UNPINNED (see include/sfgwas_hip.h).
+namespace mpc {
+struct RingRefreshShares { std::shared_ptr<crypto::RingBuf> h0, h1; size_t nct = 0; int level = 0; };      // [nct][level+1][N], [nct][nq][N]
+// mhe.go:251,315: GenShares(skShard, levelStart, nParties, ct, parameters.Scale(), crp, ...) for nct device-resident ciphertexts of one level and scale ctScale
+inline RingRefreshShares CollectiveBootstrapGenShares(crypto::RingParams *rp, const uint64_t *ct_dev, size_t nct, int level, double ctScale, double paramsScale,
+                                                      const RefreshRandomness &rnd) {
+    RingRefreshShares sh; sh.nct = nct; sh.level = level;
+    const size_t N = (size_t)rp->N();
+    sh.h0 = std::make_shared<crypto::RingBuf>(rp, nct * (level + 1) * N * 8);
+    sh.h1 = std::make_shared<crypto::RingBuf>(rp, nct * rp->nq * N * 8);
+    rp->check(sfg_ring_refresh_gen_shares_scaled_dev(rp->ring, ct_dev, (int)nct, level, ctScale, paramsScale, rnd.crs, rnd.mask, rnd.maskLimbs, rnd.e0, rnd.e1,
+                                                     sh.h0->u(), sh.h1->u()), "RefreshProtocol.GenShares");
+    return sh;
+}
+// mhe.go:256-258,329-331: Decrypt, Recode(ct, parameters.Scale()), Recrypt with the aggregated shares: [nct][2][nq][N] at level nq - 1 and scale paramsScale
+inline std::shared_ptr<crypto::RingBuf> CollectiveBootstrapFinish(crypto::RingParams *rp, const uint64_t *ct_dev, size_t nct, int level, double ctScale, double paramsScale,
+                                                                  const uint64_t *h0agg, const uint64_t *h1agg, const uint64_t *crs) {
+    auto out = std::make_shared<crypto::RingBuf>(rp, nct * 2 * rp->nq * (size_t)rp->N() * 8);
+    rp->check(sfg_ring_refresh_finish_scaled_dev(rp->ring, ct_dev, (int)nct, level, ctScale, paramsScale, h0agg, h1agg, crs, out->u()),
+              "RefreshProtocol.Decrypt/Recode/Recrypt");
+    return out;
+}
+}  // namespace mpc
