@@ -9,6 +9,13 @@ X12    12    3 just below 2^61    2          the widest words: 4q near 2^63, (do
 X15    15    3 just below 2^61    2
 L19    12    17 x 36              2 x 36     19 moduli, more than the oracle ring holds; beta = 9
 P14    14    Q_PN14               P_PN14     both paths on the same parameters
+
+EDGE_NAMES (tests/test_ring_edges_ref.py, tests/test_gpu_ring_edges.py; all at logN 12 - what is at stake is the chain, not N):
+R21    12    18 x 61              3 x 61     PN15's digit shape with the widest words: alpha = 3, beta = 6, every digit full at the top level
+R38    12    34 x 61              4 x 61     PN16's shape: alpha = 4, beta = 9, a last digit of 2; the float sum can round DOWN from alpha = 4 on
+M48    12    47 x 61              1 x 61     beta = 47 single-modulus digits: the key sum's ceiling (also the bootstrap's widest chain, tests/ring_refresh_ref.py)
+A48    12    1 x 61               47 x 61    alpha = 47: one ModDown digit of 47 moduli, v up to 46 - the extension sum's ceiling
+V12    12    30, 61, 45           2 x 61     rescale and raw-copy digits whose source modulus is 2^31 times the target
 """
 import functools
 
@@ -36,10 +43,34 @@ def chain(name):
         return 12, sp(12, 36, 17), sp(12, 36, 2, skip=17)
     if name == "P14":
         return 14, list(ol.Q_PN14), list(ol.P_PN14)
+    if name == "R21":
+        m = sp(12, 61, 21)
+        return 12, m[:18], m[18:]
+    if name == "R38":
+        m = sp(12, 61, 38)
+        return 12, m[:34], m[34:]
+    if name == "M48":
+        m = sp(12, 61, 48)
+        return 12, m[:47], m[47:]
+    if name == "A48":
+        m = sp(12, 61, 48)
+        return 12, m[:1], m[1:]
+    if name == "V12":
+        return 12, sp(12, 30, 1) + sp(12, 61, 1) + sp(12, 45, 1), sp(12, 61, 2, skip=1)
     raise KeyError(name)
 
 
 NAMES = ["G12", "G13", "W15", "W16", "X12", "X15", "L19", "P14"]
+EDGE_NAMES = ["R21", "R38", "M48", "A48", "V12"]              # chains of the edge tests only: NAMES parametrises the other files and stays as it is
+
+# (chain, level) of the edge tests.  EDGE_KS: the directed rotation and product under a uniform key - W15 on both sides of np = 3 > level + 1, X15 at logN 15 (tiles
+# that span workgroups), R21 at its top and at level 9 (digits of 3, 3, 3, 1), R38's nine digits, V12's raw copies 61 -> 30 and 61 -> 45 bits and, at level 0,
+# 30 -> 61 alone, A48's ModDown digit of 47 moduli.
+# EDGE_MODDOWN: the same ciphertexts under ring_ref.identity_key.
+EDGE_KS = [("W15", 3), ("W15", 1), ("W16", 2), ("X12", 2), ("X15", 2), ("L19", 16), ("P14", 9), ("P14", 4), ("R21", 17), ("R21", 9), ("R38", 33), ("V12", 2), ("V12", 0),
+           ("A48", 0)]
+EDGE_MODDOWN = [("W15", 3), ("X12", 2), ("R21", 17), ("R38", 33), ("A48", 0)]
+EDGE_RESCALE = [("V12", 2), ("V12", 1), ("R21", 17), ("M48", 46)]
 
 
 def levels(name):

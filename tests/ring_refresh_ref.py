@@ -2,9 +2,9 @@
 tests/test_ring_refresh_ref.py and tests/test_gpu_ring_refresh.py, as tests/refresh_ref.py is for the PN14 path.
 
   * the statement: int(f) for the scales, the truncating quo, the tie x == floor(Q / 2) counted as negative (expected_shares, expected_finish);
-  * WideRing: a ring of any modulus count, its transforms served by as many 16-modulus oracle rings as it takes (ring_ref.SplitRing stops at 32);
-  * the chains: G12, G13, W15, W16, X12, L19, P14 of ring_cases, and M48 (47 + 1 moduli of 61 bits: Q_46 has 2867 bits, the widest integer the ring admits) and
-    M33 (32 + 1 moduli: a middle width) defined here;
+  * WideRing: a ring of any modulus count, its transforms served by as many 16-modulus oracle rings as it takes;
+  * the chains: G12, G13, W15, W16, X12, L19, P14 of ring_cases, M48 of ring_cases' edge chains (47 + 1 moduli of 61 bits: Q_46 has 2867 bits, the widest integer the
+    ring admits) and M33 (32 + 1 moduli: a middle width) defined here;
   * directed plaintext integers, masks and scale pairs, placed at coefficients 0, 63, 64, 255, 256, N - 1 and a seeded spread, the rest a seeded random fill;
   * a limb-level model of gring_refresh_arith.hpp (lists of 64-bit words) with planted mistakes and a record of the branch classes its inputs take.
 PARITY UNPINNED like the PN14 path: the semantics are lattigo v2.1.0 / v2.2.0 dckks/refresh.go as oracle/sfgwas_oracle.c restates them.
@@ -30,9 +30,6 @@ NAMES = ["G12", "G13", "W15", "W16", "X12", "L19", "P14", "M48", "M33"]
 @functools.lru_cache(maxsize=None)
 def chain(name):
     """-> (logN, q, p)"""
-    if name == "M48":
-        m = ol.small_primes(12, 61, 48)
-        return 12, m[:47], m[47:]
     if name == "M33":
         m = ol.small_primes(12, 61, 33)
         return 12, m[:32], m[32:]

@@ -3,6 +3,11 @@ transforms, rotations, conjugation, the evaluator operations, the 19-modulus cha
 against the specialised Context, an end-to-end rotate / square / rescale on two wide chains, every refusal with its message, and the rotation, the product
 and the rescale on batches that need a second chunk of the workspace.  The launch splits at 16384 ciphertexts and at 32768 rows need gigabytes per operand and
 are not run here: tests/test_ring_ref.py holds the split helper and the caps on the CPU.
+What holds the key switch beyond this file: the words here are uniform or one of five directed rows, which put the basis extension's float sum on an integer with
+probability around 2^-50, and the chains add at most 9 terms of 36 bits or 2 of 61 into a 128-bit sum.  tests/test_gpu_ring_edges.py runs directed words on both
+float boundaries of every digit and of ModDown, 61-bit chains of 18 + 3, 34 + 4, 47 + 1 and 1 + 47 moduli with the sums at their ceilings, and the rescale onto a
+modulus 2^31 times smaller; tests/test_ring_edges_ref.py asserts from the model's trace that those words reach the classes v_float - v_exact = +1, 0 (and -1 from
+four moduli a digit on) and that a model which rounds v, takes it exact or multiplies by fl(1/q) gives other words.
 One device ring, one oracle ring and one key set per chain for the module."""
 import atexit
 import ctypes as C
