@@ -125,6 +125,27 @@ int sfg_mac_dev(sfg_ctx *ctx, const uint64_t *rot_dev, const uint64_t *pt_dev, u
 int sfg_mac_i8_dev(sfg_ctx *ctx, const uint64_t *rot_dev, const uint64_t *pt_half_dev, uint64_t *out_dev,
                    int K, int R, int Ncols, int L, int accumulate, int pt_form);
 
+/* Test hook (refused unless SFG_ENABLE_TEST_HOOKS=1 was set before sfg_ctx_create): the int8 MAC's plaintext transposition by itself, through the launches a
+ * product makes (i8_ride_prepare, launch_i8_pack_pt_digits, launch_move_alone, launch_ntt_plain_half with mover workgroups, i8_ride_finish; mac_i8.hip).
+ * panel_dev: the caller's digit-plane panel of K rows x Ncols columns x the first L moduli, panel_bytes long, in layout 0 (rows of N/2 words, planes first;
+ * pt_k / pt_n = words between consecutive k / columns), 1 (compact: a plaintext's planes back to back; same strides) or 2 (K-major
+ * [column][plane][128-byte block][k < K][128 B]; strides ignored).  The mover addresses rows up to the end of the last 64-row chunk, so the panel must reach
+ * that far (layout 2: (64 ceil(K/64) - K) * 128 bytes past its last plane); the hook refuses a shorter one.  It fills the tile buffers and 4096 guard bytes behind
+ * each with `sentinel`, then transposes by
+ *   mode 0  the pass (k_i8_pack_pt_digits) over every item;
+ *   mode 1  one launch of a2 mover workgroups alone over items [a0, a0 + a1);
+ *   mode 2  the ride: i8_ride_prepare for a0 predicted NTT launches and a1 mover workgroups (a multiple of 8), then a2 <= 11 plaintext-NTT launches of 8
+ *           plaintexts each (coefficients pc_host [a2 * 8][N/2] doubles, digit-plane K-major form, into a scratch second panel of one 91-row column that was
+ *           filled with `sentinel`), each carrying the slice launch_encode_rows would give it, then i8_ride_finish.  no_mover != 0: the same NTT launches and
+ *           nothing else.
+ * and copies back tiles_small_host (n_small * (N/2) * ceil(Ncols/16) * ceil(K/64) * 5 * 1024 bytes + 4096; *_cap = the buffer's size), tiles_big_host (the same
+ * with 6 for the one modulus above 2^36, if any) and, in mode 2, panel2_host (planes * 64 * 91 * 128 bytes).  info[8]: [0] 1 if the ride was prepared - 0 means
+ * it declined (no 35-bit modulus, a six-digit modulus above the int8 range, offsets beyond 32 bits) and NOTHING was launched or written; [1] items the leftover
+ * launch of i8_ride_finish took; [2], [3] five- and six-digit items; [4] items per NTT launch; [5] 35-bit moduli, [6] the first of them, [7] the big one or -1. */
+int sfg_i8_move_for_test(sfg_ctx *ctx, const uint64_t *panel_dev, size_t panel_bytes, int layout, size_t pt_k, size_t pt_n, int K, int Ncols, int L,
+                         int mode, int a0, int a1, int a2, int no_mover, const double *pc_host, int sentinel,
+                         uint8_t *tiles_small_host, size_t small_cap, uint8_t *tiles_big_host, size_t big_cap, uint8_t *panel2_host, size_t panel2_cap, int *info);
+
 /* ---- A6/A7: diagonal extraction + CKKS encode (matmult.go:636-731, EncodeNTT) ----
  * Encodes the generalized diagonals `shift` in [shift0, shift0+nshift) of one <= slots x slots int8 block
  * (block rows r, cols c, row stride ld; transposed != 0 reads the block transposed), each right-rotated by

@@ -202,6 +202,7 @@ def _sig(L):
         "sfg_intt_rows": (i, [vp, vp, i, C.POINTER(i)]),
         "sfg_mac_dev": (i, [vp, vp, vp, vp, i, i, i, i, i]),
         "sfg_mac_i8_dev": (i, [vp, vp, vp, vp, i, i, i, i, i, i]),
+        "sfg_i8_move_for_test": (i, [vp, vp, sz, i, sz, sz, i, i, i, i, i, i, i, i, vp, i, vp, sz, vp, sz, vp, sz, C.POINTER(i)]),
         "sfg_encode_diags_dev": (i, [vp, vp, sz, i, i, i, i, i, i, vp]),
         "sfg_encode_coeffs_host": (i, [vp, C.POINTER(d), i, C.POINTER(C.c_int64)]),
         "sfg_encode_vectors_dev": (i, [vp, C.POINTER(d), i, i, vp]),
@@ -571,6 +572,47 @@ def _ctx_mac_i8(self, rot, pt_half, L, K=None, out_init=None, pt_form=0):
 
 
 Context.mac_i8 = _ctx_mac_i8
+
+
+I8T_GUARD = 4096
+
+
+def _ctx_i8_move_for_test(self, panel, layout, pt_k, pt_n, K, Ncols, L, mode, a0=0, a1=0, a2=0, no_mover=False, pc=None, sentinel=0xA5):
+    """sfg_i8_move_for_test (test hook): the int8 MAC's plaintext transposition through the product's own launches.  panel: the digit-plane panel as host bytes
+    (tests/i8tile_ref.py places one); mode 0: the pass, 1: a0 = first, a1 = count, a2 = mover workgroups alone, 2: a0 = predicted NTT launches, a1 = mover
+    workgroups, a2 = launches made of 8 plaintexts each, pc [a2 * 8][N/2] doubles.  Returns a dict: on (False: the ride declined and nothing was launched),
+    leftover, n5, n6, per, small / big (the tile buffers with their guard bands, uint8; big is None without a six-digit modulus), panel2 (mode 2), panel_after
+    (the caller's panel read back)."""
+    panel = np.ascontiguousarray(panel, dtype=np.uint8)
+    H = self.N // 2
+    nch, njt = (K + 63) // 64, (Ncols + 15) // 16
+    small_q = [q < (1 << 36) for q in self.q[:L]]
+    n_small, n_big = sum(small_q), L - sum(small_q)
+    planes = 5 * n_small + 6 * n_big
+    small = np.zeros(max(n_small, 1) * H * njt * nch * 5 * 1024 + I8T_GUARD, dtype=np.uint8)
+    big = np.zeros(H * njt * nch * 6 * 1024 + I8T_GUARD, dtype=np.uint8) if n_big else None
+    panel2 = np.zeros(planes * 64 * 91 * 128, dtype=np.uint8) if mode == 2 else None
+    pcp = None
+    if mode == 2:
+        pc = np.ascontiguousarray(pc, dtype=np.float64)
+        assert pc.size >= a2 * 8 * H
+        pcp = pc.ctypes.data_as(C.c_void_p)
+    info = (C.c_int * 8)()
+    d_panel = self.to_device(panel)
+    try:
+        self.check(lib().sfg_i8_move_for_test(self.h, d_panel, panel.nbytes, layout, pt_k, pt_n, K, Ncols, L, mode, a0, a1, a2, int(no_mover), pcp, sentinel,
+                                              small.ctypes.data_as(C.c_void_p), small.nbytes,
+                                              None if big is None else big.ctypes.data_as(C.c_void_p), 0 if big is None else big.nbytes,
+                                              None if panel2 is None else panel2.ctypes.data_as(C.c_void_p), 0 if panel2 is None else panel2.nbytes, info),
+                   "sfg_i8_move_for_test")
+        after = self.to_host(d_panel, panel.shape, np.uint8)
+    finally:
+        self.free(d_panel)
+    return dict(on=bool(info[0]), leftover=info[1], n5=info[2], n6=info[3], per=info[4], n_small=info[5], l_small0=info[6], l_big=info[7],
+                small=small, big=big, panel2=panel2, panel_after=after)
+
+
+Context.i8_move_for_test = _ctx_i8_move_for_test
 
 
 def _ctx_encode_diags(self, block, shift0, nshift, L, transposed=False):

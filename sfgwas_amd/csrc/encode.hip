@@ -489,8 +489,8 @@ int launch_encode_rows(sfg_ctx *ctx, const int8_t *D, int shift0, int nshift, in
         if (half_rows && G > 0) {
             // the riding transposition: this launch's share of the previous MAC launch's panel goes along as mover workgroups (k_ntt_half3_move)
             MoveJob mj; const MoveJob *mv = nullptr; double moved = 0;
-            if (ride && ride->on && ride->next < ride->total()) {
-                mj = ride->job; mj.first = ride->next; mj.count = std::min(ride->per, ride->total() - ride->next); ride->next += mj.count; mv = &mj;
+            if (ride && i8_ride_take(*ride, mj)) {
+                mv = &mj;
                 const unsigned hi = mj.first + mj.count, n5 = mj.n5, in5 = mj.first < n5 ? std::min(hi, n5) - mj.first : 0u;
                 moved = in5 * ride->item_bytes5 + (mj.count - in5) * ride->item_bytes6;
                 if (sampled) { PhaseStat &ps = ctx->phases["pt_ride"]; ps.launches += 1; ps.bytes += moved; }       // (the timed launches' share: same sample as ntt_plain_ride)

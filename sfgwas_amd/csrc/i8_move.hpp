@@ -39,6 +39,15 @@ struct PtRide {
     unsigned total() const { return job.n5 + job.n6; }
     double item_bytes5 = 0, item_bytes6 = 0;      // bytes read + written per item (phase statistics)
 };
+// host: the slice the next NTT launch carries - `per` items from `next`, the last one whatever is left; false (and mj untouched) once everything is dealt or the
+// ride is off.  The ONE place that deals slices: launch_encode_rows (encode.hip) and the test hook sfg_i8_move_for_test (mac_i8.hip) both call it, and
+// i8_ride_finish takes [next, total) afterwards.  tests/i8tile_ref.py launch_slices states the same dealing in plain integers.
+inline bool i8_ride_take(PtRide &ride, MoveJob &mj) {
+    if (!ride.on || ride.next >= ride.total()) return false;
+    const unsigned left = ride.total() - ride.next;
+    mj = ride.job; mj.first = ride.next; mj.count = ride.per < left ? ride.per : left; ride.next += mj.count;
+    return true;
+}
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 constexpr int I8_ND = 5;                   // digits per operand word of a 35-bit modulus (the 46-bit one: 6)

@@ -613,3 +613,86 @@ extern "C" int sfg_mac_i8_dev(sfg_ctx *ctx, const uint64_t *rot, const uint64_t 
     (void)hipStreamSynchronize(ctx->stream); (void)hipFree(rotf); (void)hipFree(ptp);
     return rc;
 }
+
+// ---- test hook: the plaintext transposition by itself (tests/test_gpu_i8_move.py; refused without SFG_ENABLE_TEST_HOOKS=1).  Not a second implementation: the args of
+// every launch come from i8_ride_prepare, the slices from i8_ride_take, the launches are launch_i8_pack_pt_digits / launch_move_alone / launch_ntt_plain_half /
+// i8_ride_finish as matmul.hip and encode.hip make them.  The hook owns only the sentinel fill, the bounds it checks on the caller's panel, and the copies back.
+constexpr size_t I8T_GUARD = 4096;         // sentinel bytes behind each tile buffer
+extern "C" int sfg_i8_move_for_test(sfg_ctx *ctx, const uint64_t *panel_dev, size_t panel_bytes, int layout, size_t pt_k, size_t pt_n, int K, int Ncols, int L,
+                                    int mode, int a0, int a1, int a2, int no_mover, const double *pc_host, int sentinel,
+                                    uint8_t *tiles_small_host, size_t small_cap, uint8_t *tiles_big_host, size_t big_cap, uint8_t *panel2_host, size_t panel2_cap, int *info) {
+    SFG_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->test_hooks) SFG_FAIL(ctx, "sfg_i8_move_for_test: test hook, enabled only by SFG_ENABLE_TEST_HOOKS=1 at context creation");
+    if (!panel_dev || !info) SFG_FAIL(ctx, "sfg_i8_move_for_test: null argument");
+    if (L < 1 || L > ctx->nq || K < 1 || K > 4096 || Ncols < 1 || Ncols > 96) SFG_FAIL(ctx, "sfg_i8_move_for_test: 1 <= L <= %d, 1 <= K <= 4096, 1 <= Ncols <= 96", ctx->nq);
+    if (layout < 0 || layout > 2 || mode < 0 || mode > 2) SFG_FAIL(ctx, "sfg_i8_move_for_test: layout is 0, 1 or 2 and mode 0 (pass), 1 (alone) or 2 (riding)");
+    const size_t H = SFG_N / 2;
+    for (int i = 0; i < 8; i++) info[i] = 0;
+    int l_small0, n_small, l_big;
+    if (!i8_ride_moduli(ctx, L, l_small0, n_small, l_big)) return 0;                        // declined: nothing launched, nothing written
+    const int nch = (K + 63) / 64, njt = (Ncols + 15) / 16;
+    size_t planes = 0; for (int t = 0; t < L; t++) planes += ctx->q[t] < (1ULL << 36) ? 5 : 6;
+    // every byte the transposition may read lies in the caller's panel: rows up to the end of the last 64-row chunk are addressed (and zeroed afterwards) by the mover
+    size_t reach;
+    if (layout == 2) reach = (size_t)Ncols * planes * 64 * K * 128 + (size_t)(nch * 64 - K) * 128;
+    else {
+        if (!pt_k || !pt_n) SFG_FAIL(ctx, "sfg_i8_move_for_test: layouts 0 and 1 take the caller's strides");
+        reach = ((size_t)(nch * 64 - 1) * pt_k + (size_t)(Ncols - 1) * pt_n) * 8 + (layout == 0 ? (size_t)L * H * 8 : planes * H);
+    }
+    if (panel_bytes < reach) SFG_FAIL(ctx, "sfg_i8_move_for_test: the panel holds %zu bytes, the transposition addresses %zu", panel_bytes, reach);
+    const size_t small_bytes = (size_t)n_small * H * njt * nch * 5 * 1024, big_bytes = l_big >= 0 ? H * njt * nch * 6 * 1024 : 0;
+    if (!tiles_small_host || small_cap < small_bytes + I8T_GUARD || (big_bytes && (!tiles_big_host || big_cap < big_bytes + I8T_GUARD)))
+        SFG_FAIL(ctx, "sfg_i8_move_for_test: the tile buffers are %zu and %zu bytes plus %zu of guard each", small_bytes, big_bytes, I8T_GUARD);
+    // the ride's own scratch entries, grown by the guard band first so that i8_ride_tiles finds them large enough and leaves them where they are
+    int8_t *Bs = nullptr, *Bb = nullptr;
+    SFG_TRY(sfg_scratch(ctx, "mi8.Bs", mac_i8_tile_bytes(K, n_small, 5) + I8T_GUARD, (void **)&Bs));
+    if (l_big >= 0) SFG_TRY(sfg_scratch(ctx, "mi8.Bb", mac_i8_tile_bytes(K, 1, 6) + I8T_GUARD, (void **)&Bb));
+    const int launches = mode == 2 ? a0 : 1, made = mode == 2 ? a2 : 0;
+    unsigned mask = 0; u64 *pt2 = nullptr; double *pc = nullptr; size_t pt2_bytes = 0;
+    if (mode == 2) {
+        if (a0 < 1 || a1 < 8 || a1 % 8 || a1 > 2048 || made < 0 || made > 11 || !pc_host) SFG_FAIL(ctx, "sfg_i8_move_for_test: riding takes >= 1 predicted launches, 8 .. 2048 mover workgroups (a multiple of 8), 0 .. 11 launches of 8 plaintexts and their coefficients");
+        mask = mac_dma_packed_mask(ctx, L) | PT_DIGITS | (l_big >= 0 ? PT_DIGITS_BIG : 0u) | PT_COMPACT | PT_KMAJOR;
+        if (!(mask & ((1u << L) - 1u))) SFG_FAIL(ctx, "sfg_i8_move_for_test: this context does not write packed plaintext rows");
+        pt2_bytes = planes * 64 * SFG_D * 128;                      // one K-major column of 91 rows: 11 launches of 8 plaintexts fit
+        if (!panel2_host || panel2_cap < pt2_bytes) SFG_FAIL(ctx, "sfg_i8_move_for_test: the second panel is %zu bytes", pt2_bytes);
+        SFG_TRY(sfg_scratch(ctx, "i8t.pt2", pt2_bytes, (void **)&pt2));
+        SFG_TRY(sfg_scratch(ctx, "i8t.pc", (size_t)(made ? made : 1) * 8 * H * 8, (void **)&pc));
+        if (made) SFG_HIP(ctx, hipMemcpyAsync(pc, pc_host, (size_t)made * 8 * H * 8, hipMemcpyHostToDevice, ctx->stream));
+        SFG_HIP(ctx, hipMemsetAsync(pt2, sentinel, pt2_bytes, ctx->stream));
+    }
+    PtRide ride;
+    const int ride_cfg = ctx->cfg.pt_ride;
+    if (mode == 2) ctx->cfg.pt_ride = a1;                           // (i8_ride_prepare takes the mover workgroup count from the configuration)
+    else if (ctx->cfg.pt_ride <= 0) ctx->cfg.pt_ride = 8;
+    const int rc = i8_ride_prepare(ctx, (const u64 *)panel_dev, K, Ncols, pt_k, pt_n, layout, L, launches, ride);
+    ctx->cfg.pt_ride = ride_cfg;
+    if (rc) return rc;
+    if (!ride.on) return 0;                                         // declined (offsets beyond 32 bits): nothing launched
+    if (ride.job.a5.B != Bs || (ride.job.n6 && ride.job.a6.B != Bb)) SFG_FAIL(ctx, "sfg_i8_move_for_test: internal: the tile buffers moved");
+    SFG_HIP(ctx, hipMemsetAsync(Bs, sentinel, small_bytes + I8T_GUARD, ctx->stream));
+    if (big_bytes) SFG_HIP(ctx, hipMemsetAsync(Bb, sentinel, big_bytes + I8T_GUARD, ctx->stream));
+    info[0] = 1; info[2] = (int)ride.job.n5; info[3] = (int)ride.job.n6; info[4] = (int)ride.per; info[5] = n_small; info[6] = l_small0; info[7] = l_big;
+    if (mode == 0) {
+        launch_i8_pack_pt_digits(ctx->stream, ride.job.a5, ride.job.n5, false);
+        if (ride.job.n6) launch_i8_pack_pt_digits(ctx->stream, ride.job.a6, ride.job.n6, true);
+        SFG_HIP(ctx, hipGetLastError());
+    } else if (mode == 1) {
+        if (a0 < 0 || a1 < 0 || a2 < 1 || a2 > 2048 || (unsigned)a0 + (unsigned)a1 > ride.total()) SFG_FAIL(ctx, "sfg_i8_move_for_test: slice [%d, %d + %d) of %u items, %d workgroups", a0, a0, a1, ride.total(), a2);
+        MoveJob j = ride.job; j.first = (unsigned)a0; j.count = (unsigned)a1; j.nblocks = (unsigned)a2;
+        if (j.count) launch_move_alone(ctx->stream, j);
+        SFG_HIP(ctx, hipGetLastError());
+    } else {
+        for (int i = 0; i < made; i++) {
+            MoveJob mj; const MoveJob *mv = nullptr;
+            if (!no_mover && i8_ride_take(ride, mj)) mv = &mj;
+            PanelMap pm{1, 0, 8 * i, mask}; pm.K = SFG_D;
+            SFG_TRY(launch_ntt_plain_half(ctx, pc + (size_t)i * 8 * H, pt2, 8, L, pm, nullptr, mv));
+        }
+        if (!no_mover) { info[1] = (int)(ride.total() - ride.next); SFG_TRY(i8_ride_finish(ctx, ride)); }
+    }
+    SFG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SFG_HIP(ctx, hipMemcpy(tiles_small_host, Bs, small_bytes + I8T_GUARD, hipMemcpyDeviceToHost));
+    if (big_bytes) SFG_HIP(ctx, hipMemcpy(tiles_big_host, Bb, big_bytes + I8T_GUARD, hipMemcpyDeviceToHost));
+    if (mode == 2) SFG_HIP(ctx, hipMemcpy(panel2_host, pt2, pt2_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}

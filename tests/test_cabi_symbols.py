@@ -190,7 +190,7 @@ def test_every_test_hook_is_declared_as_refused_without_the_test_switch():
     library must carry that refusal in its text"""
     hdr = open(os.path.join(ROOT, "include", "sfgwas_hip.h")).read()
     hooks = sorted(set(re.findall(r"\b(sfg_[a-z0-9_]+_for_test)\s*\(", hdr)))
-    assert "sfg_mgpu_inject_failure_for_test" in hooks and "sfg_ctx_encoder_inject_unsafe_for_test" in hooks
+    assert "sfg_mgpu_inject_failure_for_test" in hooks and "sfg_ctx_encoder_inject_unsafe_for_test" in hooks and "sfg_i8_move_for_test" in hooks
     for name in hooks:
         decl = hdr.index(name + "(")
         comment = hdr[hdr.rindex("/*", 0, decl):decl]
@@ -198,3 +198,4 @@ def test_every_test_hook_is_declared_as_refused_without_the_test_switch():
     from sfgwas_amd import capi
     blob = open(capi.LIB_PATH, "rb").read()
     assert b"sfg_mgpu_inject_failure_for_test: test hook, enabled only" in blob
+    assert b"sfg_i8_move_for_test: test hook, enabled only" in blob

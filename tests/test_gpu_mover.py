@@ -1,7 +1,8 @@
 """The low-occupancy mover (sfgwas_amd/csrc/i8_move.hpp) against the transposition pass it stands in for (k_i8_pack_pt_digits): random panel bytes through both, every
 word of both tile buffers compared on the device - alone on the chip and riding in front of plaintext-NTT launches (k_ntt_half3_move), at every depth of prefetch and
 with / without streaming accesses.  The hook (ubench_ntt_move, modes 6 and 7) lives in the experimenters' build, so the comparison runs in a child process on
-sfgwas_amd/lib_ab; what the PRODUCT does with the mover - the riding transposition over the K-major panel - is held against the oracle by every product test."""
+sfgwas_amd/lib_ab; what the PRODUCT does with the mover - the riding transposition over the K-major panel - is held against the oracle by every product test.
+The product library's pass, mover and ride against a reference that is not the pass, slice by slice: tests/test_gpu_i8_move.py."""
 import os
 import subprocess
 import sys
