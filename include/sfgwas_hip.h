@@ -774,7 +774,7 @@ double sfg_last_phase_bytes(const sfg_ctx *ctx, const char *phase);
  * sfg_ctx is built for PN14QP438 alone (N = 16384, moduli below 2^47 held exactly in fp64).  sfg_ring serves 12 <= logN <= 16 and any prime modulus
  * q < 2^61 with q == 1 mod 2N (lattigo's own bound) in integer arithmetic; nq >= 1, np >= 1, nq + np <= 48.  It covers the ring arithmetic of
  * crypto/basics.go on device-resident ciphertexts - every word equal to lattigo's canonical residue - and, further down, public-key encryption and the collective decryption's
- * local halves, the encoder and the decoder; the matrix products stay with the caller at these presets.  Layouts are those of the sfg_ctx twin of each call: ciphertext [nct][2][level+1][N], key [beta][2][nq+np][N] in the NTT
+ * local halves, the encoder and the decoder, collective key generation, the collective bootstrap's local halves and, last in this header, the two matrix products.  Layouts are those of the sfg_ctx twin of each call: ciphertext [nct][2][level+1][N], key [beta][2][nq+np][N] in the NTT
  * domain with beta = ceil(nq/np), montgomery_form != 0 for lattigo's stored representation.  PN14QP438's own parameters are accepted as well.
  * Every call returns 0, or 1 with the cause in sfg_ring_last_error; all device work is ordered on the ring's own non-blocking stream.
  * psi NULL: derived as lattigo's ring.NewRing derives it; otherwise psi[m] must be a primitive 2N-th root of unity modulo moduli[m]. */
@@ -956,6 +956,43 @@ int sfg_ring_refresh_gen_shares_scaled_dev(sfg_ring *ring, const uint64_t *ct_de
                                            const uint64_t *mask_dev, int mask_limbs, const int32_t *e0_dev, const int32_t *e1_dev, uint64_t *h0_dev, uint64_t *h1_dev);
 int sfg_ring_refresh_finish_scaled_dev(sfg_ring *ring, const uint64_t *ct_dev, int nct, int level, double ct_scale, double target_scale, const uint64_t *h0agg_dev,
                                        const uint64_t *h1agg_dev, const uint64_t *crs_dev, uint64_t *out_dev);
+
+/* ---- the general ring's matrix products (gring_matmul.hip): gwas/matmult.go MatMult4Stream at every ring sfg_ring_create accepts ----
+ * The twins of sfg_matmul_stream / sfg_matmul_accumulate_dev / sfg_matmul_finalize_dev above with slots = N/2 and d = ceil(sqrt(slots)), in the ring's integer
+ * arithmetic; the layouts are those of orc_matmult_accumulate / orc_matmult_finalize (oracle/sfgwas_oracle.c), so words compare directly:
+ *   A    [s][nbr][2][in_level+1][N], nbr = ceil(rows / slots) of the OPERAND (the matrix, or its transpose with SFG_TRANSPOSE)
+ *   acc  [m_ct][d][s][2][L][N] canonical residues, L = max_level, m_ct = ceil(columns of the operand / slots); zero where a giant step never became active
+ *   out  [s][m_ct][2][L][N] at level L - 1
+ * geno_dev: int8 [nrow][ld] in device memory of sfg_ring_malloc, ld >= ncol (sfg_geno belongs to sfg_ctx and is not used here).  Missing (negative) genotypes count
+ * as 0; SFG_SQUARE squares after that with the int8 wrap-around of matmult.go:1301-1303; SFG_TRANSPOSE multiplies by the transpose of the same bytes, no copy made.
+ * The level drops to min(in_level, max_level) (matmult.go:1256-1259); the diagonal of shift giant d + baby is rotated right by d giant and encoded at `scale` (a
+ * finite double >= 1; the ring carries none) over the first L moduli by sfg_ring_encode_vectors_dev's encoder, from device memory: no diagonal crosses the host.
+ * A coefficient inside that encoder's proven band of a rounding tie, or outside |p| < 2^62, fails the call with the encoder's message before `out` is written (the
+ * exact re-derivation sfg_ctx has for such coefficients is not built here).
+ * The MAC sums rot (.) pt in 128 bits with no Montgomery form: REDC(rot MForm(pt)) = rot pt mod q, so the canonical words are the reference's.  The reference's u128
+ * sum silently wraps once terms (q - 1)^2 >= 2^128 (64 terms at 61-bit moduli; d alone is 182 at logN 16); the MAC folds its sum to a word below q every
+ * floor((2^128 - q) / (q - 1)^2) terms, so the DEFINED result is the exact sum modulo q.  That equals the reference wherever the reference does not wrap, which is
+ * at every lattigo preset (55-bit words allow 2^18 terms).
+ * Each refusal returns 1 with the cause in sfg_ring_last_error, launches nothing and writes nothing: s, nrow or ncol not positive; ld < ncol; a level out of range,
+ * max_level < 1 or min(in_level, max_level) + 1 < max_level; a bad block-row or giant range; a scale that is not finite or below 1; out, acc or the matrix
+ * overlapping A; an unknown flag bit; a missing rotation key, named by its left rotation, looked for over every baby and giant the call needs before its first
+ * launch. */
+/* gwas/matmult.go:1238-1505 MatMult4Stream (block products at :1280-1439, giant-step alignment and aggregation at :1443-1502): the accumulate over all block rows
+ * followed by the finalize over all giants; the accumulator lives in the ring's workspace, in chunks of ciphertexts under the products' byte budget (32 GiB; every
+ * chunk encodes the diagonals again) */
+int sfg_ring_matmul_dev(sfg_ring *ring, const uint64_t *A_dev, int s, int in_level, int max_level, const int8_t *geno_dev, size_t nrow, size_t ncol, size_t ld,
+                        unsigned flags, double scale, uint64_t *out_dev);
+/* matmult.go:1280-1439 and the reduction of :343-366 (ModularReduceV2) for operand block rows [b0, b1): rotation cache, diagonals, encode, lazy MAC, canonical
+ * residues.  giant_active_host [d] (may be NULL) is set where a giant step became active.  Partial accumulators of disjoint ranges add up modulo q to the whole's. */
+int sfg_ring_matmul_accumulate_dev(sfg_ring *ring, const uint64_t *A_dev, int s, int in_level, int max_level, const int8_t *geno_dev, size_t nrow, size_t ncol, size_t ld,
+                                   unsigned flags, double scale, int b0, int b1, uint64_t *acc_dev, uint8_t *giant_active_host);
+/* matmult.go:1443-1502: RotateRight(acc of giant g, -g d) at level L - 1 for the active giants g > 0 of [g0, g1) (giant_active_host NULL: all) and eval.Add; out is
+ * overwritten unless `accumulate` */
+int sfg_ring_matmul_finalize_dev(sfg_ring *ring, const uint64_t *acc_dev, const uint8_t *giant_active_host, int s, int max_level, int m_ct, int g0, int g1,
+                                 int accumulate, uint64_t *out_dev);
+/* test hook (replaces nothing in the reference): the byte budget that sizes the chunks of the ring's evaluator workspaces (key switch, rescale: 768 MiB; the products: 32 GiB), so
+ * that a small shape runs in several chunks.  Refused unless the process set SFG_ENABLE_TEST_HOOKS=1 before sfg_ring_create. */
+int sfg_ring_set_ws_budget_for_test(sfg_ring *ring, size_t bytes);
 
 #ifdef __cplusplus
 }

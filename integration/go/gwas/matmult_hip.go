@@ -65,9 +65,65 @@ func finish(cps *crypto.CryptoParams, h *hip.Ctx, flat []uint64, s, mct, maxLeve
 	return out
 }
 
-// MatMult4Stream - gwas/matmult.go:1238-1505, association path: on-the-fly encode from int8 rows.
+// columnSums: the sums the reference takes on the host beside the product (matmult.go:1292-1300): after missing -> 0, before squaring; the square of an int8 wraps
+// as the reference's does.
+func columnSums(geno []int8, nrow, ncol int) (sum, sq []float64) {
+	sum, sq = make([]float64, ncol), make([]float64, ncol)
+	for i := 0; i < nrow; i++ {
+		for j := 0; j < ncol; j++ {
+			x := geno[i*ncol+j]
+			if x < 0 {
+				x = 0
+			}
+			sum[j] += float64(x)
+			sq[j] += float64(int8(x * x))
+		}
+	}
+	return
+}
+
+// matMult4StreamRing: the product at a preset other than PN14QP438, on the general ring.  The fresh zeros of crypto.CZeroMat are added on the device when it holds a
+// public key, else by lattigo as in finish.
+func matMult4StreamRing(cps *crypto.CryptoParams, h *hip.Ring, A crypto.CipherMatrix, gfs *GenoFileStream, maxLevel int,
+	computeSquaredSum, square bool) (crypto.CipherMatrix, []float64, []float64) {
+	geno, nrow, ncol := readAllRows(gfs)
+	s, inLevel := len(A), A[0][0].Level()
+	aFlat := h.FlattenCipherMatrix(asRows(A), inLevel)
+	var sum, sq []float64
+	if computeSquaredSum {
+		sum, sq = columnSums(geno, nrow, ncol)
+	}
+	flat := h.MatMult(aFlat, s, inLevel, maxLevel, geno, nrow, ncol, square, false)
+	mct := (ncol-1)/cps.GetSlots() + 1
+	outScale := A[0][0].Scale() * cps.Params.Scale()
+	w := h.CtWords(maxLevel - 1)
+	if h.CanEncrypt() {
+		flat = h.AddFreshZero(flat, s*mct, maxLevel-1)
+	}
+	out := make(crypto.CipherMatrix, s)
+	for i := range out {
+		out[i] = crypto.CipherVector(h.VecFromFlat(flat[i*mct*w:(i+1)*mct*w], mct, maxLevel-1, outScale))
+	}
+	if !h.CanEncrypt() {
+		zeros := crypto.CZeroMat(cps, mct, s)
+		cps.WithEvaluator(func(eval ckks.Evaluator) error {
+			for i := range out {
+				for j := range out[i] {
+					eval.Add(out[i][j], zeros[i][j], out[i][j])
+				}
+			}
+			return nil
+		})
+	}
+	return out, sum, sq
+}
+
+// MatMult4Stream - gwas/matmult.go:1238-1505, association path: on-the-fly encode from int8 rows.  Dispatches on the parameters as crypto/basics_hip.go does.
 func MatMult4Stream(cps *crypto.CryptoParams, A crypto.CipherMatrix, gfs *GenoFileStream, maxLevel int,
 	computeSquaredSum, square bool, nproc int) (crypto.CipherMatrix, []float64, []float64) {
+	if h, general := hip.For(cps.Params).(*hip.Ring); general {
+		return matMult4StreamRing(cps, h, A, gfs, maxLevel, computeSquaredSum, square)
+	}
 	h := hip.Default.Fork() // GenoBlockMult runs assoc_num_blocks_parallel of these at once (assoc.go:360-408)
 	defer h.Close()
 	geno, nrow, ncol := readAllRows(gfs)

@@ -1101,8 +1101,8 @@ func (h *Ctx) BeaverMatmul(pid, limbs int, modulus, ar, am, br, bm []uint64, m, 
 
 // ----------------------------------------------------------------------------------------------------------------
 // The general ring: the evaluator operations of crypto/basics.go at the presets the specialised context does not serve (gwas/gwas.go:164-177: PN12QP109,
-// PN13QP218, PN15QP880, PN16QP1761 - any logN 12..16 with prime moduli below 2^61).  Encoding, encryption, decryption and the matrix products stay on lattigo
-// there (INTEGRATION.md, "The other CKKS presets").  A Ring keeps Ctx's host-side conventions: flat [nct][2][level+1][N] words in and out, panics on failure.
+// PN13QP218, PN15QP880, PN16QP1761 - any logN 12..16 with prime moduli below 2^61), its two ends, its collective key generation and bootstrap, and the two matrix
+// products (INTEGRATION.md, "The other CKKS presets").  A Ring keeps Ctx's host-side conventions: flat [nct][2][level+1][N] words in and out, panics on failure.
 type Ring struct {
 	p      *C.sfg_ring
 	Params *ckks.Parameters
@@ -1673,3 +1673,82 @@ func (r *Ring) ExportRotKey(galEl uint64) []uint64 {
 	r.check(C.sfg_ring_export_rotkey(r.p, C.uint64_t(galEl), (*C.uint64_t)(unsafe.Pointer(&out[0]))), "ring_export_rotkey")
 	return out
 }
+
+// ----------------------------------------------------------------------------------------------------------------
+// The general ring's matrix products (gwas/matmult.go:1238-1505 at the presets other than PN14QP438).  The int8 matrix goes to device memory of the ring as it is
+// (row-major, -1 = missing); aFlat is [s][nbr][2][inLevel+1][N] as Ctx.MatmulStream takes it.  The plaintext scale is the parameters' default scale.
+func (r *Ring) mmFlags(square, transpose bool) C.uint {
+	var f C.uint
+	if square {
+		f |= C.SFG_SQUARE
+	}
+	if transpose {
+		f |= C.SFG_TRANSPOSE
+	}
+	return f
+}
+
+func (r *Ring) uploadGeno(geno []int8) unsafe.Pointer {
+	d := r.allocBytes(len(geno))
+	r.check(C.sfg_ring_memcpy_h2d(r.p, d, unsafe.Pointer(&geno[0]), C.size_t(len(geno))), "ring_memcpy_h2d")
+	return d
+}
+
+// MatMult - MatMult4Stream (matmult.go:1238-1505): out [s][mct][2][maxLevel][N] at level maxLevel-1, the deterministic sum (the caller adds the fresh zeros).
+func (r *Ring) MatMult(aFlat []uint64, s, inLevel, maxLevel int, geno []int8, nrow, ncol int, square, transpose bool) []uint64 {
+	slots := r.N / 2
+	cols := ncol
+	if transpose {
+		cols = nrow
+	}
+	mct := (cols-1)/slots + 1
+	dG := r.uploadGeno(geno)
+	defer r.freeBytes(dG)
+	return r.unary(aFlat, s*mct*2*maxLevel*r.N, "ring_matmul", func(dA, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_matmul_dev(r.p, dA, C.int(s), C.int(inLevel), C.int(maxLevel), (*C.int8_t)(dG), C.size_t(nrow), C.size_t(ncol), C.size_t(ncol),
+			r.mmFlags(square, transpose), C.double(r.Params.Scale()), dOut)
+	})
+}
+
+// MatMultD is ceil(sqrt(slots)): the number of baby and of giant steps (matmult.go:1249).
+func (r *Ring) MatMultD() int {
+	d := 1
+	for d*d < r.N/2 {
+		d++
+	}
+	return d
+}
+
+// MatMultAccumulate - matmult.go:1280-1439 and the reduction of :343-366 for operand block rows [b0, b1): acc [mct][d][s][2][maxLevel][N] canonical residues and
+// the giants that became active.  Partial accumulators of disjoint ranges add up modulo q (Binary "add" on their words) to the whole's.
+func (r *Ring) MatMultAccumulate(aFlat []uint64, s, inLevel, maxLevel int, geno []int8, nrow, ncol int, square, transpose bool, b0, b1 int) ([]uint64, []uint8) {
+	slots, d := r.N/2, r.MatMultD()
+	cols := ncol
+	if transpose {
+		cols = nrow
+	}
+	mct := (cols-1)/slots + 1
+	active := make([]uint8, d)
+	dG := r.uploadGeno(geno)
+	defer r.freeBytes(dG)
+	acc := r.unary(aFlat, mct*d*s*2*maxLevel*r.N, "ring_matmul_accumulate", func(dA, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_matmul_accumulate_dev(r.p, dA, C.int(s), C.int(inLevel), C.int(maxLevel), (*C.int8_t)(dG), C.size_t(nrow), C.size_t(ncol), C.size_t(ncol),
+			r.mmFlags(square, transpose), C.double(r.Params.Scale()), C.int(b0), C.int(b1), dOut, (*C.uint8_t)(unsafe.Pointer(&active[0])))
+	})
+	return acc, active
+}
+
+// MatMultFinalize - matmult.go:1443-1502: the active giants g > 0 rotated by -g d at level maxLevel-1 and summed: out [s][mct][2][maxLevel][N].
+func (r *Ring) MatMultFinalize(acc []uint64, active []uint8, s, maxLevel, mct int) []uint64 {
+	return r.unary(acc, s*mct*2*maxLevel*r.N, "ring_matmul_finalize", func(dAcc, dOut *C.uint64_t) C.int {
+		return C.sfg_ring_matmul_finalize_dev(r.p, dAcc, (*C.uint8_t)(unsafe.Pointer(&active[0])), C.int(s), C.int(maxLevel), C.int(mct), 0, C.int(r.MatMultD()), 0, dOut)
+	})
+}
+
+// FlattenCipherMatrix: rows [s][nbr] of ciphertexts -> [s][nbr][2][level+1][N], Ctx's own layout on the ring's parameters.
+func (r *Ring) FlattenCipherMatrix(rows [][]*ckks.Ciphertext, level int) []uint64 {
+	return r.host().FlattenCipherMatrix(rows, level)
+}
+
+// CanEncrypt: a public key is loaded and the sampler is keyed (Ring.LoadPublicKey, Ring.SeedEncryptor): the fresh zeros of a product can be made on the device.
+func (r *Ring) CanEncrypt() bool { return r.HasPublicKey() }

@@ -121,6 +121,10 @@ def _ring_sig():
         "sfg_ring_refresh_finish_dev": (i, [vp, vp, i, i, vp, vp, vp, vp]),
         "sfg_ring_refresh_gen_shares_scaled_dev": (i, [vp, vp, i, i, C.c_double, C.c_double, vp, vp, i, vp, vp, vp, vp]),
         "sfg_ring_refresh_finish_scaled_dev": (i, [vp, vp, i, i, C.c_double, C.c_double, vp, vp, vp, vp]),
+        "sfg_ring_matmul_dev": (i, [vp, vp, i, i, i, vp, sz, sz, sz, C.c_uint, C.c_double, vp]),
+        "sfg_ring_matmul_accumulate_dev": (i, [vp, vp, i, i, i, vp, sz, sz, sz, C.c_uint, C.c_double, i, i, vp, C.POINTER(C.c_uint8)]),
+        "sfg_ring_matmul_finalize_dev": (i, [vp, vp, C.POINTER(C.c_uint8), i, i, i, i, i, i, vp]),
+        "sfg_ring_set_ws_budget_for_test": (i, [vp, sz]),
     }
 
 
@@ -1984,3 +1988,67 @@ class Ring:
         n = len(mod_idx)
         mi = (C.c_int * max(n, 1))(*[int(x) for x in mod_idx])
         return self._kg("sfg_ring_crp_fill_dev", [], [(max(n, 1), self.N)], lambda d, o: lib().sfg_ring_crp_fill_dev(self.h, key32, int(first_row), n, mi, o[0]), keep, out)[0]
+
+    # ---- the matrix products (gring_matmul.hip)
+    def mm_shape(self, geno_shape, flags=0):
+        """-> (nbr, m_ct, d) of the operand: the matrix, or its transpose with SFG_TRANSPOSE"""
+        import math
+        nrow, ncol = geno_shape
+        rows, cols = (ncol, nrow) if flags & SFG_TRANSPOSE else (nrow, ncol)
+        d = math.isqrt(self.slots - 1) + 1
+        return (rows - 1) // self.slots + 1, (cols - 1) // self.slots + 1, d
+
+    def _mm_operands(self, A, in_level, geno, flags):
+        A = np.ascontiguousarray(A, dtype=np.uint64)
+        geno = np.ascontiguousarray(geno, dtype=np.int8)
+        nbr, m_ct, d = self.mm_shape(geno.shape, flags)
+        if A.ndim != 5 or A.shape[1:] != (nbr, 2, in_level + 1, self.N):
+            raise ValueError(f"A must be [s][{nbr}][2][{in_level + 1}][{self.N}], got {A.shape}")
+        return A, geno, nbr, m_ct, d
+
+    def matmul(self, A, in_level, max_level, geno, scale, flags=0):
+        """MatMult4Stream: A [s][nbr][2][in_level+1][N] x geno int8 [nrow][ncol] -> [s][m_ct][2][max_level][N]"""
+        A, geno, nbr, m_ct, d = self._mm_operands(A, in_level, geno, flags)
+        s = A.shape[0]
+        g = self.to_device(geno)
+        try:
+            return self._run("sfg_ring_matmul_dev", [A], (s, m_ct, 2, max_level, self.N),
+                             lambda dv, o: lib().sfg_ring_matmul_dev(self.h, dv[0], s, in_level, max_level, g, geno.shape[0], geno.shape[1], geno.shape[1], flags, float(scale), o))
+        finally:
+            self.free(g)
+
+    def matmul_accumulate(self, A, in_level, max_level, geno, scale, flags=0, b0=0, b1=None):
+        """-> (acc [m_ct][d][s][2][max_level][N] canonical, giant_active uint8 [d]) over operand block rows [b0, b1)"""
+        A, geno, nbr, m_ct, d = self._mm_operands(A, in_level, geno, flags)
+        s = A.shape[0]
+        b1 = nbr if b1 is None else b1
+        active = np.zeros(d, dtype=np.uint8)
+        g = self.to_device(geno)
+        try:
+            acc = self._run("sfg_ring_matmul_accumulate_dev", [A], (m_ct, d, s, 2, max_level, self.N),
+                            lambda dv, o: lib().sfg_ring_matmul_accumulate_dev(self.h, dv[0], s, in_level, max_level, g, geno.shape[0], geno.shape[1], geno.shape[1], flags,
+                                                                               float(scale), int(b0), int(b1), o, active.ctypes.data_as(C.POINTER(C.c_uint8))))
+        finally:
+            self.free(g)
+        return acc, active
+
+    def matmul_finalize(self, acc, giant_active, max_level, g0=0, g1=None, into=None):
+        """acc [m_ct][d][s][2][max_level][N] -> out [s][m_ct][2][max_level][N]: the giants of [g0, g1) that giant_active marks (None: all), added to `into` when given"""
+        acc = np.ascontiguousarray(acc, dtype=np.uint64)
+        m_ct, d, s = acc.shape[:3]
+        g1 = d if g1 is None else g1
+        ga = None if giant_active is None else np.ascontiguousarray(giant_active, dtype=np.uint8)
+        gp = None if ga is None else ga.ctypes.data_as(C.POINTER(C.c_uint8))
+        shape = (s, m_ct, 2, max_level, self.N)
+        devs = [self.to_device(acc)]
+        out = self.to_device(np.ascontiguousarray(into, dtype=np.uint64)) if into is not None else self.malloc(int(np.prod(shape)) * 8)
+        try:
+            self.check(lib().sfg_ring_matmul_finalize_dev(self.h, devs[0], gp, s, max_level, m_ct, int(g0), int(g1), int(into is not None), out), "sfg_ring_matmul_finalize_dev")
+            return self.to_host(out, shape)
+        finally:
+            for d_ in devs + [out]:
+                self.free(d_)
+
+    def set_ws_budget_for_test(self, nbytes):
+        """test hook (SFG_ENABLE_TEST_HOOKS=1 before the ring was made): the byte budget that sizes the chunks of the evaluator's workspaces"""
+        self.check(lib().sfg_ring_set_ws_budget_for_test(self.h, int(nbytes)), "sfg_ring_set_ws_budget_for_test")

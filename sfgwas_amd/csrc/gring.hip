@@ -323,15 +323,14 @@ int gr_extend(sfg_ring *r, const GrExt &e, const u64 *src, u64 *Y, uint32_t *V, 
     return 0;
 }
 
-// workspace of one chunk of key switches: the regions of gr_ks_layout (gring_plan.hpp) in the ring's workspace
-struct GrKsWs { u64 *c2, *Y, *ext, *accQ, *accP, *Y2, *ext2; uint32_t *V, *V2; GrJob *jobs; };
-static GrKsWs gr_ks_ws(void *ws, const GrKsLayout &l) {
+// workspace of one chunk of key switches (GrKsWs, gring_dev.hpp): the regions of gr_ks_layout (gring_plan.hpp) in the ring's workspace
+GrKsWs gr_ks_ws(void *ws, const GrKsLayout &l) {
     u64 *p = (u64 *)ws;
     return GrKsWs{p + l.c2, p + l.Y, p + l.ext, p + l.accQ, p + l.accP, p + l.Y2, p + l.ext2, (uint32_t *)(p + l.V), (uint32_t *)(p + l.V2), (GrJob *)(p + l.jobs)};
 }
 // lattigo switchKeysInPlace on J jobs whose c2 rows (NTT domain) are in w.c2 and whose job list is uploaded: out[ct][p] = d_p (+ add[ct][p] where add_mask says so),
 // read through the job's automorphism index
-static int gr_keyswitch(sfg_ring *r, int level, size_t J, const GrKsWs &w, const u64 *add, int add_mask, u64 *out) {
+int gr_keyswitch(sfg_ring *r, int level, size_t J, const GrKsWs &w, const u64 *add, int add_mask, u64 *out) {
     const int nl = level + 1, np = r->np, nt = nl + np, N = r->N; const unsigned gx = N / GR_T;
     GrLevel *L; GR_TRY(gr_level(r, level, &L));
     const int beta = L->up.e.ndig;
@@ -346,29 +345,13 @@ static int gr_keyswitch(sfg_ring *r, int level, size_t J, const GrKsWs &w, const
     GR_HIP(r, hipGetLastError());
     return 0;
 }
-// a batch of key switches in the chunks of gr_ks_plan: per chunk the job list is uploaded, front(first job, jobs, workspace) launches what fills the chunk's c2
-// rows (a job's ciphertext index is absolute, its workspace rows are the chunk's), and the key switch runs
-template <class Front>
-static int gr_ks_batch(sfg_ring *r, int level, const std::vector<GrJob> &jobs, const u64 *add, int add_mask, u64 *out, Front front) {
-    const GrChunks plan = gr_ks_plan(jobs.size(), level, r->np, (size_t)r->N, r->ws_budget);
-    GR_TRY(gr_reserve(r, r->ws, plan.bytes));
-    const GrKsWs w = gr_ks_ws(r->ws.p, gr_ks_layout(level, r->np, (size_t)r->N, plan.chunk));
-    for (size_t c = 0; c < plan.nchunks; c++) {
-        const size_t j0 = plan.first(c), n = plan.count(c, jobs.size());
-        GR_TRY(gr_upload(r, w.jobs, jobs.data() + j0, n * sizeof(GrJob)));
-        front(j0, n, w);
-        GR_TRY(gr_keyswitch(r, level, n, w, add, add_mask, out));
-    }
-    return 0;
-}
-
-static bool gr_overlap(const void *a, size_t na, const void *b, size_t nb) { const char *x = (const char *)a, *y = (const char *)b; return x < y + nb && y < x + na; }
+bool gr_overlap(const void *a, size_t na, const void *b, size_t nb) { const char *x = (const char *)a, *y = (const char *)b; return x < y + nb && y < x + na; }
 int gr_check_level(sfg_ring *r, const char *what, int nct, int level) {
     if (nct < 0) GR_FAIL(r, "%s: negative ciphertext count %d", what, nct);
     if (level < 0 || level >= r->nq) GR_FAIL(r, "%s: level %d out of range 0..%d", what, level, r->nq - 1);
     return 0;
 }
-static u64 gr_galois(const sfg_ring *r, int k) { const u64 M = 2ULL * r->N; int n = r->N / 2; k %= n; if (k < 0) k += n; u64 g = 1; for (int i = 0; i < k; i++) g = (g * 5) % M; return g; }
+u64 gr_galois(const sfg_ring *r, int k) { const u64 M = 2ULL * r->N; int n = r->N / 2; k %= n; if (k < 0) k += n; u64 g = 1; for (int i = 0; i < k; i++) g = (g * 5) % M; return g; }
 
 // automorphisms of a batch: ct j under galois[j] (0 = copy)
 static int gr_apply_galois(sfg_ring *r, const char *what, const u64 *in, u64 *out, int nct, int level, const std::vector<u64> &gal) {

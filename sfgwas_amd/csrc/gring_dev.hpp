@@ -1,5 +1,5 @@
 // gring_dev.hpp - what the general ring's translation units share (gring.hip: the ring, its transform, its evaluator; gring_io.hip: keys, sampler, encryption,
-// collective decryption): the device-side tables, the owners of what a ring holds, struct sfg_ring, the error macros, the host modular helpers and the host
+// collective decryption; gring_matmul.hip: the matrix products, which batch their rotations through gr_ks_batch and share the encoder's device half): the device-side tables, the owners of what a ring holds, struct sfg_ring, the error macros, the host modular helpers and the host
 // functions gring.hip defines.  Included by .hip files only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,6 +7,7 @@
 #include <map>
 #include <string>
 #include <utility>
+#include <vector>
 #include "../../include/sfgwas_hip.h"
 #include "gring_arith.hpp"
 #include "gring_plan.hpp"
@@ -99,7 +100,10 @@ struct sfg_ring {
     GrBuf<void> ws;                                    // grow-only workspace of the key switch and the rescale
     GrBuf<int> modidx;                                 // sfg_ring_ntt_rows' modulus table
     GrBuf<u64> small;                                  // the inner sum's rotated ciphertext
+    GrBuf<u64> mm_fold;                                // gring_matmul.hip: the fold bound of every modulus row (32-bit), built at first use
+    GrBuf<void> mm_ws;                                 // grow-only workspace of the matrix products (gring_matmul.hip), apart from ws: the key switches they batch use that one
     size_t ws_budget = 768ull << 20;
+    size_t mm_budget = 0;                              // the products' workspace budget; 0 = kMmBudgetBytes (gring_matmul_plan.hpp)
     bool test_hooks = false;                           // SFG_ENABLE_TEST_HOOKS=1 when the ring was made: the *_for_test entry points may be called
     GrIo io;
     GrKeygen kg;
@@ -127,6 +131,28 @@ int gr_transform_cols_fwd(sfg_ring *r, u64 *rows, size_t nrows, GrRowMap map);  
 GrRowMap gr_map(int period, int split, int base0, int base1);
 int gr_extend(sfg_ring *r, const GrExt &e, const u64 *src, u64 *Y, uint32_t *V, u64 *out, int ntgt, size_t npoly);
 int gr_check_level(sfg_ring *r, const char *what, int nct, int level);
+bool gr_overlap(const void *a, size_t na, const void *b, size_t nb);
+u64 gr_galois(const sfg_ring *r, int k_left);
+// workspace of one chunk of key switches: the regions of gr_ks_layout (gring_plan.hpp) in the ring's workspace
+struct GrKsWs { u64 *c2, *Y, *ext, *accQ, *accP, *Y2, *ext2; uint32_t *V, *V2; GrJob *jobs; };
+GrKsWs gr_ks_ws(void *ws, const GrKsLayout &l);
+// lattigo switchKeysInPlace on J jobs whose c2 rows (NTT domain) are in w.c2 and whose job list is uploaded
+int gr_keyswitch(sfg_ring *r, int level, size_t J, const GrKsWs &w, const u64 *add, int add_mask, u64 *out);
+// a batch of key switches in the chunks of gr_ks_plan: per chunk the job list is uploaded, front(first job, jobs, workspace) launches what fills the chunk's c2
+// rows (a job's ciphertext index is absolute, its workspace rows are the chunk's), and the key switch runs
+template <class Front>
+static int gr_ks_batch(sfg_ring *r, int level, const std::vector<GrJob> &jobs, const u64 *add, int add_mask, u64 *out, Front front) {
+    const GrChunks plan = gr_ks_plan(jobs.size(), level, r->np, (size_t)r->N, r->ws_budget);
+    GR_TRY(gr_reserve(r, r->ws, plan.bytes));
+    const GrKsWs w = gr_ks_ws(r->ws.p, gr_ks_layout(level, r->np, (size_t)r->N, plan.chunk));
+    for (size_t c = 0; c < plan.nchunks; c++) {
+        const size_t j0 = plan.first(c), n = plan.count(c, jobs.size());
+        GR_TRY(gr_upload(r, w.jobs, jobs.data() + j0, n * sizeof(GrJob)));
+        front(j0, n, w);
+        GR_TRY(gr_keyswitch(r, level, n, w, add, add_mask, out));
+    }
+    return 0;
+}
 int gr_rows_from_mont(sfg_ring *r, u64 *rows, size_t nrows);      // lattigo ring.InvMForm on key rows [.][nmod][N], enqueued on the ring's stream
 // gring_io.hip
 struct GriDecTab { const u64 *qmod, *winv, *half; };               // the decoder's tables of a level
@@ -134,3 +160,10 @@ int gri_dec_tab(sfg_ring *r, int level, GriDecTab *out);           // built at t
 int gri_add_c0(sfg_ring *r, const u64 *ct, const u64 *h, u64 *pt, int nb, int level);          // pt [nb][nl][N] = c0 + h, one launch
 int gri_digits_inplace(sfg_ring *r, u64 *X, int nb, int level, const GriDecTab &tab);          // NTT-domain rows -> mixed-radix digits in place
 int gri_take_indices(sfg_ring *r, const char *what, int nct, u64 *first);       // nct consecutive encryption indices from the ring's one counter; refuses an unseeded encryptor
+// the encoder's device half, shared by gri_encode (host vectors) and the products' diagonals (gring_matmul.hip)
+struct GriDdTab { const double4 *W, *Z; const uint32_t *slot_m, *slot_pos; };      // W [n/2] exp(-2 pi i k / n); Z [n] zeta^-c = exp(-pi i c / N); m_t; brev(m_t)
+int gri_dd_tab(sfg_ring *r, GriDdTab *out);                        // built at first use, kept by the ring
+// A [nb][n] (v_t at m_t, zero elsewhere) -> the transform, the rounding with the band test band[vec] and the residues modulo the first nl moduli, coefficient domain, in
+// R [nb][nl][N].  flags[0] += unproven coefficients, flags[1] += coefficients outside |p| < 2^62: the caller zeroes and reads them.
+int gri_encode_dft(sfg_ring *r, double4 *A, int nb, const GriDdTab &tab, const double *band_dev, unsigned *flags, u64 *R, int nl, double scale);
+int gri_encode_refuse(sfg_ring *r, const char *what, const unsigned *f, double scale);           // the encoder's two refusals from the flags read back (0 = none)

@@ -369,7 +369,6 @@ extern "C" int sfg_ring_decode_coeffs(sfg_ring *r, const uint64_t *pt, size_t pt
 // conjugate at the place of m_t: bit reversal, twist and slot permutation are addressing, and one transform serves both directions.
 // Index bounds: a tile index is < 1024 by construction; the columns pass reads (r << b) + c0 + c with r < 2^a, c0 + c < 2^b; twiddle indices are < n / 2 (see the loops).
 constexpr int GDD_TILE = 1024;
-struct GriDdTab { const double4 *W, *Z; const uint32_t *slot_m, *slot_pos; };      // W [n/2] exp(-2 pi i k / n); Z [n] zeta^-c = exp(-pi i c / N); m_t; brev(m_t)
 __device__ __forceinline__ gio::cdd gdd_of(double4 v) { gio::cdd r; r.re.hi = v.x; r.re.lo = v.y; r.im.hi = v.z; r.im.lo = v.w; return r; }
 __device__ __forceinline__ double4 gdd_to(gio::cdd v) { return make_double4(v.re.hi, v.re.lo, v.im.hi, v.im.lo); }
 __device__ __forceinline__ gio::cdd gdd_lds(const double (*t)[GDD_TILE], int i) { gio::cdd r; r.re.hi = t[0][i]; r.re.lo = t[1][i]; r.im.hi = t[2][i]; r.im.lo = t[3][i]; return r; }
@@ -470,7 +469,7 @@ static void gdd_expm(long long num, long long den, double *out4) {
     if (negc) c = dd_neg(c);
     out4[0] = c.hi; out4[1] = c.lo; out4[2] = -s.hi; out4[3] = -s.lo;
 }
-static int gri_dd_tab(sfg_ring *r, GriDdTab *out) {
+int gri_dd_tab(sfg_ring *r, GriDdTab *out) {
     const int N = r->N, n = N / 2;
     if (!r->io.dd_tab) {
         const size_t bW = (size_t)(n / 2) * 32, bZ = (size_t)n * 32, bS = (size_t)n * 4;
@@ -501,9 +500,21 @@ static int gdd_transform(sfg_ring *r, double4 *A, int nvec, const GriDdTab &t) {
     return 0;
 }
 
+int gri_encode_dft(sfg_ring *r, double4 *A, int nb, const GriDdTab &tab, const double *band_dev, unsigned *flags, u64 *R, int nl, double scale) {
+    const int n = r->N / 2, logn = r->logN - 1;
+    GR_TRY(gdd_transform(r, A, nb, tab));
+    hipLaunchKernelGGL(k_gdd_enc_post, dim3(n / GR_T, 1, (unsigned)nb), dim3(GR_T), 0, r->stream, (const double4 *)A, tab.Z, R, flags, band_dev, r->modc, scale / n, logn, nl);
+    GR_HIP(r, hipGetLastError());
+    return 0;
+}
+int gri_encode_refuse(sfg_ring *r, const char *what, const unsigned *f, double scale) {
+    if (f[1]) GR_FAIL(r, "%s: %u coefficients are outside the domain |p| < 2^62 (scale %g)", what, f[1], scale);
+    if (f[0]) GR_FAIL(r, "%s: %u coefficients lie within the proven band of a rounding tie: no plaintext is handed out", what, f[0]);
+    return 0;
+}
 // real slot vectors -> NTT-domain plaintext rows dst [nvec][level+1][N] (device).  Nothing is written to dst unless every coefficient of every vector is proven.
 static int gri_encode(sfg_ring *r, const char *what, const double *values, int nvec, int level, double scale, u64 *dst) {
-    const int nl = level + 1, N = r->N, n = N / 2, logn = r->logN - 1;
+    const int nl = level + 1, N = r->N, n = N / 2;
     if (!(scale >= 1.0) || !std::isfinite(scale)) GR_FAIL(r, "%s: scale %g must be finite and at least 1", what, scale);
     std::vector<double> band(nvec);
     for (int v = 0; v < nvec; v++) {
@@ -526,14 +537,12 @@ static int gri_encode(sfg_ring *r, const char *what, const double *values, int n
             GR_HIP(r, hipMemsetAsync(flags, 0, 8, r->stream));
             GR_HIP(r, hipMemsetAsync(A, 0, (size_t)nb * n * 32, r->stream));
             hipLaunchKernelGGL(k_gdd_enc_load, dim3(n / GR_T, 1, (unsigned)nb), dim3(GR_T), 0, r->stream, (const double *)vals, A, tab.slot_m, n);
-            GR_TRY(gdd_transform(r, A, nb, tab));
-            hipLaunchKernelGGL(k_gdd_enc_post, dim3(n / GR_T, 1, (unsigned)nb), dim3(GR_T), 0, r->stream, (const double4 *)A, tab.Z, R, flags, (const double *)bandd, r->modc, scale / n, logn, nl);
             GR_HIP(r, hipGetLastError());
+            GR_TRY(gri_encode_dft(r, A, nb, tab, bandd, flags, R, nl, scale));
             unsigned f[2];
             GR_HIP(r, hipMemcpyAsync(f, flags, 8, hipMemcpyDeviceToHost, r->stream));
             GR_HIP(r, hipStreamSynchronize(r->stream));
-            if (f[1]) GR_FAIL(r, "%s: %u coefficients are outside the domain |p| < 2^62 (scale %g)", what, f[1], scale);
-            if (f[0]) GR_FAIL(r, "%s: %u coefficients lie within the proven band of a rounding tie: no plaintext is handed out", what, f[0]);
+            GR_TRY(gri_encode_refuse(r, what, f, scale));
             if (pass == 0) continue;
             GR_TRY(gr_transform(r, R, (size_t)nb * nl, gr_map(nl, nl, 0, 0), false));
             GR_HIP(r, hipMemcpyAsync(dst + (size_t)c0 * nl * N, R, (size_t)nb * nl * N * 8, hipMemcpyDeviceToDevice, r->stream));

@@ -1682,3 +1682,44 @@ inline std::shared_ptr<crypto::RingBuf> CollectiveBootstrapFinish(crypto::RingPa
     return out;
 }
 }  // namespace mpc
+
+// ---- the two matrix products at the other CKKS presets: the general ring's twins of MatMult4Stream and of its accumulate / finalize halves (gring_matmul.hip;
+//      DESIGN.md section 18; gwas/matmult.go:1238-1505).  The int8 matrix is device memory of the ring (crypto::RingBuf), row-major with leading dimension ld,
+//      -1 = missing; the ciphertexts stay on the device: A [s][nbr][2][inLevel+1][N] in, [s][mct][2][maxLevel][N] at level maxLevel - 1 out, the deterministic sum
+//      (the fresh zeros of crypto.CZeroMat are sfg_ring_ct_add_fresh_zero_dev's).  The ring carries no scale: paramsScale is Params.Scale().
+namespace gwas {
+struct RingMatShape { int d = 0, nbr = 0, mct = 0; };
+inline RingMatShape RingMatMultShape(const crypto::RingParams *rp, size_t nrow, size_t ncol, bool transpose) {
+    RingMatShape sh; const size_t slots = (size_t)rp->GetSlots(), rows = transpose ? ncol : nrow, cols = transpose ? nrow : ncol;
+    sh.d = 1; while ((size_t)sh.d * sh.d < slots) sh.d++;                  // matmult.go:1249
+    sh.nbr = (int)((rows - 1) / slots) + 1; sh.mct = (int)((cols - 1) / slots) + 1;   // :1253-1254
+    return sh;
+}
+inline unsigned ringMatFlags(bool square, bool transpose) { return (square ? SFG_SQUARE : 0u) | (transpose ? SFG_TRANSPOSE : 0u); }
+// MatMult4Stream (matmult.go:1238-1505)
+inline std::shared_ptr<crypto::RingBuf> MatMult4Stream(crypto::RingParams *rp, const uint64_t *A_dev, int s, int inLevel, int maxLevel, const int8_t *geno_dev, size_t nrow,
+                                                      size_t ncol, size_t ld, bool square, bool transpose, double paramsScale) {
+    const RingMatShape sh = RingMatMultShape(rp, nrow, ncol, transpose);
+    auto out = std::make_shared<crypto::RingBuf>(rp, (size_t)s * sh.mct * 2 * maxLevel * rp->N() * 8);
+    rp->check(sfg_ring_matmul_dev(rp->ring, A_dev, s, inLevel, maxLevel, geno_dev, nrow, ncol, ld, ringMatFlags(square, transpose), paramsScale, out->u()), "MatMult4Stream");
+    return out;
+}
+// matmult.go:1280-1439 for operand block rows [b0, b1): the canonical accumulator [mct][d][s][2][maxLevel][N] and the giants that became active
+struct RingMatAccumulator { std::shared_ptr<crypto::RingBuf> acc; std::vector<uint8_t> giantActive; int s = 0, maxLevel = 0, mct = 0; };
+inline RingMatAccumulator MatMult4StreamAccumulate(crypto::RingParams *rp, const uint64_t *A_dev, int s, int inLevel, int maxLevel, const int8_t *geno_dev, size_t nrow,
+                                                   size_t ncol, size_t ld, bool square, bool transpose, double paramsScale, int b0, int b1) {
+    const RingMatShape sh = RingMatMultShape(rp, nrow, ncol, transpose);
+    RingMatAccumulator a; a.s = s; a.maxLevel = maxLevel; a.mct = sh.mct; a.giantActive.assign(sh.d, 0);
+    a.acc = std::make_shared<crypto::RingBuf>(rp, (size_t)sh.mct * sh.d * s * 2 * maxLevel * rp->N() * 8);
+    rp->check(sfg_ring_matmul_accumulate_dev(rp->ring, A_dev, s, inLevel, maxLevel, geno_dev, nrow, ncol, ld, ringMatFlags(square, transpose), paramsScale, b0, b1, a.acc->u(),
+                                             a.giantActive.data()), "MatMult4Stream (accumulate)");
+    return a;
+}
+// matmult.go:1443-1502: the giant-step alignment and the aggregation
+inline std::shared_ptr<crypto::RingBuf> MatMult4StreamFinalize(crypto::RingParams *rp, const RingMatAccumulator &a) {
+    auto out = std::make_shared<crypto::RingBuf>(rp, (size_t)a.s * a.mct * 2 * a.maxLevel * rp->N() * 8);
+    rp->check(sfg_ring_matmul_finalize_dev(rp->ring, a.acc->u(), a.giantActive.data(), a.s, a.maxLevel, a.mct, 0, (int)a.giantActive.size(), 0, out->u()),
+              "MatMult4Stream (finalize)");
+    return out;
+}
+}  // namespace gwas
