@@ -967,8 +967,11 @@ int sfg_ring_refresh_finish_scaled_dev(sfg_ring *ring, const uint64_t *ct_dev, i
  * as 0; SFG_SQUARE squares after that with the int8 wrap-around of matmult.go:1301-1303; SFG_TRANSPOSE multiplies by the transpose of the same bytes, no copy made.
  * The level drops to min(in_level, max_level) (matmult.go:1256-1259); the diagonal of shift giant d + baby is rotated right by d giant and encoded at `scale` (a
  * finite double >= 1; the ring carries none) over the first L moduli by sfg_ring_encode_vectors_dev's encoder, from device memory: no diagonal crosses the host.
- * A coefficient inside that encoder's proven band of a rounding tie, or outside |p| < 2^62, fails the call with the encoder's message before `out` is written (the
- * exact re-derivation sfg_ctx has for such coefficients is not built here).
+ * A coefficient inside that encoder's proven band of a rounding tie is re-derived exactly on the device (gring_tie.hpp: the slot values read again from the matrix
+ * bytes, a fixed-point cosine table of 191 fractional bits kept by the ring, integer sums; no host synchronisation is added) and counted by
+ * sfg_ring_encoder_resolved.  Only a coefficient whose exact value is itself within the table's error of a tie (S 2^-191, S = scale sum |v_t| / n; an exact tie
+ * included), one past the 512 flagged coefficients a batch of diagonals may hold, or one outside |p| < 2^62 fails the call with the encoder's message before `out`
+ * is written.
  * The MAC sums rot (.) pt in 128 bits with no Montgomery form: REDC(rot MForm(pt)) = rot pt mod q, so the canonical words are the reference's.  The reference's u128
  * sum silently wraps once terms (q - 1)^2 >= 2^128 (64 terms at 61-bit moduli; d alone is 182 at logN 16); the MAC folds its sum to a word below q every
  * floor((2^128 - q) / (q - 1)^2) terms, so the DEFINED result is the exact sum modulo q.  That equals the reference wherever the reference does not wrap, which is
@@ -993,6 +996,13 @@ int sfg_ring_matmul_finalize_dev(sfg_ring *ring, const uint64_t *acc_dev, const 
 /* test hook (replaces nothing in the reference): the byte budget that sizes the chunks of the ring's evaluator workspaces (key switch, rescale: 768 MiB; the products: 32 GiB), so
  * that a small shape runs in several chunks.  Refused unless the process set SFG_ENABLE_TEST_HOOKS=1 before sfg_ring_create. */
 int sfg_ring_set_ws_budget_for_test(sfg_ring *ring, size_t bytes);
+/* diagonal coefficients the products re-derived exactly since the last reset (every re-derivation counts: a product in several chunks of ciphertexts encodes its
+ * diagonals once per chunk and once more in its checking pass).  Host arithmetic; the count is complete when the product has returned. */
+int sfg_ring_encoder_resolved(sfg_ring *ring, unsigned long long *count, int reset);
+/* test hook (replaces nothing in the reference): the floor 2^log2_floor (-50 .. -2; the library's is 2^-50) of the band inside which a coefficient of the PRODUCTS'
+ * diagonals goes to the exact re-derivation, so that ordinary data exercises it.  sfg_ring_encode_vectors_dev and sfg_ring_encrypt_vectors_dev keep their band.
+ * Refused unless the process set SFG_ENABLE_TEST_HOOKS=1 before sfg_ring_create. */
+int sfg_ring_set_tie_band_for_test(sfg_ring *ring, int log2_floor);
 
 #ifdef __cplusplus
 }

@@ -1710,6 +1710,17 @@ func (r *Ring) MatMult(aFlat []uint64, s, inLevel, maxLevel int, geno []int8, nr
 	})
 }
 
+// EncoderResolved is the number of diagonal coefficients the products re-derived exactly (inside the encoder's band of a rounding tie) since the last reset.
+func (r *Ring) EncoderResolved(reset bool) uint64 {
+	var n C.ulonglong
+	flag := 0
+	if reset {
+		flag = 1
+	}
+	r.check(C.sfg_ring_encoder_resolved(r.p, &n, C.int(flag)), "ring_encoder_resolved")
+	return uint64(n)
+}
+
 // MatMultD is ceil(sqrt(slots)): the number of baby and of giant steps (matmult.go:1249).
 func (r *Ring) MatMultD() int {
 	d := 1

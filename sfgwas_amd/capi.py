@@ -125,6 +125,8 @@ def _ring_sig():
         "sfg_ring_matmul_accumulate_dev": (i, [vp, vp, i, i, i, vp, sz, sz, sz, C.c_uint, C.c_double, i, i, vp, C.POINTER(C.c_uint8)]),
         "sfg_ring_matmul_finalize_dev": (i, [vp, vp, C.POINTER(C.c_uint8), i, i, i, i, i, i, vp]),
         "sfg_ring_set_ws_budget_for_test": (i, [vp, sz]),
+        "sfg_ring_encoder_resolved": (i, [vp, C.POINTER(C.c_ulonglong), i]),
+        "sfg_ring_set_tie_band_for_test": (i, [vp, i]),
     }
 
 
@@ -2052,3 +2054,13 @@ class Ring:
     def set_ws_budget_for_test(self, nbytes):
         """test hook (SFG_ENABLE_TEST_HOOKS=1 before the ring was made): the byte budget that sizes the chunks of the evaluator's workspaces"""
         self.check(lib().sfg_ring_set_ws_budget_for_test(self.h, int(nbytes)), "sfg_ring_set_ws_budget_for_test")
+
+    def encoder_resolved(self, reset=False):
+        """diagonal coefficients the products re-derived exactly (inside the encoder's band of a rounding tie) since the last reset"""
+        n = C.c_ulonglong(0)
+        self.check(lib().sfg_ring_encoder_resolved(self.h, C.byref(n), int(bool(reset))), "sfg_ring_encoder_resolved")
+        return int(n.value)
+
+    def set_tie_band_for_test(self, log2_floor):
+        """test hook (SFG_ENABLE_TEST_HOOKS=1 before the ring was made): the floor 2^log2_floor of the band of the products' diagonals"""
+        self.check(lib().sfg_ring_set_tie_band_for_test(self.h, int(log2_floor)), "sfg_ring_set_tie_band_for_test")

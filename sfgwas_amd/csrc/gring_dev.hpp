@@ -104,6 +104,10 @@ struct sfg_ring {
     GrBuf<void> mm_ws;                                 // grow-only workspace of the matrix products (gring_matmul.hip), apart from ws: the key switches they batch use that one
     size_t ws_budget = 768ull << 20;
     size_t mm_budget = 0;                              // the products' workspace budget; 0 = kMmBudgetBytes (gring_matmul_plan.hpp)
+    GrBuf<u64> tie_tab;                                // gring_matmul.hip: the fixed-point cosine table of the tie resolver (gring_tie.hpp), built at first use
+    GrBuf<unsigned> tie_list;                          // the resolver's list of one batch (GriTies), allocated with the table
+    unsigned long long tie_resolved = 0;               // coefficients re-derived since the last reset (sfg_ring_encoder_resolved)
+    int tie_band_log2 = -50;                           // the floor of the band of the products' diagonals (sfg_ring_set_tie_band_for_test)
     bool test_hooks = false;                           // SFG_ENABLE_TEST_HOOKS=1 when the ring was made: the *_for_test entry points may be called
     GrIo io;
     GrKeygen kg;
@@ -163,7 +167,12 @@ int gri_take_indices(sfg_ring *r, const char *what, int nct, u64 *first);       
 // the encoder's device half, shared by gri_encode (host vectors) and the products' diagonals (gring_matmul.hip)
 struct GriDdTab { const double4 *W, *Z; const uint32_t *slot_m, *slot_pos; };      // W [n/2] exp(-2 pi i k / n); Z [n] zeta^-c = exp(-pi i c / N); m_t; brev(m_t)
 int gri_dd_tab(sfg_ring *r, GriDdTab *out);                        // built at first use, kept by the ring
+// The products' list of the coefficients of one batch of diagonals that fell inside the band (32-bit words in device memory, kept by the ring): the count of the
+// batch (reset by k_gr_mm_band; it may pass the capacity, entries past it were counted unproven), the coefficients re-derived since the flags were last read, then
+// kCap pairs (vector of the batch, coefficient index < N).
+struct GriTies { enum { kCount = 0, kResolved = 1, kEntries = 2, kCap = 512, kWords = kEntries + 2 * kCap }; };
 // A [nb][n] (v_t at m_t, zero elsewhere) -> the transform, the rounding with the band test band[vec] and the residues modulo the first nl moduli, coefficient domain, in
-// R [nb][nl][N].  flags[0] += unproven coefficients, flags[1] += coefficients outside |p| < 2^62: the caller zeroes and reads them.
-int gri_encode_dft(sfg_ring *r, double4 *A, int nb, const GriDdTab &tab, const double *band_dev, unsigned *flags, u64 *R, int nl, double scale);
+// R [nb][nl][N].  flags[0] += unproven coefficients, flags[1] += coefficients outside |p| < 2^62: the caller zeroes and reads them.  ties (nullable): see GriTies; with
+// it a coefficient inside the band goes to the list, not to flags[0].
+int gri_encode_dft(sfg_ring *r, double4 *A, int nb, const GriDdTab &tab, const double *band_dev, unsigned *flags, unsigned *ties, u64 *R, int nl, double scale);
 int gri_encode_refuse(sfg_ring *r, const char *what, const unsigned *f, double scale);           // the encoder's two refusals from the flags read back (0 = none)

@@ -418,12 +418,22 @@ __global__ __launch_bounds__(GR_T) void k_gdd_enc_load(const double *vals, doubl
 }
 // encoder out: y = (scale / n) zeta^-c X_c; p_c = round(Re y), p_(c+n) = round(Im y), half away from zero, with the band test; p reduced modulo every q_i into
 // R [nvec][nl][N] (coefficient domain).  flags[0] counts unproven coefficients, flags[1] those outside the domain.  grid (n / 256, 1, nvec)
-__global__ __launch_bounds__(GR_T) void k_gdd_enc_post(const double4 *A, const double4 *Z, u64 *R, unsigned *flags, const double *band, const GrMod *modc, double mul, int logn, int nl) {
+// ties (null for the real-slot-vector entry points: a coefficient in the band is refused there): the products' list of a batch (GriTies, gring_dev.hpp).  A coefficient
+// in the band is appended as (vector, coefficient index) for the resolver to re-derive and does not count as unproven - unless the list is full.
+__device__ __forceinline__ void gdd_flag(unsigned *flags, unsigned *ties, unsigned vec, unsigned coeff) {
+    if (ties) {
+        const unsigned k = atomicAdd(&ties[GriTies::kCount], 1u);
+        if (k < (unsigned)GriTies::kCap) { ties[GriTies::kEntries + 2 * k] = vec; ties[GriTies::kEntries + 2 * k + 1] = coeff; return; }
+    }
+    atomicAdd(&flags[0], 1u);
+}
+__global__ __launch_bounds__(GR_T) void k_gdd_enc_post(const double4 *A, const double4 *Z, u64 *R, unsigned *flags, unsigned *ties, const double *band, const GrMod *modc, double mul, int logn,
+                                                       int nl) {
     const int c = blockIdx.x * GR_T + threadIdx.x, n = 1 << logn, N = 2 * n; const size_t vec = blockIdx.z;
     const gio::cdd y = gio::cdd_mul(gdd_of(A[vec * n + (__brev((unsigned)c) >> (32 - logn))]), gdd_of(Z[c]));
     long long pr, pi;
     const int sr = gio::round_half_away(gio::dd_mul_d(y.re, mul), band[vec], pr), si = gio::round_half_away(gio::dd_mul_d(y.im, mul), band[vec], pi);
-    if (sr == 1) atomicAdd(&flags[0], 1u); if (si == 1) atomicAdd(&flags[0], 1u);
+    if (sr == 1) gdd_flag(flags, ties, (unsigned)vec, (unsigned)c); if (si == 1) gdd_flag(flags, ties, (unsigned)vec, (unsigned)(c + n));
     if (sr == 2) atomicAdd(&flags[1], 1u); if (si == 2) atomicAdd(&flags[1], 1u);
     for (int i = 0; i < nl; i++) {
         const GrMod mc = modc[i]; u64 *row = R + (vec * nl + i) * N;
@@ -500,10 +510,10 @@ static int gdd_transform(sfg_ring *r, double4 *A, int nvec, const GriDdTab &t) {
     return 0;
 }
 
-int gri_encode_dft(sfg_ring *r, double4 *A, int nb, const GriDdTab &tab, const double *band_dev, unsigned *flags, u64 *R, int nl, double scale) {
+int gri_encode_dft(sfg_ring *r, double4 *A, int nb, const GriDdTab &tab, const double *band_dev, unsigned *flags, unsigned *ties, u64 *R, int nl, double scale) {
     const int n = r->N / 2, logn = r->logN - 1;
     GR_TRY(gdd_transform(r, A, nb, tab));
-    hipLaunchKernelGGL(k_gdd_enc_post, dim3(n / GR_T, 1, (unsigned)nb), dim3(GR_T), 0, r->stream, (const double4 *)A, tab.Z, R, flags, band_dev, r->modc, scale / n, logn, nl);
+    hipLaunchKernelGGL(k_gdd_enc_post, dim3(n / GR_T, 1, (unsigned)nb), dim3(GR_T), 0, r->stream, (const double4 *)A, tab.Z, R, flags, ties, band_dev, r->modc, scale / n, logn, nl);
     GR_HIP(r, hipGetLastError());
     return 0;
 }
@@ -538,7 +548,7 @@ static int gri_encode(sfg_ring *r, const char *what, const double *values, int n
             GR_HIP(r, hipMemsetAsync(A, 0, (size_t)nb * n * 32, r->stream));
             hipLaunchKernelGGL(k_gdd_enc_load, dim3(n / GR_T, 1, (unsigned)nb), dim3(GR_T), 0, r->stream, (const double *)vals, A, tab.slot_m, n);
             GR_HIP(r, hipGetLastError());
-            GR_TRY(gri_encode_dft(r, A, nb, tab, bandd, flags, R, nl, scale));
+            GR_TRY(gri_encode_dft(r, A, nb, tab, bandd, flags, nullptr, R, nl, scale));
             unsigned f[2];
             GR_HIP(r, hipMemcpyAsync(f, flags, 8, hipMemcpyDeviceToHost, r->stream));
             GR_HIP(r, hipStreamSynchronize(r->stream));

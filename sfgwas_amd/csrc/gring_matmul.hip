@@ -6,7 +6,8 @@
 //   1. the rotation cache: RotateRight(A, -baby) at the dropped level for every active baby, one batch of key switches (gr_ks_batch); the key switch hands out the
 //      permuted d_p, k_gr_mm_add_c0 adds the permuted c0 (the automorphism is additive, so the words are those of rotating c0 + d_0)
 //   2. per active giant, in batches of diagonals: k_gr_mm_diag (the diagonals straight into the encoder's DFT input, their sum of magnitudes beside them),
-//      k_gr_mm_band, the encoder's shared device half (gri_encode_dft), the ring's forward transform of the plaintext rows
+//      k_gr_mm_band, the encoder's shared device half (gri_encode_dft), k_gr_mm_tie (the coefficients the encoder could not prove rounded, re-derived exactly from
+//      the matrix bytes: gring_tie.hpp), the ring's forward transform of the plaintext rows
 //   3. k_gr_mm_mac: the batch's products summed in 128-bit registers, reduced, added into the canonical accumulator rows
 // and the finalize (orc_matmult_finalize): giant g > 0 rotated by -g d at level L - 1 through the same batch, the giants of one output summed by k_gr_mm_fin.
 // All launches go on the ring's stream.  Every word written is canonical.
@@ -23,6 +24,7 @@
 #include "gring_dev.hpp"
 #include "gring_io_arith.hpp"
 #include "gring_matmul_plan.hpp"
+#include "gring_tie.hpp"
 
 struct MmVec { int shift, bj, slot, pad; };                                 // one diagonal of a batch: its shift, its block column, its baby's slot of the rotation cache
 struct MmJob { u64 src; const uint32_t *idx; long long ct; };               // one rotation: word offset of its source ciphertext, its index table, its slot
@@ -31,28 +33,87 @@ static_assert(sizeof(MmVec) == 16 && sizeof(MmJob) == 24, "gring_matmul_plan.hpp
 // ---------------------------------------------------------------- kernels; x < N and t < n by the grids: N / 2 is a multiple of 256
 // Diagonal `shift` of operand block (bi, bj), rotated right by rotg = d giant: slot t holds diag[jp], jp = t - rotg mod n, and diag[jp] = X[(shift + jp) mod n][jp]
 // (matmult.go:636-672), zero outside the block.  The operand is the resident matrix (element (I, J) at I ld + J) or its transpose (at J ld + I): I < R and J < C
-// bound the address in both.  Missing (negative) -> 0, then the optional square with the int8 wrap-around.  The value goes to the encoder's DFT input position
-// m_t (a permutation of 0 .. n-1: every point of the vector is written); sums[vec] += |v|, an integer below 2^7 n.   grid (n / 256, 1, nvec)
-__global__ __launch_bounds__(GR_T) void k_gr_mm_diag(const int8_t *geno, size_t ld, size_t R, size_t C, int transpose, int square, int bi, int rotg, const MmVec *vecs,
-                                                     double4 *A, const uint32_t *slot_m, unsigned *sums, int n) {
-    const int t = blockIdx.x * GR_T + threadIdx.x; const size_t vec = blockIdx.z; const MmVec v = vecs[vec];
-    int jp = t - rotg; if (jp < 0) jp += n;
+// bound the address in both.  Missing (negative) -> 0, then the optional square with the int8 wrap-around.  One function for the extraction and for the resolver,
+// which reads the slot again (the encoder's DFT input was transformed in place).
+struct MmOperand { const int8_t *geno; size_t ld, R, C; int transpose, square, bi, rotg; };
+__device__ __forceinline__ int gr_mm_slot(const MmOperand &o, const MmVec &v, int t, int n) {
+    int jp = t - o.rotg; if (jp < 0) jp += n;
     int i = v.shift + jp; if (i >= n) i -= n;
-    const size_t I = (size_t)bi * n + i, J = (size_t)v.bj * n + jp;
+    const size_t I = (size_t)o.bi * n + i, J = (size_t)v.bj * n + jp;
     int x = 0;
-    if (I < R && J < C) x = geno[transpose ? J * ld + I : I * ld + J];
+    if (I < o.R && J < o.C) x = o.geno[o.transpose ? J * o.ld + I : I * o.ld + J];
     if (x < 0) x = 0;
-    if (square) x = (int8_t)(x * x);
+    if (o.square) x = (int8_t)(x * x);
+    return x;
+}
+// The value goes to the encoder's DFT input position m_t (a permutation of 0 .. n-1: every point of the vector is written); sums[vec] += |v|, an integer below
+// 2^7 n.   grid (n / 256, 1, nvec)
+__global__ __launch_bounds__(GR_T) void k_gr_mm_diag(MmOperand o, const MmVec *vecs, double4 *A, const uint32_t *slot_m, unsigned *sums, int n) {
+    const int t = blockIdx.x * GR_T + threadIdx.x; const size_t vec = blockIdx.z;
+    const int x = gr_mm_slot(o, vecs[vec], t, n);
     A[vec * n + slot_m[t]] = make_double4((double)x, 0.0, 0.0, 0.0);
     unsigned a = (unsigned)(x < 0 ? -x : x);
     for (int off = 32; off; off >>= 1) a += __shfl_down(a, off);
     if ((threadIdx.x & 63) == 0) atomicAdd(&sums[vec], a);
 }
-// the band of a vector from its exact sum of magnitudes, as gri_encode forms it on the host
-__global__ __launch_bounds__(GR_T) void k_gr_mm_band(const unsigned *sums, double *band, double mul, int nvec) {
+// the band of a vector from its exact sum of magnitudes, as gri_encode forms it on the host; `floor` is gio::kEncBandFloor unless the test hook widened it.  The
+// batch's list of flagged coefficients starts empty.
+__global__ __launch_bounds__(GR_T) void k_gr_mm_band(const unsigned *sums, double *band, double mul, double floor, int nvec, unsigned *ties) {
     const int v = blockIdx.x * GR_T + threadIdx.x;
-    if (v < nvec) band[v] = gio::enc_band((double)sums[v] * mul * (1.0 + 0x1p-40));
+    if (v == 0) ties[GriTies::kCount] = 0;
+    if (v < nvec) { const double b = gio::enc_band((double)sums[v] * mul * (1.0 + 0x1p-40)); band[v] = b > floor ? b : floor; }
 }
+// The resolver: workgroup k re-derives entry k of the batch's list (gring_tie.hpp has the arithmetic and its bounds); workgroups beyond the count leave at once.
+// The threads stride over the n slots: the slot's value from the matrix, the angle pi (5^t j mod 2N) / N with 5^t = 4 m_t + 1 folded to the table, the term added
+// into a 256-bit signed sum in registers.  The sums meet as eight columns of 32-bit limbs (a wave's by shuffles, the four waves' through LDS); thread 0 carries them
+// into four words (modulo 2^256: the true sum is far below 2^255) and decides: proven -> the rounded value modulo every q_i into the coefficient-domain rows
+// R [nvec][nl][N] in place of the encoder's, ties[kResolved] += 1; otherwise flags[0] += 1 (unproven) or flags[1] += 1 (outside |p| < 2^62).
+// An entry's vector is < nvec and its coefficient < N: k_gdd_enc_post wrote both from its own grid.   grid (GriTies::kCap)
+__global__ __launch_bounds__(GR_T) void k_gr_mm_tie(MmOperand o, const MmVec *vecs, const uint32_t *slot_m, const unsigned *sums, const u64 *ctab, unsigned *ties, u64 *R, unsigned *flags,
+                                                    const GrMod *modc, u64 scale_m, int scale_e, int logn, int nl) {
+    __shared__ u64 part[GR_T / 64][8];
+    const unsigned count = ties[GriTies::kCount];
+    if (blockIdx.x >= (count < (unsigned)GriTies::kCap ? count : (unsigned)GriTies::kCap)) return;       // uniform
+    const unsigned vec = ties[GriTies::kEntries + 2 * blockIdx.x], j = ties[GriTies::kEntries + 2 * blockIdx.x + 1];
+    const int n = 1 << logn; const unsigned N = 2u * n;
+    const MmVec v = vecs[vec];
+    gtie::Acc acc; acc.zero();
+    for (int t = threadIdx.x; t < n; t += GR_T) {
+        const int x = gr_mm_slot(o, v, t, n);
+        if (!x) continue;
+        bool neg; const unsigned k = gtie::fold(((4u * slot_m[t] + 1u) * j) & (2u * N - 1u), N, neg);     // k <= N / 2: inside the table's N / 2 + 1 entries
+        const u64 *c = ctab + (size_t)k * gtie::kWords;
+        const u64 cw[3] = {c[0], c[1], c[2]};
+        acc.addmul(cw, x, neg);
+    }
+    u64 col[8];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { col[2 * i] = acc.w[i] & 0xFFFFFFFFu; col[2 * i + 1] = acc.w[i] >> 32; }
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        for (int off = 32; off; off >>= 1) col[i] += __shfl_down(col[i], off);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][i] = col[i];
+    }
+    __syncthreads();
+    if (threadIdx.x) return;
+    u64 X[4], carry = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        u64 lo = carry, hi;
+#pragma unroll
+        for (int w = 0; w < GR_T / 64; w++) lo += part[w][2 * i];                                         // 256 limbs and a carry: below 2^41
+        hi = lo >> 32;
+#pragma unroll
+        for (int w = 0; w < GR_T / 64; w++) hi += part[w][2 * i + 1];
+        X[i] = (lo & 0xFFFFFFFFu) | (hi << 32); carry = hi >> 32;
+    }
+    long long p;
+    const int st = gtie::decide(X, scale_m, scale_e, logn, (u64)sums[vec], p);
+    if (st) { atomicAdd(&flags[st - 1], 1u); return; }
+    for (int i = 0; i < nl; i++) { const GrMod mc = modc[i]; R[((size_t)vec * nl + i) * N + j] = gio::reduce_i62(p, mc.q, mc.uhi, mc.ulo); }
+    atomicAdd(&ties[GriTies::kResolved], 1u);
+}
+static_assert((int)GriTies::kCap == gtie::kCap, "one capacity");
 // slot 0 of the cache: the ciphertext itself at the dropped level.  grid (N / 256, nl, sc * 2)
 __global__ __launch_bounds__(GR_T) void k_gr_mm_drop(const u64 *A, u64 *rot, int nbr, int bi, int d, int nl_in, int nl, int N) {
     const int x = blockIdx.x * GR_T + threadIdx.x, m = blockIdx.y, p = blockIdx.z & 1; const size_t i = blockIdx.z >> 1;
@@ -138,6 +199,17 @@ static int mm_fold_tab(sfg_ring *r, const unsigned **out) {
     *out = (const unsigned *)r->mm_fold.p;
     return 0;
 }
+// the resolver's cosine table and its list, on the device (built at first use)
+static int mm_tie_tab(sfg_ring *r) {
+    if (!r->tie_tab) {
+        const std::vector<u64> h = gtie::build_table(r->logN);
+        GrBuf<unsigned> l; GR_HIP(r, l.alloc(GriTies::kWords * sizeof(unsigned)));
+        GR_HIP(r, hipMemsetAsync(l.p, 0, GriTies::kWords * sizeof(unsigned), r->stream));
+        GrBuf<u64> d; GR_TRY(gr_table(r, d, h.data(), h.size() * 8));
+        r->tie_list = std::move(l); r->tie_tab = std::move(d);
+    }
+    return 0;
+}
 // rotations of a list of jobs (slot = job.ct, source = job.src words into `in`, whose ciphertexts have nl_in rows a polynomial) at `level`, into slots of
 // 2 (level + 1) N words at `out`: one batch of key switches, then the permuted c0
 static int mm_rotate(sfg_ring *r, const MmWs &w, const std::vector<GrJob> &jobs, const std::vector<MmJob> &mj, const u64 *in, int nl_in, int level, u64 *out) {
@@ -175,6 +247,9 @@ static int mm_accumulate_chunk(sfg_ring *r, const char *what, const MmShape &sh,
     const int N = sh.N, n = sh.slots, d = sh.d;
     GriDdTab tab; GR_TRY(gri_dd_tab(r, &tab));
     const unsigned *fold; GR_TRY(mm_fold_tab(r, &fold));
+    GR_TRY(mm_tie_tab(r));
+    u64 scale_m; int scale_e; gtie::split_scale(sh.scale, scale_m, scale_e);
+    const double band_floor = std::ldexp(1.0, r->tie_band_log2);
     const size_t ctw_in = (size_t)2 * sh.nl_in * N;
     for (int bi = b0; bi < b1; bi++) {
         const MmShifts t = mm_shifts(sh.R, sh.C, n, bi);
@@ -200,11 +275,14 @@ static int mm_accumulate_chunk(sfg_ring *r, const char *what, const MmShape &sh,
                 GR_TRY(gr_upload(r, w.vecs, vecs.data() + f0, nb * sizeof(MmVec)));
                 GR_TRY(gr_upload(r, w.first, first.data(), first.size() * sizeof(int)));
                 GR_HIP(r, hipMemsetAsync(w.sums, 0, nb * 4, r->stream));
-                hipLaunchKernelGGL(k_gr_mm_diag, dim3(n / GR_T, 1, (unsigned)nb), dim3(GR_T), 0, r->stream, sh.geno, sh.ld, sh.R, sh.C, (int)sh.tr, (int)sh.sq, bi, g * d, (const MmVec *)w.vecs,
-                                   w.dft, tab.slot_m, w.sums, n);
-                hipLaunchKernelGGL(k_gr_mm_band, dim3((unsigned)((nb + GR_T - 1) / GR_T)), dim3(GR_T), 0, r->stream, (const unsigned *)w.sums, w.band, sh.scale / n, (int)nb);
+                const MmOperand op{sh.geno, sh.ld, sh.R, sh.C, (int)sh.tr, (int)sh.sq, bi, g * d};
+                hipLaunchKernelGGL(k_gr_mm_diag, dim3(n / GR_T, 1, (unsigned)nb), dim3(GR_T), 0, r->stream, op, (const MmVec *)w.vecs, w.dft, tab.slot_m, w.sums, n);
+                hipLaunchKernelGGL(k_gr_mm_band, dim3((unsigned)((nb + GR_T - 1) / GR_T)), dim3(GR_T), 0, r->stream, (const unsigned *)w.sums, w.band, sh.scale / n, band_floor, (int)nb,
+                                   (unsigned *)r->tie_list);
                 GR_HIP(r, hipGetLastError());
-                GR_TRY(gri_encode_dft(r, w.dft, (int)nb, tab, w.band, w.flags, w.pt, sh.L, sh.scale));
+                GR_TRY(gri_encode_dft(r, w.dft, (int)nb, tab, w.band, w.flags, r->tie_list, w.pt, sh.L, sh.scale));
+                hipLaunchKernelGGL(k_gr_mm_tie, dim3(GriTies::kCap), dim3(GR_T), 0, r->stream, op, (const MmVec *)w.vecs, tab.slot_m, (const unsigned *)w.sums, (const u64 *)r->tie_tab,
+                                   (unsigned *)r->tie_list, w.pt, w.flags, r->modc, scale_m, scale_e, r->logN - 1, sh.L);
                 GR_TRY(gr_transform(r, w.pt, nb * sh.L, gr_map(sh.L, sh.L, 0, 0), false));
                 if (sc == 1) mm_launch_mac<1>(r, sh, w, acc, fold, sc, g, acc_s, acc_i0);
                 else if (sc == 2) mm_launch_mac<2>(r, sh, w, acc, fold, sc, g, acc_s, acc_i0);
@@ -236,11 +314,21 @@ static int mm_finalize_chunk(sfg_ring *r, const char *what, const MmWs &w, int L
     }
     return 0;
 }
-// the encoder's flags of a whole call, read once
+// a call starts with no refusal and no re-derivation counted
+static int mm_clear_flags(sfg_ring *r, const MmWs &w) {
+    GR_TRY(mm_tie_tab(r));
+    GR_HIP(r, hipMemsetAsync(w.flags, 0, 8, r->stream));
+    GR_HIP(r, hipMemsetAsync((unsigned *)r->tie_list + GriTies::kResolved, 0, 4, r->stream));
+    return 0;
+}
+// the encoder's flags of a whole call, read once, with the resolver's count of re-derived coefficients (taken and cleared)
 static int mm_read_flags(sfg_ring *r, const char *what, const MmWs &w, double scale) {
-    unsigned f[2];
+    unsigned f[2], resolved = 0;
     GR_HIP(r, hipMemcpyAsync(f, w.flags, 8, hipMemcpyDeviceToHost, r->stream));
+    GR_HIP(r, hipMemcpyAsync(&resolved, (unsigned *)r->tie_list + GriTies::kResolved, 4, hipMemcpyDeviceToHost, r->stream));
+    GR_HIP(r, hipMemsetAsync((unsigned *)r->tie_list + GriTies::kResolved, 0, 4, r->stream));
     GR_HIP(r, hipStreamSynchronize(r->stream));
+    r->tie_resolved += resolved;
     return gri_encode_refuse(r, what, f, scale);
 }
 
@@ -279,6 +367,20 @@ extern "C" int sfg_ring_set_ws_budget_for_test(sfg_ring *r, size_t bytes) {
     return 0;
 }
 
+/* test hook */
+extern "C" int sfg_ring_set_tie_band_for_test(sfg_ring *r, int log2_floor) {
+    if (!r->test_hooks) GR_FAIL(r, "sfg_ring_set_tie_band_for_test: test hook, enabled only in a process that set the test switch before creating the ring");
+    if (log2_floor < -50 || log2_floor > -2) GR_FAIL(r, "sfg_ring_set_tie_band_for_test: the floor 2^%d is outside 2^-50 .. 2^-2", log2_floor);
+    r->tie_band_log2 = log2_floor;
+    return 0;
+}
+extern "C" int sfg_ring_encoder_resolved(sfg_ring *r, unsigned long long *count, int reset) {
+    if (!count) GR_FAIL(r, "sfg_ring_encoder_resolved: null result pointer");
+    *count = r->tie_resolved;
+    if (reset) r->tie_resolved = 0;
+    return 0;
+}
+
 extern "C" int sfg_ring_matmul_accumulate_dev(sfg_ring *r, const uint64_t *A, int s, int in_level, int max_level, const int8_t *geno, size_t nrow, size_t ncol, size_t ld, unsigned flags,
                                               double scale, int b0, int b1, uint64_t *acc, uint8_t *giant_active_host) {
     const char *what = "sfg_ring_matmul_accumulate_dev";
@@ -293,7 +395,7 @@ extern "C" int sfg_ring_matmul_accumulate_dev(sfg_ring *r, const uint64_t *A, in
     GR_TRY(gr_reserve(r, r->mm_ws, plan.bytes));
     const MmWs w = mm_ws(r->mm_ws.p, mm_layout(sh.d, sh.nl, sh.L, sh.m_ct, (size_t)sh.N, plan.sc, plan.vc, false));
     GR_HIP(r, hipMemsetAsync(acc, 0, accw * 8, r->stream));
-    GR_HIP(r, hipMemsetAsync(w.flags, 0, 8, r->stream));
+    GR_TRY(mm_clear_flags(r, w));
     for (size_t c = 0; c < plan.nsc; c++) {
         const size_t i0 = plan.first(c), sc = plan.count(c, (size_t)s);
         GR_TRY(mm_accumulate_chunk(r, what, sh, plan, w, (const u64 *)A + i0 * sh.nbr * 2 * sh.nl_in * sh.N, (int)sc, b0, b1, (u64 *)acc, s, (int)i0));
@@ -338,7 +440,7 @@ extern "C" int sfg_ring_matmul_dev(sfg_ring *r, const uint64_t *A, int s, int in
     const MmWs w = mm_ws(r->mm_ws.p, mm_layout(sh.d, sh.nl, sh.L, sh.m_ct, (size_t)sh.N, plan.sc, plan.vc, true));
     std::vector<uint8_t> active(sh.d, 0);
     for (int bi = 0; bi < sh.nbr; bi++) { const MmShifts t = mm_shifts(sh.R, sh.C, sh.slots, bi); for (int g = 0; g < sh.d; g++) active[g] |= t.giant[g]; }
-    GR_HIP(r, hipMemsetAsync(w.flags, 0, 8, r->stream));
+    GR_TRY(mm_clear_flags(r, w));
     // the encoder's refusals come before `out` is written: with several chunks a checking pass over the first chunk's accumulate comes first
     for (int pass = plan.nsc > 1 ? 0 : 1; pass < 2; pass++)
         for (size_t c = 0; c < plan.nsc; c++) {

@@ -1715,6 +1715,12 @@ inline RingMatAccumulator MatMult4StreamAccumulate(crypto::RingParams *rp, const
                                              a.giantActive.data()), "MatMult4Stream (accumulate)");
     return a;
 }
+// diagonal coefficients the products re-derived exactly (inside the encoder's band of a rounding tie) since the last reset
+inline unsigned long long EncoderResolved(crypto::RingParams *rp, bool reset) {
+    unsigned long long n = 0;
+    rp->check(sfg_ring_encoder_resolved(rp->ring, &n, reset ? 1 : 0), "EncoderResolved");
+    return n;
+}
 // matmult.go:1443-1502: the giant-step alignment and the aggregation
 inline std::shared_ptr<crypto::RingBuf> MatMult4StreamFinalize(crypto::RingParams *rp, const RingMatAccumulator &a) {
     auto out = std::make_shared<crypto::RingBuf>(rp, (size_t)a.s * a.mct * 2 * a.maxLevel * rp->N() * 8);
